@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- env-steps/sec of the batched PDE-environment stepper on MI355X.
 
-Contract (driver):  python bench.py --gpus N --steps K --warmup W
+Contract (driver):  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   N>1 is launched by the driver as  python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
   (one rank per GPU; instances are independent, so there is NO data-path collective: the only
   communication is the barrier / max-over-ranks of the timing).
@@ -10,7 +10,7 @@ A "step" = one env-step of EVERY instance of the batch = one launch of the fused
 (S PDE sub-steps + norms + reward + observation + auto-reset), inputs already resident in HBM.
 Default workload = BASELINE.json configs[1]: ReactionDiffusionPDE1D ("Parabolic1D") nx=256, batch 4096
 per GPU, fp32, S=100 sub-steps per env-step (SURVEY.md section 8d).  Other workloads (--workload NAME prints NAME's own line;
-the default run measures all of them too: a compact `secondary` list in the printed line, everything in bench_also.json): transport_c3, burgers_c3 (extension), parabolic_c2_policy_loop (C2 with its MLP
+a --full run measures all of them too: a compact `secondary` list in the printed line, everything in bench_also.json): transport_c3, burgers_c3 (extension), parabolic_c2_policy_loop (C2 with its MLP
 controller evaluated on the device every step), parabolic_c2_rollout (the same loop as ONE kernel per 25 env-steps: here a
 "step" is one launch and `value` still counts env-steps), parabolic_c2_policy_loop_256 / parabolic_c2_rollout_256 (the same two with
 the 257-256-256-1 ReLU actor SB3's SAC builds), parabolic_c2_open_loop_rollout (25 env-steps per launch, commands given ahead),
@@ -22,9 +22,16 @@ bench_also.json additionally carries vecenv_host: the SB3-facing PDEVecEnv.step 
 single_env: microseconds per env.step() of ONE environment through the drop-in face beside the un-batched NumPy oracle (bench_single.py),
 and hbm_probe: the measured copy / read / fill rate of the box (tools/hbm_probe.hip).
 
+A plain run does only what the headline needs: set up, W untimed warm-up steps, ONE timed region of exactly K steps, the result line.
+`ms_per_step` is the time of one of those K steps.  --dump-outputs DIR then writes what the last timed step returned (observations,
+rewards, flags; the rollout workloads: every slot of the last launch) as DIR/<name>.npy, float32 or float64, at most 64 MB in all
+(a larger array as a fixed, seeded sample of its values); the inputs depend only on the arguments, so two builds can be compared
+output for output.  --full adds everything else: the headline's rocprofv3 counters collected live, the CPU baseline, the median of
+5 timed regions, the isolated per-launch time, the secondary workloads, the host-facing faces and the HBM probe.
+
 Prints ONE JSON line (rank 0), kept under 4 KB (final_line): metric / value / unit / n_gpus / steps / warmup / ms_per_step /
-higher_is_better / scaling / vs_baseline / dtype / data / config + roofline + cpu_baseline + secondary (+ the per-rank fields for N > 1).
-The complete result of the run -- every workload's configuration, region times and full roofline block -- is written to
+higher_is_better / scaling / vs_baseline / dtype / data / config + roofline (+ cpu_baseline + secondary with --full, + the per-rank
+fields for N > 1).  The complete result of a --full run -- every workload's configuration, region times and full roofline block -- is written to
 bench_also.json next to this script (and to gpurun_out/ when that directory exists).
 """
 from __future__ import annotations
@@ -174,6 +181,9 @@ class ParabolicPolicyLoop(Parabolic1D):
         self.obs = out[0]
         return out
 
+    def outputs(self, ret):
+        return dict(zip(("obs", "reward", "terminated", "truncated"), ret), action=self.act)
+
     def config(self):
         c = super().config()
         c["policy"] = f"MLP 257-{self.HIDDEN}-{self.HIDDEN}-1 {self.ACT}, float32, pdegym_mlp_forward (MFMA), clamp to [-1, 1] fused"
@@ -203,6 +213,9 @@ class ParabolicRollout(ParabolicPolicyLoop):
         self.env.rollout(self.robs, self.ract, self.rrew, self.rte, self.rtr, policy=self.policy)
         self.robs[0].copy_(self.robs[self.CHUNK])         # the next chunk starts where this one ended
         self.i += 1
+
+    def outputs(self, ret):
+        return {"obs": self.robs[1:], "action": self.ract, "reward": self.rrew, "terminated": self.rte, "truncated": self.rtr}
 
     def units_per_step(self):
         return self.B * self.CHUNK
@@ -258,6 +271,9 @@ class ParabolicOpenLoopRollout(Parabolic1D):
         self.env.rollout(self.robs, self.actions[self.i * T:(self.i + 1) * T], self.rrew, self.rte, self.rtr)
         self.robs[0].copy_(self.robs[T])
         self.i += 1
+
+    def outputs(self, ret):
+        return {"obs": self.robs[1:], "reward": self.rrew, "terminated": self.rte, "truncated": self.rtr}
 
     def units_per_step(self):
         return self.B * self.CHUNK
@@ -412,6 +428,7 @@ class TrafficARZ:
     name = "TrafficPDE1D M=51 f64 B=16384 control_freq=2 (reference notebook configuration)"
     dtype = "f64"
     B, S = 16384, 2
+    OUTPUT_NAMES = ("obs", "reward", "done", "truncated")
 
     def __init__(self, device, seed, B=None, S=None):
         import torch
@@ -497,6 +514,9 @@ class TrafficARZRollout(TrafficARZ):
         self.env.rollout(self.robs, self.actions[self.i * T:(self.i + 1) * T], self.rrew, self.rdn, self.rtr)
         self.i += 1
 
+    def outputs(self, ret):
+        return {"obs": self.robs[1:], "reward": self.rrew, "done": self.rdn, "truncated": self.rtr}
+
     def units_per_step(self):
         return self.B * self.CHUNK
 
@@ -518,6 +538,7 @@ class BrainTumor:
     name = "BrainTumor1D nx=201 f64 B=65536 (reference notebook configuration)"
     dtype = "f64"
     B, S = 65536, 1
+    OUTPUT_NAMES = ("u", "reward", "terminated", "truncated")
 
     def __init__(self, device, seed, B=None, S=None):
         import numpy as np
@@ -742,20 +763,53 @@ def _timed(fn, world):
     return time.perf_counter() - t0, ev0.elapsed_time(ev1)
 
 
-def run_workload(wl, steps, warmup, world, graph=False, repeats=REPEATS):
+def step_outputs(wl, ret):
+    """name -> device tensor: what a caller of the workload's timed path receives from one step (`ret` = what wl.step() returned)."""
+    if hasattr(wl, "outputs"):
+        return wl.outputs(ret)
+    return dict(zip(getattr(wl, "OUTPUT_NAMES", ("obs", "reward", "terminated", "truncated")), ret))
+
+
+def _device_storages(wl):
+    """Every device storage the workload and its engine hold (state, inputs, output buffers), one entry per allocation."""
+    import torch
+    found = {}
+
+    def visit(x, depth):
+        if isinstance(x, torch.Tensor):
+            if x.device.type == "cuda":
+                found.setdefault(x.untyped_storage().data_ptr(), x.untyped_storage())
+        elif depth < 4 and isinstance(x, dict):
+            for v in x.values():
+                visit(v, depth + 1)
+        elif depth < 4 and isinstance(x, (list, tuple)):
+            for v in x:
+                visit(v, depth + 1)
+    visit(vars(wl), 0)
+    if getattr(wl, "env", None) is not None:
+        visit(vars(wl.env), 0)
+    return list(found.values())
+
+
+def run_workload(wl, steps, warmup, world, graph=False, repeats=REPEATS, isolated=True, keep_outputs=False):
     """W untimed warm-up steps, then `repeats` timed regions of EXACTLY `steps` steps each (barrier + synchronize on both
     sides of every region).  Returns a dict: the median region (seconds, max over ranks), this rank's own median, every
-    region's time, the per-step duration from HIP events over the median region, and the median duration of isolated
-    single launches timed one by one afterwards.  graph=True: the `steps` launches are captured once into a hipGraph and
-    each region is one replay (no Python between launches)."""
+    region's time, the per-step duration from HIP events over the median region, and (isolated=True) the median duration of
+    isolated single launches timed one by one afterwards.  graph=True: the `steps` launches are captured once into a hipGraph and
+    each region is one replay (no Python between launches).  keep_outputs=True: `outputs` = host copies of what the last timed
+    step returned (step_outputs).  The number of untimed warm replays depends on timing, so in graph mode the timed replays are
+    then repeated, untimed, from the state the capture left, and the outputs are the same from run to run; the timed regions
+    themselves run exactly as without keep_outputs."""
     import torch
     from pdecontrolgym_amd.sharding import max_over_ranks
-    extra = min(steps, 50)
+    extra = min(steps, 50) if isolated else 0
     begin = getattr(wl, "begin_region", lambda: None)     # workloads with finite episodes and no auto-reset restart here
-    wl.prepare(warmup + ((repeats + 2) * steps) + extra)
+    # commands for the warm-up, the timed regions (one captured set of `steps` in graph mode) and the isolated launches
+    wl.prepare(warmup + (1 if graph else repeats) * steps + extra + 1)
     for _ in range(warmup):
         wl.step()
     regions = []
+    final = [None]      # what the last step returned
     if graph:
         torch.cuda.synchronize()
         side = torch.cuda.Stream()
@@ -767,8 +821,12 @@ def run_workload(wl, steps, warmup, world, graph=False, repeats=REPEATS):
             with torch.cuda.graph(g, stream=side):
                 begin()
                 for _ in range(steps):
-                    wl.step()
+                    final[0] = wl.step()
         torch.cuda.current_stream().wait_stream(side)
+        saved = None
+        if keep_outputs:
+            torch.cuda.synchronize()
+            saved = [(s, s.clone()) for s in _device_storages(wl)]
         # untimed replays (graph upload, clocks, caches) until at least WARM_SECONDS have passed: short regions used to be
         # timed while the box was still speeding up (five consecutive regions fell monotonically by 6-10 %)
         # ... and, round 5, until two consecutive replays agree to 1 % (at most WARM_MAX_SECONDS): after a different workload the
@@ -788,17 +846,30 @@ def run_workload(wl, steps, warmup, world, graph=False, repeats=REPEATS):
                 break
         for _ in range(repeats):
             regions.append(_timed(g.replay, world))
+        if saved:       # untimed, after the timing: the same replays again from the state the capture left
+            for s, copy in saved:
+                s.copy_(copy)
+            del saved
+            for _ in range(repeats):
+                g.replay()
+            torch.cuda.synchronize()
     else:
         def loop():
             begin()
             for _ in range(steps):
-                wl.step()
+                final[0] = wl.step()
         for _ in range(repeats):
             regions.append(_timed(loop, world))
+    outputs = None
+    if keep_outputs:
+        outputs = {k: v.detach().cpu().clone() for k, v in step_outputs(wl, final[0]).items()}
     # the only communication of a multi-GPU run (no data-path collective): MAX over ranks of every region's time
     maxes = [max_over_ranks(r[0], device="cuda") for r in regions]
     med = sorted(range(repeats), key=lambda k: maxes[k])[repeats // 2]
     el, (el_local, ev_ms) = maxes[med], regions[med]
+    res = {"seconds": el, "seconds_this_rank": el_local, "step_ms_events": ev_ms / steps, "all_regions_s": maxes, "outputs": outputs}
+    if not isolated:
+        return res
     # per-launch duration with HIP events on the launch stream (outside the timed regions)
     evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(extra)]
     begin()
@@ -808,8 +879,8 @@ def run_workload(wl, steps, warmup, world, graph=False, repeats=REPEATS):
         b.record()
     torch.cuda.synchronize()
     ms = sorted(a.elapsed_time(b) for a, b in evs)
-    return {"seconds": el, "seconds_this_rank": el_local, "step_ms_events": ev_ms / steps, "isolated_step_ms_median": ms[len(ms) // 2],
-            "all_regions_s": maxes}
+    res["isolated_step_ms_median"] = ms[len(ms) // 2]
+    return res
 
 
 def vecenv_host_rate(device, B=4096, steps=60, warmup=8):
@@ -930,6 +1001,34 @@ def roofline_block(wl, key, step_ms, default_config, live=None):
     return out
 
 
+DUMP_BYTES = 63_000_000     # --dump-outputs: array bytes in all (with the .npy headers, under 64 MB)
+
+
+def dump_outputs(outputs, dirname, budget=DUMP_BYTES):
+    """outputs (name -> host tensor) -> dirname/<name>.npy, float64 kept, everything else as float32.  Within `budget` bytes in all:
+    an array whose share does not hold it whole is written as a fixed sample (seed 0, sorted flat indices, the same from run to run
+    for the same shape) of its flattened values.  Returns {name: [shape, elements written]}."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrs = {}
+    for k, v in outputs.items():
+        a = v.numpy()
+        arrs[k] = a if a.dtype == np.float64 else a.astype(np.float32)
+    left, info = budget, {}
+    for i, k in enumerate(sorted(arrs, key=lambda k: arrs[k].nbytes)):       # smallest first: they are kept whole
+        a = arrs[k]
+        share = left // (len(arrs) - i)
+        flat = a.reshape(-1)
+        if a.nbytes > share:
+            take = share // a.itemsize
+            flat = flat[np.sort(np.random.default_rng(0).choice(flat.size, take, replace=False))]
+            a = flat
+        np.save(os.path.join(dirname, f"{k}.npy"), a)
+        left -= a.nbytes
+        info[k] = [list(arrs[k].shape), int(a.size)]
+    return info
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -939,19 +1038,29 @@ def main():
     ap.add_argument("--batch", type=int, default=None, help="instances per GPU (default: the BASELINE batch)")
     ap.add_argument("--substeps", type=int, default=None)
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="skip the secondary workloads in the default run")
+    ap.add_argument("--no-also", action="store_true", help="skip the secondary workloads of a --full run")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--no-live-counters", action="store_true",
                     help="do not collect the headline kernel's counters with rocprofv3 children first (committed counters are used)")
-    ap.add_argument("--repeats", type=int, default=REPEATS, help="timed regions of K steps each; the median is reported")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help=f"timed regions of K steps each; the median is reported (default: 1, with --full {REPEATS})")
     ap.add_argument("--eager", action="store_true",
                     help="one Python call per launch instead of replaying the K timed launches from one captured hipGraph")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: live rocprofv3 counters, the CPU baseline, the secondary "
+                         "workloads, the host-facing faces, the HBM probe and the isolated per-launch time")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     ap.add_argument("--cpu-worker", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--seed", type=int, default=0, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.cpu_worker:                      # child of cpu_baseline_report: NumPy only, prints env-steps/s
         print(cpu_port_rate(args.cpu_worker, args.cpu_seconds, args.seed)[0])
         return
+    if args.repeats is None:
+        args.repeats = REPEATS if args.full else 1
+    if not args.full:                        # a plain run measures the headline only
+        args.no_also = args.no_cpu_baseline = args.no_live_counters = True
     # Live counters + CPU baseline first: their children must be started before this process initialises the GPU
     live = None
     if (int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_live_counters and not args.no_also and not args.batch
@@ -973,8 +1082,9 @@ def main():
         kw["S"] = args.substeps
     wl = WORKLOADS[args.workload](device, 1234 + rank, **kw)
     use_graph = not args.eager
+    dump = bool(args.dump_outputs) and rank == 0
     try:
-        res = run_workload(wl, args.steps, args.warmup, world, graph=use_graph, repeats=args.repeats)
+        res = run_workload(wl, args.steps, args.warmup, world, graph=use_graph, repeats=args.repeats, isolated=args.full, keep_outputs=dump)
     except Exception as ex:                 # capture unsupported in this environment -> time the eager loop instead
         if not use_graph:
             raise
@@ -982,7 +1092,9 @@ def main():
         use_graph = False
         torch.cuda.synchronize()
         wl = WORKLOADS[args.workload](device, 1234 + rank, **kw)
-        res = run_workload(wl, args.steps, args.warmup, world, graph=False, repeats=args.repeats)
+        res = run_workload(wl, args.steps, args.warmup, world, graph=False, repeats=args.repeats, isolated=args.full, keep_outputs=dump)
+    if dump:
+        dump_outputs(res["outputs"], args.dump_outputs)
     el = res["seconds"]
     value = wl.units_per_step() * args.steps * world / el
     default_config = not args.batch and not args.substeps
@@ -991,11 +1103,13 @@ def main():
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": el / args.steps * 1e3,
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": wl.dtype, "data": "synthetic",
         "config": dict(wl.config(), launch="hipGraph replay of the K timed launches" if use_graph else "eager (one Python call per launch)",
-                       timing=f"median of {args.repeats} regions of exactly K steps, each bracketed by barrier + synchronize; max over ranks"),
+                       timing=(f"median of {args.repeats} regions" if args.repeats > 1 else "one region") +
+                              " of exactly K steps, each bracketed by barrier + synchronize; max over ranks"),
         "timed_regions_s": res["all_regions_s"],
         "roofline": roofline_block(wl, args.workload, res["step_ms_events"], default_config, live),
     }
-    out["roofline"]["isolated_step_ms_median"] = res["isolated_step_ms_median"]
+    if "isolated_step_ms_median" in res:
+        out["roofline"]["isolated_step_ms_median"] = res["isolated_step_ms_median"]
     if world > 1:
         # per-rank figures so that a scaling record can be cross-checked: every rank steps its own full per-GPU batch
         # (weak scaling), so each per-rank value should equal the N=1 line of the same box

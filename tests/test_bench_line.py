@@ -3,6 +3,11 @@ line of round 4 gave BENCH_r04.json `parsed: null`).  Built here from a real ful
 line round 4 printed) and from a synthetic worst case -- no GPU."""
 import json
 import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
 
 import bench
 
@@ -193,3 +198,57 @@ def test_live_counters_parse_rocprof_csvs_and_fail_soft(tmp_path, monkeypatch):
     assert bench.live_counters("parabolic_c2", budget_s=7.0, first_timeout_s=1.0) is None
     assert bench.time.perf_counter() - t0 < 10
     assert bench.live_counters("ns2d_c4") is None             # only the headline has a live path
+
+
+def test_dump_outputs_keeps_the_dtypes_stays_within_64_mb_and_samples_the_same_way_every_time(tmp_path):
+    """--dump-outputs: float64 stays float64, everything else becomes float32; small arrays are written whole, an array that does not
+    fit its share of the budget as the same seeded sample of its flattened values every time; the files stay under 64 MB in all."""
+    import torch
+    g = torch.Generator().manual_seed(0)
+    outs = {"obs": torch.rand(4096, 257, generator=g), "reward": torch.rand(4096, generator=g),
+            "terminated": torch.randint(0, 2, (4096,), dtype=torch.uint8, generator=g),
+            "trajectory": torch.rand(26, 4096, 257, dtype=torch.float64, generator=g)}
+    info = bench.dump_outputs(outs, str(tmp_path / "a"))
+    bench.dump_outputs(outs, str(tmp_path / "b"))
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["obs.npy", "reward.npy", "terminated.npy", "trajectory.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64_000_000
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    assert got["trajectory"].dtype == np.float64 and all(got[k].dtype == np.float32 for k in ("obs", "reward", "terminated"))
+    np.testing.assert_array_equal(got["obs"], outs["obs"].numpy())
+    np.testing.assert_array_equal(got["terminated"], outs["terminated"].numpy().astype(np.float32))
+    assert info["trajectory"][0] == [26, 4096, 257] and 0 < got["trajectory"].size == info["trajectory"][1] < outs["trajectory"].numel()
+    assert np.isin(got["trajectory"], outs["trajectory"].numpy().reshape(-1)).all()
+    for f in files:
+        np.testing.assert_array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+
+
+@pytest.mark.gpu
+def test_plain_run_times_exactly_k_steps_and_dumps_the_same_outputs_every_time(tmp_path):
+    """A plain run: the headline line only (no CPU baseline, no secondary workloads, no live counters), ONE timed region of exactly
+    --steps steps, and --dump-outputs writes the last step's observations / rewards / flags -- identical in two separate runs."""
+    lines = []
+    for tag in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "30", "--warmup", "5",
+                            "--dump-outputs", str(tmp_path / tag)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
+                           timeout=300, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines.append(json.loads(r.stdout.strip().splitlines()[-1]))
+    for d in lines:
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in d, k
+        assert d["steps"] == 30 and d["warmup"] == 5 and d["dtype"] == "f32" and d["higher_is_better"] is True
+        assert "cpu_baseline" not in d and "secondary" not in d and d["roofline"]["counters_live"] is False
+        assert d["config"]["launch"].startswith("hipGraph")         # the dump must not push the run off the captured path
+    with open(os.path.join(ROOT, "bench_parabolic_c2.json")) as fh:      # written by the second run: compared with its own line
+        full = json.load(fh)
+    d = lines[1]
+    assert len(full["timed_regions_s"]) == 1
+    assert abs(d["ms_per_step"] - full["timed_regions_s"][0] / 30 * 1e3) <= 2e-5 * d["ms_per_step"]       # (6 digits in the line)
+    assert abs(d["value"] - 4096 * 30 / full["timed_regions_s"][0]) <= 2e-5 * d["value"]
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["obs.npy", "reward.npy", "terminated.npy", "truncated.npy"]
+    obs = np.load(tmp_path / "a" / "obs.npy")
+    assert obs.shape == (4096, 257) and obs.dtype == np.float32 and np.isfinite(obs).all()
+    for f in files:
+        np.testing.assert_array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))

@@ -114,7 +114,7 @@ def test_two_rank_shards_on_the_hip_backend_equal_single_process_bitwise(tmp_pat
 
 @pytest.mark.timeout(900)
 def test_bench_two_ranks_prints_per_rank_values():
-    r = _launch([os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "3", "--repeats", "3"],
+    r = _launch([os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "3", "--repeats", "3", "--full"],
                 extra_env={"PDEGYM_BENCH_SHARE_GPU": "1"})
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.stdout[-2000:], r.stderr[-3000:])

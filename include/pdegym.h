@@ -134,7 +134,9 @@ typedef struct pdegym_bufs1d {
   float* norm_back;         /* [B] out  ||u_{t-100}||_2 (0 for an unwritten row)                              */
   uint8_t* terminated;      /* [B] out                                                                        */
   uint8_t* truncated;       /* [B] out                                                                        */
-  float* history;           /* optional [B, nt, n] full trajectory (NULL = keep only the live row)            */
+  float* history;           /* optional [B, nt, n] full trajectory (NULL = keep only the live row): a step writes the
+                               whole rows t_in+1 .. t_in+nsub of each instance (every node, the parabolic node 0 included)
+                               and no other row; pdegym_reset1d_masked writes row 0 = init and zero-fills the rest        */
   const float* reset_init;  /* optional [B, n] pool of next initial conditions: when non-NULL an instance whose
                                step ends terminated|truncated is restarted INSIDE the same launch (state := pool row,
                                time_index := 0) and obs[b] is the first observation of the new episode            */
@@ -440,7 +442,8 @@ enum {
   PDEGYM_TUMOR_RUN_TO_END = 3   /* every live instance: step(0) until terminated or truncated (benchmark())  :488-503   */
 };
 
-/* One day per call.  Instances with time_index >= nt-1 are left untouched (reward 0, flags 0).  nx <= 4096. */
+/* One day per call.  nx <= 4096.  An active instance with time_index >= nt-1 (its episode is over) keeps its state and out[b];
+ * the call writes reward[b] = 0, terminated[b] = truncated[b] = 0 for it. */
 int pdegym_tumor_step(const pdegym_params_tumor* prm, const pdegym_bufs_tumor* buf, int32_t B, void* stream);
 /* Up to max_days days per participating instance inside ONE launch (row and stage machine stay on chip between days);
  * control is 0 on every day of modes 1-3; reward / flags / out are those of the LAST simulated day; instances that do not

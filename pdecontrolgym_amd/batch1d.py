@@ -177,6 +177,7 @@ class PDEBatch1D(EngineCheckpoint):
             raise ValueError(f"beta must have {self.n} nodes, got {tuple(beta.shape)}")
         self.t["beta"] = beta
         self.params.beta_f64 = 1 if dtype == torch.float64 else 0
+        self._drop_prepared_call()
 
     def reset(self, init, beta=None, mask=None):
         """(Re)start instances from ``init`` [B, n]; where ``mask`` [B] (uint8/bool) is given only those."""
@@ -221,12 +222,14 @@ class PDEBatch1D(EngineCheckpoint):
             self.t["reset_beta"] = bp
         self.t["final_obs"] = (torch.zeros(self.num_envs, self.obs_dim, dtype=torch.float32, device=self.device)
                                if keep_final_obs else None)
+        self._drop_prepared_call()
 
     def disable_auto_reset(self):
         self.t["reset_init"] = None
         self.t["final_obs"] = None
         self.t["reset_beta"] = None
         self.t["reset_count"] = None
+        self._drop_prepared_call()
 
     def step(self, action, out_obs=None, out_reward=None, out_terminated=None, out_truncated=None, action_kind=None):
         """Advance every instance by one env-step (S sub-steps). action: [B] tensor.

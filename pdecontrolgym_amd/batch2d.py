@@ -144,10 +144,12 @@ class NSBatch2D(EngineCheckpoint):
         self.t["reset_count"] = torch.zeros(self.num_envs, dtype=torch.int32, device=self.device)
         self.t["final_obs"] = (torch.zeros(self.num_envs, self.ny, self.nx, 2, dtype=self.dtype, device=self.device)
                                if keep_final_obs else None)
+        self._drop_prepared_call()
 
     def disable_auto_reset(self):
         for k in ("reset_u0", "reset_v0", "reset_p0", "final_obs", "reset_count"):
             self.t[k] = None
+        self._drop_prepared_call()
 
     def reset(self, u0, v0, p0, mask=None):
         import torch

@@ -55,6 +55,14 @@ class EngineCheckpoint:
             else:                                          # a pool / optional tensor this engine has not allocated (yet)
                 self.t[k] = v.to(self.device).clone()
         self._after_load(sd)
+        self._drop_prepared_call()
 
     def _after_load(self, sd):
         pass
+
+    def _drop_prepared_call(self):
+        """Forget the prepared call of the host-io face (``enable_host_io`` / ``step_host``): its argument structures hold the
+        addresses of the tensors in ``self.t``, so every method that replaces one of them drops it and the next step rebuilds it."""
+        io = getattr(self, "_hio", None)
+        if io is not None:
+            io["call"] = None

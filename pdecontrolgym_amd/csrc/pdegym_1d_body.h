@@ -495,11 +495,15 @@ __device__ __forceinline__ void run_substeps(Row<EPL>& R, const float (&beta)[EP
       if (hist) {
         hrow = hist + (size_t)R.t * n + J0;
         any_part = __builtin_amdgcn_ballot_w64(hpart) != 0ull;
+        if constexpr (PARABOLIC) {
+          for (int i = lane; i < nsub; i += kWave) hist[(size_t)(R.t + 1 + i) * n] = 0.0f;   // rows t_in+1 .. t_in+nsub <= nt-1
+        }
       }
     }
     // PART: some lane straddles the row's end (decided once per call: the loops below exist in both forms, so the common form has no
-    // test and no skipped block inside).  Node 0 of a parabolic row is not stored: it is 0 after any sub-step and every row >= 1 of the
-    // trajectory is zero-filled by the reset (reset_history_kernel, the fused auto-reset), so the word already holds it.
+    // test and no skipped block inside).  Node 0 of a parabolic row (0 after any sub-step, parabolic.py:146) is not part of the
+    // slots: the nsub words of column 0 are stored once above, one per lane, so the rows are complete whatever the buffer held
+    // before (history is a plain output, include/pdegym.h) and the sub-step loop carries no extra store.
     auto store_row = [&](auto part_tag) {
       if constexpr (HIST) {
         hrow += n;

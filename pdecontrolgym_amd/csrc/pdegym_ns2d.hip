@@ -280,9 +280,10 @@ __device__ __forceinline__ void gen_front(const NSConst& C, const NSScal<T>& S, 
   compute_rhs<T>(us, vs, rhs, ny, nx, S);
 }
 
-// back: corrector (with the solved pressure pfin) -> apply_boundary -> observation, reward, flags
+// back: corrector (with the solved pressure pfin) -> apply_boundary -> observation, reward, flags.  `part`: at least nx entries of
+// LDS that are idle by now (the Jacobi buffer), for the reward's column sums.
 template <typename T>
-__device__ __forceinline__ void gen_back(const NSConst& C, const NSScal<T>& S, const NSPtrs<T>& P, int b, const T* pfin, T* red) {
+__device__ __forceinline__ void gen_back(const NSConst& C, const NSScal<T>& S, const NSPtrs<T>& P, int b, const T* pfin, T* part) {
   const int nx = C.nx, ny = C.ny, ncell = nx * ny;
   T* u = (P.u && !P.state_in) ? P.u + (size_t)b * ncell : nullptr;
   T* v = (P.v && !P.state_in) ? P.v + (size_t)b * ncell : nullptr;
@@ -310,7 +311,6 @@ __device__ __forceinline__ void gen_back(const NSConst& C, const NSScal<T>& S, c
   const int tr = t < C.nt_ref ? t : C.nt_ref - 1;
   const T* uref = P.U_ref + (size_t)tr * ncell * 2;
   T* obs = P.obs + (size_t)b * ncell * 2;
-  T acc = 0;
   for (int c = threadIdx.x; c < ncell; c += blockDim.x) {
     const int i = c / nx, j = c - i * nx;
     T un, vn;
@@ -327,12 +327,26 @@ __device__ __forceinline__ void gen_back(const NSConst& C, const NSScal<T>& S, c
     }
     obs[2 * (size_t)c] = un;
     obs[2 * (size_t)c + 1] = vn;
-    const T du = un - uref[2 * (size_t)c], dv = vn - uref[2 * (size_t)c + 1];
-    acc += du * du;
-    acc += dv * dv;
   }
-  const T ss = block_sum<T>(acc, red);
+  __syncthreads();
+  // ||U - Uref||^2 in the order of the column kernels (ns_col_body), whatever the workgroup size: column j adds du^2 then dv^2
+  // for rows 0 .. ny-1, then thread 0 adds the column sums j = 0 .. nx-1 in sequence.  An instance's reward bits thus do not
+  // depend on its batch size, its position in the batch or the kernel the launcher picks (every grid but the tiled ones).
+  for (int j = threadIdx.x; j < nx; j += blockDim.x) {
+    T acc = 0;
+#pragma unroll 4
+    for (int i = 0; i < ny; ++i) {
+      const size_t c = (size_t)i * nx + j;    // the observation this workgroup has just written (visible after the barrier)
+      const T du = obs[2 * c] - uref[2 * c], dv = obs[2 * c + 1] - uref[2 * c + 1];
+      acc += du * du;
+      acc += dv * dv;
+    }
+    part[j] = acc;
+  }
+  __syncthreads();
   if (threadIdx.x == 0) {
+    T ss = 0;
+    for (int j = 0; j < nx; ++j) ss += part[j];
     T asq = 0;
     const T aref = P.action_ref[tr];
     for (int k = 0; k < C.action_dim; ++k) {
@@ -348,8 +362,7 @@ __device__ __forceinline__ void gen_back(const NSConst& C, const NSScal<T>& S, c
 
 template <typename T, int LDSJ>   // 0: global-memory Jacobi, 1: two LDS copies, 2: one LDS copy
 __global__ __launch_bounds__(1024) void ns_generic_step(NSConst C, NSScal<T> S, NSPtrs<T> P, int B) {
-  __shared__ T red[16];
-  extern __shared__ double ns_dyn_lds[];
+  extern __shared__ double ns_dyn_lds[];   // LDSJ 1 / 2: the Jacobi copies of p; every mode: >= nx entries for gen_back
   const int b = blockIdx.x;
   if (b >= B) return;
   const int ncell = C.nx * C.ny;
@@ -368,7 +381,7 @@ __global__ __launch_bounds__(1024) void ns_generic_step(NSConst C, NSScal<T> S, 
   } else {
     jacobi_sweeps<T>(p, pB, rhs, C.ny, C.nx, C.iters, S.dxdy);
   }
-  gen_back<T>(C, S, P, b, p, red);
+  gen_back<T>(C, S, P, b, p, reinterpret_cast<T*>(ns_dyn_lds));
 }
 
 // ================================================================================================
@@ -1270,7 +1283,7 @@ __global__ __launch_bounds__(64 * (128 / PR), PR == 16 ? 2 : 4) void ns_tile_ste
         const double2 w0 = *reinterpret_cast<const double2*>(uref + o), w1 = *reinterpret_cast<const double2*>(uref + o + 2);
         *reinterpret_cast<double2*>(obs + o) = make_double2(uf[la][0], vf[la][0]);
         *reinterpret_cast<double2*>(obs + o + 2) = make_double2(uf[la][1], vf[la][1]);
-        // accumulation order of gen_back: cells in index order, du^2 then dv^2 (the reduction order across lanes differs: rtol 1e-12)
+        // per thread: its cells in index order, du^2 then dv^2; then block_sum across lanes (not gen_back's column order: rtol 1e-12)
         const double d0 = uf[la][0] - w0.x, d1 = vf[la][0] - w0.y, d2 = uf[la][1] - w1.x, d3 = vf[la][1] - w1.y;
         acc += d0 * d0;
         acc += d1 * d1;
@@ -1306,7 +1319,8 @@ __global__ __launch_bounds__(64 * (128 / PR), PR == 16 ? 2 : 4) void ns_tile_ste
 // wall cell equal its nearest interior cell after each sweep, so from the second sweep on a stencil next to a wall reads
 // the cell's own old value instead of the wall (first sweep: the walls as given); the walls are written out once at the end.
 // Same expression trees as ns_generic_step<T> (IEEE division for double) -> bit-identical fields (tested against the goldens
-// of the reference and the generic kernel); the reward is summed per column then over the instance's lanes in order.
+// of the reference and the generic kernel); the reward is summed per column then over the instance's lanes in order -- the
+// canonical order that gen_back follows too, so rewards are the same bits on either kernel.
 // ================================================================================================
 __device__ __forceinline__ float lane_from_left(float v) { return lane_left(v); }
 __device__ __forceinline__ float lane_from_right(float v) { return lane_right(v); }
@@ -1954,7 +1968,8 @@ int ns_step_launch(const pdegym_params_ns2d* prm, const pdegym_bufs_ns2d* buf, i
       return pdegym::fail(-4, "cannot raise the dynamic LDS limit");
     hipLaunchKernelGGL((ns_generic_step<T, 2>), dim3(B), dim3(1024), (size_t)ncell * sizeof(T), (hipStream_t)stream, C, S, P, B);
   } else {
-    hipLaunchKernelGGL((ns_generic_step<T, 0>), dim3(B), dim3(block_threads(ncell)), 0, (hipStream_t)stream, C, S, P, B);
+    hipLaunchKernelGGL((ns_generic_step<T, 0>), dim3(B), dim3(block_threads(ncell)), (size_t)C.nx * sizeof(T), (hipStream_t)stream,
+                       C, S, P, B);
   }
   return pdegym::check_launch("ns2d_step");
 }

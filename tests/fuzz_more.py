@@ -77,6 +77,25 @@ def ns_case(rng, idx):
         assert np.allclose(r.cpu().numpy(), r_ref, rtol=1e-12, atol=1e-300), desc + f" step {i}: reward {r.cpu().numpy()} {r_ref}"
         assert np.array_equal(te.cpu().numpy().astype(bool), te_ref), desc + f" step {i}: terminate"
     _dbg("DEBUG_NS_COL_MIN_BATCH", -1)
+    # the column kernel and the workgroup kernel: every output bit for bit, rewards included (one summation order)
+    if m in (8, 11, 16, 21, 26, 31, 32) and n <= 64:
+        outs = []
+        for mb in ("0", "1000000"):
+            _dbg("DEBUG_NS_COL_MIN_BATCH", mb)
+            try:
+                e2 = NSBatch2D(num_envs=B, device="cuda", dtype=torch.float64, interleaved_state=inter, action_dim=adim, **kw)
+                e2.reset(u0, v0, p0)
+                acts = np.random.default_rng(idx + 1).uniform(2, 4, (nt - 1, B, adim))
+                res = []
+                for a in acts:
+                    obs, r, te = e2.step(a)
+                    res.append((obs.cpu().numpy().copy(), e2.p.cpu().numpy().copy(), r.cpu().numpy().copy()))
+                outs.append(res)
+            finally:
+                _dbg("DEBUG_NS_COL_MIN_BATCH", -1)
+        for (o1, p1, r1), (o2, p2, r2) in zip(*outs):
+            assert bits_equal(o1, o2) and bits_equal(p1, p2), desc + " column != workgroup (fields)"
+            assert bits_equal(r1, r2), desc + f" column != workgroup (rewards {r1} {r2})"
     # float32: tiled kernel == generic kernel for the sizes the tiled path exists for
     if n == m and n in (64, 128):
         outs = []

@@ -21,6 +21,15 @@ def _dbg(key, value):
     N.load().pdegym_debug_set(getattr(N, key), int(value))
 
 
+def _assert_same_bits(x, y, what):
+    """x and y hold the same bit patterns (-0.0 != +0.0); the message names the output and the first differing entry."""
+    assert x.dtype == y.dtype and x.shape == y.shape, (what, x.dtype, y.dtype, x.shape, y.shape)
+    xb, yb = x.view(np.uint8).reshape(x.shape + (-1,)), y.view(np.uint8).reshape(y.shape + (-1,))
+    bad = np.argwhere((xb != yb).any(-1)) if x.ndim else np.argwhere(np.atleast_1d((xb != yb).any()))
+    assert len(bad) == 0, f"{what}: {len(bad)} entries differ in their bits, first at {bad[0].tolist()}: " \
+                          f"{x[tuple(bad[0])] if x.ndim else x!r} vs {y[tuple(bad[0])] if y.ndim else y!r}"
+
+
 def _mk(kw, B, dtype):
     from pdecontrolgym_amd.batch2d import NSBatch2D
     return NSBatch2D(num_envs=B, device="cuda", dtype=dtype, **kw)
@@ -268,7 +277,9 @@ def test_ns_masked_reset_and_properties_c4_size():
 @pytest.mark.parametrize("n", [128, 64, 256])
 def test_ns_f32_tiled_kernel_equals_generic_kernel_bitwise(n):
     """The register-tiled float32 kernel and the generic float32 kernel evaluate the same expression tree:
-    fields, pressure and observations must agree bit for bit over several steps (reward: summation order)."""
+    fields, pressure and observations must agree bit for bit over several steps.  Rewards only to rounding: the tiled kernels
+    keep their own reduction order (their selection depends on grid and dtype alone, never on the batch; every term of their
+    sum is pinned by test_gpu_batch_invariance.py::test_ns_planted_reward_terms)."""
     import os
     kw, u0, v0, p0, acts = _random_case(n, 5, 50 if n != 256 else 37, 900 + n, BC_MIX)    # 256: an odd sweep count (the row rotation ends off the identity map)
     outs = []
@@ -294,7 +305,8 @@ def test_ns_f32_tiled_kernel_equals_generic_kernel_bitwise(n):
 def test_ns_f64_tiled_kernel_equals_generic_kernel_and_oracle_bitwise(K, interleaved, adim):
     """The float64 register-tiled 128x128 kernel (the reference's precision on the fast path): fields, pressure and
     observations bit-identical to the generic float64 kernel AND to the NumPy oracle; even / odd / zero sweep counts, the
-    interleaved (observation = state) and the separate-u,v state layouts, scalar and per-node boundary actions."""
+    interleaved (observation = state) and the separate-u,v state layouts, scalar and per-node boundary actions.  Rewards to rounding:
+    the tiled kernel keeps its own reduction order (chosen by grid and dtype alone; test_ns_planted_reward_terms pins each term)."""
     import os
     from oracle import pde_oracle as po
     from pdecontrolgym_amd.batch2d import NSBatch2D
@@ -336,7 +348,8 @@ def test_ns_f64_256_slab_passes_equal_generic_kernel_bitwise(K, interleaved, adi
     workgroup-per-instance kernel bit for bit: one launch (K <= 25: front + sweeps + back in the same kernel), exactly 25,
     25 + 1, two full passes (BASELINE), 50 + 1 (three passes), four passes, odd and even counts per pass, none; both state
     layouts (the interleaved one ping-pongs the pressure field, the separate one brings it home in an even number of passes),
-    scalar and per-node boundary actions."""
+    scalar and per-node boundary actions.  Rewards to rounding: the slab passes keep their own reduction order (chosen by grid and
+    dtype alone; test_ns_planted_reward_terms pins each term)."""
     from pdecontrolgym_amd.batch2d import NSBatch2D
     B = 2
     kw, u0, v0, p0, acts = _random_case(256, B, K, 5000 + K, BC_MIX, adim)
@@ -368,7 +381,8 @@ def test_ns_f64_256_slab_passes_equal_generic_kernel_bitwise(K, interleaved, adi
                                        (65, "float64", 9)])
 def test_ns_lds_resident_jacobi_equals_global_memory_jacobi_bitwise(n, dtype, K):
     """Grids of <= 4096 cells keep p in LDS during the sweeps; same arithmetic as the global-memory loop -> identical
-    fields, pressure (incl. the public solve_pressure) and rewards.  Odd and even K, both dtypes."""
+    fields, pressure (incl. the public solve_pressure) and rewards (one summation order whatever the workgroup size), bit for
+    bit.  Odd and even K, both dtypes."""
     import os
     td = getattr(torch, dtype)
     kw, u0, v0, p0, acts = _random_case(n, 3, K, 77 + n + K, BC_MIX)
@@ -388,12 +402,9 @@ def test_ns_lds_resident_jacobi_equals_global_memory_jacobi_bitwise(n, dtype, K)
         finally:
             _dbg("DEBUG_NS_NO_LDS_JACOBI", "0")
             _dbg("DEBUG_NS_GENERIC", "0")
-    for a, b in zip(*outs):
-        for x, y in zip(a, b):
-            if x.ndim == 1:      # rewards: the block reduction order follows the workgroup size, which differs between the paths
-                np.testing.assert_allclose(x, y, rtol=1e-5 if dtype == "float32" else 1e-13)
-            else:
-                np.testing.assert_array_equal(x, y)
+    for t, (a, b) in enumerate(zip(*outs)):
+        for name, x, y in zip(("obs", "p", "reward", "solve_pressure p"), a, b):
+            _assert_same_bits(x, y, f"step {t}: {name}")
 
 
 @pytest.mark.parametrize("n,dtype", [(128, "float32"), (40, "float32"), (21, "float64"), (256, "float32")])
@@ -524,7 +535,7 @@ def _rect_case(ny, nx, B, K, seed, bc, action_dim=1):
                                                          (64, 3, 6, True, False)])     # per-node actions need a square grid
 def test_ns_column_kernel_equals_workgroup_kernel_bitwise(dtype, nx, B, K, interleaved, per_node):
     """ns_col_step (21 rows, one lane per column, floor(64 / nx) instances per wave, no barriers) against ns_generic_step:
-    identical velocity, pressure, flags; rewards to the rounding of a different summation order.  Ragged batches (idle lane
+    identical velocity, pressure, flags and rewards (both sum in the canonical order), bit for bit.  Ragged batches (idle lane
     groups), the first / later sweep forms (K = 0, 1, 2, more), mixed boundary conditions with scalar and per-node actions."""
     import os
     from pdecontrolgym_amd.batch2d import NSBatch2D
@@ -547,10 +558,9 @@ def test_ns_column_kernel_equals_workgroup_kernel_bitwise(dtype, nx, B, K, inter
         finally:
             _dbg("DEBUG_NS_COL_MIN_BATCH", -1)
             _dbg("DEBUG_NS_NO_COL", "0")
-    for a, b in zip(*outs):
-        for x, y in zip(a[:-1], b[:-1]):
-            np.testing.assert_array_equal(x, y)
-        np.testing.assert_allclose(a[-1], b[-1], rtol=1e-5 if dtype == "float32" else 1e-12)
+    for t, (a, b) in enumerate(zip(*outs)):
+        for name, x, y in zip(("obs", "p", "u", "time_index", "terminated", "reward"), a, b):
+            _assert_same_bits(x, y, f"step {t}: {name}")
 
 
 @pytest.mark.parametrize("dtype", ["float64", "float32"])
@@ -577,10 +587,9 @@ def test_ns_column_kernel_other_heights_bitwise(dtype, ny, nx, B, K):
         finally:
             _dbg("DEBUG_NS_COL_MIN_BATCH", -1)
             _dbg("DEBUG_NS_NO_COL", "0")
-    for a, b in zip(*outs):
-        np.testing.assert_array_equal(a[0], b[0])
-        np.testing.assert_array_equal(a[1], b[1])
-        np.testing.assert_allclose(a[2], b[2], rtol=1e-5 if dtype == "float32" else 1e-12)
+    for t, (a, b) in enumerate(zip(*outs)):
+        for name, x, y in zip(("obs", "p", "reward"), a, b):
+            _assert_same_bits(x, y, f"step {t}: {name}")
 
 
 def test_ns_column_kernel_reproduces_target_npz_and_oracle(golden_ns):
@@ -643,10 +652,9 @@ def test_ns_column_kernel_default_dispatch_large_batch(B):
             outs.append(res)
         finally:
             _dbg("DEBUG_NS_NO_COL", "0")
-    for a, b in zip(*outs):
-        np.testing.assert_array_equal(a[0], b[0])
-        np.testing.assert_array_equal(a[1], b[1])
-        np.testing.assert_allclose(a[2], b[2], rtol=1e-12)
+    for t, (a, b) in enumerate(zip(*outs)):
+        for name, x, y in zip(("obs", "p", "reward"), a, b):
+            _assert_same_bits(x, y, f"step {t}: {name}")
 
 
 @pytest.mark.parametrize("n,dtype,K,B,T,adim", [(21, "float64", 40, 7, 9, 1), (21, "float32", 25, 64, 9, 1), (11, "float64", 7, 5, 6, 11),
@@ -665,8 +673,7 @@ def test_ns_rollout_kernel_equals_step_calls_bitwise(n, dtype, K, B, T, adim):
     pools = [rng.uniform(-1, 1, (2 * B, n, n)) for _ in range(3)]
     acts = torch.as_tensor(rng.uniform(2, 4, (T, B, adim)), dtype=td, device="cuda")
     outs = []
-    # the step calls take the column kernel too (small float64 batches default to the workgroup kernel, whose FIELDS are the same
-    # bits but whose reward sum runs in another order)
+    # the step calls take the column kernel too (test_ns_rollout_vs_default_dispatch_small_float64_batch: the workgroup kernel)
     _dbg("DEBUG_NS_COL_MIN_BATCH", "0")
     for mode in ("steps", "rollout"):
         env = NSBatch2D(num_envs=B, device="cuda", dtype=td, **kw)
@@ -698,8 +705,8 @@ def test_ns_rollout_kernel_equals_step_calls_bitwise(n, dtype, K, B, T, adim):
 
 def test_ns_rollout_vs_default_dispatch_small_float64_batch():
     """with the DEFAULT dispatch a float64 batch below the column kernel's minimum (400 per 1024 SIMDs) steps on the
-    workgroup kernel while the rollout always runs the column kernel: every FIELD, flag and counter is still the same bits, the
-    rewards agree to rounding (another summation order), as include/pdegym.h states."""
+    workgroup kernel while the rollout always runs the column kernel: every field, flag, counter and reward is still the same bits
+    (both kernels sum the reward in the canonical order), as include/pdegym.h states."""
     from pdecontrolgym_amd.batch2d import NSBatch2D
     n, K, B, T = 21, 30, 9, 6
     kw, u0, v0, p0, _ = _random_case(n, B, K, 7321, BC_MIX, 1)
@@ -721,6 +728,5 @@ def test_ns_rollout_vs_default_dispatch_small_float64_batch():
         else:
             env.rollout(obs, acts, rew, te)
         outs.append([x.cpu().numpy().copy() for x in (obs, te, env.p, env.t["time_index"], rew)])
-    for a, b in zip(outs[0][:4], outs[1][:4]):
-        np.testing.assert_array_equal(a, b)
-    np.testing.assert_allclose(outs[0][4], outs[1][4], rtol=1e-13)
+    for name, a, b in zip(("obs", "terminated", "p", "time_index", "rewards"), outs[0], outs[1]):
+        _assert_same_bits(a, b, f"steps vs rollout: {name}")

@@ -625,15 +625,8 @@ __device__ __forceinline__ void step1d_body(const pdegym_params1d& P, const pdeg
   static_assert(!HFAST || HIST, "HFAST is a history mode");
   constexpr bool kFast = !NEUMANN && !M64 && (!HIST || HFAST);
   static_assert(!CARRY || kFast, "the carried state is the float32 Dirichlet rollout path");
-#ifdef PDEGYM_TIMING
-  const unsigned long long tm0 = __builtin_amdgcn_s_memtime();
-  const unsigned long long tr0 = __builtin_amdgcn_s_memrealtime();
-#endif
   static_assert(!FULL || kFast, "FULL rows: the float32 Dirichlet fast path only");
   const int n = FULL ? kWave * EPL + J0 : P.n, ns = n - J0, s0 = lane * EPL;
-#ifdef PDEGYM_TIMING
-  const unsigned long long tmk = __builtin_amdgcn_s_memtime() + (unsigned long long)(n == 0x7fffffff);  // kernarg arrived
-#endif
   // state_in given: the row comes from the previous call's observation and goes to obs only (include/pdegym.h)
   const float* urow_in = (Bf.state_in ? Bf.state_in : Bf.u) + (size_t)inst * n;
   float* urow = Bf.state_in ? nullptr : Bf.u + (size_t)inst * n;
@@ -699,9 +692,6 @@ __device__ __forceinline__ void step1d_body(const pdegym_params1d& P, const pdeg
   R.back_row = (!zero_row && !from_ring) ? src_row : -1;
   R.back_norm = 0.f;
 
-#ifdef PDEGYM_TIMING
-  const unsigned long long tm1 = __builtin_amdgcn_s_memtime() + (unsigned long long)(R.x[0] != R.x[0]);
-#endif
   // NormReward "differential" (norm_reward.py:55-59): ||u[t] - u[t-1]|| over FINE rows, so the row before the last sub-step is
   // kept.  Only the select-form instantiations evaluate it (launch_epl routes the request there; rollouts refuse it).
   const bool differential = !kFast && P.reward_horizon == PDEGYM_HORIZON_DIFFERENTIAL && P.reward_kind >= PDEGYM_REWARD_NORM_L1;
@@ -791,9 +781,6 @@ __device__ __forceinline__ void step1d_body(const pdegym_params1d& P, const pdeg
     norm_now = sqrtf(slots_sumsq<EPL>(R.x, s0, ns) + R.bl * R.bl);
   }
   const int t = R.t;
-#ifdef PDEGYM_TIMING
-  const unsigned long long tm2 = __builtin_amdgcn_s_memtime() + (unsigned long long)(norm_now != norm_now);
-#endif
 
   // ---- epilogue: norms, flags, reward, observation ------------------------------------------------
   const bool rec_all = P.nt <= PDEGYM_RING;
@@ -962,19 +949,6 @@ __device__ __forceinline__ void step1d_body(const pdegym_params1d& P, const pdeg
     carry->bl = R.bl;
     carry->ring = ring;
   }
-#ifdef PDEGYM_TIMING
-  if (lane == 0) {
-    const unsigned long long tm3 = __builtin_amdgcn_s_memtime();
-    unsigned int* dbg = reinterpret_cast<unsigned int*>(ring_mem) + 116;
-    dbg[0] = (unsigned int)tm0; dbg[1] = (unsigned int)(tm0 >> 32);
-    dbg[2] = (unsigned int)(tm1 - tm0); dbg[3] = (unsigned int)(tm2 - tm1); dbg[4] = (unsigned int)(tm3 - tm2);
-    dbg[5] = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));   // HW_ID
-    dbg[6] = __builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11));  // XCC_ID
-    const unsigned long long tr3 = __builtin_amdgcn_s_memrealtime();          // 100 MHz constant clock
-    dbg[7] = (unsigned int)tr0; dbg[8] = (unsigned int)(tr3 - tr0);
-    dbg[9] = (unsigned int)(tmk - tm0);
-  }
-#endif
 }
 
 // The state a rollout launch starts from, read ONCE: row (observation slot 0), beta, time index and |u[-1]| sum.

@@ -54,8 +54,6 @@ constexpr int kLdsBytes = kHaloBytes + kRL * kNT * 16;
 static_assert(kRL % 2 == 0 && kRL >= 2 && kRL < kPR && kRR % 2 == 0, "LDS rows come in two-row blocks");
 static_assert(kLdsBytes <= 160 * 1024, "LDS budget of one CU");
 
-__device__ __forceinline__ constexpr int rq_reg(int a) { return a; }
-
 // ---- one Jacobi sweep (state ST: 0 = UP, 1 = DOWN; see jacobi_sweep_bous), right-hand side partly in LDS -------------
 template <int ST>
 __device__ __forceinline__ void sweep256(float (&ph)[kPR + 1][4], const float (&rq)[kRR][4], const float4* rql, const EdgeFlags& E,
@@ -83,8 +81,8 @@ __device__ __forceinline__ void sweep256(float (&ph)[kPR + 1][4], const float (&
         if (a + 2 == PR) jacobi_pair_up(da, ph[a], ph[a + 1], hlast, buf[jl & 1][0], buf[jl & 1][1]);
         else jacobi_pair_up(da, ph[a], ph[a + 1], ph[a + 2], buf[jl & 1][0], buf[jl & 1][1]);
       } else {
-        if (a + 2 == PR) jacobi_pair_up(da, ph[a], ph[a + 1], hlast, rq[rq_reg(a)], rq[rq_reg(a + 1)]);
-        else jacobi_pair_up(da, ph[a], ph[a + 1], ph[a + 2], rq[rq_reg(a)], rq[rq_reg(a + 1)]);
+        if (a + 2 == PR) jacobi_pair_up(da, ph[a], ph[a + 1], hlast, rq[a], rq[a + 1]);
+        else jacobi_pair_up(da, ph[a], ph[a + 1], ph[a + 2], rq[a], rq[a + 1]);
       }
     }
     jacobi_walls_state<PR, 1>(ph, E);
@@ -103,8 +101,8 @@ __device__ __forceinline__ void sweep256(float (&ph)[kPR + 1][4], const float (&
         if (a == 1) jacobi_pair_down(ph[a], ph[a - 1], ph[bphys<PR>(0, 1)], hlast, buf[jl & 1][1], buf[jl & 1][0]);
         else jacobi_pair_down(ph[a], ph[a - 1], ph[bphys<PR>(a - 1, 1)], ph[bphys<PR>(a - 2, 1)], buf[jl & 1][1], buf[jl & 1][0]);
       } else {
-        if (a == 1) jacobi_pair_down(ph[a], ph[a - 1], ph[bphys<PR>(0, 1)], hlast, rq[rq_reg(a)], rq[rq_reg(a - 1)]);
-        else jacobi_pair_down(ph[a], ph[a - 1], ph[bphys<PR>(a - 1, 1)], ph[bphys<PR>(a - 2, 1)], rq[rq_reg(a)], rq[rq_reg(a - 1)]);
+        if (a == 1) jacobi_pair_down(ph[a], ph[a - 1], ph[bphys<PR>(0, 1)], hlast, rq[a], rq[a - 1]);
+        else jacobi_pair_down(ph[a], ph[a - 1], ph[bphys<PR>(a - 1, 1)], ph[bphys<PR>(a - 2, 1)], rq[a], rq[a - 1]);
       }
     }
     jacobi_walls_state<PR, 0>(ph, E);
@@ -129,13 +127,6 @@ __global__ __launch_bounds__(kNT, 2) void ns256_fused_step(NSConst C, NSScal<flo
   const float a0 = act[0];
 
   float rq[kRR][4];
-#ifdef PDEGYM_NS256_TIMING      // developer build (tools/attic/timing_probe_ns256.py): s_memtime at the phase boundaries of every wave
-  unsigned long long tm[6];
-  tm[0] = __builtin_amdgcn_s_memtime();
-#define NS256_STAMP(i, dep) tm[i] = __builtin_amdgcn_s_memtime() + (unsigned long long)((dep) != (dep))
-#else
-#define NS256_STAMP(i, dep)
-#endif
 
   // ---- front: predictor -> apply_boundary(u*, v*) (:140) -> 0.25 dx dy rhs (:101-103, :108), a row pipeline ----
   // iteration `it` works on grid row r = r0 - 1 + it:  P(r) = predictor of row r;  F(r-1) = row r-1 after the boundary rule
@@ -229,7 +220,6 @@ __global__ __launch_bounds__(kNT, 2) void ns256_fused_step(NSConst C, NSScal<flo
     rows(kRR, kPR, kRR);
   }
 
-  NS256_STAMP(1, rq[0][0]);
   // ---- K Jacobi sweeps (:104-114): p in registers, period-two row rotation ----
   float ph[kPR + 1][4];
   {
@@ -242,7 +232,6 @@ __global__ __launch_bounds__(kNT, 2) void ns256_fused_step(NSConst C, NSScal<flo
 #pragma unroll
     for (int k = 0; k < 4; ++k) ph[kPR][k] = 0.f;
   }
-  NS256_STAMP(2, ph[0][0]);
   int xc = 0;
   {
     int it = 0;
@@ -263,7 +252,6 @@ __global__ __launch_bounds__(kNT, 2) void ns256_fused_step(NSConst C, NSScal<flo
       for (int k = 0; k < 4; ++k) ph[0][k] = t[k];
     }
   }
-  NS256_STAMP(3, ph[0][0]);
   {
     float* pd = (P.p_out ? P.p_out : P.p) + (size_t)b * kCells + (size_t)r0 * kN + c0;
 #pragma unroll
@@ -387,27 +375,8 @@ __global__ __launch_bounds__(kNT, 2) void ns256_fused_step(NSConst C, NSScal<flo
     // the block's last row: C(r0+31) is in c1; the wall rule of row 255 reads C(254) = c2
     finish_row(r0 + kPR - 1, c1u, c1v, rf[kPR % DF]);
   }
-  NS256_STAMP(4, acc);
-#ifdef PDEGYM_NS256_TIMING
-  if (lane == 0) {
-    unsigned int* dbg = reinterpret_cast<unsigned int*>(P.scratch + (size_t)b * 4 * kCells) + w * 8;
-    for (int i = 0; i < 4; ++i) dbg[i] = (unsigned int)(tm[i + 1] - tm[i]);
-    dbg[4] = (unsigned int)tm[0];
-    dbg[5] = (unsigned int)tm[4];
-  }
-#endif
   const float ss = block_sum<float>(acc, lds);     // the halo buffers are idle now (block_sum syncs first)
-  if (tid == 0) {
-    float asq = 0.f;
-    const float aref = P.action_ref[tr];
-    for (int k = 0; k < C.action_dim; ++k) {
-      const float d = act[k] - aref;
-      asq += d * d;
-    }
-    P.reward[b] = ((-0.5f * ss) / (float)kN) / (float)kN - S.gamma_half * asq;
-    P.time_index[b] = t_new;
-    P.terminated[b] = (t_new >= C.nt - 1) ? 1 : 0;      // navier_stokes2D.py:159-168
-  }
+  if (tid == 0) step_epilogue<float>(C, S, P, b, ss, act, t_new, tr, (float)kN, (float)kN);
 }
 
 // separate-field state layout: the observation just written is copied out into u and v

@@ -60,9 +60,6 @@ static_assert(kLdsBytes <= 160 * 1024, "LDS budget of one CU");
 
 enum : int { kPassFront = 1, kPassBack = 2 };
 
-__device__ __forceinline__ double shr_f64(double v) { return lane_left(v); }     // lane i <- lane i-1 (lane 0: 0, a domain-edge lane)
-__device__ __forceinline__ double shl_f64(double v) { return lane_right(v); }    // lane i <- lane i+1
-
 // LDS layout (round 5): a thread's four doubles are kept as TWO 16-byte halves in two PLANES (plane a: columns 0-1, plane b: columns
 // 2-3), each plane indexed by the thread id -- so every ds_read_b128 / ds_write_b128 is lane-contiguous (16-byte lane stride).  The
 // round-4 array-of-struct form (32 bytes per thread) put the 16-lane groups of a ds_read_b128 on each bank twice: SQ_LDS_BANK_CONFLICT
@@ -125,7 +122,7 @@ __device__ __forceinline__ void sweep4(double (&ph)[kPR + 1][4], const double (&
   };
   auto update = [&](double (&dst)[4], const double (&x)[4], const double (&sv)[4], const double (&nv)[4], const double (&q)[4])
       __attribute__((always_inline)) {
-    const double xl = shr_f64(x[3]), xr = shl_f64(x[0]);
+    const double xl = lane_left(x[3]), xr = lane_right(x[0]);
     double o[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -439,15 +436,7 @@ __global__ void ns256_finish_f64(NSConst C, NSScal<double> S, NSPtrs<double> P, 
   const int t = P.time_index[b] + 1;
   const int tr = t < C.nt_ref ? t : C.nt_ref - 1;
   const double* act = P.action + (size_t)b * C.action_dim;
-  double asq = 0.0;
-  const double aref = P.action_ref[tr];
-  for (int k = 0; k < C.action_dim; ++k) {
-    const double d = act[k] - aref;
-    asq += d * d;
-  }
-  P.reward[b] = ((-0.5 * ss) / (double)kN) / (double)kN - S.gamma_half * asq;
-  P.time_index[b] = t;
-  P.terminated[b] = (t >= C.nt - 1) ? 1 : 0;                               // navier_stokes2D.py:159-168
+  step_epilogue<double>(C, S, P, b, ss, act, t, tr, (double)kN, (double)kN);
 }
 
 // With separate u, v fields the state is read from them and the interleaved observation is the hand-over: a slab's back phase

@@ -11,21 +11,6 @@ namespace rows256 {
 
 constexpr int kN = 256;
 
-__device__ __forceinline__ double lane_left(double v) {       // lane i <- lane i-1 (lane 0: 0, a domain-edge lane)
-  const long long b = __builtin_bit_cast(long long, v);
-  const int lo = __builtin_amdgcn_update_dpp(0, (int)b, 0x138, 0xf, 0xf, true);
-  const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), 0x138, 0xf, 0xf, true);
-  return __builtin_bit_cast(double, ((long long)hi << 32) | (unsigned int)lo);
-}
-__device__ __forceinline__ double lane_right(double v) {      // lane i <- lane i+1
-  const long long b = __builtin_bit_cast(long long, v);
-  const int lo = __builtin_amdgcn_update_dpp(0, (int)b, 0x130, 0xf, 0xf, true);
-  const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), 0x130, 0xf, 0xf, true);
-  return __builtin_bit_cast(double, ((long long)hi << 32) | (unsigned int)lo);
-}
-using pdegym::ns::lane_left;
-using pdegym::ns::lane_right;
-
 // (u, v) of columns 4 lane .. 4 lane + 3 of grid row `row` (clamped: rows outside the grid only feed values nobody reads)
 template <bool INTERLEAVED, typename T>
 __device__ __forceinline__ void load_state_row(const T* su, const T* sv, int row, int c0, T (&fu)[4], T (&fv)[4]) {

@@ -347,16 +347,7 @@ __device__ __forceinline__ void gen_back(const NSConst& C, const NSScal<T>& S, c
   if (threadIdx.x == 0) {
     T ss = 0;
     for (int j = 0; j < nx; ++j) ss += part[j];
-    T asq = 0;
-    const T aref = P.action_ref[tr];
-    for (int k = 0; k < C.action_dim; ++k) {
-      const T d = act[k] - aref;
-      asq += d * d;
-    }
-    // - 1/2 * ||U - Uref||^2 / nx / ny - gamma/2 * ||a - aref||^2
-    P.reward[b] = (((T)-0.5 * ss) / (T)nx) / (T)ny - S.gamma_half * asq;
-    P.time_index[b] = t;
-    P.terminated[b] = (t >= C.nt - 1) ? 1 : 0;  // navier_stokes2D.py:159-168
+    step_epilogue<T>(C, S, P, b, ss, act, t, tr, (T)nx, (T)ny);
   }
 }
 
@@ -426,44 +417,15 @@ __device__ __forceinline__ void store_patch(const float (&f)[PR][PC], float* g, 
   for (int a = 0; a < PR; ++a) *reinterpret_cast<V*>(g + ((r0 + a) * n + c0)) = pack_row<PC>(f[a]);
 }
 
-// apply_boundary on a patch: the four ordered passes (lower, upper, left, right) only touch cells of edge
-// threads and only read the line next to the edge, which lives in the same patch -> no communication.
-template <int PR, int PC>
-__device__ __forceinline__ void apply_bc_patch(float (&f)[PR][PC], const EdgeFlags& E, const int (&bc)[4][2], int comp,
-                                               const float* act, int action_dim, int r0, int c0) {
-  auto aval = [&](int idx) -> float { return action_dim == 1 ? act[0] : act[idx]; };
-  if (E.top) {
-    const int c = bc[PDEGYM_EDGE_LOWER][comp];
-#pragma unroll
-    for (int b = 0; b < PC; ++b) f[0][b] = (c == PDEGYM_BC_NEUMANN) ? f[1][b] : ((c == PDEGYM_BC_DIRICHLET) ? 0.0f : aval(c0 + b));
-  }
-  if (E.bot) {
-    const int c = bc[PDEGYM_EDGE_UPPER][comp];
-#pragma unroll
-    for (int b = 0; b < PC; ++b)
-      f[PR - 1][b] = (c == PDEGYM_BC_NEUMANN) ? f[PR - 2][b] : ((c == PDEGYM_BC_DIRICHLET) ? 0.0f : aval(c0 + b));
-  }
-  if (E.lef) {
-    const int c = bc[PDEGYM_EDGE_LEFT][comp];
-#pragma unroll
-    for (int a = 0; a < PR; ++a) f[a][0] = (c == PDEGYM_BC_NEUMANN) ? f[a][1] : ((c == PDEGYM_BC_DIRICHLET) ? 0.0f : aval(r0 + a));
-  }
-  if (E.rig) {
-    const int c = bc[PDEGYM_EDGE_RIGHT][comp];
-#pragma unroll
-    for (int a = 0; a < PR; ++a)
-      f[a][PC - 1] = (c == PDEGYM_BC_NEUMANN) ? f[a][PC - 2] : ((c == PDEGYM_BC_DIRICHLET) ? 0.0f : aval(r0 + a));
-  }
-}
-
-// apply_boundary restricted to HR consecutive patch rows held in f (first_half: they start at patch row 0, last_half: they
-// end at patch row PR-1).  Same four ordered passes as apply_bc_patch: the lower / upper pass of the block's edge row
-// reads the neighbouring row of the same block (HR >= 2), the left / right passes are row-local, so running the passes
-// block by block gives the values of the whole-patch version.
+// apply_boundary on HR consecutive rows of a thread's patch, held in f: the four ordered passes (lower, upper, left, right) only
+// touch cells of edge threads and only read the line next to the edge, which lives in the same patch -> no communication.
+// first_half: the rows start at patch row 0, last_half: they end at patch row PR-1 (both: f is the whole patch).  The lower /
+// upper pass of the block's edge row reads the neighbouring row of the same block (HR >= 2), the left / right passes are
+// row-local, so running the passes block by block gives the values of the whole-patch call.
 template <int HR, int PC, typename T>
 __device__ __forceinline__ void apply_bc_rows(T (&f)[HR][PC], const EdgeFlags& E, const int (&bc)[4][2], int comp,
-                                              const T* act, int action_dim, int row0, int c0, bool first_half,
-                                              bool last_half) {
+                                              const T* act, int action_dim, int row0, int c0, bool first_half = true,
+                                              bool last_half = true) {
   static_assert(HR >= 2, "the edge row's neighbour must be in the block");
   auto aval = [&](int idx) -> T { return action_dim == 1 ? act[0] : act[idx]; };
   if (first_half && E.top) {
@@ -626,12 +588,6 @@ __device__ __forceinline__ void unrotate(const float (&ph)[PR + 1][PC], float (&
 }
 
 
-#ifndef PDEGYM_NS_F64_TILE_ROWS
-#define PDEGYM_NS_F64_TILE_ROWS 16
-#endif
-#ifndef PDEGYM_NS_BACK_ROWS
-#define PDEGYM_NS_BACK_ROWS 2
-#endif
 template <int PR, int PC, bool INTERLEAVED>
 __global__ __launch_bounds__(512, 4) void ns_tile_step(NSConst C, NSScal<float> S, NSPtrs<float> P, int B) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -649,13 +605,6 @@ __global__ __launch_bounds__(512, 4) void ns_tile_step(NSConst C, NSScal<float> 
   const float* act = P.action + (size_t)b * C.action_dim;
   const float* sin = INTERLEAVED ? P.state_in + (size_t)b * ncell * 2 : nullptr;
   int xc = 0;
-#ifdef PDEGYM_TIMING
-  unsigned long long tm[8];
-  tm[0] = __builtin_amdgcn_s_memtime();
-#define PDEGYM_STAMP(i, dep) tm[i] = __builtin_amdgcn_s_memtime() + (unsigned long long)((dep) != (dep))
-#else
-#define PDEGYM_STAMP(i, dep)
-#endif
 
   float rq[PR][PC];  // 0.25*dx*dy*rhs, kept for all sweeps
   // u* and v* wait on chip for the corrector: v* and two u* rows in registers (next to rq and p they fill 108 of the 128
@@ -727,10 +676,9 @@ __global__ __launch_bounds__(512, 4) void ns_tile_step(NSConst C, NSScal<float> 
         }
       }
     }
-    PDEGYM_STAMP(1, uf[0][0]);
     // ---- apply_boundary(u*, v*) (:140) ----
-    apply_bc_patch<PR, PC>(uf, E, C.bc, 0, act, C.action_dim, r0, c0);
-    apply_bc_patch<PR, PC>(vf, E, C.bc, 1, act, C.action_dim, r0, c0);
+    apply_bc_rows<PR, PC>(uf, E, C.bc, 0, act, C.action_dim, r0, c0);
+    apply_bc_rows<PR, PC>(vf, E, C.bc, 1, act, C.action_dim, r0, c0);
     {
       using V = typename VecOf<PC>::type;
       V* park = reinterpret_cast<V*>(smem_raw + TileCfg<PR, PC>::LDS_BYTES);
@@ -769,7 +717,6 @@ __global__ __launch_bounds__(512, 4) void ns_tile_step(NSConst C, NSScal<float> 
       }
     }
   }
-  PDEGYM_STAMP(2, rq[0][0]);
 
   // ---- K Jacobi sweeps (:104-114), p and rq in registers, rotating row map (no copies) ----
   float pf[PR][PC];
@@ -816,7 +763,6 @@ __global__ __launch_bounds__(512, 4) void ns_tile_step(NSConst C, NSScal<float> 
       unrotate<PR, PC, 0>(ph, pf, rot);
     }
   }
-  PDEGYM_STAMP(3, pf[0][0]);
   store_patch<PR, PC>(pf, P.p_out ? P.p_out + (size_t)b * ncell : p, n, r0, c0);
 
   // ---- corrector (:143-146), observation, reward ----
@@ -827,7 +773,7 @@ __global__ __launch_bounds__(512, 4) void ns_tile_step(NSConst C, NSScal<float> 
     // Blocks of HR rows: u*, v* and the reference rows of a block are fetched, corrected, bounded, written and reduced
     // before the next block's loads are issued -- the whole-patch form (64 + 32 more live registers next to pf) spilled the
     // freshly loaded rows to scratch memory and read them back (80 bytes per lane of extra HBM traffic each way).
-    constexpr int HR = PDEGYM_NS_BACK_ROWS, NBLK = PR / HR;
+    constexpr int HR = 2, NBLK = PR / HR;
     static_assert(PR % HR == 0, "row blocks must tile the patch");
     // thread coordinates re-derived from an opaque copy: kept from the top of the kernel, the patch offsets and edge flags are
     // live (spilled) across the predictor and the sweeps
@@ -900,31 +846,15 @@ __global__ __launch_bounds__(512, 4) void ns_tile_step(NSConst C, NSScal<float> 
       __builtin_amdgcn_sched_barrier(0);
     }
   }
-  PDEGYM_STAMP(4, acc);
   float* red = lds;   // halo buffers are idle now (block_sum syncs first)
   const float ss = block_sum<float>(acc, red);
-  if (tid == 0) {
-    float asq = 0.f;
-    const float aref = P.action_ref[tr];
-    for (int k = 0; k < C.action_dim; ++k) {
-      const float d = act[k] - aref;
-      asq += d * d;
-    }
-    P.reward[b] = ((-0.5f * ss) / (float)n) / (float)n - S.gamma_half * asq;
-    P.time_index[b] = t;
-    P.terminated[b] = (t >= C.nt - 1) ? 1 : 0;
-#ifdef PDEGYM_TIMING
-    tm[5] = __builtin_amdgcn_s_memtime();
-    unsigned int* dbg = reinterpret_cast<unsigned int*>(P.scratch + (size_t)b * 4 * ncell + 2 * ncell);   // the scratch is unused here
-    for (int i = 0; i < 5; ++i) dbg[i] = (unsigned int)(tm[i + 1] - tm[i]);
-#endif
-  }
+  if (tid == 0) step_epilogue<float>(C, S, P, b, ss, act, t, tr, (float)n, (float)n);
 }
 
 // ================================================================================================
 // float64 register-tiled step for 128x128 (the reference's own precision, BASELINE config 4 at float64): 1024 threads per
 // instance, one WAVE per thread row: lane tx of wave ty owns the 8 x 2 patch at rows 8 ty .. 8 ty + 7, columns 2 tx, 2 tx + 1.
-//   * left/right neighbours are the neighbouring lanes (two v_mov_b32_dpp per double);
+//   * left/right neighbours are the neighbouring lanes (lane_left / lane_right: two v_mov_b32_dpp per double);
 //   * top/bottom halo rows (2 doubles = 16 bytes per lane) cross waves through a double-buffered LDS area, one barrier per
 //     exchange;
 //   * p and dx dy rhs stay in registers for all K sweeps; the rows rotate with period two (UP / DOWN sweeps, see
@@ -932,93 +862,20 @@ __global__ __launch_bounds__(512, 4) void ns_tile_step(NSConst C, NSScal<float> 
 //   * every expression is the one of ns_generic_step<double> -- IEEE division included -- so the result is bit-identical to
 //     NumPy (tests: goldens N3, oracle at 128x128, equality with the generic kernel).
 // ================================================================================================
-__device__ __forceinline__ double dpp_shr_f64(double v) {       // lane i <- lane i-1 (lane 0: 0, a domain-edge lane)
-  const long long b = __builtin_bit_cast(long long, v);
-  const int lo = __builtin_amdgcn_update_dpp(0, (int)b, 0x138, 0xf, 0xf, true);
-  const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), 0x138, 0xf, 0xf, true);
-  return __builtin_bit_cast(double, ((long long)hi << 32) | (unsigned int)lo);
-}
-__device__ __forceinline__ double dpp_shl_f64(double v) {       // lane i <- lane i+1
-  const long long b = __builtin_bit_cast(long long, v);
-  const int lo = __builtin_amdgcn_update_dpp(0, (int)b, 0x130, 0xf, 0xf, true);
-  const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), 0x130, 0xf, 0xf, true);
-  return __builtin_bit_cast(double, ((long long)hi << 32) | (unsigned int)lo);
-}
-
-// top/bottom halo rows of a 2-wide double patch through LDS (waves are thread rows: RS = 64); NT threads per workgroup
-template <int NT>
-__device__ __forceinline__ void halo_tb_f64(const double (&top)[2], const double (&bot)[2], double (&ht)[2], double (&hb)[2], double* lds,
-                                            int& xc, int tid, int ty) {
-  constexpr int RS = 64;
-  double2* base = reinterpret_cast<double2*>(lds) + (xc & 1) * (2 * NT);
-  ++xc;
-  double2* eT = base;
-  double2* eB = base + NT;
-  eT[tid] = make_double2(top[0], top[1]);
-  eB[tid] = make_double2(bot[0], bot[1]);
-  __syncthreads();
-  const int up = (ty > 0) ? tid - RS : tid, dn = (ty < NT / RS - 1) ? tid + RS : tid;
-  const double2 a = eB[up], b = eT[dn];
-  ht[0] = a.x; ht[1] = a.y;
-  hb[0] = b.x; hb[1] = b.y;
-}
-
-template <int PR>
-__device__ __forceinline__ void apply_bc_patch_f64(double (&f)[PR][2], const EdgeFlags& E, const int (&bc)[4][2], int comp,
-                                                   const double* act, int action_dim, int r0, int c0) {
-  auto aval = [&](int idx) -> double { return action_dim == 1 ? act[0] : act[idx]; };
-  if (E.top) {
-    const int c = bc[PDEGYM_EDGE_LOWER][comp];
-#pragma unroll
-    for (int b = 0; b < 2; ++b) f[0][b] = (c == PDEGYM_BC_NEUMANN) ? f[1][b] : ((c == PDEGYM_BC_DIRICHLET) ? 0.0 : aval(c0 + b));
-  }
-  if (E.bot) {
-    const int c = bc[PDEGYM_EDGE_UPPER][comp];
-#pragma unroll
-    for (int b = 0; b < 2; ++b) f[PR - 1][b] = (c == PDEGYM_BC_NEUMANN) ? f[PR - 2][b] : ((c == PDEGYM_BC_DIRICHLET) ? 0.0 : aval(c0 + b));
-  }
-  if (E.lef) {
-    const int c = bc[PDEGYM_EDGE_LEFT][comp];
-#pragma unroll
-    for (int a = 0; a < PR; ++a) f[a][0] = (c == PDEGYM_BC_NEUMANN) ? f[a][1] : ((c == PDEGYM_BC_DIRICHLET) ? 0.0 : aval(r0 + a));
-  }
-  if (E.rig) {
-    const int c = bc[PDEGYM_EDGE_RIGHT][comp];
-#pragma unroll
-    for (int a = 0; a < PR; ++a) f[a][1] = (c == PDEGYM_BC_NEUMANN) ? f[a][0] : ((c == PDEGYM_BC_DIRICHLET) ? 0.0 : aval(r0 + a));
-  }
-}
-
-// Neumann pressure walls on the new rows in state ST (see bphys)
-template <int PR, int ST>
-__device__ __forceinline__ void jacobi_walls_f64(double (&ph)[PR + 1][2], const EdgeFlags& E) {
-  constexpr int n0 = bphys<PR>(0, ST), n1 = bphys<PR>(1, ST), nl = bphys<PR>(PR - 1, ST), nm = bphys<PR>(PR - 2, ST);
-  if (E.top) { ph[n0][0] = ph[n1][0]; ph[n0][1] = ph[n1][1]; }
-  if (E.bot) { ph[nl][0] = ph[nm][0]; ph[nl][1] = ph[nm][1]; }
-  if (E.lef) {
-#pragma unroll
-    for (int a = 0; a < PR; ++a) ph[bphys<PR>(a, ST)][0] = ph[bphys<PR>(a, ST)][1];
-  }
-  if (E.rig) {
-#pragma unroll
-    for (int a = 0; a < PR; ++a) ph[bphys<PR>(a, ST)][1] = ph[bphys<PR>(a, ST)][0];
-  }
-}
-
 // one float64 Jacobi sweep from state ST (0: UP, rows 0 -> PR-1, 1: DOWN); 1/4 (((W + S) + E) + N - dx dy rhs) (:106-108)
 template <int PR, int ST>
 __device__ __forceinline__ void jacobi_sweep_f64(double (&ph)[PR + 1][2], const double (&rq)[PR][2], const EdgeFlags& E, double* lds,
                                                  int& xc, int tid, int ty) {
   double hlast[2];
   auto update = [&](double (&dst)[2], const double (&x)[2], const double (&sv)[2], const double (&nv)[2], const double (&q)[2]) {
-    const double xl = dpp_shr_f64(x[1]), xr = dpp_shl_f64(x[0]);
+    const double xl = lane_left(x[1]), xr = lane_right(x[0]);
     const double s0 = ((xl + sv[0]) + x[1]) + nv[0];
     const double s1 = ((x[0] + sv[1]) + xr) + nv[1];
     dst[0] = 0.25 * (s0 - q[0]);
     dst[1] = 0.25 * (s1 - q[1]);
   };
   if constexpr (ST == 0) {
-    halo_tb_f64<64 * (128 / PR)>(ph[0], ph[PR - 1], ph[PR], hlast, lds, xc, tid, ty);            // top halo -> free row PR
+    halo_tb<2, 64 * (128 / PR), 64>(ph[0], ph[PR - 1], ph[PR], hlast, lds, xc, tid, ty);            // top halo -> free row PR
 #pragma unroll
     for (int a = 0; a < PR; ++a) {
       // new row a overwrites old row a-1 (its South neighbour, dead afterwards); dst may alias sv: all reads come first
@@ -1028,9 +885,9 @@ __device__ __forceinline__ void jacobi_sweep_f64(double (&ph)[PR + 1][2], const 
       ph[a == 0 ? PR : a - 1][0] = out[0];
       ph[a == 0 ? PR : a - 1][1] = out[1];
     }
-    jacobi_walls_f64<PR, 1>(ph, E);
+    jacobi_walls_state<PR, 1>(ph, E);
   } else {
-    halo_tb_f64<64 * (128 / PR)>(ph[bphys<PR>(0, 1)], ph[bphys<PR>(PR - 1, 1)], hlast, ph[PR - 1], lds, xc, tid, ty);   // bottom halo -> free row PR-1
+    halo_tb<2, 64 * (128 / PR), 64>(ph[bphys<PR>(0, 1)], ph[bphys<PR>(PR - 1, 1)], hlast, ph[PR - 1], lds, xc, tid, ty);   // bottom halo -> free row PR-1
 #pragma unroll
     for (int a = PR - 1; a >= 0; --a) {
       double out[2];
@@ -1039,27 +896,25 @@ __device__ __forceinline__ void jacobi_sweep_f64(double (&ph)[PR + 1][2], const 
       ph[a][0] = out[0];
       ph[a][1] = out[1];
     }
-    jacobi_walls_f64<PR, 0>(ph, E);
+    jacobi_walls_state<PR, 0>(ph, E);
   }
 }
 
-// Two shapes.  PR = 8: 16 waves of 8 rows, 128 registers per lane, five u* rows wait in LDS, the others and v* in the caller's
-// scratch (round 2).  PR = 16 (round 3): 8 waves of 16 rows, 256 registers per lane -- float64 issues at a quarter of the
-// float32 rate, two waves per SIMD keep the pipe as busy as four -- and nothing is parked in memory: ALL u* rows wait in LDS
-// (128 KB next to 32 KB of halo buffers), ALL v* rows in registers: HBM traffic 753 -> ~430 MB per 512 env-steps.
-template <int PR>
+// The shape (round 3): 8 waves of 16 rows, 256 registers per lane -- float64 issues at a quarter of the float32 rate, two waves per
+// SIMD keep the pipe as busy as four -- and nothing is parked in memory: ALL u* rows wait in LDS (128 KB next to 32 KB of halo
+// buffers), ALL v* rows in registers.
 struct F64Tile {
+  static constexpr int PR = 16;                                 // grid rows per wave
   static constexpr int NW = 128 / PR, NT = 64 * NW;
   static constexpr int HALO_BYTES = 2 * 2 * NT * 16;            // two buffers x (top, bottom) x one double2 per thread
-  static constexpr int PARK_ROWS = PR == 16 ? 16 : 5;           // u* rows in LDS (16 bytes per thread and row)
-  static constexpr bool V_IN_REGS = PR == 16;
-  static constexpr int LDS_BYTES = HALO_BYTES + PARK_ROWS * NT * 16;
+  static constexpr int LDS_BYTES = HALO_BYTES + PR * NT * 16;   // + every u* row (16 bytes per thread and row)
   static_assert(LDS_BYTES <= 160 * 1024, "LDS budget of one CU");
 };
 template <bool INTERLEAVED, int PR>
-__global__ __launch_bounds__(64 * (128 / PR), PR == 16 ? 2 : 4) void ns_tile_step_f64(NSConst C, NSScal<double> S, NSPtrs<double> P, int B) {
-  using Cfg = F64Tile<PR>;
-  constexpr int kF64HaloBytes = Cfg::HALO_BYTES, kF64ParkRows = Cfg::PARK_ROWS, NT = Cfg::NT;
+__global__ __launch_bounds__(F64Tile::NT, 2) void ns_tile_step_f64(NSConst C, NSScal<double> S, NSPtrs<double> P, int B) {
+  static_assert(PR == F64Tile::PR, "one shape");
+  using Cfg = F64Tile;
+  constexpr int kF64HaloBytes = Cfg::HALO_BYTES, NT = Cfg::NT;
   constexpr int n = 128, ncell = n * n;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   double* lds = reinterpret_cast<double*>(smem_raw);
@@ -1073,16 +928,13 @@ __global__ __launch_bounds__(64 * (128 / PR), PR == 16 ? 2 : 4) void ns_tile_ste
   double* v = INTERLEAVED ? nullptr : P.v + (size_t)b * ncell;
   const double* p = P.p + (size_t)b * ncell;
   double* pout = (P.p_out ? P.p_out : P.p) + (size_t)b * ncell;
-  double* us = P.scratch + (size_t)b * 4 * ncell;
-  double* vs = us + ncell;
   const double* act = P.action + (size_t)b * C.action_dim;
   const double* sin = INTERLEAVED ? P.state_in + (size_t)b * ncell * 2 : nullptr;
   int xc = 0;
   auto edge_cell = [&](int a, int k) { return (a == 0 && E.top) || (a == PR - 1 && E.bot) || (k == 0 && E.lef) || (k == 1 && E.rig); };
 
   double rq[PR][2];     // dx dy rhs, kept for all sweeps
-  double keep_v[Cfg::V_IN_REGS ? PR : 1][2];    // PR = 16: v* waits here for the corrector phase
-  (void)keep_v;
+  double keep_v[PR][2]; // v* waits here for the corrector phase
   {
     auto load_row = [&](int grow, double (&ru)[2], double (&rv)[2]) {
       if constexpr (INTERLEAVED) {
@@ -1096,8 +948,8 @@ __global__ __launch_bounds__(64 * (128 / PR), PR == 16 ? 2 : 4) void ns_tile_ste
       }
     };
     // ---- predictor (:130-138), apply_boundary(u*, v*) (:140), rhs (:101-103, :108) as a ROW PIPELINE ----
-    // Iteration a: load the old row a+1, predict row a, finalise row a-1 (boundary rule), store it (u* partly in LDS, v* in the
-    // caller's scratch) and form dx dy rhs of row a-2, whose stencil reaches the finalised rows a-3 ... a-1.  A row's values
+    // Iteration a: load the old row a+1, predict row a, finalise row a-1 (boundary rule), keep it (u* in LDS, v* in
+    // registers) and form dx dy rhs of row a-2, whose stencil reaches the finalised rows a-3 ... a-1.  A row's values
     // are dead two iterations after they are made, so next to rq only a five-row window is live -- with the whole patch of
     // u, v, u*, v* in flight around the division-heavy stencil the compiler spilled ~190 bytes per lane to scratch memory
     // (HBM traffic both ways).  The old rows just above / below the patch come straight from the state in global memory (the
@@ -1136,17 +988,12 @@ __global__ __launch_bounds__(64 * (128 / PR), PR == 16 ? 2 : 4) void ns_tile_ste
           fin[i][0] = t0;
           fin[i][1] = t1;
         }
-        if (i < kF64ParkRows) park[i * NT + tid] = make_double2(fin_u[i][0], fin_u[i][1]);
-        else *reinterpret_cast<double2*>(us + (r0 + i) * n + c0) = make_double2(fin_u[i][0], fin_u[i][1]);
-        if constexpr (Cfg::V_IN_REGS) {
-          keep_v[i][0] = fin_v[i][0];
-          keep_v[i][1] = fin_v[i][1];
-        } else {
-          *reinterpret_cast<double2*>(vs + (r0 + i) * n + c0) = make_double2(fin_v[i][0], fin_v[i][1]);
-        }
+        park[i * NT + tid] = make_double2(fin_u[i][0], fin_u[i][1]);
+        keep_v[i][0] = fin_v[i][0];
+        keep_v[i][1] = fin_v[i][1];
       };
       auto rhs_row = [&](int i, const double (&vbelow)[2], const double (&vabove)[2]) {
-        const double ul = dpp_shr_f64(fin_u[i][1]), ur = dpp_shl_f64(fin_u[i][0]);
+        const double ul = lane_left(fin_u[i][1]), ur = lane_right(fin_u[i][0]);
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
           const double uw = (k == 0) ? ul : fin_u[i][0], ue = (k == 1) ? ur : fin_u[i][1];
@@ -1163,7 +1010,7 @@ __global__ __launch_bounds__(64 * (128 / PR), PR == 16 ? 2 : 4) void ns_tile_ste
         load_row((a == PR - 1 && E.bot) ? r0 + PR - 1 : r0 + a + 1, old_n[0], old_n[1]);
         {
           const double (&cu)[2] = old_c[0], (&cv)[2] = old_c[1];
-          const double ul = dpp_shr_f64(cu[1]), ur = dpp_shl_f64(cu[0]), vl = dpp_shr_f64(cv[1]), vr = dpp_shl_f64(cv[0]);
+          const double ul = lane_left(cu[1]), ur = lane_right(cu[0]), vl = lane_left(cv[1]), vr = lane_right(cv[0]);
 #pragma unroll
           for (int k = 0; k < 2; ++k) {
             const double uc = cu[k], vc = cv[k];
@@ -1192,7 +1039,7 @@ __global__ __launch_bounds__(64 * (128 / PR), PR == 16 ? 2 : 4) void ns_tile_ste
       finalise(PR - 1);
       rhs_row(PR - 2, fin_v[PR - 3], fin_v[PR - 1]);
       double vt[2], vb[2];
-      halo_tb_f64<NT>(fin_v[0], fin_v[PR - 1], vt, vb, lds, xc, tid, ty);
+      halo_tb<2, NT, 64>(fin_v[0], fin_v[PR - 1], vt, vb, lds, xc, tid, ty);
       rhs_row(0, vt, fin_v[1]);
       rhs_row(PR - 1, fin_v[PR - 2], vb);
     }
@@ -1234,7 +1081,7 @@ __global__ __launch_bounds__(64 * (128 / PR), PR == 16 ? 2 : 4) void ns_tile_ste
     // loads are issued: see ns_tile_step -- the whole-patch form spilled 268 bytes per lane
     constexpr int HR = 2, NBLK = PR / HR;
     double pt[2], pb[2];
-    halo_tb_f64<NT>(pf[0], pf[PR - 1], pt, pb, lds, xc, tid, ty);
+    halo_tb<2, NT, 64>(pf[0], pf[PR - 1], pt, pb, lds, xc, tid, ty);
     const double* uref = P.U_ref + (size_t)tr * ncell * 2;
     double* obs = P.obs + (size_t)b * ncell * 2;
 #pragma unroll
@@ -1243,22 +1090,15 @@ __global__ __launch_bounds__(64 * (128 / PR), PR == 16 ? 2 : 4) void ns_tile_ste
       double uf[HR][2], vf[HR][2];
 #pragma unroll
       for (int la = 0; la < HR; ++la) {
-        const double2 wu = (a0 + la < kF64ParkRows)
-                               ? reinterpret_cast<const double2*>(smem_raw + kF64HaloBytes)[(a0 + la) * NT + tid]
-                               : *reinterpret_cast<const double2*>(us + (r0 + a0 + la) * n + c0);   // written by this same thread above
+        const double2 wu = reinterpret_cast<const double2*>(smem_raw + kF64HaloBytes)[(a0 + la) * NT + tid];   // written by this same thread above
         uf[la][0] = wu.x; uf[la][1] = wu.y;
-        if constexpr (Cfg::V_IN_REGS) {
-          vf[la][0] = keep_v[a0 + la][0];
-          vf[la][1] = keep_v[a0 + la][1];
-        } else {
-          const double2 wv = *reinterpret_cast<const double2*>(vs + (r0 + a0 + la) * n + c0);
-          vf[la][0] = wv.x; vf[la][1] = wv.y;
-        }
+        vf[la][0] = keep_v[a0 + la][0];
+        vf[la][1] = keep_v[a0 + la][1];
       }
 #pragma unroll
       for (int la = 0; la < HR; ++la) {
         const int a = a0 + la;
-        const double pl = dpp_shr_f64(pf[a][1]), pr = dpp_shl_f64(pf[a][0]);
+        const double pl = lane_left(pf[a][1]), pr = lane_right(pf[a][0]);
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
           const double pw = (k == 0) ? pl : pf[a][0], pe = (k == 1) ? pr : pf[a][1];
@@ -1295,17 +1135,7 @@ __global__ __launch_bounds__(64 * (128 / PR), PR == 16 ? 2 : 4) void ns_tile_ste
     }
   }
   const double ss = block_sum<double>(acc, lds);
-  if (tid == 0) {
-    double asq = 0.0;
-    const double aref = P.action_ref[tr];
-    for (int k = 0; k < C.action_dim; ++k) {
-      const double d = act[k] - aref;
-      asq += d * d;
-    }
-    P.reward[b] = ((-0.5 * ss) / (double)n) / (double)n - S.gamma_half * asq;
-    P.time_index[b] = t;
-    P.terminated[b] = (t >= C.nt - 1) ? 1 : 0;
-  }
+  if (tid == 0) step_epilogue<double>(C, S, P, b, ss, act, t, tr, (double)n, (double)n);
 }
 
 // ================================================================================================
@@ -1322,22 +1152,18 @@ __global__ __launch_bounds__(64 * (128 / PR), PR == 16 ? 2 : 4) void ns_tile_ste
 // of the reference and the generic kernel); the reward is summed per column then over the instance's lanes in order -- the
 // canonical order that gen_back follows too, so rewards are the same bits on either kernel.
 // ================================================================================================
-__device__ __forceinline__ float lane_from_left(float v) { return lane_left(v); }
-__device__ __forceinline__ float lane_from_right(float v) { return lane_right(v); }
-__device__ __forceinline__ double lane_from_left(double v) { return dpp_shr_f64(v); }
-__device__ __forceinline__ double lane_from_right(double v) { return dpp_shl_f64(v); }
 // A lane shift must execute with every lane of the wave active: when its only use is a per-lane select (edge lanes keep
 // their value, the lanes next to a wall substitute their own), the compiler may fold the shift into the selecting lanes'
 // branch, and a DPP read from a lane that is masked off returns 0.  The empty asm pins the shift where it is written.
 template <typename T>
 __device__ __forceinline__ T pinned_from_left(T v) {
-  T r = lane_from_left(v);
+  T r = lane_left(v);
   asm volatile("" : "+v"(r));
   return r;
 }
 template <typename T>
 __device__ __forceinline__ T pinned_from_right(T v) {
-  T r = lane_from_right(v);
+  T r = lane_right(v);
   asm volatile("" : "+v"(r));
   return r;
 }
@@ -1563,15 +1389,7 @@ __device__ __forceinline__ void ns_col_body(const NSConst& C, const NSScal<T>& S
   if (live && j == 0) {
     T ss = 0;
     for (int k = 0; k < nx; ++k) ss += red[lane + k];
-    T asq = 0;
-    const T aref = P.action_ref[tr];
-    for (int k = 0; k < C.action_dim; ++k) {
-      const T d = act[k] - aref;
-      asq += d * d;
-    }
-    P.reward[b] = (((T)-0.5 * ss) / (T)nx) / (T)NY - S.gamma_half * asq;
-    P.time_index[b] = t;
-    P.terminated[b] = (t >= C.nt - 1) ? 1 : 0;
+    step_epilogue<T>(C, S, P, b, ss, act, t, tr, (T)nx, (T)NY);
   }
 }
 
@@ -1666,6 +1484,8 @@ __global__ __launch_bounds__(64, (sizeof(T) == 8 || NY > 21 ? 2 : 3)) void ns_co
 // float64 a lone instance finishes sooner on the workgroup-per-instance kernel (seven waves per instance; 0.77 vs 0.98 ms per
 // env-step at 21 x 21, K = 2000), so batches below a minimum (PDEGYM_DEBUG_NS_COL_MIN_BATCH overrides it; default: 400 for float64 -- round 4, tools/attic/probe_ns_col_min_batch.py: column kernel 0.87 ms flat up to 3072 instances, workgroup kernel 0.80 ms at 256, 0.96 at 512, 1.30 at 768 -- and 1 for float32, where
 // the two kernels are equal at B = 1) stay there.
+#define PDEGYM_NS_COL_HEIGHTS(X) X(8) X(11) X(16) X(21) X(26) X(31) X(32)
+
 template <typename T>
 bool launch_ns_col(const NSConst& C, const NSScal<T>& S, const NSPtrs<T>& P, int B, hipStream_t st) {
   if (C.nx < 3 || C.nx > 64) return false;
@@ -1679,24 +1499,20 @@ bool launch_ns_col(const NSConst& C, const NSScal<T>& S, const NSPtrs<T>& P, int
   const dim3 grid((B + G - 1) / G), block(64);
   if constexpr (sizeof(T) == 8) {
     if ((int)grid.x <= simds) {  // at most one wave per SIMD anyway: the build without spills (ns_col_step_w1)
+#define PDEGYM_LAUNCH(NY) case NY: hipLaunchKernelGGL((ns_col_step_w1<T, NY>), grid, block, 0, st, C, S, P, B); return true;
       switch (C.ny) {
-        case 16: hipLaunchKernelGGL((ns_col_step_w1<T, 16>), grid, block, 0, st, C, S, P, B); return true;
-        case 21: hipLaunchKernelGGL((ns_col_step_w1<T, 21>), grid, block, 0, st, C, S, P, B); return true;
-        case 26: hipLaunchKernelGGL((ns_col_step_w1<T, 26>), grid, block, 0, st, C, S, P, B); return true;
+        PDEGYM_LAUNCH(16) PDEGYM_LAUNCH(21) PDEGYM_LAUNCH(26)
         default: break;          // 8 / 11 rows do not spill either way; 31 / 32 rows spill either way
       }
+#undef PDEGYM_LAUNCH
     }
   }
+#define PDEGYM_LAUNCH(NY) case NY: hipLaunchKernelGGL((ns_col_step<T, NY>), grid, block, 0, st, C, S, P, B); return true;
   switch (C.ny) {
-    case 8: hipLaunchKernelGGL((ns_col_step<T, 8>), grid, block, 0, st, C, S, P, B); return true;
-    case 11: hipLaunchKernelGGL((ns_col_step<T, 11>), grid, block, 0, st, C, S, P, B); return true;
-    case 16: hipLaunchKernelGGL((ns_col_step<T, 16>), grid, block, 0, st, C, S, P, B); return true;
-    case 21: hipLaunchKernelGGL((ns_col_step<T, 21>), grid, block, 0, st, C, S, P, B); return true;
-    case 26: hipLaunchKernelGGL((ns_col_step<T, 26>), grid, block, 0, st, C, S, P, B); return true;
-    case 31: hipLaunchKernelGGL((ns_col_step<T, 31>), grid, block, 0, st, C, S, P, B); return true;
-    case 32: hipLaunchKernelGGL((ns_col_step<T, 32>), grid, block, 0, st, C, S, P, B); return true;
+    PDEGYM_NS_COL_HEIGHTS(PDEGYM_LAUNCH)
     default: return false;
   }
+#undef PDEGYM_LAUNCH
 }
 
 template <typename T>
@@ -1705,16 +1521,12 @@ bool launch_ns_col_rollout(const NSConst& C, const NSScal<T>& S, const NSPtrs<T>
   if (C.nx < 3 || C.nx > 64) return false;
   const int G = 64 / C.nx;
   const dim3 grid((B + G - 1) / G), block(64);
+#define PDEGYM_LAUNCH(NY) case NY: hipLaunchKernelGGL((ns_col_rollout<T, NY>), grid, block, 0, st, C, S, P, Ro, R, B); return true;
   switch (C.ny) {
-    case 8: hipLaunchKernelGGL((ns_col_rollout<T, 8>), grid, block, 0, st, C, S, P, Ro, R, B); return true;
-    case 11: hipLaunchKernelGGL((ns_col_rollout<T, 11>), grid, block, 0, st, C, S, P, Ro, R, B); return true;
-    case 16: hipLaunchKernelGGL((ns_col_rollout<T, 16>), grid, block, 0, st, C, S, P, Ro, R, B); return true;
-    case 21: hipLaunchKernelGGL((ns_col_rollout<T, 21>), grid, block, 0, st, C, S, P, Ro, R, B); return true;
-    case 26: hipLaunchKernelGGL((ns_col_rollout<T, 26>), grid, block, 0, st, C, S, P, Ro, R, B); return true;
-    case 31: hipLaunchKernelGGL((ns_col_rollout<T, 31>), grid, block, 0, st, C, S, P, Ro, R, B); return true;
-    case 32: hipLaunchKernelGGL((ns_col_rollout<T, 32>), grid, block, 0, st, C, S, P, Ro, R, B); return true;
+    PDEGYM_NS_COL_HEIGHTS(PDEGYM_LAUNCH)
     default: return false;
   }
+#undef PDEGYM_LAUNCH
 }
 
 template <typename T, int LDSJ>
@@ -1830,7 +1642,6 @@ int fill(const pdegym_params_ns2d* prm, NSConst& C, NSScal<T>& S) {
   return 0;
 }
 
-// LDS-resident Jacobi: every thread owns at most kLdsCPT cells
 // LDS-resident Jacobi: every thread owns at most kLdsCPT cells.  A lone wave issues an instruction only every ~6.5 cycles,
 // so when the batch leaves CUs idle anyway (B <= 512: at most two workgroups per CU) one thread per cell (up to 512) cuts the
 // per-sweep latency (21x21, K = 2000, B = 1: 1.06 -> 0.74 ms per env-step); big batches keep the 4-cells-per-thread shape,
@@ -1861,31 +1672,104 @@ inline int block_threads(int ncell) {
   return 256;
 }
 
+// How ns_generic_step / ns_generic_pressure run a grid: Jacobi mode (the kernels' LDSJ), workgroup size, bytes of LDS for the sweeps
+struct GenericShape {
+  int mode, threads;
+  size_t jacobi_bytes;
+};
 template <typename T>
-int ns_step_launch(const pdegym_params_ns2d* prm, const pdegym_bufs_ns2d* buf, int B, void* stream);
-
-template <typename T>
-int ns_step(const pdegym_params_ns2d* prm, const pdegym_bufs_ns2d* buf, int B, void* stream) {
-  if (int rc = ns_step_launch<T>(prm, buf, B, stream)) return rc;
-  if (B <= 0 || !buf->reset_u0) return 0;
-  if (!buf->reset_v0 || !buf->reset_p0) return pdegym::fail(-3, "reset_u0 needs reset_v0 and reset_p0");
-  NSConst C;
-  NSScal<T> S;
-  if (int rc = fill<T>(prm, C, S)) return rc;
-  NSPtrs<T> P{(T*)buf->u, (T*)buf->v, (T*)buf->p, (T*)buf->scratch, (const T*)buf->action, buf->time_index,
-              (const T*)buf->U_ref, (const T*)buf->action_ref, (T*)buf->obs, (T*)buf->reward, buf->terminated,
-              (const T*)buf->state_in, (T*)buf->p_out};
-  NSAutoReset<T> R{(const T*)buf->reset_u0, (const T*)buf->reset_v0, (const T*)buf->reset_p0, (T*)buf->final_obs, buf->reset_count,
-                   buf->reset_pool_rows};
-  const int ncell = C.nx * C.ny;
-  const int gx = (ncell + 255) / 256 > 64 ? 64 : (ncell + 255) / 256;
-  hipLaunchKernelGGL(ns_auto_reset_kernel<T>, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, C, P, R, B);
-  hipLaunchKernelGGL(ns_auto_reset_finish<T>, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, P, R, B);
-  return pdegym::check_launch("ns2d_auto_reset");
+inline GenericShape generic_shape(int ncell, int B) {
+  const int mode = lds_jacobi_mode<T>(ncell);
+  if (mode == 1) return {1, lds_block_threads(ncell, B), 2 * (size_t)ncell * sizeof(T)};
+  if (mode == 2) return {2, 1024, (size_t)ncell * sizeof(T)};
+  return {0, block_threads(ncell), 0};
 }
 
 template <typename T>
-int ns_step_launch(const pdegym_params_ns2d* prm, const pdegym_bufs_ns2d* buf, int B, void* stream) {
+NSPtrs<T> make_ptrs(const pdegym_bufs_ns2d* buf) {
+  return {(T*)buf->u, (T*)buf->v, (T*)buf->p, (T*)buf->scratch, (const T*)buf->action, buf->time_index,
+          (const T*)buf->U_ref, (const T*)buf->action_ref, (T*)buf->obs, (T*)buf->reward, buf->terminated,
+          (const T*)buf->state_in, (T*)buf->p_out};
+}
+
+template <typename T>
+NSAutoReset<T> make_auto_reset(const pdegym_bufs_ns2d* buf) {
+  return {(const T*)buf->reset_u0, (const T*)buf->reset_v0, (const T*)buf->reset_p0, (T*)buf->final_obs, buf->reset_count,
+          buf->reset_pool_rows};
+}
+
+// picks and launches the kernel(s) of one env-step
+template <typename T>
+int ns_step_launch(const NSConst& C, const NSScal<T>& S, const NSPtrs<T>& P, int B, hipStream_t stream) {
+  // small grids: one lane per column, up to three instances per wave, no barriers (ns_col_step)
+  if (!pdegym_force_generic() && !pdegym_ns_no_col() && launch_ns_col<T>(C, S, P, B, stream))
+    return pdegym::check_launch("ns2d_col_step");
+  // state_in given -> the velocity state is the previous observation and u, v are not written (if the caller
+  // also passed u, v they are simply left untouched)
+  const bool inter = P.state_in != nullptr;
+  if constexpr (sizeof(T) == 4) {
+    // register-tiled float32 path for the square grids it is instantiated for (BASELINE config 4 is 128x128)
+    if (!pdegym_force_generic() && C.nx == C.ny && (C.nx == 128 || C.nx == 64)) {
+      constexpr int lds128 = TileCfg<8, 4>::LDS_BYTES + TileCfg<8, 4>::PARK_BYTES, lds64 = TileCfg<4, 2>::LDS_BYTES;
+      if (C.nx == 128) {   // 80 KB of dynamic LDS: above the 64 KB a kernel gets without asking
+        static signed char attr_i[pdegym::kMaxDevices] = {}, attr_s[pdegym::kMaxDevices] = {};
+        const bool ok = inter
+            ? pdegym::raise_dynamic_lds_limit(reinterpret_cast<const void*>(&ns_tile_step<8, 4, true>), lds128, attr_i)
+            : pdegym::raise_dynamic_lds_limit(reinterpret_cast<const void*>(&ns_tile_step<8, 4, false>), lds128, attr_s);
+        if (!ok) return pdegym::fail(-4, "cannot raise the dynamic LDS limit of ns_tile_step");
+      }
+      if (C.nx == 128 && inter)
+        hipLaunchKernelGGL((ns_tile_step<8, 4, true>), dim3(B), dim3(512), lds128, stream, C, S, P, B);
+      else if (C.nx == 128)
+        hipLaunchKernelGGL((ns_tile_step<8, 4, false>), dim3(B), dim3(512), lds128, stream, C, S, P, B);
+      else if (inter)
+        hipLaunchKernelGGL((ns_tile_step<4, 2, true>), dim3(B), dim3(512), lds64, stream, C, S, P, B);
+      else
+        hipLaunchKernelGGL((ns_tile_step<4, 2, false>), dim3(B), dim3(512), lds64, stream, C, S, P, B);
+      return pdegym::check_launch("ns2d_tile_step");
+    }
+  }
+  if constexpr (sizeof(T) == 8) {
+    // register-tiled float64 path for 128x128 (BASELINE config 4 at the reference's own precision)
+    if (!pdegym_force_generic() && C.nx == 128 && C.ny == 128) {
+      constexpr int PR = F64Tile::PR, lds_bytes = F64Tile::LDS_BYTES, nt = F64Tile::NT;
+      static signed char attr_a[pdegym::kMaxDevices] = {}, attr_b[pdegym::kMaxDevices] = {};
+      if (inter) {
+        if (!pdegym::raise_dynamic_lds_limit(reinterpret_cast<const void*>(&ns_tile_step_f64<true, PR>), lds_bytes, attr_a))
+          return pdegym::fail(-4, "cannot raise the dynamic LDS limit");
+        hipLaunchKernelGGL((ns_tile_step_f64<true, PR>), dim3(B), dim3(nt), lds_bytes, stream, C, S, P, B);
+      } else {
+        if (!pdegym::raise_dynamic_lds_limit(reinterpret_cast<const void*>(&ns_tile_step_f64<false, PR>), lds_bytes, attr_b))
+          return pdegym::fail(-4, "cannot raise the dynamic LDS limit");
+        hipLaunchKernelGGL((ns_tile_step_f64<false, PR>), dim3(B), dim3(nt), lds_bytes, stream, C, S, P, B);
+      }
+      return pdegym::check_launch("ns2d_tile_step_f64");
+    }
+  }
+  if constexpr (sizeof(T) == 8) {
+    // 256x256 float64 (BASELINE config 5 at the reference's precision): pdegym_ns256_f64.hip
+    if (!pdegym_force_generic() && C.nx == 256 && C.ny == 256) return launch_ns256_step_f64(C, S, P, B, stream);
+  }
+  if constexpr (sizeof(T) == 4) {
+    // 256x256 float32 (BASELINE config 5): the whole env-step in one launch, one workgroup per instance (pdegym_ns256.hip)
+    if (!pdegym_force_generic() && C.nx == 256 && C.ny == 256) return launch_ns256_fused(C, S, P, B, stream);
+  }
+  const GenericShape g = generic_shape<T>(C.nx * C.ny, B);
+  if (g.mode == 1) {
+    hipLaunchKernelGGL((ns_generic_step<T, 1>), dim3(B), dim3(g.threads), g.jacobi_bytes, stream, C, S, P, B);
+  } else if (g.mode == 2) {
+    static signed char attr_done[pdegym::kMaxDevices] = {};
+    if (!pdegym::raise_dynamic_lds_limit(reinterpret_cast<const void*>(&ns_generic_step<T, 2>), kLds1MaxBytes, attr_done))
+      return pdegym::fail(-4, "cannot raise the dynamic LDS limit");
+    hipLaunchKernelGGL((ns_generic_step<T, 2>), dim3(B), dim3(g.threads), g.jacobi_bytes, stream, C, S, P, B);
+  } else {   // no Jacobi copy in LDS: only gen_back's column sums
+    hipLaunchKernelGGL((ns_generic_step<T, 0>), dim3(B), dim3(g.threads), (size_t)C.nx * sizeof(T), stream, C, S, P, B);
+  }
+  return pdegym::check_launch("ns2d_step");
+}
+
+template <typename T>
+int ns_step(const pdegym_params_ns2d* prm, const pdegym_bufs_ns2d* buf, int B, void* stream) {
   NSConst C;
   NSScal<T> S;
   if (int rc = fill<T>(prm, C, S)) return rc;
@@ -1898,80 +1782,19 @@ int ns_step_launch(const pdegym_params_ns2d* prm, const pdegym_bufs_ns2d* buf, i
   if ((buf->u == nullptr) != (buf->v == nullptr)) return pdegym::fail(-3, "u and v must be given together");
   if (buf->state_in == buf->obs) return pdegym::fail(-3, "state_in must not alias obs (double-buffer the observations)");
   if (buf->nt_ref < 1) return pdegym::fail(-2, "nt_ref must be >= 1");
-  C.nt_ref = buf->nt_ref;
-  NSPtrs<T> P{(T*)buf->u, (T*)buf->v, (T*)buf->p, (T*)buf->scratch, (const T*)buf->action, buf->time_index,
-              (const T*)buf->U_ref, (const T*)buf->action_ref, (T*)buf->obs, (T*)buf->reward, buf->terminated,
-              (const T*)buf->state_in, (T*)buf->p_out};
   if (buf->p_out && buf->p_out == buf->p) return pdegym::fail(-3, "p_out must not alias p");
-  // small grids: one lane per column, up to three instances per wave, no barriers (ns_col_step)
-  if (!pdegym_force_generic() && !pdegym_ns_no_col() && launch_ns_col<T>(C, S, P, B, (hipStream_t)stream))
-    return pdegym::check_launch("ns2d_col_step");
-  if constexpr (sizeof(T) == 4) {
-    // register-tiled float32 path for the square grids it is instantiated for (BASELINE config 4 is 128x128)
-    if (!pdegym_force_generic() && C.nx == C.ny && (C.nx == 128 || C.nx == 64)) {
-      constexpr int lds128 = TileCfg<8, 4>::LDS_BYTES + TileCfg<8, 4>::PARK_BYTES, lds64 = TileCfg<4, 2>::LDS_BYTES;
-      if (C.nx == 128) {   // 80 KB of dynamic LDS: above the 64 KB a kernel gets without asking
-        static signed char attr_i[pdegym::kMaxDevices] = {}, attr_s[pdegym::kMaxDevices] = {};
-        const bool ok = buf->state_in
-            ? pdegym::raise_dynamic_lds_limit(reinterpret_cast<const void*>(&ns_tile_step<8, 4, true>), lds128, attr_i)
-            : pdegym::raise_dynamic_lds_limit(reinterpret_cast<const void*>(&ns_tile_step<8, 4, false>), lds128, attr_s);
-        if (!ok) return pdegym::fail(-4, "cannot raise the dynamic LDS limit of ns_tile_step");
-      }
-      // state_in given -> the velocity state is the previous observation and u, v are not written (if the caller
-      // also passed u, v they are simply left untouched)
-      const bool inter = buf->state_in != nullptr;
-      if (C.nx == 128 && inter)
-        hipLaunchKernelGGL((ns_tile_step<8, 4, true>), dim3(B), dim3(512), lds128, (hipStream_t)stream, C, S, P, B);
-      else if (C.nx == 128)
-        hipLaunchKernelGGL((ns_tile_step<8, 4, false>), dim3(B), dim3(512), lds128, (hipStream_t)stream, C, S, P, B);
-      else if (inter)
-        hipLaunchKernelGGL((ns_tile_step<4, 2, true>), dim3(B), dim3(512), lds64, (hipStream_t)stream, C, S, P, B);
-      else
-        hipLaunchKernelGGL((ns_tile_step<4, 2, false>), dim3(B), dim3(512), lds64, (hipStream_t)stream, C, S, P, B);
-      return pdegym::check_launch("ns2d_tile_step");
-    }
-  }
-  if constexpr (sizeof(T) == 8) {
-    // register-tiled float64 path for 128x128 (BASELINE config 4 at the reference's own precision)
-    if (!pdegym_force_generic() && C.nx == 128 && C.ny == 128) {
-      constexpr int kPRf64 = PDEGYM_NS_F64_TILE_ROWS;
-      constexpr int lds_bytes = F64Tile<kPRf64>::LDS_BYTES, nt = F64Tile<kPRf64>::NT;
-      static signed char attr_a[pdegym::kMaxDevices] = {}, attr_b[pdegym::kMaxDevices] = {};
-      if (buf->state_in) {
-        if (!pdegym::raise_dynamic_lds_limit(reinterpret_cast<const void*>(&ns_tile_step_f64<true, kPRf64>), lds_bytes, attr_a))
-          return pdegym::fail(-4, "cannot raise the dynamic LDS limit");
-        hipLaunchKernelGGL((ns_tile_step_f64<true, kPRf64>), dim3(B), dim3(nt), lds_bytes, (hipStream_t)stream, C, S, P, B);
-      } else {
-        if (!pdegym::raise_dynamic_lds_limit(reinterpret_cast<const void*>(&ns_tile_step_f64<false, kPRf64>), lds_bytes, attr_b))
-          return pdegym::fail(-4, "cannot raise the dynamic LDS limit");
-        hipLaunchKernelGGL((ns_tile_step_f64<false, kPRf64>), dim3(B), dim3(nt), lds_bytes, (hipStream_t)stream, C, S, P, B);
-      }
-      return pdegym::check_launch("ns2d_tile_step_f64");
-    }
-  }
-  if constexpr (sizeof(T) == 8) {
-    // 256x256 float64 (BASELINE config 5 at the reference's precision): pdegym_ns256_f64.hip
-    if (!pdegym_force_generic() && C.nx == 256 && C.ny == 256) return launch_ns256_step_f64(C, S, P, B, (hipStream_t)stream);
-  }
-  if constexpr (sizeof(T) == 4) {
-    // 256x256 float32 (BASELINE config 5): the whole env-step in one launch, one workgroup per instance (pdegym_ns256.hip)
-    if (!pdegym_force_generic() && C.nx == 256 && C.ny == 256) return launch_ns256_fused(C, S, P, B, (hipStream_t)stream);
-  }
+  C.nt_ref = buf->nt_ref;
+  const NSPtrs<T> P = make_ptrs<T>(buf);
+  if (int rc = ns_step_launch<T>(C, S, P, B, (hipStream_t)stream)) return rc;
+  if (!buf->reset_u0) return 0;
+  // fused auto-reset (same stream, no host round trip)
+  if (!buf->reset_v0 || !buf->reset_p0) return pdegym::fail(-3, "reset_u0 needs reset_v0 and reset_p0");
+  const NSAutoReset<T> R = make_auto_reset<T>(buf);
   const int ncell = C.nx * C.ny;
-  const int mode = lds_jacobi_mode<T>(ncell);
-  if (mode == 1) {
-    hipLaunchKernelGGL((ns_generic_step<T, 1>), dim3(B), dim3(lds_block_threads(ncell, B)), 2 * (size_t)ncell * sizeof(T),
-                       (hipStream_t)stream, C, S, P, B);
-  } else if (mode == 2) {
-    static signed char attr_done[pdegym::kMaxDevices] = {};
-    if (!pdegym::raise_dynamic_lds_limit(reinterpret_cast<const void*>(&ns_generic_step<T, 2>), kLds1MaxBytes, attr_done))
-      return pdegym::fail(-4, "cannot raise the dynamic LDS limit");
-    hipLaunchKernelGGL((ns_generic_step<T, 2>), dim3(B), dim3(1024), (size_t)ncell * sizeof(T), (hipStream_t)stream, C, S, P, B);
-  } else {
-    hipLaunchKernelGGL((ns_generic_step<T, 0>), dim3(B), dim3(block_threads(ncell)), (size_t)C.nx * sizeof(T), (hipStream_t)stream,
-                       C, S, P, B);
-  }
-  return pdegym::check_launch("ns2d_step");
+  const int gx = (ncell + 255) / 256 > 64 ? 64 : (ncell + 255) / 256;
+  hipLaunchKernelGGL(ns_auto_reset_kernel<T>, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, C, P, R, B);
+  hipLaunchKernelGGL(ns_auto_reset_finish<T>, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, P, R, B);
+  return pdegym::check_launch("ns2d_auto_reset");
 }
 
 template <typename T>
@@ -1983,20 +1806,19 @@ int ns_pressure(const pdegym_params_ns2d* prm, const void* u, const void* v, con
   if (B <= 0) return 0;
   if (!u || !v || !p_in || !p_out || !scratch) return pdegym::fail(-3, "null device buffer");
   C.nt_ref = 1;
-  const int ncell = C.nx * C.ny;
-  const int mode = lds_jacobi_mode<T>(ncell);
-  if (mode == 1) {
-    hipLaunchKernelGGL((ns_generic_pressure<T, 1>), dim3(B), dim3(lds_block_threads(ncell, B)), 2 * (size_t)ncell * sizeof(T),
-                       (hipStream_t)stream, C, S, (const T*)u, (const T*)v, (const T*)p_in, (T*)p_out, (T*)scratch, B);
-  } else if (mode == 2) {
+  const GenericShape g = generic_shape<T>(C.nx * C.ny, B);
+  if (g.mode == 1) {
+    hipLaunchKernelGGL((ns_generic_pressure<T, 1>), dim3(B), dim3(g.threads), g.jacobi_bytes, (hipStream_t)stream, C, S, (const T*)u,
+                       (const T*)v, (const T*)p_in, (T*)p_out, (T*)scratch, B);
+  } else if (g.mode == 2) {
     static signed char attr_done[pdegym::kMaxDevices] = {};
     if (!pdegym::raise_dynamic_lds_limit(reinterpret_cast<const void*>(&ns_generic_pressure<T, 2>), kLds1MaxBytes, attr_done))
       return pdegym::fail(-4, "cannot raise the dynamic LDS limit");
-    hipLaunchKernelGGL((ns_generic_pressure<T, 2>), dim3(B), dim3(1024), (size_t)ncell * sizeof(T), (hipStream_t)stream, C, S,
-                       (const T*)u, (const T*)v, (const T*)p_in, (T*)p_out, (T*)scratch, B);
+    hipLaunchKernelGGL((ns_generic_pressure<T, 2>), dim3(B), dim3(g.threads), g.jacobi_bytes, (hipStream_t)stream, C, S, (const T*)u,
+                       (const T*)v, (const T*)p_in, (T*)p_out, (T*)scratch, B);
   } else {
-    hipLaunchKernelGGL((ns_generic_pressure<T, 0>), dim3(B), dim3(block_threads(ncell)), 0, (hipStream_t)stream, C, S,
-                       (const T*)u, (const T*)v, (const T*)p_in, (T*)p_out, (T*)scratch, B);
+    hipLaunchKernelGGL((ns_generic_pressure<T, 0>), dim3(B), dim3(g.threads), g.jacobi_bytes, (hipStream_t)stream, C, S, (const T*)u,
+                       (const T*)v, (const T*)p_in, (T*)p_out, (T*)scratch, B);
   }
   return pdegym::check_launch("ns2d_solve_pressure");
 }
@@ -2010,8 +1832,9 @@ int ns_reset(const pdegym_params_ns2d* prm, const pdegym_bufs_ns2d* buf, const v
   if (!buf || !u0 || !v0 || !p0) return pdegym::fail(-1, "null bufs/initial fields");
   if (B <= 0) return 0;
   C.nt_ref = 1;
-  NSPtrs<T> P{(T*)buf->u, (T*)buf->v, (T*)buf->p, (T*)buf->scratch, (const T*)buf->action, buf->time_index,
-              (const T*)buf->U_ref, (const T*)buf->action_ref, (T*)buf->obs, (T*)buf->reward, buf->terminated, nullptr, nullptr};
+  NSPtrs<T> P = make_ptrs<T>(buf);
+  P.state_in = nullptr;
+  P.p_out = nullptr;
   const int ncell = C.nx * C.ny;
   const int gx = (ncell + 255) / 256 > 64 ? 64 : (ncell + 255) / 256;
   hipLaunchKernelGGL(ns_reset_kernel<T>, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, C, P, (const T*)u0, (const T*)v0,
@@ -2031,11 +1854,13 @@ int ns_rollout(const pdegym_params_ns2d* prm, const pdegym_bufs_ns2d* buf, const
   if (buf->nt_ref < 1) return pdegym::fail(-2, "nt_ref must be >= 1");
   if (buf->reset_u0 && (!buf->reset_v0 || !buf->reset_p0)) return pdegym::fail(-3, "reset_u0 needs reset_v0 and reset_p0");
   C.nt_ref = buf->nt_ref;
-  NSPtrs<T> P{nullptr, nullptr, (T*)buf->p, (T*)buf->scratch, nullptr, buf->time_index, (const T*)buf->U_ref, (const T*)buf->action_ref,
-              nullptr, nullptr, nullptr, nullptr, nullptr};
+  // the state, the command, the observation, the reward and the flag of every step live in the rollout arrays (ns_col_rollout)
+  NSPtrs<T> P = make_ptrs<T>(buf);
+  P.u = P.v = P.obs = P.reward = P.p_out = nullptr;
+  P.action = P.state_in = nullptr;
+  P.terminated = nullptr;
   NSRollout<T> Ro{ro->T, (T*)ro->obs, (const T*)ro->actions, (T*)ro->rewards, ro->terminated};
-  NSAutoReset<T> R{(const T*)buf->reset_u0, (const T*)buf->reset_v0, (const T*)buf->reset_p0, (T*)buf->final_obs, buf->reset_count,
-                   buf->reset_pool_rows};
+  const NSAutoReset<T> R = make_auto_reset<T>(buf);
   if (!launch_ns_col_rollout<T>(C, S, P, Ro, R, B, (hipStream_t)stream))
     return pdegym::fail(-2, "ns2d rollout: grids of 8, 11, 16, 21, 26, 31 or 32 rows and at most 64 columns (the column-per-lane kernel)");
   return pdegym::check_launch("ns2d_col_rollout");

@@ -8,14 +8,7 @@
 
 #include "pdegym.h"
 
-#ifndef PDEGYM_NS_DPP_NOP
-#define PDEGYM_NS_DPP_NOP 1
-#endif
-#if PDEGYM_NS_DPP_NOP
-#define PDEGYM_DPP_NOP "s_nop 0\n\t"
-#else
-#define PDEGYM_DPP_NOP
-#endif
+#define PDEGYM_DPP_NOP "s_nop 0\n\t"   // ahead of every DPP add of the pair blocks below (see jacobi_pair_up)
 
 namespace pdegym {
 namespace ns {
@@ -96,20 +89,42 @@ __device__ __forceinline__ T block_sum(T v, T* red /* >= 16 entries of LDS */) {
   return s;
 }
 
-template <int N>
+// The one-thread end of an env-step of instance b: reward (ns_reward.py:28)
+//   - 1/2 * ||U - Uref||^2 / nx / ny - gamma/2 * ||a - aref||^2
+// from the instance's sum of squares ss (how ss is reduced is each kernel's own business), then the time index and the
+// terminated flag (navier_stokes2D.py:159-168).  The two divisors are arguments so that a kernel with a compile-time grid side
+// divides by constants.
+template <typename T>
+__device__ __forceinline__ void step_epilogue(const NSConst& C, const NSScal<T>& S, const NSPtrs<T>& P, int b, T ss, const T* act, int t,
+                                              int tr, T nx, T ny) {
+  T asq = 0;
+  const T aref = P.action_ref[tr];
+  for (int k = 0; k < C.action_dim; ++k) {
+    const T d = act[k] - aref;
+    asq += d * d;
+  }
+  P.reward[b] = (((T)-0.5 * ss) / nx) / ny - S.gamma_half * asq;
+  P.time_index[b] = t;
+  P.terminated[b] = (t >= C.nt - 1) ? 1 : 0;
+}
+
+template <int N, typename T = float>
 struct VecOf;
 template <>
-struct VecOf<4> { using type = float4; };
+struct VecOf<4, float> { using type = float4; };
 template <>
-struct VecOf<2> { using type = float2; };
+struct VecOf<2, float> { using type = float2; };
+template <>
+struct VecOf<2, double> { using type = double2; };
 
-template <int PC>
-__device__ __forceinline__ typename VecOf<PC>::type pack_row(const float (&r)[PC]) {
+template <int PC, typename T>
+__device__ __forceinline__ typename VecOf<PC, T>::type pack_row(const T (&r)[PC]) {
   if constexpr (PC == 4) return make_float4(r[0], r[1], r[2], r[3]);
+  else if constexpr (sizeof(T) == 8) return make_double2(r[0], r[1]);
   else return make_float2(r[0], r[1]);
 }
-template <int PC>
-__device__ __forceinline__ void unpack_row(const typename VecOf<PC>::type& v, float (&r)[PC]) {
+template <int PC, typename T>
+__device__ __forceinline__ void unpack_row(const typename VecOf<PC, T>::type& v, T (&r)[PC]) {
   r[0] = v.x;
   r[1] = v.y;
   if constexpr (PC == 4) {
@@ -118,9 +133,6 @@ __device__ __forceinline__ void unpack_row(const typename VecOf<PC>::type& v, fl
   }
 }
 
-#ifndef PDEGYM_NS_PARK_ROWS
-#define PDEGYM_NS_PARK_ROWS 6
-#endif
 template <int PR, int PC>
 struct TileCfg {
   static constexpr int NT = 512;
@@ -130,7 +142,7 @@ struct TileCfg {
   // rows of u* that wait in LDS (one PC-wide vector per thread and row) while the pressure solve runs -- the others and v* stay
   // in registers: 128x128 -> 6 of 8 rows = 48 KB, so that two workgroups (2 x 80 KB) share a CU's 160 KB exactly
   // (5 rows: B = 4096 528 instead of 521 us; 4 rows: 533)
-  static constexpr int PARK_ROWS = (PR == 8 && PC == 4) ? PDEGYM_NS_PARK_ROWS : 0;
+  static constexpr int PARK_ROWS = (PR == 8 && PC == 4) ? 6 : 0;
   static constexpr int PARK_BYTES = PARK_ROWS * NT * PC * 4;
   static_assert(16 * PR == 32 * PC, "square grids only");
 };
@@ -146,6 +158,19 @@ __device__ __forceinline__ float lane_left(float v) {
 }
 __device__ __forceinline__ float lane_right(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x130, 0xf, 0xf, true));
+}
+// double: the two halves move separately (two v_mov_b32_dpp per value)
+__device__ __forceinline__ double lane_left(double v) {
+  const long long b = __builtin_bit_cast(long long, v);
+  const int lo = __builtin_amdgcn_update_dpp(0, (int)b, 0x138, 0xf, 0xf, true);
+  const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), 0x138, 0xf, 0xf, true);
+  return __builtin_bit_cast(double, ((long long)hi << 32) | (unsigned int)lo);
+}
+__device__ __forceinline__ double lane_right(double v) {
+  const long long b = __builtin_bit_cast(long long, v);
+  const int lo = __builtin_amdgcn_update_dpp(0, (int)b, 0x130, 0xf, 0xf, true);
+  const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), 0x130, 0xf, 0xf, true);
+  return __builtin_bit_cast(double, ((long long)hi << 32) | (unsigned int)lo);
 }
 
 // y + (value of x in the lane to the left / right): the DPP shift rides on the add itself (hipcc keeps a separate
@@ -163,10 +188,11 @@ __device__ __forceinline__ float add_lane_right(float x, float y) {
 
 // top/bottom halo rows through LDS: ht = bottom row of the thread above, hb = top row of the thread below.
 // Domain-edge threads re-read their own row (valid address, value never used): every access is unconditional.
-template <int PC, int NT = 512, int RS = 32>
-__device__ __forceinline__ void halo_tb(const float (&top)[PC], const float (&bot)[PC], float (&ht)[PC], float (&hb)[PC],
-                                        float* lds, int& xc, int tid, int ty) {
-  using V = typename VecOf<PC>::type;
+// NT threads per workgroup, RS threads per thread row (32: two thread rows per wave; 64: one wave per thread row).
+template <int PC, int NT = 512, int RS = 32, typename T>
+__device__ __forceinline__ void halo_tb(const T (&top)[PC], const T (&bot)[PC], T (&ht)[PC], T (&hb)[PC], T* lds, int& xc, int tid,
+                                        int ty) {
+  using V = typename VecOf<PC, T>::type;
   V* base = reinterpret_cast<V*>(lds) + (xc & 1) * (2 * NT);
   ++xc;
   V* eT = base;
@@ -191,58 +217,6 @@ __device__ __forceinline__ void halo_tb(const float (&top)[PC], const float (&bo
 template <int PR>
 __device__ constexpr int bphys(int a, int state) {          // physical row of logical row a (a = -1: top halo in an UP sweep)
   return state == 0 ? a : (a == 0 ? PR : a - 1);
-}
-
-// ((W + S) + E) + N -> fma(0.25, ., -rq), in place on the registers of the South row (UP) ...
-__device__ __forceinline__ void jacobi_row_into_south(float (&sv)[4], const float (&xv)[4], const float (&nn)[4], const float (&rq)[4]) {
-  asm volatile(
-      "v_add_f32 %1, %4, %1\n\t"
-      "v_add_f32 %2, %5, %2\n\t"
-      "v_add_f32 %3, %6, %3\n\t"
-      PDEGYM_DPP_NOP
-      "v_add_f32_dpp %0, %7, %0 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-      "v_add_f32 %0, %0, %5\n\t"
-      "v_add_f32 %1, %1, %6\n\t"
-      "v_add_f32 %2, %2, %7\n\t"
-      PDEGYM_DPP_NOP
-      "v_add_f32_dpp %3, %4, %3 wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-      "v_add_f32 %0, %0, %8\n\t"
-      "v_add_f32 %1, %1, %9\n\t"
-      "v_add_f32 %2, %2, %10\n\t"
-      "v_add_f32 %3, %3, %11\n\t"
-      "v_fma_f32 %0, %0, %16, -%12\n\t"
-      "v_fma_f32 %1, %1, %16, -%13\n\t"
-      "v_fma_f32 %2, %2, %16, -%14\n\t"
-      "v_fma_f32 %3, %3, %16, -%15"
-      : "+v"(sv[0]), "+v"(sv[1]), "+v"(sv[2]), "+v"(sv[3])
-      : "v"(xv[0]), "v"(xv[1]), "v"(xv[2]), "v"(xv[3]), "v"(nn[0]), "v"(nn[1]), "v"(nn[2]), "v"(nn[3]), "v"(rq[0]), "v"(rq[1]),
-        "v"(rq[2]), "v"(rq[3]), "s"(0.25f));
-}
-// ... and on the registers of the North row (DOWN): the partial sums (W + S) + E need four temporaries
-__device__ __forceinline__ void jacobi_row_into_north(float (&nv)[4], const float (&xv)[4], const float (&ss)[4], const float (&rq)[4]) {
-  float t0, t1, t2, t3;
-  asm volatile(
-      "v_add_f32 %5, %8, %13\n\t"
-      "v_add_f32 %6, %9, %14\n\t"
-      "v_add_f32 %7, %10, %15\n\t"
-      PDEGYM_DPP_NOP
-      "v_add_f32_dpp %4, %11, %12 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-      "v_add_f32 %4, %4, %9\n\t"
-      "v_add_f32 %5, %5, %10\n\t"
-      "v_add_f32 %6, %6, %11\n\t"
-      PDEGYM_DPP_NOP
-      "v_add_f32_dpp %7, %8, %7 wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-      "v_add_f32 %0, %4, %0\n\t"
-      "v_add_f32 %1, %5, %1\n\t"
-      "v_add_f32 %2, %6, %2\n\t"
-      "v_add_f32 %3, %7, %3\n\t"
-      "v_fma_f32 %0, %0, %20, -%16\n\t"
-      "v_fma_f32 %1, %1, %20, -%17\n\t"
-      "v_fma_f32 %2, %2, %20, -%18\n\t"
-      "v_fma_f32 %3, %3, %20, -%19"
-      : "+v"(nv[0]), "+v"(nv[1]), "+v"(nv[2]), "+v"(nv[3]), "=&v"(t0), "=&v"(t1), "=&v"(t2), "=&v"(t3)
-      : "v"(xv[0]), "v"(xv[1]), "v"(xv[2]), "v"(xv[3]), "v"(ss[0]), "v"(ss[1]), "v"(ss[2]), "v"(ss[3]), "v"(rq[0]), "v"(rq[1]),
-        "v"(rq[2]), "v"(rq[3]), "s"(0.25f));
 }
 
 // An s_nop 0 goes ahead of every DPP add: without it a DPP operand costs the SIMD ~15 cycles in these blocks -- the two waves of a
@@ -351,17 +325,17 @@ __device__ __forceinline__ void jacobi_pair_down(float (&da)[4], float (&db)[4],
       : "v"(rqa[0]), "v"(rqa[1]), "v"(rqa[2]), "v"(rqa[3]), "v"(rqb[0]), "v"(rqb[1]), "v"(rqb[2]), "v"(rqb[3]), "s"(0.25f));
 }
 
-// Neumann walls (:110-113) on the new rows, which sit in state `st`
-template <int PR, int ST>
-__device__ __forceinline__ void jacobi_walls_state(float (&ph)[PR + 1][4], const EdgeFlags& E) {
+// Neumann walls (:110-113) on the new rows, which sit in state ST (see bphys)
+template <int PR, int ST, int PC, typename T>
+__device__ __forceinline__ void jacobi_walls_state(T (&ph)[PR + 1][PC], const EdgeFlags& E) {
   constexpr int n0 = bphys<PR>(0, ST), n1 = bphys<PR>(1, ST), nl = bphys<PR>(PR - 1, ST), nm = bphys<PR>(PR - 2, ST);
   if (E.top) {
 #pragma unroll
-    for (int k = 0; k < 4; ++k) ph[n0][k] = ph[n1][k];
+    for (int k = 0; k < PC; ++k) ph[n0][k] = ph[n1][k];
   }
   if (E.bot) {
 #pragma unroll
-    for (int k = 0; k < 4; ++k) ph[nl][k] = ph[nm][k];
+    for (int k = 0; k < PC; ++k) ph[nl][k] = ph[nm][k];
   }
   if (E.lef) {
 #pragma unroll
@@ -369,7 +343,7 @@ __device__ __forceinline__ void jacobi_walls_state(float (&ph)[PR + 1][4], const
   }
   if (E.rig) {
 #pragma unroll
-    for (int a = 0; a < PR; ++a) ph[bphys<PR>(a, ST)][3] = ph[bphys<PR>(a, ST)][2];
+    for (int a = 0; a < PR; ++a) ph[bphys<PR>(a, ST)][PC - 1] = ph[bphys<PR>(a, ST)][PC - 2];
   }
 }
 
@@ -378,6 +352,7 @@ __device__ __forceinline__ void jacobi_walls_state(float (&ph)[PR + 1][4], const
 template <int PR, int ST, int NT, int RS>
 __device__ __forceinline__ void jacobi_sweep_bous(float (&ph)[PR + 1][4], const float (&rq)[PR][4], const EdgeFlags& E, float* lds,
                                                   int& xc, int tid, int ty) {
+  static_assert(PR % 2 == 0, "rows are updated in pairs (jacobi_pair_up / jacobi_pair_down)");
   float hlast[4];
   if constexpr (ST == 0) {
     halo_tb<4, NT, RS>(ph[bphys<PR>(0, 0)], ph[bphys<PR>(PR - 1, 0)], ph[PR], hlast, lds, xc, tid, ty);   // top halo -> free row PR
@@ -387,7 +362,6 @@ __device__ __forceinline__ void jacobi_sweep_bous(float (&ph)[PR + 1][4], const 
       if (a + 2 == PR) jacobi_pair_up(da, ph[a], ph[a + 1], hlast, rq[a], rq[a + 1]);
       else jacobi_pair_up(da, ph[a], ph[a + 1], ph[a + 2], rq[a], rq[a + 1]);
     }
-    if constexpr (PR % 2 == 1) jacobi_row_into_south(ph[PR - 2], ph[PR - 1], hlast, rq[PR - 1]);
     jacobi_walls_state<PR, 1>(ph, E);
   } else {
     // state 1: logical row a in physical row a-1 (row 0 in PR); physical row PR-1 is free -> bottom halo
@@ -398,7 +372,6 @@ __device__ __forceinline__ void jacobi_sweep_bous(float (&ph)[PR + 1][4], const 
       if (a == 1) jacobi_pair_down(ph[a], ph[a - 1], ph[bphys<PR>(0, 1)], hlast, rq[a], rq[a - 1]);
       else jacobi_pair_down(ph[a], ph[a - 1], ph[bphys<PR>(a - 1, 1)], ph[bphys<PR>(a - 2, 1)], rq[a], rq[a - 1]);
     }
-    if constexpr (PR % 2 == 1) jacobi_row_into_north(ph[0], ph[bphys<PR>(0, 1)], hlast, rq[0]);
     jacobi_walls_state<PR, 0>(ph, E);
   }
 }

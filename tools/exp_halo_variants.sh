@@ -1,8 +1,9 @@
 #!/bin/bash
 # Round-6 bounded experiment: what does the per-sweep inter-wave halo exchange of ns_tile_step_f64 cost?
-# Builds two TIMING-ONLY variants of the library from a patched copy of csrc/ (results are wrong by construction; nothing here ships):
-#   nosync : halo_tb_f64 without its workgroup barrier (LDS write + read kept)      -> cost of the barrier
-#   nohalo : halo_tb_f64 without LDS traffic and without the barrier               -> cost of the whole exchange = upper bound of what
+# Builds two TIMING-ONLY variants of the library from a patched copy of csrc/ (results are wrong by construction; nothing here ships;
+# halo_tb of pdegym_ns_common.h is shared, so every kernel of pdegym_ns2d.hip that exchanges halos is patched -- time the float64 tile only):
+#   nosync : halo_tb without its workgroup barrier (LDS write + read kept)      -> cost of the barrier
+#   nohalo : halo_tb without LDS traffic and without the barrier               -> cost of the whole exchange = upper bound of what
 #            ANY halo-blocking scheme (depth-2 temporal blocking halves the exchanges) can recover
 # usage: bash tools/exp_halo_variants.sh   (then: bash tools/ab_libs.sh "ns2d_c4_f64_b4096 ns2d_c4_f64" - pdecontrolgym_amd/lib/ab/libnosync.so pdecontrolgym_amd/lib/ab/libnohalo.so)
 set -e
@@ -10,18 +11,18 @@ R=$(cd "$(dirname "$0")/.." && pwd)
 for v in nosync nohalo; do
   W=/tmp/pdegym_exp_$v
   rm -rf $W && mkdir -p $W && cp -r $R/pdecontrolgym_amd/csrc $W/csrc
-  python3 - $W/csrc/pdegym_ns2d.hip $v <<'PY'
+  python3 - $W/csrc/pdegym_ns_common.h $v <<'PY'
 import sys
 p, v = sys.argv[1], sys.argv[2]
 s = open(p).read()
-i = s.index("__device__ __forceinline__ void halo_tb_f64(")
-j = s.index("template <int PR>", i)
+i = s.index("__device__ __forceinline__ void halo_tb(")
+j = s.index("// ---- boustrophedon sweeps", i)
 body = s[i:j]
 if v == "nosync":
     new = body.replace("__syncthreads();", "__builtin_amdgcn_wave_barrier();")
 else:
     k = body.index("{", body.index("int ty)"))
-    new = body[:k] + "{\n  ht[0] = top[0]; ht[1] = top[1]; hb[0] = bot[0]; hb[1] = bot[1]; ++xc; (void)lds; (void)tid; (void)ty;\n}\n\n"
+    new = body[:k] + "{\n  for (int k = 0; k < PC; ++k) { ht[k] = top[k]; hb[k] = bot[k]; }\n  ++xc; (void)lds; (void)tid; (void)ty;\n}\n\n"
 assert new != body
 open(p, "w").write(s[:i] + new + s[j:])
 PY

@@ -38,19 +38,12 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void step1d_kernel(pdegym_pa
 // owned by the wave (node j lives in lane j % 64; wave-level ordering only, no workgroup barrier).  This is the plain
 // select form of the reference arithmetic -- same expressions and order as run_substeps<..., FAST = false> -- with the
 // same bookkeeping (reward ring, look-back, history, sensing, fused auto-reset).  n <= PDEGYM_MAX_N1D_WIDE.
-// ================================================================================================
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_wave_barrier();
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-}
-
 // M64 = the reference's mixed-precision arithmetic for a float64 beta and/or a float64 / Python-float control input
 // (pdegym_params1d.beta_f64 / action_kind): the parity mode of the docs quickstart (beta = np.ones(nx)).  Rows of ANY length
 // take this kernel in that mode; with M64 = false it is the float32 kernel for rows beyond the register-resident limit.
 template <bool PARABOLIC, bool BURGERS, bool M64 = false>
 __global__ __launch_bounds__(kWave) void step1d_wide_kernel(pdegym_params1d P, pdegym_bufs1d Bf, int B) {
   extern __shared__ float wl[];
-  constexpr int J0 = PARABOLIC ? 1 : 0;
   const int lane = threadIdx.x;
   const int inst = blockIdx.x;
   if (inst >= B) return;
@@ -257,7 +250,7 @@ __global__ __launch_bounds__(kWave) void step1d_wide_kernel(pdegym_params1d P, p
     }
   } else {
     if (Bf.final_obs) emit_obs(Bf.final_obs, cur);
-    const int prow = pool_row(Bf, inst, B);
+    const int prow = pool_row(Bf.reset_pool_rows, Bf.reset_count, inst, B);
     const float* irow = Bf.reset_init + (size_t)prow * n;
     if (Bf.reset_beta && Bf.beta_stride != 0) {      // the reference redraws beta at every reset (hyperbolic.py:208)
       if (beta64) {
@@ -288,7 +281,6 @@ __global__ __launch_bounds__(kWave) void step1d_wide_kernel(pdegym_params1d P, p
       ring[0] = n0;
     }
   }
-  (void)J0;
 }
 
 // ---- reset (state part of hyperbolic.py:214-227 / parabolic.py:208-221) -----------------------------

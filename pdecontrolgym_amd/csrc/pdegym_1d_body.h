@@ -1,5 +1,5 @@
 // pdegym_1d_body.h -- the device-side body shared by the 1D step kernels (pdegym_1d.hip) and the 1D rollout kernels
-// (pdegym_1d_rollout.hip): lane shifts and wave reductions, the sub-step loops, one env-step of one instance by one wave
+// (pdegym_1d_rollout.hip): the magnitude maxima on the wave reduction of pdegym_common.h, the sub-step loops, one env-step of one instance by one wave
 // (step1d_body) and the state a rollout carries in registers.  Two translation units so that they compile in parallel and so
 // that a change of the rollout kernels leaves the fingerprint of the step kernels (and the counters committed for them) alone.
 // Design notes: at the top of pdegym_1d.hip.
@@ -10,64 +10,15 @@
 
 #include <type_traits>
 
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-
 #include "pdegym.h"
 #include "pdegym_common.h"
 
 namespace {
 
+using namespace pdegym::wave;      // kWave, kWavesPerBlock, lane shifts, wave_reduce / wave_sum, lane_value, drain_vmem, pool_row
 
-constexpr int kWave = 64;
-constexpr int kWavesPerBlock = 4;
-
-// lane i <- lane i-1 ; lane 0 <- `edge`      (DPP wave_shr:1, gfx9 wave-wide shift)
-__device__ __forceinline__ float from_left_lane(float v, float edge) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, edge), __builtin_bit_cast(int, v),
-                                                               0x138, 0xf, 0xf, false));
-}
-// lane i <- lane i+1 ; lane 63 <- `edge`     (DPP wave_shl:1)
-__device__ __forceinline__ float from_right_lane(float v, float edge) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, edge), __builtin_bit_cast(int, v),
-                                                               0x130, 0xf, 0xf, false));
-}
-
-// Wave-wide reductions on DPP (result in every lane).  __shfl_xor compiles to ds_bpermute_b32, an LDS round trip per step:
-// six dependent ones per reduction, four reductions per env-step on the critical path of a wave's prologue / epilogue.
-// Steps: the lane pair, the quad (quad_perm), the half row and the row (row_half_mirror / row_mirror: lane i pairs with
-// lane 7-i / 15-i), then lane 15 of rows 0 and 2 into rows 1 and 3 (row_bcast:15) and lane 31 into rows 2, 3
-// (row_bcast:31): lane 63 holds the total, v_readlane hands it to everybody.  A fixed order (deterministic), not the
-// butterfly's -- norms and rewards were never bitwise against a BLAS dot product anyway (tests: rtol 1e-6).
-template <typename Op>
-__device__ __forceinline__ float wave_reduce(float v, float identity, Op op) {
-  auto dpp = [&](float x, const int ctrl_tag) {
-    const int xi = __builtin_bit_cast(int, x), idn = __builtin_bit_cast(int, identity);
-    int r;
-    switch (ctrl_tag) {
-      case 0: r = __builtin_amdgcn_update_dpp(idn, xi, 0xB1, 0xf, 0xf, false); break;    // quad_perm:[1,0,3,2]
-      case 1: r = __builtin_amdgcn_update_dpp(idn, xi, 0x4E, 0xf, 0xf, false); break;    // quad_perm:[2,3,0,1]
-      case 2: r = __builtin_amdgcn_update_dpp(idn, xi, 0x141, 0xf, 0xf, false); break;   // row_half_mirror
-      case 3: r = __builtin_amdgcn_update_dpp(idn, xi, 0x140, 0xf, 0xf, false); break;   // row_mirror
-      case 4: r = __builtin_amdgcn_update_dpp(idn, xi, 0x142, 0xa, 0xf, false); break;   // row_bcast:15 -> rows 1, 3
-      default: r = __builtin_amdgcn_update_dpp(idn, xi, 0x143, 0xc, 0xf, false); break;  // row_bcast:31 -> rows 2, 3
-    }
-    return __builtin_bit_cast(float, r);
-  };
-  v = op(v, dpp(v, 0));
-  v = op(v, dpp(v, 1));
-  v = op(v, dpp(v, 2));
-  v = op(v, dpp(v, 3));
-  v = op(v, dpp(v, 4));
-  v = op(v, dpp(v, 5));
-  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-}
-__device__ __forceinline__ float wave_sum(float v) {
-  return wave_reduce(v, 0.0f, [](float a, float b) { return a + b; });
-}
 __device__ __forceinline__ float wave_max(float v) {      // callers pass magnitudes: 0 is the identity
-  return wave_reduce(v, 0.0f, [](float a, float b) { return fmaxf(a, b); });
+  return wave_reduce(v, [](float a, float b) { return fmaxf(a, b); });
 }
 // max of two magnitudes (sign bit clear) that propagates NaN like np.max: non-negative floats order as their bit patterns,
 // and every NaN pattern lies above +inf.  The Linf reward norms use it (np.linalg.norm(row, ord=inf) of a row holding NaN is NaN).
@@ -76,7 +27,7 @@ __device__ __forceinline__ float mag_max(float a, float b) {
   return __uint_as_float(ua > ub ? ua : ub);
 }
 __device__ __forceinline__ float wave_mag_max(float v) {
-  return wave_reduce(v, 0.0f, [](float a, float b) { return mag_max(a, b); });
+  return wave_reduce(v, [](float a, float b) { return mag_max(a, b); });
 }
 
 // value of slot s when lane l holds slots [l*EPL, l*EPL+EPL)
@@ -99,12 +50,6 @@ __device__ __forceinline__ float slots_sumsq(const float (&x)[EPL], int s0, int 
 
 // (a+1)*m-m, base_env_1d.py:36-39
 __device__ __forceinline__ float normalize_ctrl(float a, float m, int on) { return on ? (a + 1.0f) * m - m : a; }
-
-// s_waitcnt vmcnt(0) as a real instruction (the compiler's wait-count pass sees it): the carried rollout loop ends every RARE
-// path that loads (exact redo, auto-reset) with it, so that no register is "possibly still being loaded" at the loop's back edge --
-// otherwise the pass puts a static vmcnt(0) in front of the first use of each such register in EVERY iteration, and on gfx9 that
-// also waits for all the stores in flight (vmcnt counts both).
-__device__ __forceinline__ void drain_vmem() { __builtin_amdgcn_s_waitcnt(0x0F70); }      // vmcnt(0), expcnt / lgkmcnt untouched
 
 // The norm ring of one instance (PDEGYM_RING slots, slot = fine time index mod PDEGYM_RING) as the step body sees it.
 // RingMem: the ring in memory, written and read by lane 0 alone (program order of one lane).
@@ -172,13 +117,6 @@ __device__ __forceinline__ void load_slots(const float* base, float (&x)[EPL], i
 #pragma unroll
     for (int e = 0; e < EPL; ++e) x[e] = (s0 + e < ns) ? base[s0 + e] : 0.f;
   }
-}
-
-// Row of the reset pools that the next restart of instance `inst` takes (see pdegym_bufs1d.reset_pool_rows).
-__device__ __forceinline__ int pool_row(const pdegym_bufs1d& Bf, int inst, int B) {
-  const int rows = Bf.reset_pool_rows > 0 ? Bf.reset_pool_rows : B;
-  const long long k = Bf.reset_count ? (long long)Bf.reset_count[inst] : 0;
-  return (int)(((long long)inst + k * (long long)B) % rows);
 }
 
 // normalize(control_update(control, neighbour, dx), max_control_value) as NumPy evaluates it for the given kind of `control`
@@ -897,7 +835,7 @@ __device__ __forceinline__ void step1d_body(const pdegym_params1d& P, const pdeg
   } else {
     // fused VecEnv auto-reset: keep the terminal observation, restart from the pool row (hyperbolic.py:214-227)
     if (Bf.final_obs) emit_obs(Bf.final_obs);
-    const int prow = pool_row(Bf, inst, B);
+    const int prow = pool_row(Bf.reset_pool_rows, Bf.reset_count, inst, B);
     const float* irow = Bf.reset_init + (size_t)prow * n;
     if (Bf.reset_beta && Bf.beta_stride != 0) {      // the reference redraws beta at every reset (hyperbolic.py:208)
       if (beta64) {

@@ -47,7 +47,7 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void rollout1d_kernel(pdegym
       a_cur = command_batch(t);
       drain_vmem();
     }
-    const float a = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, a_cur), j));
+    const float a = lane_value(a_cur, j);
     step1d_body<EPL, PARABOLIC, false, false, BURGERS, false, true, true, FULL>(P, S, B, inst, lane, &a, &C, t == Ro.T - 1);
     S.state_in = S.obs;
     S.obs += slot;
@@ -113,7 +113,7 @@ __device__ __forceinline__ void sense_noise(const float* obs_noise, float* obs_s
     xw[j] = v;
     if (obs_seen) obs_seen[base + j] = v;
   }
-  pdegym_policy::wave_lds_sync();
+  wave_lds_sync();
 }
 
 // WIDE: a network with a layer of more than 64 units, evaluated by the 16 waves together (pdegym_policy.h: eval_wide) -- every wave of
@@ -150,12 +150,12 @@ __global__ __launch_bounds__(kWave* pdegym_policy::kWaves) void rollout1d_policy
 #pragma unroll
       for (int e = 0; e < EPL; ++e)
         if (s0 + e < ns) xw[J0 + s0 + e] = C.x[e];
-      pol::wave_lds_sync();
+      wave_lds_sync();
       sense_noise(Ro.obs_noise, Ro.obs_seen, xw, n, B, inst, lane, t);
     }
     float a;
     if constexpr (WIDE) a = pol::eval_wide(N, Wd, n, wave, lane);
-    else a = pol::lane_value(pol::eval(N, St, pol_smem, xw, hw, n, lane), 0);      // neuron 0 of the last layer
+    else a = lane_value(pol::eval(N, St, pol_smem, xw, hw, n, lane), 0);      // neuron 0 of the last layer
     if (!active) continue;
     if (N.noise) a += N.noise[((size_t)t * B + inst) * N.noise_stride];
     if (N.clamp) a = fminf(fmaxf(a, N.lo), N.hi);
@@ -199,12 +199,12 @@ __global__ __launch_bounds__(kWave* pdegym_policy::kWaves) void rollout1d_policy
     if (active) {
       const float* orow = Ro.obs + ((size_t)t * B + inst) * od;
       for (int j = lane; j < od; j += kWave) xw[j] = orow[j];
-      pol::wave_lds_sync();
+      wave_lds_sync();
       sense_noise(Ro.obs_noise, Ro.obs_seen, xw, od, B, inst, lane, t);
     }
     float a;
     if constexpr (WIDE) a = pol::eval_wide(N, Wd, od, wave, lane);
-    else a = pol::lane_value(pol::eval(N, St, pol_smem, xw, hw, od, lane), 0);
+    else a = lane_value(pol::eval(N, St, pol_smem, xw, hw, od, lane), 0);
     if (!active) continue;
     if (N.noise) a += N.noise[((size_t)t * B + inst) * N.noise_stride];
     if (N.clamp) a = fminf(fmaxf(a, N.lo), N.hi);

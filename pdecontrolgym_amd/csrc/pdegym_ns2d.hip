@@ -1152,22 +1152,6 @@ __global__ __launch_bounds__(F64Tile::NT, 2) void ns_tile_step_f64(NSConst C, NS
 // of the reference and the generic kernel); the reward is summed per column then over the instance's lanes in order -- the
 // canonical order that gen_back follows too, so rewards are the same bits on either kernel.
 // ================================================================================================
-// A lane shift must execute with every lane of the wave active: when its only use is a per-lane select (edge lanes keep
-// their value, the lanes next to a wall substitute their own), the compiler may fold the shift into the selecting lanes'
-// branch, and a DPP read from a lane that is masked off returns 0.  The empty asm pins the shift where it is written.
-template <typename T>
-__device__ __forceinline__ T pinned_from_left(T v) {
-  T r = lane_left(v);
-  asm volatile("" : "+v"(r));
-  return r;
-}
-template <typename T>
-__device__ __forceinline__ T pinned_from_right(T v) {
-  T r = lane_right(v);
-  asm volatile("" : "+v"(r));
-  return r;
-}
-
 // Fused auto-reset, run right after the step kernels of the same call (same stream, no host round trip): instances whose
 // step ended terminated keep their last observation in final_obs and restart from a pool row.
 template <typename T>
@@ -1453,6 +1437,7 @@ __global__ __launch_bounds__(64, (sizeof(T) == 8 || NY > 21 ? 2 : 3)) void ns_co
     if (R.u0) {                                       // fused auto-reset, as ns_auto_reset_kernel / _finish after a step call
       const bool done = live && Q.terminated[b] != 0;
       if (done) {
+        // (pool_row of pdegym_common.h written out: called here, the register kernels of this loop come out in another order)
         const int rows = R.pool_rows > 0 ? R.pool_rows : B;
         const long long k = R.reset_count ? (long long)R.reset_count[b] : 0;
         const size_t src = (size_t)(((long long)b + k * (long long)B) % rows) * ncell, off = (size_t)b * ncell;
@@ -1580,9 +1565,7 @@ __global__ void ns_auto_reset_kernel(NSConst C, NSPtrs<T> P, NSAutoReset<T> R, i
   const int b = blockIdx.y;
   if (b >= B || !P.terminated[b]) return;
   const int ncell = C.nx * C.ny;
-  const int rows = R.pool_rows > 0 ? R.pool_rows : B;
-  const long long k = R.reset_count ? (long long)R.reset_count[b] : 0;
-  const size_t src = (size_t)(((long long)b + k * (long long)B) % rows) * ncell, off = (size_t)b * ncell;
+  const size_t src = (size_t)pool_row(R.pool_rows, R.reset_count, b, B) * ncell, off = (size_t)b * ncell;
   T* pnew = P.p_out ? P.p_out : P.p;      // where this call left the pressure (the caller swaps p and p_out afterwards)
   for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < ncell; c += gridDim.x * blockDim.x) {
     if (R.final_obs) {

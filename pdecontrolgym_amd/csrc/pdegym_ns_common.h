@@ -7,11 +7,14 @@
 #include <cstdint>
 
 #include "pdegym.h"
+#include "pdegym_common.h"
 
 #define PDEGYM_DPP_NOP "s_nop 0\n\t"   // ahead of every DPP add of the pair blocks below (see jacobi_pair_up)
 
 namespace pdegym {
 namespace ns {
+
+using namespace wave;      // lane_left / lane_right, pinned_from_left / pinned_from_right, pool_row
 
 struct NSConst {
   int nx, ny, nt, iters, action_dim, nt_ref;
@@ -150,28 +153,6 @@ struct TileCfg {
 struct EdgeFlags {
   bool top, bot, lef, rig;
 };
-
-// lane i <- lane i-1 / lane i+1 (DPP wave_shr:1 / wave_shl:1); the lane without a source gets 0 (never used:
-// it is a domain-edge thread)
-__device__ __forceinline__ float lane_left(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x138, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float lane_right(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x130, 0xf, 0xf, true));
-}
-// double: the two halves move separately (two v_mov_b32_dpp per value)
-__device__ __forceinline__ double lane_left(double v) {
-  const long long b = __builtin_bit_cast(long long, v);
-  const int lo = __builtin_amdgcn_update_dpp(0, (int)b, 0x138, 0xf, 0xf, true);
-  const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), 0x138, 0xf, 0xf, true);
-  return __builtin_bit_cast(double, ((long long)hi << 32) | (unsigned int)lo);
-}
-__device__ __forceinline__ double lane_right(double v) {
-  const long long b = __builtin_bit_cast(long long, v);
-  const int lo = __builtin_amdgcn_update_dpp(0, (int)b, 0x130, 0xf, 0xf, true);
-  const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), 0x130, 0xf, 0xf, true);
-  return __builtin_bit_cast(double, ((long long)hi << 32) | (unsigned int)lo);
-}
 
 // y + (value of x in the lane to the left / right): the DPP shift rides on the add itself (hipcc keeps a separate
 // v_mov_b32_dpp otherwise).  s_nop 1 covers the VALU-write -> DPP-read hazard for operands hipcc cannot see into.

@@ -23,7 +23,8 @@
 
 namespace pdegym_policy {
 
-constexpr int kWave = 64;
+using pdegym::wave::kWave;
+using pdegym::wave::wave_lds_sync;
 constexpr int kWaves = 16;             // waves (= instances) per workgroup
 constexpr int kMaxWidth = 64;          // widest layer: one neuron per lane
 constexpr int kMaxLdsBytes = 160 * 1024;
@@ -73,17 +74,6 @@ inline const char* check(const pdegym_mlp& N, int n_in, int n_out, bool allow_wi
     return is_wide(N) ? "policy inside the rollout kernel: 16 observation rows do not fit into 160 KB of LDS"
                       : "policy inside the rollout kernel: the network does not fit into 160 KB of LDS";
   return nullptr;
-}
-
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_wave_barrier();
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-}
-
-__device__ __forceinline__ float activate(float v, int act) {
-  if (act == PDEGYM_MLP_TANH) return tanhf(v);
-  if (act == PDEGYM_MLP_RELU) return v > 0.f ? v : 0.f;
-  return v;
 }
 
 struct Staged {
@@ -154,7 +144,7 @@ __device__ __forceinline__ float eval(const pdegym_mlp& N, const Staged& S, cons
         acc = __builtin_fmaf(xv.z, wv.z, acc);
         acc = __builtin_fmaf(xv.w, wv.w, acc);
       }
-      const float o = activate(acc + smem[S.boff[l] + jj], N.layer[l].act);
+      const float o = pdegym_mlp_tile::activate(acc + smem[S.boff[l] + jj], N.layer[l].act);
       if (l == N.n_layers - 1) {
         out = o;
       } else {
@@ -247,10 +237,6 @@ __device__ __forceinline__ float eval_wide(const pdegym_mlp& N, const Wide& W, i
 }
 
 __device__ __forceinline__ float wide_out(const Wide& W, int wave, int k) { return W.act[wave * kWideOut + k]; }
-
-__device__ __forceinline__ float lane_value(float v, int l) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l));
-}
 
 }  // namespace pdegym_policy
 #endif

@@ -8,65 +8,15 @@
 // fields are bit-identical to NumPy; the reward norms are wave reductions (rtol 1e-14 vs BLAS ddot).
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "pdegym.h"
 #include "pdegym_common.h"
 #include "pdegym_policy.h"
 
 namespace {
 
-constexpr int kWave = 64;
-constexpr int kWavesPerBlock = 4;
-
-// Wave-wide float64 sum on DPP (result in every lane).  Round 5: __shfl_xor compiles to ds_bpermute_b32 -- two per double and
-// step, 24 LDS round trips for the two reward norms of an env-step, each ~25 cycles of the wave's SIMD (docs/HISTORY.md section 4:
-// tools/attic/ab_ns_col.py).  Same scheme as wave_reduce of the 1D kernels: lane pair, quad (quad_perm), half row, row (row_half_mirror /
-// row_mirror), lane 15 of rows 0 and 2 into rows 1 and 3 (row_bcast:15), lane 31 into rows 2, 3 (row_bcast:31); lane 63 holds the
-// total and v_readlane hands it to everybody.  A fixed order (deterministic): the reward norms were never bitwise against BLAS
-// ddot (tests: rtol 1e-12); step and rollout kernels share it, so they stay bit-identical to each other.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double dpp_move_d(double v) {      // lanes without a source (or masked rows) read 0.0
-  const long long b = __builtin_bit_cast(long long, v);
-  const int lo = __builtin_amdgcn_update_dpp(0, (int)b, CTRL, ROW_MASK, 0xf, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, ROW_MASK, 0xf, false);
-  return __builtin_bit_cast(double, ((long long)hi << 32) | (unsigned int)lo);
-}
-__device__ __forceinline__ double wave_sum_d(double v) {
-  v += dpp_move_d<0xB1, 0xf>(v);     // quad_perm:[1,0,3,2]
-  v += dpp_move_d<0x4E, 0xf>(v);     // quad_perm:[2,3,0,1]
-  v += dpp_move_d<0x141, 0xf>(v);    // row_half_mirror
-  v += dpp_move_d<0x140, 0xf>(v);    // row_mirror
-  v += dpp_move_d<0x142, 0xa>(v);    // row_bcast:15 -> rows 1, 3
-  v += dpp_move_d<0x143, 0xc>(v);    // row_bcast:31 -> rows 2, 3
-  const long long b = __builtin_bit_cast(long long, v);
-  const int lo = __builtin_amdgcn_readlane((int)b, 63), hi = __builtin_amdgcn_readlane((int)(b >> 32), 63);
-  return __builtin_bit_cast(double, ((long long)hi << 32) | (unsigned int)lo);
-}
-
-// Neighbouring lanes of a double: two v_mov_b32_dpp each (wave_shl / wave_shr; the lane without a source reads 0, which no
-// valid node ever uses).  The empty asm pins the shift where it is written: folded into a branch that masks lanes off (the
-// inner update runs on lanes 1 .. M-2 only), a DPP read from a masked-off neighbour would return 0.  ds_bpermute
-// (__shfl_up / __shfl_down, what this kernel used first) costs an LDS round trip per shuffle.
-__device__ __forceinline__ double lane_next(double v) {        // lane i <- lane i + 1
-  const long long b = __builtin_bit_cast(long long, v);
-  const int lo = __builtin_amdgcn_update_dpp(0, (int)b, 0x130, 0xf, 0xf, true);
-  const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), 0x130, 0xf, 0xf, true);
-  double r = __builtin_bit_cast(double, ((long long)hi << 32) | (unsigned int)lo);
-  asm volatile("" : "+v"(r));
-  return r;
-}
-__device__ __forceinline__ double lane_prev(double v) {        // lane i <- lane i - 1
-  const long long b = __builtin_bit_cast(long long, v);
-  const int lo = __builtin_amdgcn_update_dpp(0, (int)b, 0x138, 0xf, 0xf, true);
-  const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), 0x138, 0xf, 0xf, true);
-  double r = __builtin_bit_cast(double, ((long long)hi << 32) | (unsigned int)lo);
-  asm volatile("" : "+v"(r));
-  return r;
-}
-__device__ __forceinline__ double lane_value(double v, int l) {   // l: wave-uniform
-  const long long b = __builtin_bit_cast(long long, v);
-  const int lo = __builtin_amdgcn_readlane((int)b, l), hi = __builtin_amdgcn_readlane((int)(b >> 32), l);
-  return __builtin_bit_cast(double, ((long long)hi << 32) | (unsigned int)lo);
-}
+using namespace pdegym::wave;      // kWave, kWavesPerBlock, wave_sum, pinned_from_left / _right, lane_value, wave_lds_sync, drain_vmem, pool_row
 
 __device__ __forceinline__ double Veq(double vm, double rm, double rho) { return vm * (1 - rho / rm); }  // :270-272
 __device__ __forceinline__ double F_r(double vm, double rm, double rho, double y) { return y + rho * Veq(vm, rm, rho); }
@@ -89,11 +39,50 @@ inline TrafficConsts traffic_consts(const pdegym_params_traffic& P) {
   return K;
 }
 
+// The commands of a step: action clip (:151-156) -- np.clip(a, low, high) = min(max(a, low), high) -- and which end each one drives
+__device__ __forceinline__ void traffic_commands(const pdegym_params_traffic& P, double qc, double qs, double a0, double a1, double& q_in,
+                                                 double& q_out) {
+  const double lo = qc * 0.8, hi = 1.2 * qc;
+  a0 = fmin(fmax(a0, lo), hi);
+  a1 = fmin(fmax(a1, lo), hi);
+  if (P.sim == PDEGYM_TRAFFIC_BOTH) { q_in = a0; q_out = a1; }
+  else if (P.sim == PDEGYM_TRAFFIC_INLET) { q_in = a0; q_out = qs; }
+  else { q_in = qs; q_out = a0; }
+}
+// ... read from bufs.action (action_stride 1: one command per freeway, no second column to read)
+__device__ __forceinline__ void traffic_load_action(const pdegym_bufs_traffic& Bf, int inst, double& a0, double& a1) {
+  const int astr = Bf.action_stride > 0 ? Bf.action_stride : 2;
+  a0 = Bf.action[(size_t)inst * astr];
+  a1 = astr > 1 ? Bf.action[(size_t)inst * astr + 1] : 0.0;
+}
+
+// The end of an env-step (whole wave): reward (traffic_arz_reward.py:22) from the wave sums sv = sum (v - vs)^2 and sr = sum (r - rs)^2,
+// flags from "some node of this lane is over the limits" / "... has moved"; `time` returns to zero on termination.
+struct TrafficEnd {
+  double reward;
+  bool done, trunc;
+};
+__device__ __forceinline__ TrafficEnd traffic_step_end(const pdegym_params_traffic& P, const TrafficConsts& K, double sv, double sr, bool over,
+                                                       bool moved, double& time, double vs, double rs, int lane) {
+  // ||v - vs|| / vs + ||r - rs|| / rs: the two square roots and the two divisions act on wave-uniform values, so they share ONE
+  // float64 sqrt and ONE division sequence -- lane 0 takes the speed term, every other lane the density term (same operands, same
+  // operations: the same bits as two scalar evaluations)
+  const double term_ = sqrt(lane == 0 ? sv : sr) / (lane == 0 ? vs : rs);
+  TrafficEnd e;
+  e.reward = -(lane_value(term_, 0) + lane_value(term_, 1));
+  const bool term = time >= K.t_end;               // :106 (seconds compared with a step count -- kept)
+  if (term) time = 0.0;
+  bool trunc = false;
+  if (P.limit) trunc = __any(over);
+  e.trunc = trunc || !__any(moved);                // exact steady state (:127-128)
+  e.done = (P.sim == PDEGYM_TRAFFIC_OUTLET_TRAIN) ? term : (term || e.reward > -0.00023);
+  return e;
+}
+
 // One env-step of one freeway held by one wave (M <= 64: node j in lane j): action clip, control_freq Lax-Wendroff sub-steps,
 // speed, reward, flags.  Shared by traffic_step_kernel and every iteration of traffic_rollout_kernel.
-struct TrafficStepOut {
-  double v, reward, vs;
-  bool done, trunc;
+struct TrafficStepOut : TrafficEnd {
+  double v, vs;
 };
 
 __device__ __forceinline__ TrafficStepOut traffic_step_wave(const pdegym_params_traffic& P, const TrafficConsts& K, double& r, double& y,
@@ -101,19 +90,12 @@ __device__ __forceinline__ TrafficStepOut traffic_step_wave(const pdegym_params_
                                                             const int lane) {
   const int M = P.M;
   const bool in = lane < M;
-  const double vm = P.vm, rm = P.rm, dt = P.dt, dx = P.dx;
+  const double vm = P.vm, rm = P.rm;
   const double vs = Veq(vm, rm, rs);              // :66-72
-  const double qs = rs * vs;
-  // action clip (:151-156) -- np.clip(a, low, high) = min(max(a, low), high)
-  const double lo = qc * 0.8, hi = 1.2 * qc;
-  a0 = fmin(fmax(a0, lo), hi);
-  a1 = fmin(fmax(a1, lo), hi);
   double q_in, q_out;
-  if (P.sim == PDEGYM_TRAFFIC_BOTH) { q_in = a0; q_out = a1; }
-  else if (P.sim == PDEGYM_TRAFFIC_INLET) { q_in = a0; q_out = qs; }
-  else { q_in = qs; q_out = a0; }
+  traffic_commands(P, qc, rs * vs, a0, a1, q_in, q_out);
 
-  time = time + dt;                               // :146
+  time = time + P.dt;                             // :146
   const double c1 = K.c1, c2 = K.c2, c3 = K.c3, c4 = K.c4;
   if (time < P.T) {                               // :172  (time does not change inside the loop)
     for (int s = 0; s < P.control_freq; ++s) {
@@ -127,14 +109,15 @@ __device__ __forceinline__ TrafficStepOut traffic_step_wave(const pdegym_params_
       const double ve = Veq(vm, rm, r);
       const double yb = (first ? q_in : q_out) - r * ve;
       y = (first || last) ? yb : y;
-      // nodal fluxes and the "plus" midpoint (:201-216)
+      // nodal fluxes and the "plus" midpoint (:201-216); the neighbours' values arrive by pinned lane shifts (pdegym_common.h: the
+      // inner update below runs on lanes 1 .. M-2 only, and the lane without a source reads 0, which no valid node ever uses)
       const double fr = y + r * ve, fy = y * (y / r + ve);      // F_r, F_y with the shared Veq(r)
-      const double r_p = lane_next(r), y_p = lane_next(y), fr_p = lane_next(fr), fy_p = lane_next(fy);
+      const double r_p = pinned_from_right(r), y_p = pinned_from_right(y), fr_p = pinned_from_right(fr), fy_p = pinned_from_right(fy);
       const double r_pm = 0.5 * (r_p + r) - c1 * (fr_p - fr);
       const double y_pm = (0.5 * (y_p + y) - c1 * (fy_p - fy)) - c2 * (y_p + y);
       const double Frp = F_r(vm, rm, r_pm, y_pm), Fyp = F_y(vm, rm, r_pm, y_pm);
       // the "minus" midpoint of node j is the "plus" midpoint of node j-1
-      const double Frm = lane_prev(Frp), Fym = lane_prev(Fyp), y_mm = lane_prev(y_pm);
+      const double Frm = pinned_from_left(Frp), Fym = pinned_from_left(Fyp), y_mm = pinned_from_left(y_pm);
       if (lane >= 1 && lane <= M - 2) {           // inner update :219-223
         r = r - c3 * (Frp - Frm);
         y = y - (c3 * (Fyp - Fym) + c4 * (y_pm + y_mm));
@@ -144,52 +127,52 @@ __device__ __forceinline__ TrafficStepOut traffic_step_wave(const pdegym_params_
   TrafficStepOut o;
   o.vs = vs;
   o.v = y / r + Veq(vm, rm, r);                    // :227
-  // reward (traffic_arz_reward.py:22)
   const double dv = in ? o.v - vs : 0.0, dr = in ? r - rs : 0.0;
-  // ||v - vs|| / vs + ||r - rs|| / rs: the two square roots and the two divisions act on wave-uniform values, so they share ONE
-  // float64 sqrt and ONE division sequence -- lane 0 takes the speed term, every other lane the density term (same operands, same
-  // operations: the same bits as two scalar evaluations)
-  const double sv = wave_sum_d(dv * dv), sr = wave_sum_d(dr * dr);
-  const double term_ = sqrt(lane == 0 ? sv : sr) / (lane == 0 ? vs : rs);
-  o.reward = -(lane_value(term_, 0) + lane_value(term_, 1));
-  const bool term = time >= K.t_end;               // :106 (seconds compared with a step count -- kept)
-  if (term) time = 0.0;
-  bool trunc = false;
-  if (P.limit) trunc = __any(in && (o.v > vm || r > rm));
-  o.trunc = trunc || !__any(in && (dr != 0.0 || dv != 0.0));   // exact steady state (:127-128)
-  o.done = (P.sim == PDEGYM_TRAFFIC_OUTLET_TRAIN) ? term : (term || o.reward > -0.00023);
+  static_cast<TrafficEnd&>(o) = traffic_step_end(P, K, wave_sum(dv * dv), wave_sum(dr * dr), in && (o.v > vm || r > rm),
+                                                 in && (dr != 0.0 || dv != 0.0), time, vs, rs, lane);
   return o;
 }
 
-// observation row of one freeway: (r, v), or ((r - rs)/rs, (v - vs)/vs) for outlet-train (:227-230)
+// observation of node j of one freeway: (r, v), or ((r - rs)/rs, (v - vs)/vs) for outlet-train (:227-230)
 __device__ __forceinline__ void traffic_emit_obs(const pdegym_params_traffic& P, double* o, double r, double v, double rs, double vs,
-                                                 int lane) {
+                                                 int j) {
   const int M = P.M;
-  if (lane < M) {
+  if (j < M) {
     if (P.sim == PDEGYM_TRAFFIC_OUTLET_TRAIN) {
-      o[lane] = (r - rs) / rs;
-      o[M + lane] = (v - vs) / vs;
+      o[j] = (r - rs) / rs;
+      o[M + j] = (v - vs) / vs;
     } else {
-      o[lane] = r;
-      o[M + lane] = v;
+      o[j] = r;
+      o[M + j] = v;
     }
   }
 }
 
-// pool row of the k-th restart of instance b (include/pdegym.h)
-__device__ __forceinline__ int traffic_pool_row(const pdegym_bufs_traffic& Bf, int inst, int B) {
-  const int rows = Bf.reset_pool_rows > 0 ? Bf.reset_pool_rows : B;
-  const long long k = Bf.reset_count ? (long long)Bf.reset_count[inst] : 0;
-  return (int)(((long long)inst + k * B) % rows);
-}
-
-// TrafficPDE1D.reset of one node (traffic_arz_env.py:256-258; the expressions of traffic_reset_kernel)
+// TrafficPDE1D.reset of one node (traffic_arz_env.py:256-258):
+//   r = rs*(sin(3x/L pi)*0.1 + 1) ; y = qs - vm r + vm/rm r^2 ; v = y/r + Veq(r)
 __device__ __forceinline__ void traffic_restart_node(const pdegym_params_traffic& P, double rs, double prof, double& r, double& y,
                                                      double& v) {
   const double vs = Veq(P.vm, P.rm, rs), qs = rs * vs;
   r = rs * prof;
   y = (qs * 1.0 - P.vm * r) + (P.vm / P.rm) * (r * r);
   v = y / r + Veq(P.vm, P.rm, r);
+}
+
+// Fused auto-reset of a freeway held in registers (wave-uniform): the final observation, rs of the pool row of this restart
+// (`extra`: restarts made inside the launch and not yet in reset_count), the nodes restarted with profile value `prof`, the
+// observation of the restarted state into `obs`.  What goes back to memory besides is each kernel's own business.
+__device__ __forceinline__ void traffic_auto_reset(const pdegym_params_traffic& P, const pdegym_bufs_traffic& Bf, int inst, int B, int extra,
+                                                   double prof, double& r, double& y, double& rs, double v, double vs, double* obs,
+                                                   int lane) {
+  const int M = P.M;
+  if (Bf.final_obs) traffic_emit_obs(P, Bf.final_obs + (size_t)inst * 2 * M, r, v, rs, vs, lane);
+  rs = Bf.reset_rs[pool_row(Bf.reset_pool_rows, Bf.reset_count, inst, B, extra)];
+  if (lane < M) {
+    double v0;
+    traffic_restart_node(P, rs, prof, r, y, v0);
+    obs[lane] = r;
+    obs[M + lane] = v0;
+  }
 }
 
 __global__ __launch_bounds__(kWave* kWavesPerBlock) void traffic_step_kernel(pdegym_params_traffic P, pdegym_bufs_traffic Bf, TrafficConsts K, int B) {
@@ -200,38 +183,26 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void traffic_step_kernel(pde
   const bool in = lane < M;
   double r = in ? Bf.r[(size_t)inst * M + lane] : 1.0;
   double y = in ? Bf.y[(size_t)inst * M + lane] : 0.0;
-  const double rs = Bf.rs[inst];
-  const int astr = Bf.action_stride > 0 ? Bf.action_stride : 2;      // 1: one command per freeway (no second column to read)
-  const double a0 = Bf.action[(size_t)inst * astr], a1 = astr > 1 ? Bf.action[(size_t)inst * astr + 1] : 0.0;
+  double rs = Bf.rs[inst];
+  double a0, a1;
+  traffic_load_action(Bf, inst, a0, a1);
   double time = Bf.time[inst];
   const TrafficStepOut o = traffic_step_wave(P, K, r, y, time, rs, Bf.qs_clip[inst], a0, a1, lane);
-  if (Bf.reset_rs && (o.done || o.trunc)) {       // fused auto-reset (wave-uniform)
-    if (Bf.final_obs) traffic_emit_obs(P, Bf.final_obs + (size_t)inst * 2 * M, r, o.v, rs, o.vs, lane);
-    const double rs_new = Bf.reset_rs[traffic_pool_row(Bf, inst, B)];
-    double v0 = 0.0;
-    if (in) {
-      traffic_restart_node(P, rs_new, Bf.reset_profile[lane], r, y, v0);
-      Bf.r[(size_t)inst * M + lane] = r;
-      Bf.y[(size_t)inst * M + lane] = y;
-      double* ob = Bf.obs + (size_t)inst * 2 * M;
-      ob[lane] = r;
-      ob[M + lane] = v0;
-    }
+  double* ob = Bf.obs + (size_t)inst * 2 * M;
+  if (Bf.reset_rs && (o.done || o.trunc)) {       // wave-uniform
+    traffic_auto_reset(P, Bf, inst, B, 0, in ? Bf.reset_profile[lane] : 1.0, r, y, rs, o.v, o.vs, ob, lane);
+    time = 0.0;
     if (lane == 0) {
-      Bf.rs[inst] = rs_new;
+      Bf.rs[inst] = rs;
       if (Bf.reset_count) Bf.reset_count[inst] += 1;
-      Bf.time[inst] = 0.0;
-      Bf.reward[inst] = o.reward;
-      Bf.done[inst] = o.done ? 1 : 0;
-      Bf.truncated[inst] = o.trunc ? 1 : 0;
     }
-    return;
+  } else {
+    traffic_emit_obs(P, ob, r, o.v, rs, o.vs, lane);
   }
   if (in) {
     Bf.r[(size_t)inst * M + lane] = r;
     Bf.y[(size_t)inst * M + lane] = y;
   }
-  traffic_emit_obs(P, Bf.obs + (size_t)inst * 2 * M, r, o.v, rs, o.vs, lane);
   if (lane == 0) {
     Bf.time[inst] = time;
     Bf.reward[inst] = o.reward;
@@ -287,9 +258,9 @@ __global__ __launch_bounds__(kWave* pdegym_policy::kWaves) void traffic_rollout_
     return (!has_policy && t0 + lane < Ro.T && col < A) ? Ro.actions[((size_t)(t0 + lane) * B + inst) * A + col] : 0.0;
   };
   double b0 = command_batch(0, 0), b1 = command_batch(0, 1);
-  // vmcnt(0) as a real instruction wherever the open-loop form loads (here, at a batch hand-over, after a restart): the wait-count pass
-  // then knows that nothing is pending at the joins of the loop and puts no static wait into its steady state
-  if constexpr (!has_policy) __builtin_amdgcn_s_waitcnt(0x0F70);
+  // drain_vmem() wherever the open-loop form loads (here, at a batch hand-over, after a restart): the wait-count pass then knows
+  // that nothing is pending at the joins of the loop and puts no static wait into its steady state
+  if constexpr (!has_policy) drain_vmem();
   for (int t = 0; t < Ro.T; ++t) {
     double* arow = Ro.actions + ((size_t)t * B + inst) * A;
     double a0, a1 = 0.0;
@@ -297,7 +268,7 @@ __global__ __launch_bounds__(kWave* pdegym_policy::kWaves) void traffic_rollout_
     if (!has_policy && tj == 0 && t) {      // wave-uniform, once per 64 env-steps; the loop's only wait for memory
       b0 = command_batch(t, 0);
       b1 = command_batch(t, 1);
-      __builtin_amdgcn_s_waitcnt(0x0F70);
+      drain_vmem();
     }
     if constexpr (has_policy) {
       const double* xrow = Ro.obs + (size_t)t * slot + (size_t)inst * D;
@@ -311,10 +282,10 @@ __global__ __launch_bounds__(kWave* pdegym_policy::kWaves) void traffic_rollout_
         c1 = A > 1 ? pol::wide_out(Wd, wave, 1) : 0.f;
       } else {
         for (int j = lane; j < xpad; j += kWave) xw[j] = j < D ? (float)xrow[j] : 0.f;
-        pol::wave_lds_sync();
+        wave_lds_sync();
         const float o = pol::eval(N, St, pol_smem, xw, hw, D, lane);
-        c0 = pol::lane_value(o, 0);
-        c1 = A > 1 ? pol::lane_value(o, 1) : 0.f;
+        c0 = lane_value(o, 0);
+        c1 = A > 1 ? lane_value(o, 1) : 0.f;
       }
       if (N.noise) {
         const float* nz = N.noise + ((size_t)t * B + inst) * N.noise_stride;
@@ -337,20 +308,11 @@ __global__ __launch_bounds__(kWave* pdegym_policy::kWaves) void traffic_rollout_
     }
     const TrafficStepOut o = traffic_step_wave(P, K, r, y, time, rs, qc, a0, a1, lane);
     double* onext = Ro.obs + (size_t)(t + 1) * slot + (size_t)inst * D;
-    if (Bf.reset_rs && (o.done || o.trunc)) {     // fused auto-reset, as in traffic_step_kernel
-      if (Bf.final_obs) traffic_emit_obs(P, Bf.final_obs + (size_t)inst * D, r, o.v, rs, o.vs, lane);
-      const int rows = Bf.reset_pool_rows > 0 ? Bf.reset_pool_rows : B;
-      const long long k = (Bf.reset_count ? (long long)Bf.reset_count[inst] : 0) + restarts;
-      rs = Bf.reset_rs[(int)(((long long)inst + k * B) % rows)];
+    if (Bf.reset_rs && (o.done || o.trunc)) {     // wave-uniform
+      traffic_auto_reset(P, Bf, inst, B, restarts, prof, r, y, rs, o.v, o.vs, onext, lane);
       ++restarts;
-      double v0 = 0.0;
-      if (in) {
-        traffic_restart_node(P, rs, prof, r, y, v0);
-        onext[lane] = r;
-        onext[M + lane] = v0;
-      }
       time = 0.0;
-      if constexpr (!has_policy) __builtin_amdgcn_s_waitcnt(0x0F70);
+      if constexpr (!has_policy) drain_vmem();
     } else {
       traffic_emit_obs(P, onext, r, o.v, rs, o.vs, lane);
     }
@@ -380,12 +342,9 @@ __global__ __launch_bounds__(kWave* pdegym_policy::kWaves) void traffic_rollout_
 
 // ---- rows of more than 64 nodes (finer grids than the reference notebook's M = 51): one wave still owns one freeway,
 // node j lives in lane j % 64; the fields and the per-sub-step intermediates go through a wave-private LDS region so that
-// every node reaches its neighbours (wave-level ordering only: no workgroup barrier).  Same expressions, same order.
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_wave_barrier();
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-}
-
+// every node reaches its neighbours (wave-level ordering only: no workgroup barrier).  Same expressions, same order; the commands
+// and the end of the step are the register kernel's (traffic_commands, traffic_step_end), the sub-step loop and the auto-reset are
+// strided loops over the LDS rows and stay this kernel's own.
 __global__ __launch_bounds__(kWave* kWavesPerBlock) void traffic_step_wide_kernel(pdegym_params_traffic P, pdegym_bufs_traffic Bf, TrafficConsts K, int B) {
   extern __shared__ double tl[];
   const int lane = threadIdx.x & (kWave - 1);
@@ -400,25 +359,17 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void traffic_step_wide_kerne
   double* YPM = FY + M;
   double* FRP = YPM + M;
   double* FYP = FRP + M;
-  const double vm = P.vm, rm = P.rm, dt = P.dt, dx = P.dx;
+  const double vm = P.vm, rm = P.rm;
   for (int j = lane; j < M; j += kWave) {
     R[j] = Bf.r[(size_t)inst * M + j];
     Y[j] = Bf.y[(size_t)inst * M + j];
   }
   const double rs = Bf.rs[inst];
   const double vs = Veq(vm, rm, rs);
-  const double qs = rs * vs;
-  const double qc = Bf.qs_clip[inst];
-  const int astr = Bf.action_stride > 0 ? Bf.action_stride : 2;      // 1: one command per freeway (no second column to read)
-  double a0 = Bf.action[(size_t)inst * astr], a1 = astr > 1 ? Bf.action[(size_t)inst * astr + 1] : 0.0;
-  const double lo = qc * 0.8, hi = 1.2 * qc;
-  a0 = fmin(fmax(a0, lo), hi);
-  a1 = fmin(fmax(a1, lo), hi);
-  double q_in, q_out;
-  if (P.sim == PDEGYM_TRAFFIC_BOTH) { q_in = a0; q_out = a1; }
-  else if (P.sim == PDEGYM_TRAFFIC_INLET) { q_in = a0; q_out = qs; }
-  else { q_in = qs; q_out = a0; }
-  double time = Bf.time[inst] + dt;
+  double a0, a1, q_in, q_out;
+  traffic_load_action(Bf, inst, a0, a1);
+  traffic_commands(P, Bf.qs_clip[inst], rs * vs, a0, a1, q_in, q_out);
+  double time = Bf.time[inst] + P.dt;
   const double c1 = K.c1, c2 = K.c2, c3 = K.c3, c4 = K.c4;
   wave_lds_sync();
   if (time < P.T) {
@@ -471,24 +422,11 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void traffic_step_wide_kerne
     moved = moved || dr != 0.0 || dv != 0.0;
     Bf.r[(size_t)inst * M + j] = r;
     Bf.y[(size_t)inst * M + j] = y;
-    if (P.sim == PDEGYM_TRAFFIC_OUTLET_TRAIN) {
-      o[j] = (r - rs) / rs;
-      o[M + j] = (v - vs) / vs;
-    } else {
-      o[j] = r;
-      o[M + j] = v;
-    }
+    traffic_emit_obs(P, o, r, v, rs, vs, j);
   }
-  const double nv = sqrt(wave_sum_d(sv)), nr = sqrt(wave_sum_d(sr));
-  const double reward = -(nv / vs + nr / rs);
-  const bool term = time >= K.t_end;
-  if (term) time = 0.0;
-  bool trunc = false;
-  if (P.limit) trunc = __any(over);
-  trunc = trunc || !__any(moved);
-  const bool done = (P.sim == PDEGYM_TRAFFIC_OUTLET_TRAIN) ? term : (term || reward > -0.00023);
-  if (Bf.reset_rs && (done || trunc)) {           // fused auto-reset, as in traffic_step_kernel (each lane re-reads its own stores)
-    const double rs_new = Bf.reset_rs[traffic_pool_row(Bf, inst, B)];
+  const TrafficEnd e = traffic_step_end(P, K, wave_sum(sv), wave_sum(sr), over, moved, time, vs, rs, lane);
+  if (Bf.reset_rs && (e.done || e.trunc)) {       // fused auto-reset, as traffic_auto_reset (each lane re-reads its own stores)
+    const double rs_new = Bf.reset_rs[pool_row(Bf.reset_pool_rows, Bf.reset_count, inst, B)];
     double* fo = Bf.final_obs ? Bf.final_obs + (size_t)inst * 2 * M : nullptr;
     for (int j = lane; j < M; j += kWave) {
       if (fo) {
@@ -510,9 +448,9 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void traffic_step_wide_kerne
   }
   if (lane == 0) {
     Bf.time[inst] = time;
-    Bf.reward[inst] = reward;
-    Bf.done[inst] = done ? 1 : 0;
-    Bf.truncated[inst] = trunc ? 1 : 0;
+    Bf.reward[inst] = e.reward;
+    Bf.done[inst] = e.done ? 1 : 0;
+    Bf.truncated[inst] = e.trunc ? 1 : 0;
   }
 }
 
@@ -522,13 +460,10 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void traffic_reset_kernel(pd
   const int inst = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
   if (inst >= B || (mask && !mask[inst])) return;
   const int M = P.M;
+  const double rs = Bf.rs[inst];
   for (int j = lane; j < M; j += kWave) {
-    const double rs = Bf.rs[inst];
-    const double vs = Veq(P.vm, P.rm, rs), qs = rs * vs;
-    // :256-258   r = rs*(sin(3x/L pi)*0.1 + 1) ; y = qs - vm r + vm/rm r^2 ; v = y/r + Veq(r)
-    const double r = rs * profile[j];
-    const double y = (qs * 1.0 - P.vm * r) + (P.vm / P.rm) * (r * r);
-    const double v = y / r + Veq(P.vm, P.rm, r);
+    double r, y, v;
+    traffic_restart_node(P, rs, profile[j], r, y, v);
     Bf.r[(size_t)inst * M + j] = r;
     Bf.y[(size_t)inst * M + j] = y;
     Bf.obs[(size_t)inst * 2 * M + j] = r;
@@ -591,18 +526,20 @@ int pdegym_traffic_rollout(const pdegym_params_traffic* prm, const pdegym_bufs_t
     if (const char* why = pdegym_policy::check(net, 2 * prm->M, A, true)) return pdegym::fail(-2, why);
     wide = pdegym_policy::is_wide(net);
     lds_bytes = (size_t)pdegym_policy::lds_floats(net, 2 * prm->M) * sizeof(float);
-    static signed char attr[2][pdegym::kMaxDevices] = {};
-    const void* fn = wide ? reinterpret_cast<const void*>(&traffic_rollout_kernel<true, true>) : reinterpret_cast<const void*>(&traffic_rollout_kernel<false, true>);
-    if (!pdegym::raise_dynamic_lds_limit(fn, pdegym_policy::kMaxLdsBytes, attr[wide ? 1 : 0]))
-      return pdegym::fail(-4, "cannot raise the dynamic LDS limit of traffic_rollout_kernel");
   }
   const dim3 grid((B + pdegym_policy::kWaves - 1) / pdegym_policy::kWaves), block(kWave * pdegym_policy::kWaves);
-  if (wide)
-    hipLaunchKernelGGL((traffic_rollout_kernel<true, true>), grid, block, lds_bytes, (hipStream_t)stream, *prm, *buf, *ro, net, traffic_consts(*prm), B);
-  else if (ro->policy)
-    hipLaunchKernelGGL((traffic_rollout_kernel<false, true>), grid, block, lds_bytes, (hipStream_t)stream, *prm, *buf, *ro, net, traffic_consts(*prm), B);
-  else
-    hipLaunchKernelGGL((traffic_rollout_kernel<false, false>), grid, block, lds_bytes, (hipStream_t)stream, *prm, *buf, *ro, net, traffic_consts(*prm), B);
+  bool ok = true;
+  auto launch = [&](auto wide_tag, auto policy_tag) {
+    constexpr bool W = decltype(wide_tag)::value, Pol = decltype(policy_tag)::value;
+    static signed char attr[pdegym::kMaxDevices] = {};      // one per kernel: a static of each instantiation of this lambda
+    if constexpr (Pol) ok = pdegym::raise_dynamic_lds_limit(reinterpret_cast<const void*>(&traffic_rollout_kernel<W, Pol>), pdegym_policy::kMaxLdsBytes, attr);
+    if (ok)
+      hipLaunchKernelGGL((traffic_rollout_kernel<W, Pol>), grid, block, lds_bytes, (hipStream_t)stream, *prm, *buf, *ro, net, traffic_consts(*prm), B);
+  };
+  if (wide) launch(std::true_type{}, std::true_type{});
+  else if (ro->policy) launch(std::false_type{}, std::true_type{});
+  else launch(std::false_type{}, std::false_type{});
+  if (!ok) return pdegym::fail(-4, "cannot raise the dynamic LDS limit of traffic_rollout_kernel");
   return pdegym::check_launch("traffic_rollout");
 }
 

@@ -16,19 +16,12 @@
 
 namespace {
 
-constexpr int kWave = 64;
-constexpr int kWavesPerBlock = 4;
+using namespace pdegym::wave;      // kWave, kWavesPerBlock, wave_lds_sync
 constexpr int kMaxNx = 4096;
 
 // index of the highest lane set in a chunk's ballot (chunks are visited left to right, so a later hit wins)
 __device__ __forceinline__ int rightmost(unsigned long long ballot, int chunk_base, int so_far) {
   return ballot ? chunk_base + 63 - __builtin_clzll(ballot) : so_far;
-}
-
-__device__ __forceinline__ int wave_max_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
-  return v;
 }
 
 // brain_tumor_env.py:221-245, one interior node.
@@ -122,8 +115,7 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void tumor_step_kernel(pdegy
   double reward = 0.0, T1 = nan, T2 = nan, treat_r = 0.0, applied = 0.0;
   bool term = false, lethal = false;
   for (int day = 0; day < max_days; ++day) {
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                 // the row written by the previous day is visible
+    wave_lds_sync();                                                   // the row written by the previous day is visible
     t += 1;
     const int stage0 = stage;
     const bool therapy = stage0 == PDEGYM_TUMOR_THERAPY;
@@ -220,8 +212,7 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void tumor_step_kernel(pdegy
     if (mode == PDEGYM_TUMOR_RUN_GROWTH && stage != PDEGYM_TUMOR_GROWTH) break;
   }
   if constexpr (!SINGLE_DAY) {
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wave_lds_sync();
     for (int i = lane; i < nx; i += kWave) g[i] = cur[i];
   }
   if (lane != 0) return;

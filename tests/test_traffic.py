@@ -69,15 +69,19 @@ def test_traffic_hip_matches_reference_golden(golden_traffic, case):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("sim,cf,B", [("inlet", 1, 37), ("outlet", 2, 64), ("both", 1, 5), ("outlet-train", 3, 130)])
-def test_traffic_hip_matches_oracle_batched(sim, cf, B):
-    """Per-instance steady states / actions, masked reset mid-run: every field bit-exact vs the oracle."""
+@pytest.mark.parametrize("sim,cf,B,X", [
+    pytest.param("inlet", 1, 37, 500, id="inlet-1-37"), pytest.param("outlet", 2, 64, 500, id="outlet-2-64"),
+    pytest.param("both", 1, 5, 500, id="both-1-5"), pytest.param("outlet-train", 3, 130, 500, id="outlet-train-3-130"),
+    # the LDS kernel of rows beyond one node per lane: M = 66 (the first such rows), M = 151 (normalised observations; two commands)
+    ("inlet", 2, 7, 650), ("outlet-train", 3, 9, 1500), ("both", 1, 5, 1500)])
+def test_traffic_hip_matches_oracle_batched(sim, cf, B, X):
+    """Per-instance steady states / actions, masked reset mid-run: every field bit-exact vs the oracle (X = 500: M = 51)."""
     from oracle import pde_oracle as po
     from pdecontrolgym_amd.batch_traffic import TrafficBatch
     rng = np.random.default_rng(B)
     rs = rng.choice([0.115, 0.12, 0.125], B)
-    orc = po.TrafficOracle(240, 0.25, 500, 10, sim, 40, 0.16, 60, True, cf)
-    env = TrafficBatch(240, 0.25, 500, 10, sim, 40, 0.16, 60, True, cf, num_envs=B, device="cuda")
+    orc = po.TrafficOracle(240, 0.25, X, 10, sim, 40, 0.16, 60, True, cf)
+    env = TrafficBatch(240, 0.25, X, 10, sim, 40, 0.16, 60, True, cf, num_envs=B, device="cuda")
     qclip = rng.choice([0.115, 0.12, 0.125], B)
     qclip = qclip * (40 * (1 - qclip / 0.16))
     env.set_action_bounds(qclip)
@@ -100,7 +104,7 @@ def test_traffic_hip_matches_oracle_batched(sim, cf, B):
     mask = (np.arange(B) % 3 == 0)
     rs2 = np.where(mask, 0.125, rs)
     env.reset(rs2, mask=torch.tensor(mask.astype(np.uint8)))
-    fresh = po.TrafficOracle(240, 0.25, 500, 10, sim, 40, 0.16, 60, True, cf)
+    fresh = po.TrafficOracle(240, 0.25, X, 10, sim, 40, 0.16, 60, True, cf)
     fresh.reset(rs2, qclip)
     np.testing.assert_array_equal(env.t["r"].cpu().numpy()[mask], fresh.r[mask])
     np.testing.assert_array_equal(env.t["r"].cpu().numpy()[~mask], orc.r[~mask])

@@ -149,6 +149,10 @@ class BrainTumor1D(PDEEnv1D):
             self.dosage_vs_time[self.time_index] = applied_dosage
             if self.stage == "Post-Therapy":
                 self.firstPostTherapyDay = self.time_index + 1
+            if isinstance(self.dx, (int, np.integer)) and treatmentRadius != 0:
+                # the reference's radius is ``index * dx + 25``: a NumPy integer when dx is an int (the shipped dx=1), and
+                # ``radius ** -0.685`` then takes NumPy's power loop, whose last bit differs from pow() at some radii
+                treatmentRadius = np.int64(treatmentRadius)
             reward = self.reward_class.reward(
                 uVec=self.u, time_index=self.time_index, terminate=self._terminated, truncate=self._truncated,
                 action=control, verbose=self.verbose, t_benchmark=self.t_benchmark, tumor_radius=T1,

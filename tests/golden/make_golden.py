@@ -533,12 +533,364 @@ def gen_tumor(src, out=HERE):
     np.savez_compressed(os.path.join(out, "tumor.npz"), **store)
 
 
+# ---- parameter sweeps: the ranges the differential fuzzers draw (tests/fuzz_*.py), pinned to the reference ------------------
+# Every case stores its own constructor parameters next to its data ("<case>/<name>" keys: scalars, strings, the BC name
+# array), so the consumers (tests/test_oracle_sweep.py, tests/test_gpu_sweep.py) need no mirrored table.  Cases are small: a
+# handful of env-steps on the smallest grid that reaches the code path.  Configurations the reference rejects are recorded
+# under "unpinnable/<name>" with the exception class it raises, and the generator asserts that they still raise.
+def _scalars(store, prefix, **kw):
+    """Constructor parameters as data: numbers as 0-d float64 / int64 / bool arrays, strings (None -> "") as 0-d str arrays."""
+    for k, v in kw.items():
+        if v is None or isinstance(v, str):
+            store[f"{prefix}/{k}"] = np.array("" if v is None else v)
+        elif isinstance(v, (bool, np.bool_)):
+            store[f"{prefix}/{k}"] = np.bool_(v)
+        elif isinstance(v, (int, np.integer)):
+            store[f"{prefix}/{k}"] = np.int64(v)
+        else:
+            store[f"{prefix}/{k}"] = np.float64(v)
+
+
+def _raises(fn):
+    """Name of the exception class fn() raises (the generator fails if it does not raise)."""
+    try:
+        fn()
+    except Exception as e:      # noqa: BLE001 -- the class is the datum
+        return type(e).__name__
+    raise AssertionError("the reference no longer rejects this configuration")
+
+
+def _ragged_slots(epl):
+    """Row widths of tests/test_gpu_buffer_contract.py (STEP_CASES): a slot count that takes ``epl`` elements per lane, leaves a
+    straddling lane and idle lanes.  tests/test_oracle_sweep.py checks that the fixture still covers that module's list."""
+    s = 64 * (epl - 1) + 37 if epl > 1 else 37
+    return s + 1 if s % epl == 0 else s
+
+
+SENSING_T = [("Dirchilet", "full", None), ("Neumann", "full", None), ("Dirchilet", "collocated", None), ("Neumann", "collocated", None),
+             ("Dirchilet", "opposite", "Neumann"), ("Neumann", "opposite", "Neumann"), ("Dirchilet", "opposite", "Dirchilet"),
+             ("Neumann", "opposite", "Dirchilet")]
+SENSING_P = SENSING_T[:6]       # parabolic: opposite / Dirchilet raises by design (parabolic.py:85,114)
+
+
+def gen_sweep_1d(src, out=HERE):
+    """TransportPDE1D and ReactionDiffusionPDE1D at one row width per class the step kernels dispatch on (elements per lane 1 ..
+    32 with a ragged tail, the whole-wave widths 64 .. 512, one row past the register limit), X in {0.5, 1, 2}, max_control_value
+    in {1, 3, 20} with and without normalize, S in {1, 2, 7, 33, 100}, every control / sensing combination the reference accepts,
+    a truncating max_state_value, limit_pde_state_size=False, float64 beta / float64 and Python-float controls.  nt >= 120
+    throughout (TunedReward1D looks 100 rows back); with S in {33, 100} the sixth step is clipped by the end of the episode."""
+    store = {}
+    rng = np.random.default_rng(20261)
+    widths = [("e%d" % e, _ragged_slots(e)) for e in (1, 2, 3, 4, 5, 6, 8, 12, 16, 24, 32)] + \
+             [("full%d" % w, w) for w in (64, 128, 256, 512)] + [("wide", 2049)]
+    Ss, Xs, mcvs = [1, 2, 7, 33, 100], [1, 0.5, 2], [20, 1, 3]
+    for kind, cls, sens in (("transport", "TransportPDE1D", SENSING_T), ("parabolic", "ReactionDiffusionPDE1D", SENSING_P)):
+        ghost = 1 if kind == "parabolic" else 0
+        for wi, (wname, slots) in enumerate(widths):
+            n = 2049 if wname == "wide" else slots + ghost      # array length; the reference's nx excludes the parabolic ghost node
+            nx = n - ghost
+            big = n > 256
+            ct, sl, st = sens[wi % len(sens)]
+            if big and sl == "full":                # the file's size: full observations only with rows of up to 256 nodes
+                sl = "collocated"
+            S = Ss[(wi + ghost) % len(Ss)]
+            X = Xs[(wi + 2 * ghost) % len(Xs)]
+            mcv = mcvs[(wi + ghost) % len(mcvs)]
+            norm = (wi % 2 == 0)
+            if kind == "parabolic" and ct == "Neumann" and norm and S > 7:
+                S = 7                               # normalize scales the Neumann neighbour every sub-step: keep the rows finite
+            dx = X / nx
+            dt = 0.25 * dx * dx if kind == "parabolic" else 0.5 * dx
+            nsteps = 7 if (S >= 33 and not big) else 6          # the seventh is a post-terminal call
+            nt1 = 5 * S + max(S // 3, 1) if S >= 33 else 120 + S     # nt - 1: S >= 33 clips the sixth step
+            kw = dict(T=nt1 * dt, dt=dt, X=X, dx=dx, normalize=norm, sensing_loc=sl, control_type=ct, sensing_type=st,
+                      limit_pde_state_size=True, max_state_value=1e10, max_control_value=mcv, control_sample_rate=S * dt)
+            x = np.linspace(0, 1, n)
+            if big:
+                init = (np.ones(n) * rng.uniform(1, 8)).astype(np.float32)
+            else:
+                init = (rng.uniform(1, 8) * (1 + 0.3 * np.sin(2 * np.pi * x * rng.uniform(0.5, 3)))).astype(np.float32)
+            beta = cheb_beta(x, rng.uniform(7, 8.4), 50 if kind == "parabolic" else 5)
+            action_as = "f32arr"
+            name = f"{kind[0].upper()}_{wname}"
+            if wname == "e5":
+                kw["limit_pde_state_size"] = False
+                kw["max_state_value"] = 1.0         # would truncate at once if the switch were ignored
+            acts = rng.uniform(-1, 1, nsteps).astype(np.float32)
+            with np.errstate(all="ignore"):
+                d = run_1d(src, cls, kw, init, beta, acts, (nt1, -1e3, 3e2), action_as=action_as)
+                if wname == "e3":                   # truncation: a max_state_value half way between the smallest and the largest row norm
+                    norms = np.array([np.linalg.norm(r) for r in d["rows"]])
+                    kw["max_state_value"] = float(0.5 * (norms.min() + norms.max()))
+                    d = run_1d(src, cls, kw, init, beta, acts, (nt1, -1e3, 3e2), action_as=action_as)
+                    assert d["truncate"].any() and not d["truncate"].all()
+            _store_1d(store, name, kind, kw, d, big)
+    # float64 beta and float64 / Python-float controls (the kernels' mixed-precision mode) at 1, 2, 4, 8 elements per lane
+    for kind, cls, epl, ct, norm, action_as, beta64 in [("parabolic", "ReactionDiffusionPDE1D", 1, "Dirchilet", False, "f32arr", True),
+                                                        ("transport", "TransportPDE1D", 2, "Neumann", True, "npf64", False),
+                                                        ("parabolic", "ReactionDiffusionPDE1D", 4, "Neumann", False, "pyfloat", True),
+                                                        ("transport", "TransportPDE1D", 8, "Dirchilet", True, "npf64", True)]:
+        n = _ragged_slots(epl) + 1
+        nx = n - (1 if kind == "parabolic" else 0)
+        X, S, mcv = Xs[epl % 3], [2, 7, 33][epl % 3], mcvs[epl % 3]
+        dx = X / nx
+        dt = 0.25 * dx * dx if kind == "parabolic" else 0.5 * dx
+        nt1 = 5 * S + S // 3 if S >= 33 else 120 + S
+        kw = dict(T=nt1 * dt, dt=dt, X=X, dx=dx, normalize=norm, sensing_loc="full", control_type=ct, sensing_type=None,
+                  limit_pde_state_size=True, max_state_value=1e10, max_control_value=mcv, control_sample_rate=S * dt)
+        x = np.linspace(0, 1, n)
+        init = (rng.uniform(1, 8) * (1 + 0.3 * np.sin(2 * np.pi * x * rng.uniform(0.5, 3)))).astype(np.float32)
+        amp = 50 if kind == "parabolic" else 5
+        beta = amp * np.cos(rng.uniform(7, 8.4) * np.arccos(x)) if beta64 else cheb_beta(x, 7.7, amp)
+        acts = rng.uniform(-1, 1, 6)
+        with np.errstate(all="ignore"):
+            d = run_1d(src, cls, kw, init, beta, acts, (nt1, -1e3, 3e2), action_as=action_as)
+        _store_1d(store, f"M_{kind[0]}_e{epl}", kind, kw, d, False)
+    # the reference rejects Dirichlet sensing opposite the actuator of the parabolic plant, whatever the control type
+    for ct in ("Dirchilet", "Neumann"):
+        kw = dict(T=1e-3, dt=1e-5, X=1, dx=1e-2, normalize=False, sensing_loc="opposite", control_type=ct, sensing_type="Dirchilet",
+                  limit_pde_state_size=True, max_state_value=1e10, max_control_value=20, control_sample_rate=1e-4,
+                  reward_class=src.TunedReward1D(100, -1e3, 3e2), sensing_noise_func=lambda s: s,
+                  reset_init_condition_func=lambda nx: np.ones(nx + 1), reset_recirculation_func=lambda nx: np.ones(nx + 1))
+        name = f"unpinnable/parabolic_opposite_dirichlet_{ct.lower()}"
+        store[name] = np.array(_raises(lambda: src.ReactionDiffusionPDE1D(**kw)))
+        _scalars(store, name + "_kw", control_type=ct, sensing_loc="opposite", sensing_type="Dirchilet")
+    np.savez_compressed(os.path.join(out, "sweep_1d.npz"), **store)
+
+
+def _store_1d(store, name, kind, kw, d, big):
+    """One 1D case: constructor parameters, inputs, per-step scalars for every step, rows / observations at the steps in ``keep``
+    (every step for rows of up to 256 nodes, the first and the last beyond: the last row carries every earlier one)."""
+    nsteps = len(d["actions"])
+    keep = np.array([0, nsteps - 1]) if big else np.arange(nsteps)
+    d = dict(d)
+    d["obs0"] = d["obs"][0]
+    d["norm"] = np.array([np.linalg.norm(r) for r in d["rows"]], dtype=np.float64)      # of every step's row (the rewards' scale)
+    d["obs"] = d["obs"][keep + 1]
+    d["rows"] = d["rows"][keep]
+    d["keep"] = keep
+    pack(name, d, store)
+    _scalars(store, name, kind=kind, **kw)
+
+
+def gen_sweep_ns(src, out=HERE):
+    """NavierStokes2D on square node counts n in {5, 8, 16, 21, 33} with dy != dx (Y in {0.25, 0.5, 1, 2}), density, viscosity, gamma,
+    K in {0, 1, 2, 3, 7, 51}, scalar and per-node actions, random boundary sets (every (edge, component, condition) triple occurs),
+    zero / constant / random initial fields; three steps each.  The reference cannot run nx != ny (navier_stokes2D.py:148 stores
+    an [ny, nx] field into U[t] of shape [nx, ny]): recorded under unpinnable/."""
+    store = {}
+    rng = np.random.default_rng(20262)
+    conds = ["Neumann", "Dirchilet", "Controllable"]
+    edges = ("upper", "lower", "left", "right")
+    #        n   Y     rho  nu    gamma K   per-node  initial
+    table = [(5, 0.25, 0.5, 0.01, 0.0, 0, False, "rand"), (5, 1.0, 2.0, 1.0, 2.0, 3, True, "const"), (5, 2.0, 1.0, 0.1, 0.1, 51, False, "zero"),
+             (8, 0.5, 2.0, 0.1, 2.0, 1, True, "rand"), (8, 2.0, 0.5, 1.0, 0.1, 7, False, "rand"), (8, 1.0, 1.0, 0.01, 0.0, 2, False, "const"),
+             (8, 0.25, 1.0, 0.1, 0.1, 51, True, "zero"),
+             (16, 0.25, 2.0, 0.01, 0.1, 3, False, "rand"), (16, 2.0, 0.5, 0.1, 0.0, 7, True, "rand"), (16, 0.5, 1.0, 1.0, 2.0, 0, False, "const"),
+             (16, 1.0, 0.5, 0.01, 2.0, 51, True, "rand"),
+             (21, 0.5, 0.5, 0.1, 0.1, 2, True, "rand"), (21, 2.0, 2.0, 0.01, 2.0, 7, False, "rand"), (21, 1.0, 1.0, 1.0, 0.0, 51, False, "zero"),
+             (33, 0.5, 2.0, 1.0, 0.1, 7, True, "rand"), (33, 2.0, 0.5, 0.01, 2.0, 51, False, "rand")]
+    seen = set()
+    for ci, (n, Y, rho, nu, gamma, K, per_node, ic) in enumerate(table):
+        # boundary sets: cycle the conditions so that all 24 (edge, component, condition) triples occur, then perturb at random
+        bc = {e: [conds[(ci + ei + c) % 3] if ci < 3 else str(rng.choice(conds)) for c in (0, 1)] for ei, e in enumerate(edges)}
+        if ci < 3:
+            bc = {e: [conds[(ci + ei) % 3], conds[(ci + ei + 1 + (ei % 2)) % 3]] for ei, e in enumerate(edges)}
+        for e in edges:
+            for c in (0, 1):
+                seen.add((e, c, bc[e][c]))
+        dx, dy = 1.0 / (n - 1), Y / (n - 1)
+        dt = 0.2 * 0.5 * min(dx, dy) ** 2 / nu
+        nt = 4
+        adim = n if per_node else 1
+
+        def field():
+            if ic == "zero":
+                return np.zeros((n, n))
+            if ic == "const":
+                return np.full((n, n), rng.uniform(-3, 3))
+            return rng.uniform(-1, 1, (n, n))
+        u0, v0, p0 = field(), field(), field()
+        Uref = rng.integers(-16, 17, (nt, n, n, 2)) / 16.0          # sixteenths: compresses well, still a non-trivial reference
+        aref = rng.uniform(1, 3, nt)
+        kw = dict(T=nt * dt, dt=dt, X=1, dx=dx, Y=Y, dy=dy, action_dim=adim, reward_class=src.NSReward(gamma), normalize=False,
+                  reset_init_condition_func=lambda X: (u0.copy(), v0.copy(), p0.copy()), boundary_condition=bc,
+                  U_ref=Uref, action_ref=aref, maximum_pressure_iteration=K, viscosity=nu, density=rho)
+        env = src.NavierStokes2D(**kw)
+        assert env.nx == n and env.ny == n
+        env.reset()
+        acts = rng.uniform(2, 4, (3, adim)) * np.array([1.0, -1.0, 0.5])[:, None]
+        obs_l, p_l, r_l, te_l = [], [], [], []
+        for a in acts:
+            obs, r, te, tr, _ = env.step(a.copy() if per_node else float(a[0]))
+            obs_l.append(np.array(obs))
+            p_l.append(np.array(env.p))
+            r_l.append(r)
+            te_l.append(bool(te))
+        name = f"S{ci:02d}_n{n}"
+        pack(name, dict(u0=u0, v0=v0, p0=p0, U_ref=Uref, action_ref=aref, actions=acts, obs=np.stack(obs_l), p=np.stack(p_l),
+                        rewards=np.array(r_l, dtype=np.float64), terminate=np.array(te_l),
+                        bc=np.array([bc[k][i] for k in edges for i in (0, 1)])), store)
+        _scalars(store, name, T=nt * dt, dt=dt, X=1.0, dx=dx, Y=float(Y), dy=dy, nt=nt, n=n, action_dim=adim, gamma=gamma,
+                 viscosity=nu, density=rho, maximum_pressure_iteration=K, ic=ic)
+    assert len(seen) == 24, sorted(seen)
+    # non-square node counts: reset() and the arithmetic accept them, the store of the new field into U[t] does not
+    n, m = 8, 5
+    dx, dy = 1.0 / (n - 1), 1.0 / (m - 1)
+    dt = 0.1 * min(dx, dy) ** 2 / 0.1
+    kw = dict(T=4 * dt, dt=dt, X=1, dx=dx, Y=1, dy=dy, action_dim=1, reward_class=src.NSReward(0.1), normalize=False,
+              reset_init_condition_func=lambda X: (np.zeros((m, n)), np.zeros((m, n)), np.zeros((m, n))), boundary_condition=NS_BC,
+              U_ref=np.zeros((4, m, n, 2)), action_ref=np.ones(4), maximum_pressure_iteration=1)
+
+    def non_square():
+        env = src.NavierStokes2D(**kw)
+        env.reset()
+        env.step(1.0)
+    store["unpinnable/ns_non_square"] = np.array(_raises(non_square))
+    _scalars(store, "unpinnable/ns_non_square_kw", nx=n, ny=m)
+    np.savez_compressed(os.path.join(out, "sweep_ns.npz"), **store)
+
+
+def gen_sweep_traffic(src, out=HERE):
+    """TrafficPDE1D away from the shipped notebook configuration: tau, v_max, ro_max, ro_steady, control_freq, dx (with a matching
+    dt), X, the state limit, in all four simulation types; a short T so that the ``time_index >= T`` freeze (:173) and the ``T/dt``
+    terminate comparison (:109) are crossed inside the recorded steps; a case that truncates through the state limit; an
+    'outlet-train' case whose action bounds come from another steady state than its dynamics (:66-70 against :251-256)."""
+    import contextlib
+    import io
+    import random
+    store = {}
+    rng = np.random.default_rng(20263)
+    P1 = dict(T=240, dt=0.01, X=250, dx=0.5, tau=30, v_max=40, ro_max=0.16, ro_steady=0.12)
+    P2 = dict(T=240, dt=0.1, X=400, dx=5, tau=60, v_max=30, ro_max=0.2, ro_steady=0.1)
+    P3 = dict(T=240, dt=0.25, X=400, dx=8, tau=15, v_max=40, ro_max=0.2, ro_steady=0.12)
+    P4 = dict(T=240, dt=0.25, X=500, dx=12.5, tau=30, v_max=30, ro_max=0.16, ro_steady=0.1)
+    SH = dict(T=2, dt=0.25, X=500, dx=12.5, tau=60, v_max=40, ro_max=0.16, ro_steady=0.12)      # frozen from step 8, T/dt = 8 s at step 32
+    HOT = dict(T=240, dt=0.25, X=400, dx=8, tau=60, v_max=40, ro_max=0.16, ro_steady=0.15)      # 1.1 ro_steady > ro_max
+    #        name              params sim             cf limit steps
+    table = [("fine_outlet", P1, "outlet", 5, True, 3),
+             ("p2_inlet", P2, "inlet", 1, True, 6), ("p2_outlet", P2, "outlet", 2, False, 6), ("p2_both", P2, "both", 3, True, 6),
+             ("p2_train", P2, "outlet-train", 5, True, 6),
+             ("p3_inlet", P3, "inlet", 2, False, 6), ("p3_outlet", P3, "outlet", 3, True, 6), ("p3_both", P3, "both", 5, True, 6),
+             ("p3_train", P3, "outlet-train", 1, False, 6),
+             ("p4_inlet", P4, "inlet", 3, True, 6), ("p4_outlet", P4, "outlet", 5, True, 6), ("p4_both", P4, "both", 1, False, 6),
+             ("p4_train", P4, "outlet-train", 2, True, 6),
+             ("short_inlet", SH, "inlet", 2, True, 35), ("short_train", SH, "outlet-train", 3, True, 35),
+             ("hot_limit", HOT, "both", 1, True, 4), ("hot_nolimit", HOT, "both", 1, False, 4)]
+    for name, P, sim, cf, limit, nsteps in table:
+        Veq = src.TrafficPDE1D.Veq
+        kw = dict(T=P["T"], dt=P["dt"], X=P["X"], dx=P["dx"], reward_class=src.TrafficARZReward(), simulation_type=sim,
+                  v_steady=Veq(P["v_max"], P["ro_max"], P["ro_steady"]), ro_steady=P["ro_steady"], v_max=P["v_max"],
+                  ro_max=P["ro_max"], tau=P["tau"], limit_pde_state_size=limit, control_freq=cf)
+        # 'outlet-train' draws its steady state with random.randint in the constructor and again in reset(): take the first seed
+        # pair whose two draws differ, so the clip bounds and the dynamics use different qs
+        seeds = (11, 13)
+        if sim == "outlet-train":
+            for s2 in range(13, 64):
+                random.seed(11)
+                a = random.randint(0, 2)
+                random.seed(s2)
+                if random.randint(0, 2) != a:
+                    seeds = (11, s2)
+                    break
+        random.seed(seeds[0])
+        with contextlib.redirect_stdout(io.StringIO()):
+            env = src.TrafficPDE1D(**kw)
+            qs_clip = env.qs
+            random.seed(seeds[1])
+            obs0, _ = env.reset()
+        nact = 2 if sim == "both" else 1
+        acts = rng.uniform(0.7, 1.3, (nsteps, nact)) * env.qs
+        obs, rew, done, trunc, tim = [np.array(obs0)], [], [], [], []
+        with np.errstate(all="ignore"):
+            for a in acts:
+                with contextlib.redirect_stdout(io.StringIO()):
+                    o, r, d, t, _ = env.step(a)
+                obs.append(np.array(o))
+                rew.append(r)
+                done.append(bool(d))
+                trunc.append(bool(t))
+                tim.append(env.time_index)
+        if sim == "outlet-train":
+            assert qs_clip != env.qs
+        pack(name, dict(obs=np.stack(obs), reward=np.array(rew, dtype=np.float64), done=np.array(done), trunc=np.array(trunc),
+                        time=np.array(tim, dtype=np.float64), actions=acts, rs=np.float64(env.rs), qs_clip=np.float64(qs_clip)), store)
+        _scalars(store, name, sim=sim, control_freq=cf, limit=limit, v_steady=kw["v_steady"], **P)
+    # what the short cases are for
+    t = store["short_inlet/time"]
+    assert (t[:-1] >= 2).any() and (np.diff(t) < 0).any(), "short T: the freeze and the T/dt reset must both be crossed"
+    assert store["short_train/done"].any() and not store["short_train/done"][:31].any()
+    assert store["hot_limit/trunc"].all() and not store["hot_nolimit/trunc"].any()
+    np.savez_compressed(os.path.join(out, "sweep_traffic.npz"), **store)
+
+
+def gen_sweep_tumor(src, out=HERE):
+    """BrainTumor1D whole episodes over the constructor arguments tests/fuzz_more.py draws (X, dx, D, rho, alpha, alpha/beta, k, both
+    thresholds and radii, the dosage threshold, total_dosage), ending the ways the raw episodes of tumor.npz do: lethal radius in
+    Post-Therapy with and without t_benchmark, time limit in Therapy, time limit in Post-Therapy.  Rows sub-sampled (``keep``)."""
+    import importlib
+    bt = importlib.import_module("pde_control_gym.src.environments1d.brain_tumor_env")
+    br = importlib.import_module("pde_control_gym.src.rewards.brain_tumor_reward")
+    store = {}
+    rng = np.random.default_rng(20264)
+    A = dict(X=64, dx=0.5, D=0.1, rho=0.05, alpha=0.1, alpha_beta_ratio=3, k=1.0, t1_detection_threshold=0.6, t2_detection_threshold=0.3,
+             dosage_termination_threshold=1.0, t1_detection_radius=10, t1_death_radius=25, total_dosage=30.0)
+    B = dict(X=100, dx=2, D=0.2, rho=0.03, alpha=0.04, alpha_beta_ratio=10, k=3e4, t1_detection_threshold=0.8, t2_detection_threshold=0.16,
+             dosage_termination_threshold=0.1, t1_detection_radius=15, t1_death_radius=35, total_dosage=100.0)
+    C = dict(X=300, dx=1, D=0.05, rho=0.05, alpha=0.04, alpha_beta_ratio=10, k=1e5, t1_detection_threshold=0.6, t2_detection_threshold=0.16,
+             dosage_termination_threshold=1.0, t1_detection_radius=10, t1_death_radius=35, total_dosage=61.2)
+    D = dict(X=200, dx=1, D=0.1, rho=0.03, alpha=0.04, alpha_beta_ratio=10, k=1.0, t1_detection_threshold=0.8, t2_detection_threshold=0.3,
+             dosage_termination_threshold=0.1, t1_detection_radius=15, t1_death_radius=25, total_dosage=30.0)
+    E = dict(X=100, dx=0.5, D=0.05, rho=0.03, alpha=0.04, alpha_beta_ratio=3, k=3e4, t1_detection_threshold=0.8, t2_detection_threshold=0.16,
+             dosage_termination_threshold=0.1, t1_detection_radius=10, t1_death_radius=25, total_dosage=61.2)
+    F = dict(X=64, dx=2, D=0.2, rho=0.05, alpha=0.1, alpha_beta_ratio=10, k=1e5, t1_detection_threshold=0.6, t2_detection_threshold=0.16,
+             dosage_termination_threshold=1.0, t1_detection_radius=15, t1_death_radius=25, total_dosage=30.0)
+    ends = {}
+    #                   name           set T    t_benchmark  dose range
+    for name, P, T, tb, hi in [("a_death_post", A, 600, 200, 0.05), ("b_term_therapy", B, 250, 200, 0.05), ("c_term_post", C, 300, 250, 0.3),
+                               ("d_nobench", D, 600, None, 0.05), ("e_term_post", E, 400, 300, 0.3), ("f_death_post", F, 600, 250, 0.1)]:
+        nx = int(round(P["X"] / P["dx"]) + 1)
+        init = 0.8 * P["k"] * np.exp(-0.25 * np.linspace(0, P["X"], nx) ** 2) * rng.uniform(0.9, 1.0)
+        env = bt.BrainTumor1D(T=T, dt=1, normalize=True, reward_class=br.BrainTumorReward(), verbose=False,
+                              reset_init_condition_func=lambda X, n: init, **P)
+        assert env.nx == nx
+        env.t_benchmark = tb
+        env.reset()
+        acts, rew, term, trunc, stage = [], [], [], [], []
+        while True:
+            a = float(rng.uniform(0, hi))
+            o, r, te, tr, info = env.step(a)
+            acts.append(a)
+            rew.append(float(r))
+            term.append(bool(te))
+            trunc.append(bool(tr))
+            stage.append({"Growth": 0, "Therapy": 1, "Post-Therapy": 2}[info["stage"]])
+            if te or tr:
+                break
+        n = len(acts)
+        ends[name] = (stage[-1], term[-1], trunc[-1])
+        keep = np.unique(np.concatenate([np.arange(0, n + 1, 16), [n]]))
+        pack(name, dict(init=init, actions=np.array(acts), t_benchmark=np.float64(np.nan if tb is None else tb),
+                        reward=np.array(rew), term=np.array(term), trunc=np.array(trunc), stage=np.array(stage),
+                        keep=keep, rows=env.u[keep].copy(), t1_idx=env.t1_radius_idx_vs_time[: n + 1].copy(),
+                        dosage=env.dosage_vs_time[: n + 1].copy(),
+                        days=np.array([env.growthDays, env.therapyDays, env.postTherapyDays, env.simulationDays,
+                                       -1 if env.cDeathDay is None else env.cDeathDay]),
+                        remaining=np.float64(env.remaining_dosage)), store)
+        _scalars(store, name, T=T, dt=1, **P)
+    assert ends["a_death_post"] == (2, False, True) and ends["d_nobench"] == (2, False, True) and ends["f_death_post"] == (2, False, True)
+    assert ends["b_term_therapy"] == (1, True, False) and ends["c_term_post"] == (2, True, False) and ends["e_term_post"] == (2, True, False)
+    np.savez_compressed(os.path.join(out, "sweep_tumor.npz"), **store)
+
+
 FILES = {"transport": "transport.npz", "parabolic": "parabolic.npz", "kat": "kat.npz", "mixed": "mixed.npz", "ns": "ns2d.npz",
-         "traffic": "traffic.npz", "tumor": "tumor.npz"}
+         "traffic": "traffic.npz", "tumor": "tumor.npz", "sweep_1d": "sweep_1d.npz", "sweep_ns": "sweep_ns.npz",
+         "sweep_traffic": "sweep_traffic.npz", "sweep_tumor": "sweep_tumor.npz"}
 
 
 GEN = {"transport": gen_transport, "parabolic": gen_parabolic, "kat": gen_kat, "mixed": gen_mixed, "ns": gen_ns,
-       "traffic": gen_traffic, "tumor": gen_tumor}
+       "traffic": gen_traffic, "tumor": gen_tumor, "sweep_1d": gen_sweep_1d, "sweep_ns": gen_sweep_ns,
+       "sweep_traffic": gen_sweep_traffic, "sweep_tumor": gen_sweep_tumor}
 
 
 def check(which=None):
@@ -566,10 +918,9 @@ if __name__ == "__main__":
         print("\n".join(d) if d else "fixtures == generator output")
         sys.exit(1 if d else 0)
     src = import_reference()
-    which = sys.argv[1:] or ["transport", "parabolic", "kat", "mixed", "ns", "traffic", "tumor"]
-    store_meta = dict(numpy=np.__version__)
+    which = sys.argv[1:] or list(GEN)
     for w in which:
         GEN[w](src)
         print("wrote", w)
-    with open(os.path.join(out, "VERSIONS.txt"), "w") as f:
+    with open(os.path.join(HERE, "VERSIONS.txt"), "w") as f:
         f.write(f"numpy {np.__version__}\nreference snapshot 2026-01-09 (lukebhan/PDEControlGym)\n")

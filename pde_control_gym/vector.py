@@ -16,9 +16,10 @@ navier_stokes2D.py:38-46 + the base classes), plus ``num_envs``, ``device``, and
 """
 from __future__ import annotations
 
-import numpy as np
-
 import sys
+from contextlib import contextmanager, nullcontext
+
+import numpy as np
 
 from pde_control_gym._compat import VecEnv, spaces
 
@@ -45,6 +46,8 @@ class BatchedVecEnv(VecEnv):
     batched environment and answer once per requested index, ``env_is_wrapped`` is False everywhere."""
     metadata = {"render_modes": []}
     render_mode = None
+    _fused_reset = False                   # finished instances restart inside the step launch (enable_fused_auto_reset)
+    sensing_noise_tensor_func = None       # device-side sensing-noise hook (the 1D families take one)
 
     def _finish_vec_env_init(self):
         """Runs the base-class constructor (``reset_infos``, ``_seeds``, ``_options``, the common ``render_mode``) once the
@@ -85,19 +88,20 @@ class BatchedVecEnv(VecEnv):
     # ---- checkpoint / resume (pdecontrolgym_amd/checkpoint.py) --------------------------------------------------------
     _checkpoint_attrs = ()         # device tensors kept by the face itself, next to the engine's
 
+    def _face_tensors(self):
+        import torch
+        return {k: getattr(self, k) for k in self._checkpoint_attrs if torch.is_tensor(getattr(self, k, None))}
+
     def state_dict(self):
         """Device state of the whole batch as (cloned) torch tensors -- ``torch.save``-able.  Restored by ``load_state_dict`` on
         an environment built from the same parameters; the user's reset callbacks and their random generators are the
         caller's to checkpoint."""
-        import torch
-        face = {k: getattr(self, k).detach().clone() for k in self._checkpoint_attrs if torch.is_tensor(getattr(self, k, None))}
-        return {"core": self.core.state_dict(), "face": face, "fused_reset": bool(getattr(self, "_fused_reset", False))}
+        face = {k: v.detach().clone() for k, v in self._face_tensors().items()}
+        return {"core": self.core.state_dict(), "face": face, "fused_reset": self._fused_reset}
 
     def load_state_dict(self, sd):
-        import torch
         face = sd.get("face", {})
-        mine = {k: getattr(self, k, None) for k in self._checkpoint_attrs}
-        mine = {k: v for k, v in mine.items() if torch.is_tensor(v)}
+        mine = self._face_tensors()
         # the face's own tensors (e.g. the NavierStokes2D frame history kept for a host-side reward) exist only in some
         # configurations: a checkpoint from another one is refused before anything is copied
         if set(face) != set(mine):
@@ -110,24 +114,76 @@ class BatchedVecEnv(VecEnv):
         self.core.load_state_dict(sd["core"])
         for k, v in face.items():
             mine[k].copy_(v)
-        if hasattr(self, "_fused_reset"):
-            self._fused_reset = bool(sd["fused_reset"])
+        self._fused_reset = bool(sd["fused_reset"])
         self._actions = None
+
+    # ---- what DeviceRollout asks of an environment (pde_control_gym/rollout.py) ----------------------------------------------
+    # The defaults serve an engine that is driven through step_tensor; the families override what differs.  ``buffers`` are the
+    # rollout's obs [T+1, B, ...], actions, rewards, terminated, truncated [T, B].
+    #   rollout_obs()             the tensor that holds the current observation
+    #   rollout_action_shape      the shape of one action slot after [B]
+    #   rollout_step(t, *buffers) one env-step on actions[t] into obs[t + 1], rewards[t], terminated[t], truncated[t]
+    #   rollout_state()           name -> tensor of everything a step mutates in place (the fused auto-reset advances reset_count
+    #                             and may redraw beta rows), snapshot and rewound around the warm-up run of a graph capture: the
+    #                             engine's tensors, and where the steps go through step_tensor the face's own (_checkpoint_attrs);
+    #                             an engine that is stepped directly names its own (_rollout_state_keys) and leaves the face's alone
+    #   rollout_body(obs)         context around the steps of one rollout: an engine that writes into the rollout buffers itself is
+    #                             pointed at slot 0, and gets the end state and its own output tensors back
+    #   adopt_rollout_obs(buf)    after a graph replay (PDEVecEnv below)
+    #   one_launch_fits(policy)   whether the whole rollout with the policy inside is ONE kernel launch, rollout_one_launch(*buffers,
+    #                             policy=, clamp=, noise=[, obs_noise=, obs_seen=]); one_launch_obs_noise: it takes pre-drawn sensing noise
+    _rollout_state_keys = None
+    rollout_action_shape = ()
+    one_launch_obs_noise = True
+
+    def rollout_obs(self):
+        return self.core.t["obs"]
+
+    def rollout_step(self, t, obs, actions, rewards, terminated, truncated):
+        for dst, src in zip((obs[t + 1], rewards[t], terminated[t], truncated[t]), self.step_tensor(actions[t])):
+            dst.copy_(src)
+
+    def rollout_state(self):
+        import torch
+        t = self.core.t
+        if self._rollout_state_keys is None:
+            return {**{k: v for k, v in t.items() if torch.is_tensor(v)}, **self._face_tensors()}
+        return {k: t[k] for k in self._rollout_state_keys if torch.is_tensor(t[k])}
+
+    def rollout_body(self, obs):
+        return nullcontext()
+
+    def adopt_rollout_obs(self, buf):
+        pass
+
+    def one_launch_fits(self, policy):
+        return False
+
+    def rollout_one_launch(self, *buffers, **kw):
+        self.core.rollout(*buffers, **kw)
 
 
 class PDEVecEnv(BatchedVecEnv):
+    """What does not depend on the environment family.  ``PDEVecEnv(env_id, ...)`` builds the family's subclass (below): engine and spaces,
+    initial conditions, ``reset_tensor`` / ``step_tensor`` (with the host-reward path), fused-reset pools, host-side restarts."""
     _checkpoint_attrs = ("_ns_hist",)
     _copy_note_printed = False
+    _flux = "linear"
+    _host_reward = False                   # a user reward class: reward() runs on the host, once per instance and step
+    sensing_noise_func = None
+    _obs_np_dtype = np.float32             # what step() / reset() observe in
+    _flat_actions = False                  # step_tensor takes [B] (the 1D families), not [B, action_dim]
+
+    def __new__(cls, env_id=None, *args, **kw):
+        if cls is PDEVecEnv:
+            if env_id not in _KINDS:
+                raise KeyError(f"No registered env with id: {env_id}")
+            cls = _FAMILIES[_KINDS[env_id]]
+        return super().__new__(cls)
 
     def __init__(self, env_id: str, num_envs: int, device="cuda", backend=None, batched_reset_func=None,
                  dtype=None, copy_outputs=None, **kw):
         import torch
-        if env_id not in _KINDS:
-            raise KeyError(f"No registered env with id: {env_id}")
-        self.kind = _KINDS[env_id]
-        self._flux = "linear"
-        if self.kind == "burgers":              # extension (not in the reference): transport kernel with the u u_x flux
-            self.kind, self._flux = "transport", "burgers"
         self.num_envs = int(num_envs)
         self.device = torch.device(device)
         self.batched_reset_func = batched_reset_func
@@ -148,164 +204,19 @@ class PDEVecEnv(BatchedVecEnv):
         # returned by step_tensor() / reset_tensor() IN PLACE (by default those tensors ARE the state: read-only).
         self.reward_class = kw["reward_class"]
         self._actions = None
-        self._fused_reset = False
-        if self.kind == "ns2d":
-            self._init_ns(kw, backend, dtype)
-        elif self.kind == "traffic":
-            self._init_traffic(kw, backend)
-        else:
-            self._init_1d(kw, backend)
+        self.kind = _KINDS[env_id]
+        self._build(dict(kw, dtype=dtype), backend)
         self._finish_vec_env_init()
 
-    # ---- construction ------------------------------------------------------------------------------
-    def _init_1d(self, kw, backend):
-        from pdecontrolgym_amd.batch1d import PDEBatch1D
-        from pde_control_gym.src.environments1d.base_env_1d import reward_spec_for
-        self.sensing_noise_func = kw.get("sensing_noise_func", None)
-        # device-side twin of the hook (hyperbolic.py:160-164 applies it to what sensing_update returns): a callable on TORCH
-        # tensors, [B, obs_dim] -> [B, obs_dim], evaluated on the device -- out of place, the returned tensor is what the
-        # policy sees while the plant state (which the observation tensor IS with full-state sensing) stays clean -- by
-        # step_tensor / reset_tensor and, captured into the graph, by DeviceRollout.  NumPy callbacks keep the host path.
-        self.sensing_noise_tensor_func = kw.get("sensing_noise_tensor_func", None)
-        self._beta_dtype = kw.get("beta_dtype", None)
-        self.reset_init_condition_func = kw.get("reset_init_condition_func")
-        self.reset_recirculation_func = kw.get("reset_recirculation_func")
-        spec = reward_spec_for(self.reward_class)
-        # Any other BaseReward subclass (docs/source/utils/customrewards.rst) takes the slow compatibility path: the engine
-        # records the trajectories on the device and after every step the user's reward() is called once per instance on the
-        # host with a lazy view of that instance's history (uVec[t], uVec[:, -1] ... fetch rows on demand).
-        self._host_reward = spec is None
-        default_rate = 0.1 if self.kind == "transport" else 1e-4
-        self.core = PDEBatch1D(self.kind, kw["T"], kw["dt"], kw["X"], kw["dx"], kw.get("control_sample_rate", default_rate),
-                               control_type=kw.get("control_type", "Dirchilet"), sensing_loc=kw.get("sensing_loc", "full"),
-                               sensing_type=kw.get("sensing_type", "Dirchilet"), normalize=kw.get("normalize", False),
-                               max_control_value=kw.get("max_control_value", 20),
-                               limit_pde_state_size=kw.get("limit_pde_state_size", False),
-                               max_state_value=kw.get("max_state_value", 1e10), reward=spec, num_envs=self.num_envs,
-                               device=self.device, backend=backend, flux=self._flux, record_history=self._host_reward,
-                               state_in_obs=bool(kw.get("state_in_obs", True)))
-        self.nx, self.nt = self.core.nx, self.core.nt
-        msv = kw.get("max_state_value", 1e10)
-        d = self.core.obs_dim
-        self.observation_space = spaces.Box(np.full(d, -msv, dtype="float32"), np.full(d, msv, dtype="float32"))
-        self.action_space = spaces.Box(np.full(1, -1, dtype="float32"), np.full(1, 1, dtype="float32"))
-
-    def _init_ns(self, kw, backend, dtype):
-        import torch
-        from pdecontrolgym_amd.batch2d import NSBatch2D
-        from pde_control_gym.src.rewards import NSReward
-        # Any other BaseReward subclass (docs/source/utils/customrewards.rst: the extension point is environment-agnostic)
-        # takes the slow compatibility path: the trajectories U[nt, ny, nx, 2] are recorded on the device and after every step
-        # the user's reward(U, time_index, U_ref, action, action_ref) (navier_stokes2D.py:151) is called once per instance on
-        # the host with a lazy view of that instance's trajectory.
-        self._host_reward = type(self.reward_class) is not NSReward
-        self.reset_init_condition_func = kw.get("reset_init_condition_func")
-        tdtype = dtype or torch.float32
-        if isinstance(tdtype, str):
-            tdtype = {"float32": torch.float32, "float64": torch.float64}[tdtype]
-        self.core = NSBatch2D(kw["T"], kw["dt"], kw["X"], kw["dx"], kw["Y"], kw["dy"], kw["boundary_condition"],
-                              kw["U_ref"], kw["action_ref"], action_dim=kw.get("action_dim", 1),
-                              gamma=getattr(self.reward_class, "gamma", 0.0), viscosity=kw.get("viscosity", 0.1),
-                              density=kw.get("density", 1.0),
-                              maximum_pressure_iteration=int(kw.get("maximum_pressure_iteration", 2000)),
-                              stable_factor=kw.get("stable_factor", 0.5), num_envs=self.num_envs, device=self.device,
-                              dtype=tdtype, backend=backend, interleaved_state=bool(kw.get("interleaved_state", True)))
-        self.nx, self.ny, self.nt = self.core.nx, self.core.ny, self.core.nt
-        if self._host_reward:
-            nbytes = self.num_envs * self.nt * self.ny * self.nx * 2 * (8 if tdtype == torch.float64 else 4)
-            if nbytes > (64 << 30):
-                raise MemoryError(f"a host reward callback on NavierStokes2D records every trajectory on the device: "
-                                  f"{nbytes / 2**30:.0f} GiB for {self.num_envs} instances; lower num_envs")
-            self._ns_hist = torch.zeros(self.num_envs, self.nt, self.ny, self.nx, 2, dtype=tdtype, device=self.device)
-            self._U_ref_np, self._a_ref_np = np.asarray(kw["U_ref"]), np.asarray(kw["action_ref"])
-        self.X, self.Y = np.meshgrid(np.linspace(0, kw["X"], self.nx), np.linspace(0, kw["Y"], self.ny))
-        self.observation_space = spaces.Box(np.full((self.nx, self.ny, 2), -np.inf, dtype="float32"),
-                                            np.full((self.nx, self.ny, 2), np.inf, dtype="float32"))
-        self.action_space = spaces.Box(low=-1.0, high=1.0, shape=(kw.get("action_dim", 1),), dtype=np.float32)
-
-    def _init_traffic(self, kw, backend):
-        import random
-        from pdecontrolgym_amd.batch_traffic import TrafficBatch
-        from pde_control_gym.src.rewards import TrafficARZReward
-        # any other BaseReward subclass: reward(v_desired, r_desired, v, r) (traffic_arz_env.py:228) per instance on the host
-        self._host_reward = type(self.reward_class) is not TrafficARZReward
-        sim = kw.get("simulation_type", "inlet")
-        self.core = TrafficBatch(kw["T"], kw["dt"], kw["X"], kw["dx"], sim, kw.get("v_max", 40), kw.get("ro_max", 0.16),
-                                 kw.get("tau", 60), kw.get("limit_pde_state_size", False), kw.get("control_freq", 1),
-                                 num_envs=self.num_envs, device=self.device, backend=backend)
-        self._traffic_train = sim == "outlet-train"
-        self._rs_fixed = kw.get("ro_steady", 0.12)
-        self._draw_rs = lambda k: (np.array([{0: 0.115, 1: 0.12, 2: 0.125}[random.randint(0, 2)] for _ in range(k)])
-                                   if self._traffic_train else np.full(k, self._rs_fixed))
-        rs0 = self._draw_rs(self.num_envs)                 # construction-time draw fixes the action bounds (:97-100)
-        self.core.set_action_bounds(rs0 * self.core.Veq(rs0))
-        M = self.core.M
-        lo, hi = (-10, 10) if self._traffic_train else (0, 40)
-        self.observation_space = spaces.Box(low=lo, high=hi, shape=(2 * M,), dtype=np.float64)
-        qs = float(rs0[0] * self.core.Veq(rs0[0]))
-        self.action_space = spaces.Box(dtype=np.float64, low=qs * 0.8, high=1.2 * qs, shape=(self.core.action_dim,))
-        self.nx, self.nt = M, int(round(kw["T"] / kw["dt"]))
-
-    # ---- initial conditions --------------------------------------------------------------------------
-    def _sample_1d(self, idx):
-        """Initial condition and beta rows for the instances in ``idx`` (user callbacks, reference semantics)."""
-        n = self.core.n
-        if self.batched_reset_func is not None:
-            init, beta = self.batched_reset_func(idx, self.nx)
-            if self._beta_dtype == "float32":
-                beta = np.asarray(beta, dtype=np.float32)
-            return init, beta
-        init = np.zeros((len(idx), n), dtype=np.float32)
-        beta = None
-        try:
-            for k in range(len(idx)):
-                init[k] = self.reset_init_condition_func(self.nx)
-                b = np.asarray(self.reset_recirculation_func(self.nx))
-                if beta is None:      # the dtype the callback returns selects the arithmetic, as in the reference (float64 ->
-                    # mixed-precision kernel); pass ``beta_dtype="float32"`` to make_vec to force the float32 kernels
-                    dt = np.float32 if (b.dtype in (np.float32, np.float16) or self._beta_dtype == "float32") else np.float64
-                    beta = np.zeros((len(idx), n), dtype=dt)
-                beta[k] = b
-        except:  # noqa: E722 - reference hyperbolic.py:207-213
-            raise Exception(_RESET_ERR)
-        return init, beta
-
-    def _sample_ns(self, idx):
-        if self.batched_reset_func is not None:
-            return self.batched_reset_func(idx, self.X)
-        u, v, p = (np.zeros((len(idx), self.ny, self.nx)) for _ in range(3))
-        try:
-            for k in range(len(idx)):
-                u[k], v[k], p[k] = self.reset_init_condition_func(self.X)
-        except:  # noqa: E722
-            raise Exception(_RESET_ERR)
-        return u, v, p
-
-    def _scatter(self, rows, idx, shape):
+    def _scatter(self, rows, idx, shape, dtype):
         """[len(idx), ...] rows -> full [B, ...] float tensor on the device (other rows zero)."""
         import torch
-        dt = torch.float32 if self.kind != "ns2d" else self.core.dtype
-        full = torch.zeros((self.num_envs,) + shape, dtype=dt, device=self.device)
-        full[torch.as_tensor(np.asarray(idx), device=self.device, dtype=torch.long)] = torch.as_tensor(rows, dtype=dt, device=self.device)
+        full = torch.zeros((self.num_envs,) + shape, dtype=dtype, device=self.device)
+        full[torch.as_tensor(np.asarray(idx), device=self.device, dtype=torch.long)] = torch.as_tensor(rows, dtype=dtype, device=self.device)
         return full
 
-    # ---- torch-native face ---------------------------------------------------------------------------
-    def reset_tensor(self):
-        idx = np.arange(self.num_envs)
-        if self.kind == "traffic":
-            return self.core.reset(self._draw_rs(self.num_envs))
-        if self.kind == "ns2d":
-            u, v, p = self._sample_ns(idx)
-            obs = self.core.reset(u, v, p)
-            if self._host_reward:
-                self._ns_hist.zero_()
-                self._ns_hist[:, 0] = obs
-            return obs
-        init, beta = self._sample_1d(idx)
-        return self._noise_t(self.core.reset(init, beta))
-
     def _noise_t(self, obs):
-        f = getattr(self, "sensing_noise_tensor_func", None)
+        f = self.sensing_noise_tensor_func
         return obs if f is None else f(obs)
 
     def enable_fused_auto_reset(self, init_pool=None, beta_pool=None, pool_episodes: int = 4):
@@ -314,131 +225,26 @@ class PDEVecEnv(BatchedVecEnv):
         ``pool_episodes * num_envs`` rows (initial condition AND beta), and the k-th restart of instance b takes row
         (b + k*num_envs) mod rows.  Call ``refresh_pool()`` (any time between steps) to draw fresh rows; pass explicit
         ``init_pool`` / ``beta_pool`` tensors [P >= num_envs, n] to control them (``beta_pool=False`` keeps beta fixed)."""
-        if getattr(self, "_host_reward", False):
+        if self._host_reward:
             raise NotImplementedError("a host reward callback needs the finished trajectory: use the plain auto-reset of step()")
-        if self.kind == "ns2d":
-            return self._enable_fused_auto_reset_ns(init_pool, min(int(pool_episodes), 2) if init_pool is None else 1)
-        if self.kind == "traffic":       # pool of steady-state densities (redrawn per episode in 'outlet-train', :247-252)
-            rows = self.num_envs * max(1, int(pool_episodes))
-            self.core.enable_auto_reset(self._draw_rs(rows) if init_pool is None else init_pool)
-            self._fused_reset = True
-            return
-        if init_pool is None:
-            init_pool, drawn_beta = self._sample_1d(np.arange(self.num_envs * max(1, int(pool_episodes))))
-            if beta_pool is None:
-                beta_pool = drawn_beta
-        if beta_pool is False:
-            beta_pool = None
-        self.core.enable_auto_reset(init_pool, beta_pool=beta_pool)
+        self._install_pools(init_pool, beta_pool, pool_episodes)
         self._fused_reset = True
 
     def refresh_pool(self, init_pool=None, beta_pool=None):
         """Draw (or install) fresh pool rows in place; the restart counters keep running."""
         import torch
-        if self.kind == "ns2d":
-            return self._refresh_pool_ns(init_pool)
-        if self.kind == "traffic":
-            rr = self.core.t["reset_rs"]
-            rr.copy_(torch.as_tensor(self._draw_rs(rr.shape[0]) if init_pool is None else init_pool, dtype=rr.dtype, device=self.device))
-            return
-        rows = self.core.t["reset_init"].shape[0]
-        if init_pool is None:
-            init_pool, drawn_beta = self._sample_1d(np.arange(rows))
-            if beta_pool is None:
-                beta_pool = drawn_beta
-        self.core.t["reset_init"].copy_(torch.as_tensor(init_pool, dtype=torch.float32, device=self.device))
-        if beta_pool is not None and self.core.t.get("reset_beta") is not None:
-            rb = self.core.t["reset_beta"]
-            rb.copy_(torch.as_tensor(beta_pool).to(device=self.device, dtype=rb.dtype))
-
-    def _enable_fused_auto_reset_ns(self, init_pool, pool_episodes: int = 2):
-        """NavierStokes2D: pools of initial (u, v, p) fields, drawn from ``reset_init_condition_func`` unless given as a
-        3-tuple of [P >= num_envs, ny, nx] arrays."""
-        if init_pool is None:
-            init_pool = self._sample_ns(np.arange(self.num_envs * max(1, int(pool_episodes))))
-        self.core.enable_auto_reset(*init_pool)
-        self._fused_reset = True
-
-    def _refresh_pool_ns(self, init_pool):
-        import torch
-        if init_pool is None:
-            init_pool = self._sample_ns(np.arange(self.core.t["reset_u0"].shape[0]))
-        for k, a in zip(("reset_u0", "reset_v0", "reset_p0"), init_pool):
-            self.core.t[k].copy_(torch.as_tensor(a, dtype=self.core.dtype, device=self.device))
-
-    def step_tensor(self, actions):
-        """actions: device tensor [B] (1D) / [B, action_dim] (NS).  Returns device tensors
-        (obs, reward, terminated, truncated); nothing is copied to the host."""
-        import torch
-        if self.kind == "ns2d":
-            obs, r, te = self.core.step(actions)
-            if self._host_reward:
-                r = self._host_rewards_ns(obs, actions)
-            return obs, r, te, torch.zeros_like(te)
-        out = self.core.step(actions)       # 1D envs and traffic: (obs, reward, terminated|done, truncated)
-        if getattr(self, "_host_reward", False):
-            if self.kind == "traffic":
-                return self._host_rewards_traffic(out)
-            return (self._noise_t(out[0]), self._host_rewards(out[2], out[3]), out[2], out[3])
-        if getattr(self, "sensing_noise_tensor_func", None) is not None:
-            return (self._noise_t(out[0]),) + tuple(out[1:])
-        return out
-
-    def _host_rewards_ns(self, obs, actions):
-        """NavierStokes2D with a user reward class: the step's observation joins the recorded trajectory, then one
-        reward(U, time_index, U_ref, action, action_ref) call per instance (navier_stokes2D.py:147-151)."""
-        import torch
-        from pde_control_gym.src.environments1d.base_env_1d import HistoryView
-        ti_t = self.core.time_index
-        self._ns_hist[torch.arange(self.num_envs, device=self.device), ti_t.long()] = obs
-        ti = ti_t.cpu().numpy()
-        a = torch.as_tensor(actions).detach().cpu().numpy().reshape(self.num_envs, -1)
-        vals = np.zeros(self.num_envs, dtype=np.float64)
-        for b in range(self.num_envs):
-            vals[b] = self.reward_class.reward(HistoryView(self._ns_hist[b]), int(ti[b]), self._U_ref_np, a[b], self._a_ref_np)
-        return torch.as_tensor(vals, dtype=self.core.dtype, device=self.device)
-
-    def _host_rewards_traffic(self, out):
-        """TrafficPDE1D with a user reward class: reward(v_desired, r_desired, v, r) per instance (traffic_arz_env.py:226-233);
-        outside 'outlet-train' an episode also ends when the reward exceeds -0.00023 -- with the USER's reward, as there."""
-        import torch
-        obs, _, done_t, trunc_t = out
-        c = self.core
-        r = c.t["r"].cpu().numpy()
-        y = c.t["y"].cpu().numpy()
-        rs = c.t["rs"].cpu().numpy()
-        v = y / r + c.vm * (1 - r / c.rm)
-        vs = c.vm * (1 - rs / c.rm)
-        M = c.M
-        vals = np.array([self.reward_class.reward(float(vs[b]), float(rs[b]), v[b].reshape(M, 1), r[b].reshape(M, 1))
-                         for b in range(self.num_envs)], dtype=np.float64)
-        rew = torch.as_tensor(vals, dtype=torch.float64, device=self.device)
-        if not self._traffic_train:
-            timed_out = c.t["time"] == 0           # terminate() fired: it rewinds the clock (traffic_arz_env.py:109-111)
-            done_t = (timed_out | (rew > -0.00023)).to(torch.uint8)
-        return obs, rew, done_t, trunc_t
-
-    def _host_rewards(self, te_t, tr_t):
-        """Slow path for user reward classes: one reward() call per instance on a lazy view of its device-resident history."""
-        import torch
-        from pde_control_gym.src.environments1d.base_env_1d import HistoryView
-        te, tr = te_t.cpu().numpy().astype(bool), tr_t.cpu().numpy().astype(bool)
-        ti = self.core.time_index.cpu().numpy()
-        hist = self.core.t["history"]
-        vals = np.zeros(self.num_envs, dtype=np.float32)
-        for b in range(self.num_envs):
-            view = HistoryView(hist[b])
-            vals[b] = self.reward_class.reward(view, int(ti[b]), bool(te[b]), bool(tr[b]), view[int(ti[b])][-1])
-        return torch.as_tensor(vals, device=self.device)
+        t = self.core.t
+        for k, a in zip(self._pool_keys, self._pools(t[self._pool_keys[0]].shape[0], init_pool, beta_pool)):
+            if a is not None and t.get(k) is not None:
+                t[k].copy_(torch.as_tensor(a).to(device=self.device, dtype=t[k].dtype))
 
     # ---- SB3 VecEnv face -----------------------------------------------------------------------------
     def _noise(self, obs):
-        f = getattr(self, "sensing_noise_func", None)
+        f = self.sensing_noise_func
         return obs if f is None else np.asarray(f(obs))
 
     def _obs_np(self, obs):
-        o = obs.cpu().numpy()
-        return o if self.kind == "traffic" else o.astype(np.float32, copy=False)   # the traffic env observes in float64
+        return obs.cpu().numpy().astype(self._obs_np_dtype, copy=False)
 
     def reset(self):
         obs = self._noise(self._obs_np(self.reset_tensor()))
@@ -459,7 +265,6 @@ class PDEVecEnv(BatchedVecEnv):
         is; an asynchronous copy on another stream that outlives the array is not -- ``copy_outputs=True`` serves that).  An
         SB3-style loop (copies what it keeps into its rollout buffer) therefore cycles through two or three buffers; a caller
         that appends every observation to a list keeps getting new ones (``host_buffers`` pinned, plain NumPy copies beyond)."""
-        import sys
         import torch
         if self.device.type != "cuda":
             return [t.numpy().copy() for t in tensors]
@@ -513,14 +318,14 @@ class PDEVecEnv(BatchedVecEnv):
                 tdt = getattr(torch, a_np.dtype.name)          # float32 / float64 / int64 ...
                 pin = torch.empty(a_np.shape, dtype=tdt, pin_memory=True)
                 dev_a = torch.empty(a_np.shape, dtype=tdt, device=self.device)
-                flat = dev_a.reshape(self.num_envs) if (self.kind not in ("ns2d", "traffic") and dev_a.numel() == self.num_envs) else dev_a
+                flat = dev_a.reshape(self.num_envs) if (self._flat_actions and dev_a.numel() == self.num_envs) else dev_a
                 pins[key] = (pin, dev_a, pin.numpy(), flat)
             pin, dev_a, pin_np, a = pins[key]
             pin_np[...] = a_np
             dev_a.copy_(pin, non_blocking=True)
         else:
             a = torch.as_tensor(a_np, device=self.device)
-            if self.kind not in ("ns2d", "traffic"):
+            if self._flat_actions:
                 a = a.reshape(self.num_envs)
         obs_t, r_t, te_t, tr_t = self.step_tensor(a)
         pack = getattr(self.core, "host_pack", None)
@@ -532,8 +337,7 @@ class PDEVecEnv(BatchedVecEnv):
             rew, te, tr = pk[:4 * nb].view(np.float32), pk[4 * nb:5 * nb], pk[5 * nb:6 * nb]
         else:
             obs, rew, te, tr = self._to_host([obs_t, r_t, te_t, tr_t])
-        if self.kind != "traffic":
-            obs = obs.astype(np.float32, copy=False)
+        obs = obs.astype(self._obs_np_dtype, copy=False)
         rew, te, tr = rew.astype(np.float32, copy=False), te.view(np.bool_), tr.view(np.bool_)
         dones = te | tr
         infos = self._fresh_infos()
@@ -554,33 +358,359 @@ class PDEVecEnv(BatchedVecEnv):
                 infos[i] = {"terminal_observation": (final_np[k] if final_np is not None else obs[i]).copy(),
                             "TimeLimit.truncated": bool(tr[i] and not te[i])}
             if not self._fused_reset:
-                mask = torch.as_tensor(dones.astype(np.uint8), device=self.device)
-                if self.kind == "traffic":
-                    rs = self.core.t["rs"].cpu().numpy().copy()
-                    rs[idx] = self._draw_rs(len(idx))
-                    new = self.core.reset(rs, mask=mask)
-                    obs[idx] = new.cpu().numpy()[idx]
-                elif self.kind == "ns2d":
-                    u, v, p = self._sample_ns(idx)
-                    shp = (self.ny, self.nx)
-                    new = self.core.reset(self._scatter(u, idx, shp), self._scatter(v, idx, shp), self._scatter(p, idx, shp), mask=mask)
-                    if self._host_reward:
-                        it = torch.as_tensor(idx, device=self.device)
-                        self._ns_hist[it] = 0
-                        self._ns_hist[it, 0] = new[it]
-                else:
-                    init, beta = self._sample_1d(idx)
-                    if self.core.t["beta"].dim() == 2:
-                        self.core.t["beta"][torch.as_tensor(idx, device=self.device)] = torch.as_tensor(beta).to(
-                            device=self.device, dtype=self.core.t["beta"].dtype)
-                    new = self._noise_t(self.core.reset(self._scatter(init, idx, (self.core.n,)), mask=mask))
-                if self.kind != "traffic":
-                    obs[idx] = self._noise(self._obs_np(new)[idx])
+                obs[idx] = self._noise(self._restart(idx, torch.as_tensor(dones.astype(np.uint8), device=self.device)))
         return obs, rew, dones, infos
 
     @property
     def unwrapped(self):
         return self
+
+    # ---- DeviceRollout (the protocol is listed in BatchedVecEnv) -------------------------------------------------------------
+    @contextmanager
+    def _rollout_into(self, obs, own, obs_is_state):
+        """``rollout_body`` of an engine whose step kernel writes into the rollout buffers; ``own``: the entries it re-points."""
+        t = self.core.t
+        own = {k: t[k] for k in own}
+        try:
+            if obs_is_state:
+                # slot 0 of the rollout buffer is the input state of the first step (not the engine's own buffer, which a graph
+                # warm-up run leaves in its end state)
+                t["obs"] = obs[0]
+            yield
+            # The engine's own observation buffer must end up holding slot T for EVERY engine that wrote its observations
+            # straight into the rollout buffers: the next run() (and any reader of the engine's current observation) starts
+            # from it.  Where the observation IS the state (Navier-Stokes; the 1D engines with full-state sensing) this copy
+            # is also the state hand-over; engines with a separate state (state_in_obs=False, scalar sensing, history
+            # recording) advanced ``u`` in place and only their observation would otherwise be stale (advisor finding r3).
+            own["obs"].copy_(obs[-1])
+        finally:
+            # the step kernel was pointed at slot t of the rollout buffers; hand the engine its own output tensors back so
+            # that a later plain env.step() cannot overwrite rewards[T-1] / terminated[T-1] / truncated[T-1]
+            # (graph-safe: only Python references change)
+            t.update(own)
+
+    def adopt_rollout_obs(self, buf):
+        # A replayed graph has left the end state in ``buf``, the observation tensor that was current when it was captured (its
+        # address is baked in).  The engines double-buffer their observations, so a plain step() / reset between two replays leaves
+        # the engine naming the other buffer: it is pointed back at ``buf``, otherwise the next step would restart from the
+        # pre-rollout state.
+        t = self.core.t
+        if t["obs"] is not buf:
+            if t.get("u") is t["obs"]:         # (1D, full-state sensing: ``u`` names the observation tensor, which is the state)
+                t["u"] = buf
+            for i, o in enumerate(self.core._obs):
+                if o is buf:
+                    self.core._flip = i
+            t["obs"] = buf
+
+
+class PDEVecEnv1D(PDEVecEnv):
+    """Transport, reaction-diffusion and Burgers (PDEBatch1D)."""
+    _rollout_state_keys = ("u", "time_index", "bsum", "ring", "reset_count", "beta")
+    _flat_actions = True
+    _pool_keys = ("reset_init", "reset_beta")
+    # family of the id -> engine kind, flux, default control_sample_rate (Burgers is an extension, not in the reference: the
+    # transport kernel with the u u_x flux)
+    _VARIANTS = {"transport": ("transport", "linear", 0.1), "burgers": ("transport", "burgers", 0.1),
+                 "parabolic": ("parabolic", "linear", 1e-4)}
+
+    def _build(self, kw, backend):
+        from pdecontrolgym_amd.batch1d import PDEBatch1D
+        from pde_control_gym.src.environments1d.base_env_1d import reward_spec_for
+        self.kind, self._flux, default_rate = self._VARIANTS[self.kind]
+        self.sensing_noise_func = kw.get("sensing_noise_func", None)
+        # device-side twin of the hook (hyperbolic.py:160-164 applies it to what sensing_update returns): a callable on TORCH
+        # tensors, [B, obs_dim] -> [B, obs_dim], evaluated on the device -- out of place, the returned tensor is what the
+        # policy sees while the plant state (which the observation tensor IS with full-state sensing) stays clean -- by
+        # step_tensor / reset_tensor and, captured into the graph, by DeviceRollout.  NumPy callbacks keep the host path.
+        self.sensing_noise_tensor_func = kw.get("sensing_noise_tensor_func", None)
+        self._beta_dtype = kw.get("beta_dtype", None)
+        self.reset_init_condition_func = kw.get("reset_init_condition_func")
+        self.reset_recirculation_func = kw.get("reset_recirculation_func")
+        spec = reward_spec_for(self.reward_class)
+        # Any other BaseReward subclass (docs/source/utils/customrewards.rst) takes the slow compatibility path: the engine
+        # records the trajectories on the device and after every step the user's reward() is called once per instance on the
+        # host with a lazy view of that instance's history (uVec[t], uVec[:, -1] ... fetch rows on demand).
+        self._host_reward = spec is None
+        self.core = PDEBatch1D(self.kind, kw["T"], kw["dt"], kw["X"], kw["dx"], kw.get("control_sample_rate", default_rate),
+                               control_type=kw.get("control_type", "Dirchilet"), sensing_loc=kw.get("sensing_loc", "full"),
+                               sensing_type=kw.get("sensing_type", "Dirchilet"), normalize=kw.get("normalize", False),
+                               max_control_value=kw.get("max_control_value", 20),
+                               limit_pde_state_size=kw.get("limit_pde_state_size", False),
+                               max_state_value=kw.get("max_state_value", 1e10), reward=spec, num_envs=self.num_envs,
+                               device=self.device, backend=backend, flux=self._flux, record_history=self._host_reward,
+                               state_in_obs=bool(kw.get("state_in_obs", True)))
+        self.nx, self.nt = self.core.nx, self.core.nt
+        msv = kw.get("max_state_value", 1e10)
+        d = self.core.obs_dim
+        self.observation_space = spaces.Box(np.full(d, -msv, dtype="float32"), np.full(d, msv, dtype="float32"))
+        self.action_space = spaces.Box(np.full(1, -1, dtype="float32"), np.full(1, 1, dtype="float32"))
+
+    def _sample(self, idx):
+        """Initial condition and beta rows for the instances in ``idx`` (user callbacks, reference semantics)."""
+        n = self.core.n
+        if self.batched_reset_func is not None:
+            init, beta = self.batched_reset_func(idx, self.nx)
+            if self._beta_dtype == "float32":
+                beta = np.asarray(beta, dtype=np.float32)
+            return init, beta
+        init = np.zeros((len(idx), n), dtype=np.float32)
+        beta = None
+        try:
+            for k in range(len(idx)):
+                init[k] = self.reset_init_condition_func(self.nx)
+                b = np.asarray(self.reset_recirculation_func(self.nx))
+                if beta is None:      # the dtype the callback returns selects the arithmetic, as in the reference (float64 ->
+                    # mixed-precision kernel); pass ``beta_dtype="float32"`` to make_vec to force the float32 kernels
+                    dt = np.float32 if (b.dtype in (np.float32, np.float16) or self._beta_dtype == "float32") else np.float64
+                    beta = np.zeros((len(idx), n), dtype=dt)
+                beta[k] = b
+        except:  # noqa: E722 - reference hyperbolic.py:207-213
+            raise Exception(_RESET_ERR)
+        return init, beta
+
+    def reset_tensor(self):
+        init, beta = self._sample(np.arange(self.num_envs))
+        return self._noise_t(self.core.reset(init, beta))
+
+    def _pools(self, rows, init_pool, beta_pool):       # without an init_pool both are drawn (a beta_pool the caller gave is kept)
+        if init_pool is None:
+            init_pool, drawn_beta = self._sample(np.arange(rows))
+            if beta_pool is None:
+                beta_pool = drawn_beta
+        return init_pool, beta_pool
+
+    def _install_pools(self, init_pool, beta_pool, pool_episodes):
+        init_pool, beta_pool = self._pools(self.num_envs * max(1, int(pool_episodes)), init_pool, beta_pool)
+        self.core.enable_auto_reset(init_pool, beta_pool=None if beta_pool is False else beta_pool)
+
+    def step_tensor(self, actions):
+        """actions: device tensor [B].  Returns device tensors (obs, reward, terminated, truncated); nothing goes to the host."""
+        obs, r, te, tr = self.core.step(actions)
+        if self._host_reward:
+            r = self._host_rewards(te, tr)
+        return self._noise_t(obs), r, te, tr
+
+    def _host_rewards(self, te_t, tr_t):
+        """Slow path for user reward classes: one reward() call per instance on a lazy view of its device-resident history."""
+        import torch
+        from pde_control_gym.src.environments1d.base_env_1d import HistoryView
+        te, tr = te_t.cpu().numpy().astype(bool), tr_t.cpu().numpy().astype(bool)
+        ti = self.core.time_index.cpu().numpy()
+        hist = self.core.t["history"]
+        vals = np.zeros(self.num_envs, dtype=np.float32)
+        for b in range(self.num_envs):
+            view = HistoryView(hist[b])
+            vals[b] = self.reward_class.reward(view, int(ti[b]), bool(te[b]), bool(tr[b]), view[int(ti[b])][-1])
+        return torch.as_tensor(vals, device=self.device)
+
+    def _restart(self, idx, mask):
+        import torch
+        init, beta = self._sample(idx)
+        if self.core.t["beta"].dim() == 2:
+            self.core.t["beta"][torch.as_tensor(idx, device=self.device)] = torch.as_tensor(beta).to(
+                device=self.device, dtype=self.core.t["beta"].dtype)
+        new = self._noise_t(self.core.reset(self._scatter(init, idx, (self.core.n,), torch.float32), mask=mask))
+        return self._obs_np(new)[idx]
+
+    def rollout_step(self, t, obs, actions, rewards, terminated, truncated):
+        self.core.step(actions[t], out_obs=obs[t + 1], out_reward=rewards[t], out_terminated=terminated[t], out_truncated=truncated[t])
+
+    def rollout_body(self, obs):       # ("u" names the observation tensor where that is the state, and follows it back)
+        return self._rollout_into(obs, ("obs", "u", "reward", "terminated", "truncated"), self.core.state_in_obs)
+
+    def one_launch_fits(self, policy):
+        return self.core.policy_fits_rollout(policy)
+
+
+class NSVecEnv(PDEVecEnv):
+    """NavierStokes2D (NSBatch2D)."""
+    _rollout_state_keys = ("u", "v", "p", "p_out", "time_index", "reset_count")
+    _pool_keys = ("reset_u0", "reset_v0", "reset_p0")
+
+    def _build(self, kw, backend):
+        import torch
+        from pdecontrolgym_amd.batch2d import NSBatch2D
+        from pde_control_gym.src.rewards import NSReward
+        # Any other BaseReward subclass (docs/source/utils/customrewards.rst: the extension point is environment-agnostic)
+        # takes the slow compatibility path: the trajectories U[nt, ny, nx, 2] are recorded on the device and after every step
+        # the user's reward(U, time_index, U_ref, action, action_ref) (navier_stokes2D.py:151) is called once per instance on
+        # the host with a lazy view of that instance's trajectory.
+        self._host_reward = type(self.reward_class) is not NSReward
+        self.reset_init_condition_func = kw.get("reset_init_condition_func")
+        tdtype = kw["dtype"] or torch.float32
+        if isinstance(tdtype, str):
+            tdtype = {"float32": torch.float32, "float64": torch.float64}[tdtype]
+        self.core = NSBatch2D(kw["T"], kw["dt"], kw["X"], kw["dx"], kw["Y"], kw["dy"], kw["boundary_condition"],
+                              kw["U_ref"], kw["action_ref"], action_dim=kw.get("action_dim", 1),
+                              gamma=getattr(self.reward_class, "gamma", 0.0), viscosity=kw.get("viscosity", 0.1),
+                              density=kw.get("density", 1.0),
+                              maximum_pressure_iteration=int(kw.get("maximum_pressure_iteration", 2000)),
+                              stable_factor=kw.get("stable_factor", 0.5), num_envs=self.num_envs, device=self.device,
+                              dtype=tdtype, backend=backend, interleaved_state=bool(kw.get("interleaved_state", True)))
+        self.nx, self.ny, self.nt = self.core.nx, self.core.ny, self.core.nt
+        if self._host_reward:
+            nbytes = self.num_envs * self.nt * self.ny * self.nx * 2 * (8 if tdtype == torch.float64 else 4)
+            if nbytes > (64 << 30):
+                raise MemoryError(f"a host reward callback on NavierStokes2D records every trajectory on the device: "
+                                  f"{nbytes / 2**30:.0f} GiB for {self.num_envs} instances; lower num_envs")
+            self._ns_hist = torch.zeros(self.num_envs, self.nt, self.ny, self.nx, 2, dtype=tdtype, device=self.device)
+            self._U_ref_np, self._a_ref_np = np.asarray(kw["U_ref"]), np.asarray(kw["action_ref"])
+        self.X, self.Y = np.meshgrid(np.linspace(0, kw["X"], self.nx), np.linspace(0, kw["Y"], self.ny))
+        self.observation_space = spaces.Box(np.full((self.nx, self.ny, 2), -np.inf, dtype="float32"),
+                                            np.full((self.nx, self.ny, 2), np.inf, dtype="float32"))
+        self.action_space = spaces.Box(low=-1.0, high=1.0, shape=(kw.get("action_dim", 1),), dtype=np.float32)
+        self.rollout_action_shape = (self.core.action_dim,)
+
+    def _sample(self, idx):
+        if self.batched_reset_func is not None:
+            return self.batched_reset_func(idx, self.X)
+        u, v, p = (np.zeros((len(idx), self.ny, self.nx)) for _ in range(3))
+        try:
+            for k in range(len(idx)):
+                u[k], v[k], p[k] = self.reset_init_condition_func(self.X)
+        except:  # noqa: E722
+            raise Exception(_RESET_ERR)
+        return u, v, p
+
+    def reset_tensor(self):
+        obs = self.core.reset(*self._sample(np.arange(self.num_envs)))
+        if self._host_reward:
+            self._ns_hist.zero_()
+            self._ns_hist[:, 0] = obs
+        return obs
+
+    def _pools(self, rows, init_pool, beta_pool):
+        return self._sample(np.arange(rows)) if init_pool is None else init_pool
+
+    def _install_pools(self, init_pool, beta_pool, pool_episodes):
+        """Pools of initial (u, v, p) fields, drawn from ``reset_init_condition_func`` (two episodes' worth at the most) unless
+        given as a 3-tuple of [P >= num_envs, ny, nx] arrays."""
+        self.core.enable_auto_reset(*self._pools(self.num_envs * max(1, min(int(pool_episodes), 2)), init_pool, None))
+
+    def step_tensor(self, actions):
+        """actions: device tensor [B, action_dim].  Returns device tensors (obs, reward, terminated, truncated), all on the device."""
+        import torch
+        obs, r, te = self.core.step(actions)
+        if self._host_reward:
+            r = self._host_rewards(obs, actions)
+        return obs, r, te, torch.zeros_like(te)
+
+    def _host_rewards(self, obs, actions):
+        """A user reward class: the step's observation joins the recorded trajectory, then one
+        reward(U, time_index, U_ref, action, action_ref) call per instance (navier_stokes2D.py:147-151)."""
+        import torch
+        from pde_control_gym.src.environments1d.base_env_1d import HistoryView
+        ti_t = self.core.time_index
+        self._ns_hist[torch.arange(self.num_envs, device=self.device), ti_t.long()] = obs
+        ti = ti_t.cpu().numpy()
+        a = torch.as_tensor(actions).detach().cpu().numpy().reshape(self.num_envs, -1)
+        vals = np.zeros(self.num_envs, dtype=np.float64)
+        for b in range(self.num_envs):
+            vals[b] = self.reward_class.reward(HistoryView(self._ns_hist[b]), int(ti[b]), self._U_ref_np, a[b], self._a_ref_np)
+        return torch.as_tensor(vals, dtype=self.core.dtype, device=self.device)
+
+    def _restart(self, idx, mask):
+        import torch
+        shp, dt = (self.ny, self.nx), self.core.dtype
+        new = self.core.reset(*(self._scatter(a, idx, shp, dt) for a in self._sample(idx)), mask=mask)
+        if self._host_reward:
+            it = torch.as_tensor(idx, device=self.device)
+            self._ns_hist[it] = 0
+            self._ns_hist[it, 0] = new[it]
+        return self._obs_np(new)[idx]
+
+    # ---- DeviceRollout: the observation IS the state, so slot t of the rollout buffer is also the next step's input
+    def rollout_step(self, t, obs, actions, rewards, terminated, truncated):
+        self.core.step(actions[t], out_obs=obs[t + 1], out_reward=rewards[t], out_terminated=terminated[t])
+
+    @contextmanager
+    def rollout_body(self, obs):
+        with self.core.single_pressure_buffer(), self._rollout_into(obs, ("obs", "reward", "terminated"), True):
+            yield
+
+
+class TrafficVecEnv(PDEVecEnv):
+    """TrafficPDE1D (TrafficBatch); observes in float64."""
+    one_launch_obs_noise = False           # (the traffic rollout kernel has no obs_noise input)
+    _pool_keys = ("reset_rs",)
+    _obs_np_dtype = np.float64
+
+    def _build(self, kw, backend):
+        import random
+        from pdecontrolgym_amd.batch_traffic import TrafficBatch
+        from pde_control_gym.src.rewards import TrafficARZReward
+        # any other BaseReward subclass: reward(v_desired, r_desired, v, r) (traffic_arz_env.py:228) per instance on the host
+        self._host_reward = type(self.reward_class) is not TrafficARZReward
+        sim = kw.get("simulation_type", "inlet")
+        self.core = TrafficBatch(kw["T"], kw["dt"], kw["X"], kw["dx"], sim, kw.get("v_max", 40), kw.get("ro_max", 0.16),
+                                 kw.get("tau", 60), kw.get("limit_pde_state_size", False), kw.get("control_freq", 1),
+                                 num_envs=self.num_envs, device=self.device, backend=backend)
+        self._traffic_train = sim == "outlet-train"
+        self._rs_fixed = kw.get("ro_steady", 0.12)
+        self._draw_rs = lambda k: (np.array([{0: 0.115, 1: 0.12, 2: 0.125}[random.randint(0, 2)] for _ in range(k)])
+                                   if self._traffic_train else np.full(k, self._rs_fixed))
+        rs0 = self._draw_rs(self.num_envs)                 # construction-time draw fixes the action bounds (:97-100)
+        self.core.set_action_bounds(rs0 * self.core.Veq(rs0))
+        M = self.core.M
+        lo, hi = (-10, 10) if self._traffic_train else (0, 40)
+        self.observation_space = spaces.Box(low=lo, high=hi, shape=(2 * M,), dtype=np.float64)
+        qs = float(rs0[0] * self.core.Veq(rs0[0]))
+        self.action_space = spaces.Box(dtype=np.float64, low=qs * 0.8, high=1.2 * qs, shape=(self.core.action_dim,))
+        self.nx, self.nt = M, int(round(kw["T"] / kw["dt"]))
+        self.rollout_action_shape = (2,) if self.core.action_dim == 2 else ()      # two-command traffic has [B, 2] action slots
+
+    def reset_tensor(self):
+        return self.core.reset(self._draw_rs(self.num_envs))
+
+    def _pools(self, rows, init_pool, beta_pool):
+        return (self._draw_rs(rows) if init_pool is None else init_pool,)
+
+    def _install_pools(self, init_pool, beta_pool, pool_episodes):
+        """A pool of steady-state densities (redrawn per episode in 'outlet-train', :247-252)."""
+        self.core.enable_auto_reset(*self._pools(self.num_envs * max(1, int(pool_episodes)), init_pool, None))
+
+    def step_tensor(self, actions):
+        """actions: device tensor [B] / [B, action_dim].  Returns device tensors (obs, reward, done, truncated), all on the device."""
+        out = self.core.step(actions)
+        return self._host_rewards(out) if self._host_reward else out
+
+    def _host_rewards(self, out):
+        """A user reward class: reward(v_desired, r_desired, v, r) per instance (traffic_arz_env.py:226-233);
+        outside 'outlet-train' an episode also ends when the reward exceeds -0.00023 -- with the USER's reward, as there."""
+        import torch
+        obs, _, done_t, trunc_t = out
+        c = self.core
+        r = c.t["r"].cpu().numpy()
+        y = c.t["y"].cpu().numpy()
+        rs = c.t["rs"].cpu().numpy()
+        v = y / r + c.vm * (1 - r / c.rm)
+        vs = c.vm * (1 - rs / c.rm)
+        M = c.M
+        vals = np.array([self.reward_class.reward(float(vs[b]), float(rs[b]), v[b].reshape(M, 1), r[b].reshape(M, 1))
+                         for b in range(self.num_envs)], dtype=np.float64)
+        rew = torch.as_tensor(vals, dtype=torch.float64, device=self.device)
+        if not self._traffic_train:
+            timed_out = c.t["time"] == 0           # terminate() fired: it rewinds the clock (traffic_arz_env.py:109-111)
+            done_t = (timed_out | (rew > -0.00023)).to(torch.uint8)
+        return obs, rew, done_t, trunc_t
+
+    def _restart(self, idx, mask):
+        rs = self.core.t["rs"].cpu().numpy().copy()
+        rs[idx] = self._draw_rs(len(idx))
+        # (the rows are float64 already and this family takes no sensing-noise hook: step_wait's _noise leaves them as they are)
+        return self._obs_np(self.core.reset(rs, mask=mask))[idx]
+
+    def one_launch_fits(self, policy):
+        return self.core.policy_fits_rollout(policy)
+
+    def rollout_one_launch(self, obs, actions, *outputs, noise=None, **kw):
+        if actions.dim() == 2:                 # the traffic kernel takes [T, B, action_dim]
+            actions, noise = actions.unsqueeze(2), (noise.unsqueeze(2) if noise is not None else None)
+        self.core.rollout(obs, actions, *outputs, noise=noise, **kw)
+
+
+_FAMILIES = {"transport": PDEVecEnv1D, "burgers": PDEVecEnv1D, "parabolic": PDEVecEnv1D, "ns2d": NSVecEnv, "traffic": TrafficVecEnv}
 
 
 def make_vec(env_id: str, num_envs: int, **kwargs):

@@ -116,6 +116,9 @@ class TumorVecEnv(BatchedVecEnv):
             obs = torch.where((rest & ~done)[:, None], seen, obs)
         return obs, rewards, term, trunc
 
+    def rollout_obs(self):          # (DeviceRollout: the observation IS the engine's one live row)
+        return self.core.t["u"]
+
     # ---- SB3 VecEnv face ------------------------------------------------------------------------------------------------
     def step_wait(self):
         obs, rew, term, trunc = self.step_tensor(np.asarray(self._actions, dtype=np.float64).reshape(self.num_envs))

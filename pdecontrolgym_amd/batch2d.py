@@ -12,6 +12,8 @@ mode asked for by BASELINE.json (tolerance stated in tests/test_gpu_ns2d.py).
 """
 from __future__ import annotations
 
+from contextlib import contextmanager
+
 from . import _native as N
 from .checkpoint import EngineCheckpoint
 
@@ -129,6 +131,17 @@ class NSBatch2D(EngineCheckpoint):
         if self._obs[self._flip] is prev:           # never write the observation over the state it is computed from
             self._flip ^= 1
         self.t["obs"] = self._obs[self._flip]
+
+    @contextmanager
+    def single_pressure_buffer(self):
+        """While steps are baked into a graph the pressure must stay in ONE tensor: inside this block the 256 x 256 engines do not
+        ping-pong (the C side copies the solved pressure home instead)."""
+        saved = self._p_pingpong, self.t["p_out"]
+        self._p_pingpong, self.t["p_out"] = False, None
+        try:
+            yield
+        finally:
+            self._p_pingpong, self.t["p_out"] = saved
 
     def enable_auto_reset(self, u0_pool, v0_pool, p0_pool, keep_final_obs: bool = True):
         """Fused VecEnv auto-reset: an instance whose step ends terminated restarts inside the same C-ABI call (no host

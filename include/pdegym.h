@@ -16,6 +16,9 @@
  *                           (public API: examples/NavierStokes/NS2Doptimization.py:97)
  *   pdegym_ns2d_reset_masked_f32/_f64    replaces the state part of NavierStokes2D.reset  navier_stokes2D.py:186-192
  *   pdegym_rownorm2_f32     replaces np.linalg.norm(row, 2)       hyperbolic.py:190, parabolic.py:185
+ *   pdegym_backstep_gain_transport / _parabolic  replace solveKernelFunction   examples/transportPDE/transport1Dbackstepping.py:22-29,
+ *                                                examples/reactionDiffusionPDE/reactionDiffusion1DBackstepping.py:22-35
+ *   pdegym_backstep_control replaces solveControl                 transport1Dbackstepping.py:32-36, reactionDiffusion1DBackstepping.py:38-39
  *
  * One call advances EVERY instance of a batch by one env-step (S PDE sub-steps for the 1D envs, one
  * Chorin projection step with K Jacobi sweeps for NS2D).  Instances are independent.
@@ -41,7 +44,7 @@
 extern "C" {
 #endif
 
-#define PDEGYM_ABI_VERSION 15
+#define PDEGYM_ABI_VERSION 16
 #define PDEGYM_RING 128          /* slots of the per-instance row-norm ring (look-back is 100 rows) */
 #define PDEGYM_LOOKBACK 100      /* tuned_reward_1d.py:25,40: int(1/0.01) rows */
 #define PDEGYM_MAX_N1D 2048      /* nodes per 1D row kept in registers by the wave-per-instance kernels */
@@ -492,6 +495,48 @@ typedef struct pdegym_mlp_s {
 /* y[b, :] = net(x[b, :]) for b < B; x_stride / y_stride = ELEMENTS between consecutive rows (>= the row lengths). */
 int pdegym_mlp_forward(const pdegym_mlp* net, const void* x, int64_t x_stride, void* y, int64_t y_stride, int32_t B,
                        void* stream);
+
+/* ---- backstepping baseline (the controller every result table of the reference compares the learned policies against) ------
+ * Gains: theta [R, m] float32 rows, sampled by the caller (the examples use linspace(dx, X, m), NOT the plant's grid) -> gain [R, m]
+ * float64, one wave per row, 2 <= m <= PDEGYM_MAX_N1D; dx is the Python double.  Both are BIT-IDENTICAL to the reference under
+ * NumPy >= 2 (NEP 50: a float32 scalar times a Python double stays float32):
+ *   parabolic: the last row k[m-1][:] of solveKernelFunction (the only row solveControl reads);
+ *   transport: np.flip(kappa), kappa[i] = (sum_{j<i} (kappa[i-j]*theta[j])*dx) - theta[i] added left to right from 0 -- an ordered
+ *              chain of m(m-1)/2 additions per row: computed once per theta row, never per step. */
+int pdegym_backstep_gain_parabolic(const float* theta, double* gain, int32_t R, int32_t m, double dx, void* stream);
+int pdegym_backstep_gain_transport(const float* theta, double* gain, int32_t R, int32_t m, double dx, void* stream);
+
+/* Order of the additions of the control law's dot product */
+enum {
+  PDEGYM_BACKSTEP_TREE = 0,     /* products per lane (i = lane, lane + 64, ...), then the wave reduction: the batch default     */
+  PDEGYM_BACKSTEP_ORDERED = 1   /* i ascending from 0.0, the reference's Python loop / builtin sum: commands bit-identical to it */
+};
+/* a[b] = (sum_{i<len} gain_row(b)[i] * (double)obs[b, i]) * scale, one wave per instance, the observation row read once.
+ * transport1Dbackstepping.py: len = n, scale = 1e-2; reactionDiffusion1DBackstepping.py: len = min(m, n - 1), scale = dx.
+ * gain_row(b) = gain0 + b * gain_stride until instance b has restarted; with gain_pool and reset_count[b] = c >= 1 it is pool row
+ * (b + (c - 1)*B) mod pool_rows -- the row the step kernel's fused auto-reset took reset_beta from when it started the running
+ * episode (pdegym_bufs1d.reset_count: the SAME counter, read through the same function).  The two orders differ by at most
+ * 2 * len * 2^-53 * sum|gain_i * obs_i| * |scale|. */
+typedef struct pdegym_backstep {
+  const double* gain0;        /* [B, m], or one shared row with gain_stride = 0                                             */
+  int64_t gain_stride;        /* doubles between the rows of consecutive instances                                          */
+  const double* gain_pool;    /* optional [pool_rows, m]: gains of the reset pool's theta rows (needs reset_count)           */
+  const int32_t* reset_count; /* [B] restarts so far, as the step kernels keep it; NULL = gain0 always                       */
+  int32_t pool_rows;          /* rows of gain_pool (0 = B)                                                                   */
+  int32_t m;                  /* length of a gain row                                                                        */
+  const float* obs;           /* [B, obs_stride] observation rows (full-state sensing)                                       */
+  int64_t obs_stride;         /* floats between consecutive rows (>= len)                                                    */
+  int32_t len;                /* 1 .. m terms                                                                                */
+  int32_t order;              /* PDEGYM_BACKSTEP_*                                                                           */
+  double scale;
+  double* out64;              /* [B] the command in double (PDEGYM_ACTION_F64: the reference's own call), or NULL            */
+  float* out32;               /* [B] the command rounded once to float32, + noise, clamped -- exactly one of the two outputs */
+  const float* noise;         /* optional [B], added before the clamp (out32 only)                                           */
+  int32_t clamp;              /* nonzero: clamp to [lo, hi] (out32 only)                                                     */
+  float lo, hi;
+  int32_t reserved_;
+} pdegym_backstep;
+int pdegym_backstep_control(const pdegym_backstep* c, int32_t B, void* stream);
 
 /* ---- test-only: kernel dispatch overrides -------------------------------------------------------------------------
  * Nothing on the product path calls this (the reference has no counterpart); the parity tests use it to run the SAME step

@@ -11,7 +11,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "lib", "libpdegym_hip.so")
 
-ABI_VERSION = 15
+ABI_VERSION = 16
 RING = 128
 LOOKBACK = 100
 MAX_N1D = 8192
@@ -33,11 +33,13 @@ EXPORTS = [
     "pdegym_ns2d_reset_masked_f64", "pdegym_traffic_step", "pdegym_traffic_reset_masked",
     "pdegym_tumor_step", "pdegym_tumor_advance", "pdegym_tumor_reset_masked", "pdegym_mlp_forward",
     "pdegym_transport_rollout", "pdegym_parabolic_rollout", "pdegym_traffic_rollout", "pdegym_debug_set",
+    "pdegym_backstep_gain_parabolic", "pdegym_backstep_gain_transport", "pdegym_backstep_control",
 ]
 # keys of pdegym_debug_set (test-only dispatch overrides, include/pdegym.h)
 DEBUG_NS_GENERIC, DEBUG_NS_NO_COL, DEBUG_NS_COL_MIN_BATCH, DEBUG_NS_NO_LDS_JACOBI = range(4)
 MLP_MAX_LAYERS, MLP_MAX_WIDTH, MLP_MAX_INPUT = 4, 256, 8192
 MLP_IDENTITY, MLP_TANH, MLP_RELU = 0, 1, 2
+BACKSTEP_TREE, BACKSTEP_ORDERED = 0, 1
 
 
 class Params1D(C.Structure):
@@ -137,6 +139,13 @@ class Mlp(C.Structure):
                 ("layer", MlpLayer * MLP_MAX_LAYERS)]
 
 
+class Backstep(C.Structure):
+    _fields_ = [("gain0", C.c_void_p), ("gain_stride", C.c_int64), ("gain_pool", C.c_void_p), ("reset_count", C.c_void_p),
+                ("pool_rows", C.c_int32), ("m", C.c_int32), ("obs", C.c_void_p), ("obs_stride", C.c_int64), ("len", C.c_int32),
+                ("order", C.c_int32), ("scale", C.c_double), ("out64", C.c_void_p), ("out32", C.c_void_p), ("noise", C.c_void_p),
+                ("clamp", C.c_int32), ("lo", C.c_float), ("hi", C.c_float), ("reserved_", C.c_int32)]
+
+
 class NativeError(RuntimeError):
     pass
 
@@ -199,6 +208,11 @@ def load():
     lib.pdegym_tumor_reset_masked.restype = C.c_int
     lib.pdegym_mlp_forward.argtypes = [C.POINTER(Mlp), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
     lib.pdegym_mlp_forward.restype = C.c_int
+    for f in (lib.pdegym_backstep_gain_parabolic, lib.pdegym_backstep_gain_transport):
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_void_p]
+        f.restype = C.c_int
+    lib.pdegym_backstep_control.argtypes = [C.POINTER(Backstep), C.c_int32, C.c_void_p]
+    lib.pdegym_backstep_control.restype = C.c_int
     lib.pdegym_debug_set.argtypes = [C.c_int32, C.c_int32]
     lib.pdegym_debug_set.restype = C.c_int32
     if lib.pdegym_abi_version() != ABI_VERSION:

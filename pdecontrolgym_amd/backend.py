@@ -351,6 +351,54 @@ class HipBackend:
         N.check(self.lib.pdegym_mlp_forward(C.byref(net), x.data_ptr(), x.stride(0), y.data_ptr(), y.stride(0), B,
                                             N.current_stream_ptr(x.device)), "pdegym_mlp_forward")
 
+    # ---- backstepping baseline -------------------------------------------------------------------
+    @_on_device_of("theta")
+    def backstep_gain(self, kind: str, theta, gain, dx: float):
+        """gain[r] = backstepping gain of theta[r] (pdegym_backstep_gain_*): ``theta`` float32 [R, m], ``gain`` float64 [R, m],
+        ``dx`` the Python double."""
+        import torch
+        fn = self.lib.pdegym_backstep_gain_transport if kind == "transport" else self.lib.pdegym_backstep_gain_parabolic
+        if theta.dim() != 2 or tuple(gain.shape) != tuple(theta.shape):
+            raise N.NativeError(f"backstep_gain: theta and gain must both be [R, m], got {tuple(theta.shape)} and {tuple(gain.shape)}")
+        R, m = theta.shape
+        N.check(fn(N.dptr(theta, torch.float32), N.dptr(gain, torch.float64), R, m, float(dx), N.current_stream_ptr(theta.device)),
+                f"pdegym_backstep_gain_{kind}")
+
+    @_on_device_of("obs")
+    def backstep_control(self, obs, out, gain0, length: int, scale: float, ordered: bool = False, gain_pool=None, reset_count=None,
+                         noise=None, clamp=None):
+        """out[b] = (sum_{i<length} gain_row(b)[i] * obs[b, i]) * scale (pdegym_backstep_control): ``obs`` float32 [B, >= length]
+        (row stride = stride(0)), ``gain0`` float64 [B, m] or [m] (shared), ``out`` float64 [B], or float32 [B] (+ ``noise`` [B],
+        clamped to ``clamp`` = (lo, hi)); ``gain_pool`` [P, m] + ``reset_count`` int32 [B]: see include/pdegym.h."""
+        import torch
+        if obs.dim() != 2 or obs.stride(1) != 1 or obs.dtype != torch.float32 or not obs.is_cuda:
+            raise N.NativeError("backstep_control: obs must be a float32 HIP tensor [B, width] with unit inner stride")
+        B = int(obs.shape[0])
+        if out.dtype not in (torch.float32, torch.float64) or out.numel() != B:
+            raise N.NativeError(f"backstep_control: out must be a float32 or float64 tensor of {B} elements")
+        if gain0.dim() == 2 and gain0.shape[0] != B:
+            raise N.NativeError(f"backstep_control: {gain0.shape[0]} gain rows for {B} instances")
+        c = N.Backstep()
+        c.gain0, c.gain_stride, c.m = N.dptr(gain0, torch.float64), (0 if gain0.dim() == 1 else gain0.stride(0)), int(gain0.shape[-1])
+        if gain_pool is not None:
+            if gain_pool.dim() != 2 or gain_pool.shape[1] != c.m or reset_count is None or reset_count.numel() != B:
+                raise N.NativeError("backstep_control: gain_pool must be [P, m] and come with reset_count [B]")
+            c.gain_pool, c.pool_rows = N.dptr(gain_pool, torch.float64), int(gain_pool.shape[0])
+            c.reset_count = N.dptr(reset_count, torch.int32)
+        c.obs, c.obs_stride, c.len = obs.data_ptr(), obs.stride(0), int(length)
+        c.order, c.scale = (N.BACKSTEP_ORDERED if ordered else N.BACKSTEP_TREE), float(scale)
+        if out.dtype == torch.float64:
+            c.out64 = N.dptr(out, torch.float64)
+        else:
+            c.out32 = N.dptr(out, torch.float32)
+        if noise is not None:
+            if noise.numel() != B:
+                raise N.NativeError(f"backstep_control: noise must have {B} elements")
+            c.noise = N.dptr(noise, torch.float32)
+        if clamp is not None:
+            c.clamp, c.lo, c.hi = 1, float(clamp[0]), float(clamp[1])
+        N.check(self.lib.pdegym_backstep_control(C.byref(c), B, N.current_stream_ptr(obs.device)), "pdegym_backstep_control")
+
 
 _default = None
 

@@ -1,0 +1,352 @@
+"""GPU tests of the backstepping baseline (csrc/pdegym_backstep.hip, pde_control_gym.BacksteppingController): the gain kernels
+against the reference's own gain vectors (tests/golden/kat.npz) and against the NumPy restatement of tests/test_backstepping.py
+(which reproduces those goldens bit for bit), the control law in both summation orders, the four published closed loops with the
+reference's commands reproduced bit for bit, and DeviceRollout with gains that follow the fused auto-reset."""
+import functools
+
+import numpy as np
+import pytest
+
+from tests import poison
+from tests.test_backstepping import GAIN, cheb_theta, rule_row
+from tests.test_oracle_golden import KAT_PUBLISHED
+
+pytestmark = pytest.mark.gpu
+torch = pytest.importorskip("torch")
+f32, f64 = np.float32, np.float64
+
+M_LIST = (2, 3, 5, 63, 64, 65, 129, 257, 513)      # degenerate loops; one short of / exactly / one past a wave; 2 .. 9 per lane, ragged
+R_LIST = (1, 3, 70)                                # one wave; a partial workgroup; more than one workgroup, the last one partial
+DX_LIST = (1e-2, 5e-3, 1.0 / 64)
+# every kernel launched in csrc/pdegym_backstep.hip -> the poisoned-buffer / guard-band tests that reach it (tests/test_backstepping.py
+# fails when a launched kernel is missing here)
+KERNEL_CASES = {"gain_parabolic_kernel": ["test_gain_kernels_write_exactly_their_rows"],
+                "gain_transport_kernel": ["test_gain_kernels_write_exactly_their_rows"],
+                "backstep_control_kernel": ["test_control_writes_exactly_its_outputs_and_follows_the_pool_rule"]}
+AMP = {"transport": 5.0, "parabolic": 50.0}        # the amplitudes of the two example scripts
+
+
+def _backend():
+    from pdecontrolgym_amd.backend import default_backend
+    return default_backend()
+
+
+def _dev(a, dtype=None):
+    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).cuda()
+
+
+@functools.lru_cache(maxsize=None)
+def _theta(kind, m, dx):
+    """70 Chebyshev rows amp*cos(gamma*acos(x)) on linspace(dx, 1, m), gamma in [5, 10]: the family and ranges of the examples."""
+    rng = np.random.default_rng(int(m * 1000 + dx * 1e6) + (kind == "parabolic"))
+    x = np.linspace(dx, 1.0, m)
+    th = (AMP[kind] * np.cos(rng.uniform(5, 10, (70, 1)) * np.arccos(x)[None])).astype(f32)
+    th.setflags(write=False)
+    return th
+
+
+@functools.lru_cache(maxsize=None)
+def _reference(kind, m, dx):
+    """The restatement on all 70 rows, computed once and shared (rows are independent in it: row r of any batch is row r here)."""
+    g = GAIN[kind](_theta(kind, m, dx), dx)
+    g.setflags(write=False)
+    return g
+
+
+def _gain(kind, theta, dx):
+    th = _dev(theta, torch.float32)
+    out = torch.empty(th.shape, dtype=torch.float64, device="cuda")
+    _backend().backstep_gain(kind, th, out, dx)
+    return out.cpu().numpy()
+
+
+# ---- gains ------------------------------------------------------------------------------------------------------------------------
+def test_gain_kernels_equal_the_reference_goldens_bitwise(golden_kat):
+    kt = _gain("transport", cheb_theta(np.linspace(1e-2, 1, 100), 7.35, 5)[None], 1e-2)[0]
+    np.testing.assert_array_equal(kt, golden_kat["T_u1"].kernel)
+    kp = _gain("parabolic", cheb_theta(np.linspace(5e-3, 1, 200), 8, 50)[None], 5e-3)[0]
+    np.testing.assert_array_equal(kp, golden_kat["P_u1"].kernel_row)
+
+
+@pytest.mark.parametrize("m", M_LIST)
+@pytest.mark.parametrize("kind", ["transport", "parabolic"])
+def test_gain_kernels_equal_the_restatement_bitwise(kind, m):
+    """Every m x dx x R: bit-equal to the restatement; a batch of R rows gives each row what it gets alone or in the batch of 70
+    (batch invariance: the reference rows are those of the 70-row batch)."""
+    for dx in DX_LIST:
+        ref, th = _reference(kind, m, dx), _theta(kind, m, dx)
+        for R in R_LIST:
+            np.testing.assert_array_equal(_gain(kind, th[:R], dx), ref[:R], err_msg=f"{kind} m={m} dx={dx} R={R}")
+        np.testing.assert_array_equal(_gain(kind, th[69:70], dx), ref[69:70], err_msg=f"{kind} m={m} dx={dx} row 69 alone")
+
+
+@pytest.mark.parametrize("m,R", [(2, 1), (65, 3), (129, 70), (513, 5)])
+@pytest.mark.parametrize("kind", ["transport", "parabolic"])
+def test_gain_kernels_write_exactly_their_rows(kind, m, R):
+    """Poisoned output with guard bands: every element of [R, m] is written, nothing outside it; theta is left alone."""
+    dx = 5e-3
+    arena = poison.Arena("cuda")
+    th = arena.like("theta", _dev(_theta(kind, m, dx)[:R], torch.float32))
+    out = poison.poison_(arena.new("gain", (R + 2, m), torch.float64))
+    _backend().backstep_gain(kind, th, out[1:R + 1], dx)
+    arena.check()
+    poison.assert_untouched(out, (slice(0, 1),), "row before the gains")
+    poison.assert_untouched(out, (slice(R + 1, R + 2),), "row after the gains")
+    poison.assert_written(out, (slice(1, R + 1),), "gain", like=_dev(np.concatenate([np.zeros((1, m)), _reference(kind, m, dx)[:R],
+                                                                                     np.zeros((1, m))])))
+    np.testing.assert_array_equal(th.cpu().numpy(), _theta(kind, m, dx)[:R])
+
+
+def test_gain_entry_points_refuse_bad_sizes():
+    from pdecontrolgym_amd import _native as N
+    th, out = torch.zeros(2, 1, device="cuda"), torch.zeros(2, 1, dtype=torch.float64, device="cuda")
+    with pytest.raises(N.NativeError, match=r"m must be in \[2, 2048\]"):
+        _backend().backstep_gain("parabolic", th, out, 1e-2)
+    th, out = torch.zeros(1, 2049, device="cuda"), torch.zeros(1, 2049, dtype=torch.float64, device="cuda")
+    with pytest.raises(N.NativeError, match=r"m must be in \[2, 2048\]"):
+        _backend().backstep_gain("transport", th, out, 1e-2)
+
+
+def test_widest_rows():
+    """m = PDEGYM_MAX_N1D = 2048 (32 columns per lane) on the parabolic kernel, m = 1025 (the 32-per-lane instantiation, ragged) on
+    the transport kernel, whose restatement costs m^2/2 NumPy calls."""
+    th = _theta("parabolic", 2048, 5e-3)[:2]
+    np.testing.assert_array_equal(_gain("parabolic", th, 5e-3), GAIN["parabolic"](th, 5e-3))
+    th = _theta("transport", 1025, 1e-2)[:2]
+    np.testing.assert_array_equal(_gain("transport", th, 1e-2), GAIN["transport"](th, 1e-2))
+
+
+# ---- control law ------------------------------------------------------------------------------------------------------------------
+def _law_rows(gain, obs, length, scale):
+    """solveControl per row: products added left to right from 0.0, then the scale (elementwise over the rows)."""
+    s = np.zeros(obs.shape[0])
+    for i in range(length):
+        s = s + gain[:, i] * obs[:, i].astype(f64)
+    return s * f64(scale)
+
+
+def _control(obs, gain0, length, scale, ordered, out_dtype=torch.float64, **kw):
+    out = torch.empty(obs.shape[0], dtype=out_dtype, device="cuda")
+    _backend().backstep_control(obs, out, gain0, length, scale, ordered=ordered, **kw)
+    return out.cpu().numpy()
+
+
+@pytest.mark.parametrize("m", M_LIST)
+def test_control_law_orders(m):
+    """Ordered mode equals the left-to-right NumPy chain bit for bit; tree mode stays within the summation bound of two orders of
+    the same products, 2 * len * 2^-53 * sum|g_i o_i| * |scale|, computed from the inputs.  B = 70: more than one wave per
+    workgroup and a partial last workgroup; observation rows longer than len with their own stride."""
+    rng = np.random.default_rng(m)
+    scale = 5e-3
+    for B in R_LIST:
+        gain = rng.normal(0, 30, (B, m))
+        obs = rng.uniform(-10, 10, (B, m + 3)).astype(f32)
+        for length in sorted({m, max(1, m - 1)}):
+            want = _law_rows(gain, obs, length, scale)
+            g, o = _dev(gain), _dev(obs)
+            got = _control(o, g, length, scale, ordered=True)
+            np.testing.assert_array_equal(got, want, err_msg=f"ordered m={m} B={B} len={length}")
+            tree = _control(o, g, length, scale, ordered=False)
+            bound = 2 * length * 2.0 ** -53 * np.abs(gain[:, :length] * obs[:, :length].astype(f64)).sum(axis=1) * abs(scale)
+            err = np.abs(tree - want)
+            print(f"m={m} B={B} len={length}: max |tree - ordered| / bound = {np.max(err / bound):.3g}")
+            assert np.all(err <= bound), (m, B, length, float(np.max(err / bound)))
+            # one shared gain row (stride 0)
+            shared = _control(o, g[0], length, scale, ordered=True)
+            np.testing.assert_array_equal(shared, _law_rows(np.repeat(gain[:1], B, 0), obs, length, scale))
+
+
+@pytest.mark.parametrize("ordered", [True, False])
+def test_float_output_is_the_double_rounded_once_plus_noise_then_clamp(ordered):
+    rng = np.random.default_rng(3)
+    B, m = 70, 129
+    g, o = _dev(rng.normal(0, 30, (B, m))), _dev(rng.uniform(-10, 10, (B, m)).astype(f32))
+    a64 = _control(o, g, m, 1e-2, ordered)
+    np.testing.assert_array_equal(_control(o, g, m, 1e-2, ordered, torch.float32), a64.astype(f32))
+    nz = rng.normal(0, 5, B).astype(f32)
+    lo, hi = -15.0, 12.5
+    assert (np.abs(a64) > 15).any() and (np.abs(a64) < 12).any()        # both sides of the clamp are exercised
+    got = _control(o, g, m, 1e-2, ordered, torch.float32, noise=_dev(nz), clamp=(lo, hi))
+    np.testing.assert_array_equal(got, np.minimum(np.maximum(a64.astype(f32) + nz, f32(lo)), f32(hi)))
+    np.testing.assert_array_equal(_control(o, g, m, 1e-2, ordered, torch.float32, noise=_dev(nz)), a64.astype(f32) + nz)
+
+
+def test_control_writes_exactly_its_outputs_and_follows_the_pool_rule():
+    """Poisoned outputs with guard bands, B = 6 instances inside buffers of 8; gain rows by the documented pool rule for restart
+    counters 0 .. 5 with P = 7 pool rows."""
+    rng = np.random.default_rng(11)
+    B, P, m = 6, 7, 65
+    gain0, pool = rng.normal(0, 3, (B, m)), rng.normal(0, 3, (P, m))
+    obs = rng.uniform(-2, 2, (B, m)).astype(f32)
+    counts = np.array([0, 1, 2, 3, 4, 5], dtype=np.int32)
+    rows = [rule_row(b, int(counts[b]), B, P) for b in range(B)]
+    picked = np.stack([gain0[b] if rows[b] is None else pool[rows[b]] for b in range(B)])
+    want = _law_rows(picked, obs, m, 1e-2)
+    assert not np.array_equal(want, _law_rows(np.stack([gain0[0]] + [pool[b] for b in range(1, B)]), obs, m, 1e-2))
+    arena = poison.Arena("cuda")
+    o, g, gp, rc = (arena.like(k, _dev(v)) for k, v in (("obs", obs), ("gain0", gain0), ("pool", pool), ("count", counts)))
+    for dtype, ref in ((torch.float64, want), (torch.float32, want.astype(f32))):
+        out = poison.poison_(arena.new(f"out{dtype}", (B + 2,), dtype))
+        _backend().backstep_control(o, out[1:B + 1], g, m, 1e-2, ordered=True, gain_pool=gp, reset_count=rc)
+        arena.check()
+        poison.assert_untouched(out, (slice(0, 1),), "before the commands")
+        poison.assert_untouched(out, (slice(B + 1, B + 2),), "after the commands")
+        np.testing.assert_array_equal(out[1:B + 1].cpu().numpy(), ref)
+    np.testing.assert_array_equal(rc.cpu().numpy(), counts)
+
+
+# ---- the reference's published closed loops ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", sorted(KAT_PUBLISHED))
+def test_published_closed_loops_with_the_device_controller(golden_kat, name):
+    """transport1Dbackstepping.py / reactionDiffusion1DBackstepping.py with gains and law on the device (ordered), commands handed
+    to the step kernel in float64 as the scripts do: every one of the 50 / 1000 commands equals the reference's bit for bit, and
+    so does the final row; episode reward and sum of L2 norms match the published values (rtol 1e-5, as tests/test_gpu_api.py)."""
+    from pde_control_gym import BacksteppingController
+    from pdecontrolgym_amd import _native as N
+    from pdecontrolgym_amd.batch1d import PDEBatch1D, RewardSpec
+    g = golden_kat[name]
+    u0 = 1.0 if name.endswith("u1") else 10.0
+    common = dict(X=1, control_type="Dirchilet", sensing_loc="full", sensing_type=None, normalize=False, max_control_value=20,
+                  limit_pde_state_size=True, max_state_value=1e10, num_envs=1, device="cuda")
+    if name.startswith("T"):
+        kind, dx = "transport", 1e-2
+        env = PDEBatch1D(kind, T=5, dt=1e-4, dx=dx, control_sample_rate=0.1, reward=RewardSpec(N.REWARD_TUNED1D, 50000, -1e3, 3e2), **common)
+        theta = cheb_theta(np.linspace(dx, 1, 100), 7.35, 5)
+    else:
+        kind, dx = "parabolic", 5e-3
+        env = PDEBatch1D(kind, T=1, dt=1e-5, dx=dx, control_sample_rate=1e-3, reward=RewardSpec(N.REWARD_TUNED1D, 100000, -1e3, 3e2), **common)
+        theta = cheb_theta(np.linspace(dx, 1, 200), 8, 50)
+    ctrl = BacksteppingController(kind, theta, dx, order="ordered", device="cuda")
+    steps, n = len(g.actions), env.n
+    obs = torch.zeros(steps + 1, 1, n, device="cuda")
+    acts = torch.zeros(steps, 1, dtype=torch.float64, device="cuda")
+    rew = torch.zeros(steps, 1, device="cuda")
+    te, tr = (torch.zeros(steps, 1, dtype=torch.uint8, device="cuda") for _ in range(2))
+    obs[0].copy_(env.reset(torch.full((1, n), u0), torch.tensor(g.beta)[None]))
+    for k in range(steps):
+        ctrl.forward_into(obs[k], acts[k])
+        env.step(acts[k], out_obs=obs[k + 1], out_reward=rew[k], out_terminated=te[k], out_truncated=tr[k], action_kind=N.ACTION_F64)
+    a = acts.cpu().numpy()[:, 0]
+    bad = np.nonzero(a != g.actions)[0]
+    assert bad.size == 0, f"{bad.size} of {steps} commands differ, first at step {bad[0]}: {a[bad[0]]!r} != {g.actions[bad[0]]!r}"
+    o = obs.cpu().numpy()[:, 0]
+    np.testing.assert_array_equal(o[-1], g.last_obs)
+    done = (te | tr).cpu().numpy()[:, 0]
+    assert done[-1] and not done[:-1].any()
+    total = sum(float(r) for r in rew.cpu().numpy()[:, 0])
+    l2 = sum(float(np.linalg.norm(row)) for row in o[1:])
+    pub_total, pub_l2 = KAT_PUBLISHED[name]
+    np.testing.assert_allclose(total, pub_total, rtol=1e-5)
+    np.testing.assert_allclose(l2, pub_l2, rtol=1e-5)
+
+
+# ---- DeviceRollout with gains that follow the fused auto-reset --------------------------------------------------------------------
+POOL_B, POOL_P, POOL_T, POOL_S = 6, 7, 8, 5
+CLAMP = (-20.0, 20.0)
+
+
+def _pool_case(kind):
+    """B = 6 instances, P = 7 pool rows, per-instance theta / beta for the initial rows and the pool, episodes of 3 env-steps."""
+    rng = np.random.default_rng(17 if kind == "transport" else 18)
+    if kind == "transport":
+        dx, dt, nx, amp = 1e-2, 1e-4, 100, 5.0
+    else:
+        dx, dt, nx, amp = 1e-2, 2.5e-5, 100, 50.0
+    n = nx + (kind == "parabolic")
+    m = nx
+    grid = dict(T=3 * POOL_S * dt, dt=dt, X=1, dx=dx, control_sample_rate=POOL_S * dt)
+
+    def draw(rows):
+        gam = rng.uniform(5, 10, (rows, 1))
+        beta = (amp * np.cos(gam * np.arccos(np.linspace(0, 1, n))[None])).astype(f32)
+        theta = (amp * np.cos(gam * np.arccos(np.linspace(dx, 1, m))[None])).astype(f32)
+        init = (rng.uniform(1, 10, (rows, 1)) * np.ones((1, n))).astype(f32)
+        return init, beta, theta
+    return dict(kind=kind, dx=dx, n=n, m=m, grid=grid, first=draw(POOL_B), pool=draw(POOL_P))
+
+
+def _pool_oracle(case, gain0, pool_gain, runs, wrong_rule=False):
+    """Per-instance loop over oracle.pde_oracle driven by the NumPy law (ordered, rounded once to float32, clamped): `runs`
+    consecutive rollouts of T steps.  A finished instance restarts from pool row (b + k*B) mod P at its k-th restart (initial
+    condition, beta and gain); with wrong_rule the gain is taken from pool row b always."""
+    from oracle import pde_oracle as po
+    kind, n, m, B, P, T = case["kind"], case["n"], case["m"], POOL_B, POOL_P, POOL_T
+    cls = po.TransportOracle if kind == "transport" else po.ParabolicOracle
+    length, scale = (n, 1e-2) if kind == "transport" else (min(m, n - 1), case["dx"])
+    nt_r = int(round(case["grid"]["T"] / case["grid"]["dt"]))
+    out = [dict(obs=np.zeros((T + 1, B, n), f32), actions=np.zeros((T, B), f32), rewards=np.zeros((T, B), f32),
+                terminated=np.zeros((T, B), np.uint8), truncated=np.zeros((T, B), np.uint8)) for _ in range(runs)]
+    (init, beta, _), (pinit, pbeta, _) = case["first"], case["pool"]
+    for b in range(B):
+        orc = cls(control_type="Dirchilet", sensing_loc="full", sensing_type=None, normalize=False, max_control_value=20,
+                  limit_pde_state_size=True, max_state_value=1e10, reward=po.TunedReward1DOracle(nt_r, -1e3, 3e2), keep_history=False,
+                  **case["grid"])
+        obs, gain, restarts = orc.reset(init[b:b + 1], beta[b:b + 1])[0], gain0[b], 0
+        for run in range(runs):
+            o = out[run]
+            o["obs"][0, b] = obs
+            for t in range(T):
+                a = f32(_law_rows(gain[None], obs[None], length, scale)[0])
+                a = np.minimum(np.maximum(a, f32(CLAMP[0])), f32(CLAMP[1]))
+                nobs, r, te, tr = orc.step(np.array([a], dtype=f32))
+                o["actions"][t, b], o["rewards"][t, b], o["terminated"][t, b], o["truncated"][t, b] = a, r[0], te[0], tr[0]
+                obs = nobs[0]
+                if te[0] or tr[0]:
+                    restarts += 1
+                    row = rule_row(b, restarts, B, P)
+                    obs = orc.reset(pinit[row:row + 1], pbeta[row:row + 1])[0]
+                    gain = pool_gain[b if wrong_rule else row]
+                o["obs"][t + 1, b] = obs
+            assert restarts >= 2 * (run + 1)          # every instance restarts at least twice per rollout
+    return out
+
+
+def _pool_rollouts(case, use_graph, runs):
+    """`runs` DeviceRollout.run() calls on a fresh environment; returns the controller and the buffers after each run."""
+    import pde_control_gym
+    from pde_control_gym import BacksteppingController, DeviceRollout
+    from pde_control_gym.src import TunedReward1D
+    kind = case["kind"]
+    (init, beta, theta), (pinit, pbeta, ptheta) = case["first"], case["pool"]
+    nt_r = int(round(case["grid"]["T"] / case["grid"]["dt"]))
+    params = dict(case["grid"], reward_class=TunedReward1D(nt_r, -1e3, 3e2), normalize=False, sensing_loc="full", control_type="Dirchilet",
+                  sensing_type=None, limit_pde_state_size=True, max_state_value=1e10, max_control_value=20,
+                  batched_reset_func=lambda idx, nx: (init[idx], beta[idx]))
+    env_id = "PDEControlGym-TransportPDE1D" if kind == "transport" else "PDEControlGym-ReactionDiffusionPDE1D"
+    venv = pde_control_gym.make_vec(env_id, num_envs=POOL_B, device="cuda", **params)
+    venv.reset_tensor()
+    venv.enable_fused_auto_reset(init_pool=pinit, beta_pool=pbeta)
+    ctrl = BacksteppingController(kind, theta, case["dx"], pool_theta=ptheta, order="ordered", device="cuda").attach(venv)
+    assert venv.one_launch_fits(ctrl) is False
+    ro = DeviceRollout(venv, ctrl, POOL_T, use_graph=use_graph, action_low=CLAMP[0], action_high=CLAMP[1])
+    assert ro.one_launch is False
+    snaps = []
+    for _ in range(runs):
+        ro.run()
+        torch.cuda.synchronize()
+        snaps.append({k: getattr(ro, k).cpu().numpy().copy() for k in ("obs", "actions", "rewards", "terminated", "truncated")})
+    return ctrl, snaps
+
+
+@pytest.mark.parametrize("kind", ["transport", "parabolic"])
+def test_device_rollout_gains_follow_the_fused_auto_reset(kind):
+    case = _pool_case(kind)
+    ctrl, plain = _pool_rollouts(case, use_graph=False, runs=2)
+    gain0, pool_gain = ctrl.gain.cpu().numpy(), ctrl.pool_gain.cpu().numpy()
+    np.testing.assert_array_equal(gain0, GAIN[kind](case["first"][2], case["dx"]))
+    np.testing.assert_array_equal(pool_gain, GAIN[kind](case["pool"][2], case["dx"]))
+    want = _pool_oracle(case, gain0, pool_gain, runs=2)
+    for run in range(2):
+        for k in ("obs", "actions", "terminated", "truncated"):
+            np.testing.assert_array_equal(plain[run][k], want[run][k], err_msg=f"run {run}: {k}")
+        np.testing.assert_allclose(plain[run]["rewards"], want[run]["rewards"], rtol=1e-6, atol=1e-4)
+        assert (plain[run]["terminated"] | plain[run]["truncated"]).sum(axis=0).min() >= 2
+    # discrimination: gains taken from pool row b always (right for the first restart, wrong from the second on) must differ
+    wrong = _pool_oracle(case, gain0, pool_gain, runs=1, wrong_rule=True)[0]
+    assert not np.array_equal(wrong["actions"], plain[0]["actions"])
+    np.testing.assert_array_equal(wrong["actions"][:6], plain[0]["actions"][:6])      # (the second restart ends step 5)
+    # graph replay twice == two plain runs
+    _, graph = _pool_rollouts(case, use_graph=True, runs=2)
+    for run in range(2):
+        for k in ("obs", "actions", "rewards", "terminated", "truncated"):
+            np.testing.assert_array_equal(graph[run][k], plain[run][k], err_msg=f"graph run {run}: {k}")

@@ -19,6 +19,8 @@
  *   pdegym_backstep_gain_transport / _parabolic  replace solveKernelFunction   examples/transportPDE/transport1Dbackstepping.py:22-29,
  *                                                examples/reactionDiffusionPDE/reactionDiffusion1DBackstepping.py:22-35
  *   pdegym_backstep_control replaces solveControl                 transport1Dbackstepping.py:32-36, reactionDiffusion1DBackstepping.py:38-39
+ *   pdegym_ns2d_adjoint_f64 replaces the backward march and the control read-off of the adjoint-optimisation baseline
+ *                                                examples/NavierStokes/NS2Doptimization.py:83-107
  *
  * One call advances EVERY instance of a batch by one env-step (S PDE sub-steps for the 1D envs, one
  * Chorin projection step with K Jacobi sweeps for NS2D).  Instances are independent.
@@ -44,7 +46,7 @@
 extern "C" {
 #endif
 
-#define PDEGYM_ABI_VERSION 16
+#define PDEGYM_ABI_VERSION 17
 #define PDEGYM_RING 128          /* slots of the per-instance row-norm ring (look-back is 100 rows) */
 #define PDEGYM_LOOKBACK 100      /* tuned_reward_1d.py:25,40: int(1/0.01) rows */
 #define PDEGYM_MAX_N1D 2048      /* nodes per 1D row kept in registers by the wave-per-instance kernels */
@@ -537,6 +539,37 @@ typedef struct pdegym_backstep {
   int32_t reserved_;
 } pdegym_backstep;
 int pdegym_backstep_control(const pdegym_backstep* c, int32_t B, void* stream);
+
+/* ---- adjoint-optimisation baseline of NavierStokes2D (the model-based row of the reference's NS result table) ----------------
+ * examples/NavierStokes/NS2Doptimization.py:83-107 for a whole batch in ONE launch, float64 (the script's arithmetic), on the grids of
+ * pdegym_ns2d_rollout_* (8, 11, 16, 21, 26, 31 or 32 rows, 3 .. 64 columns).  From Lam1 = Lam2 = pressure = 0 (:84-86), backward step
+ * k = 0 .. T-2 reads the forward state of obs slot s = T - k (U[-1-t], V[-1-t] of :92-93: the state at time index t0 + s) and the target
+ * frame U_ref[min(t0 + s, nt_ref - 1)] (u_target[-1-t] for the script's T = nt - 1, t0 = 0), and computes, operands in the order written:
+ *   dlam1 = ((((-2*dx(lam1))*U - dy(lam1)*V) - dx(lam2)*V) - nu*lap(lam1)) + (U - U_tgt)       :92   (nu = prm->viscosity; the script
+ *   dlam2 = ((((-2*dy(lam2))*V - dy(lam1)*U) - dx(lam2)*U) - nu*lap(lam2)) + (V - V_tgt)       :93    writes its environment's 0.1)
+ *   lam  <- lam - dt*dlam, the four walls of both fields zero                                  :94-96 (apply_boundary of :56-61)
+ *   p    <- solve_pressure(lam1, lam2, p): prm->density / dt, prm->iters sweeps, warm start    :97    (navier_stokes2D.py:94-116)
+ *   lam1 <- lam1 - dt*dx(p), lam2 <- lam2 - dt*dy(p) (no division by the density), walls zero  :98-100
+ * After backward step k, time index t = T-2-k receives (Lam1[::-1] of :103)
+ *   grad[t, b]    = sum(central_difference(lam1, "y", dy)[ny-2, :]), columns 0 .. nx-1 added in sequence from the first   :106-107
+ *   actions[t, b] = a_nom[t] - ((ratio*grad[t, b])*width)*dx      (the script: ratio = 0.1/0.1, width = 5)               :107
+ *   lam[t, b]     = (lam1, lam2) interleaved, when lam is given
+ * and t = T-1 the zero field: grad = 0, actions = a_nom[T-1].  Every value is bit-identical to the script's NumPy arithmetic.
+ * Needs action_dim == 1 and the script's boundary table (:21-26): upper u Controllable, every other entry Dirichlet -- the zeroed
+ * adjoint walls and the gradient row under the upper wall assume exactly that table. */
+typedef struct pdegym_adjoint_ns2d {
+  int32_t T;                /* forward steps of the trajectory (the script's T = 199, :65); T - 1 backward steps                 */
+  int32_t t0;               /* time index of obs slot 0 (0 after a reset)                                                        */
+  const double* obs;        /* [T + 1, B, ny, nx, 2] the forward rollout, pdegym_rollout_ns2d.obs (slot 0 is not read)   :74-76  */
+  const double* a_nom;      /* [T] nominal commands, the script's u_ref                                                  :81     */
+  double ratio, width;
+  double* grad;             /* [T, B] out                                                                                        */
+  double* actions;          /* [T, B] out                                                                                :104-107 */
+  double* lam;              /* optional [T, B, ny, nx, 2] out: Lam1[::-1] (:103) and Lam2 in the same order; NULL = not stored   */
+} pdegym_adjoint_ns2d;
+/* U_ref: [nt_ref, ny, nx, 2], the targets of :79-80 as the step kernels read them (pdegym_bufs_ns2d.U_ref). */
+int pdegym_ns2d_adjoint_f64(const pdegym_params_ns2d* prm, const void* U_ref, int32_t nt_ref, const pdegym_adjoint_ns2d* adj, int32_t B,
+                            void* stream);
 
 /* ---- test-only: kernel dispatch overrides -------------------------------------------------------------------------
  * Nothing on the product path calls this (the reference has no counterpart); the parity tests use it to run the SAME step

@@ -11,7 +11,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "lib", "libpdegym_hip.so")
 
-ABI_VERSION = 16
+ABI_VERSION = 17
 RING = 128
 LOOKBACK = 100
 MAX_N1D = 8192
@@ -34,6 +34,7 @@ EXPORTS = [
     "pdegym_tumor_step", "pdegym_tumor_advance", "pdegym_tumor_reset_masked", "pdegym_mlp_forward",
     "pdegym_transport_rollout", "pdegym_parabolic_rollout", "pdegym_traffic_rollout", "pdegym_debug_set",
     "pdegym_backstep_gain_parabolic", "pdegym_backstep_gain_transport", "pdegym_backstep_control",
+    "pdegym_ns2d_adjoint_f64",
 ]
 # keys of pdegym_debug_set (test-only dispatch overrides, include/pdegym.h)
 DEBUG_NS_GENERIC, DEBUG_NS_NO_COL, DEBUG_NS_COL_MIN_BATCH, DEBUG_NS_NO_LDS_JACOBI = range(4)
@@ -146,6 +147,11 @@ class Backstep(C.Structure):
                 ("clamp", C.c_int32), ("lo", C.c_float), ("hi", C.c_float), ("reserved_", C.c_int32)]
 
 
+class AdjointNS2D(C.Structure):
+    _fields_ = [("T", C.c_int32), ("t0", C.c_int32), ("obs", C.c_void_p), ("a_nom", C.c_void_p), ("ratio", C.c_double),
+                ("width", C.c_double), ("grad", C.c_void_p), ("actions", C.c_void_p), ("lam", C.c_void_p)]
+
+
 class NativeError(RuntimeError):
     pass
 
@@ -213,6 +219,8 @@ def load():
         f.restype = C.c_int
     lib.pdegym_backstep_control.argtypes = [C.POINTER(Backstep), C.c_int32, C.c_void_p]
     lib.pdegym_backstep_control.restype = C.c_int
+    lib.pdegym_ns2d_adjoint_f64.argtypes = [C.POINTER(ParamsNS2D), C.c_void_p, C.c_int32, C.POINTER(AdjointNS2D), C.c_int32, C.c_void_p]
+    lib.pdegym_ns2d_adjoint_f64.restype = C.c_int
     lib.pdegym_debug_set.argtypes = [C.c_int32, C.c_int32]
     lib.pdegym_debug_set.restype = C.c_int32
     if lib.pdegym_abi_version() != ABI_VERSION:

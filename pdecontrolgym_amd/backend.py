@@ -244,6 +244,26 @@ class HipBackend:
         N.check(fn(C.byref(P), N.dptr(u, dtype), N.dptr(v, dtype), N.dptr(p_in, dtype), N.dptr(p_out, dtype),
                    N.dptr(scratch, dtype), B, N.current_stream_ptr(u.device)), "pdegym_ns2d_solve_pressure")
 
+    @_on_device_of("p")
+    def ns2d_adjoint(self, P: N.ParamsNS2D, T: dict, obs, a_nom, ratio: float, width: float, grad, actions, lam=None, t0: int = 0):
+        """The backward march of the adjoint-optimisation baseline in one launch (pdegym_ns2d_adjoint_f64): ``obs``
+        [T+1, B, ny, nx, 2] float64 (a forward rollout), ``a_nom`` [T], ``grad`` / ``actions`` [T, B], optional ``lam``
+        [T, B, ny, nx, 2]; the targets are ``T["U_ref"]``."""
+        import torch
+        f64 = torch.float64
+        steps, B = int(obs.shape[0]) - 1, int(obs.shape[1])
+        want = {"obs": (steps + 1, B, P.ny, P.nx, 2), "a_nom": (steps,), "grad": (steps, B), "actions": (steps, B),
+                "lam": (steps, B, P.ny, P.nx, 2)}
+        for name, x in (("obs", obs), ("a_nom", a_nom), ("grad", grad), ("actions", actions), ("lam", lam)):
+            if x is not None and (tuple(x.shape) != want[name] or not x.is_contiguous()):
+                raise N.NativeError(f"adjoint {name} must be a contiguous {list(want[name])} tensor, got {tuple(x.shape)}")
+        a = N.AdjointNS2D()
+        a.T, a.t0, a.ratio, a.width = steps, int(t0), float(ratio), float(width)
+        a.obs, a.a_nom, a.grad, a.actions = N.dptr(obs, f64), N.dptr(a_nom, f64), N.dptr(grad, f64), N.dptr(actions, f64)
+        a.lam = N.dptr(lam, f64)
+        N.check(self.lib.pdegym_ns2d_adjoint_f64(C.byref(P), N.dptr(T["U_ref"], f64), int(T["U_ref"].shape[0]), C.byref(a), B,
+                                                 N.current_stream_ptr(T["p"].device)), "pdegym_ns2d_adjoint")
+
 
     # ---- Traffic ARZ ---------------------------------------------------------------------------
     @staticmethod

@@ -1592,38 +1592,7 @@ __global__ void ns_auto_reset_finish(NSPtrs<T> P, NSAutoReset<T> R, int B) {
   if (R.reset_count) R.reset_count[b] += 1;
 }
 
-template <typename T>
-int fill(const pdegym_params_ns2d* prm, NSConst& C, NSScal<T>& S) {
-  if (!prm) return pdegym::fail(-1, "null params");
-  if (prm->nx < 3 || prm->ny < 3) return pdegym::fail(-2, "grid must be at least 3x3");
-  if (prm->iters < 0) return pdegym::fail(-2, "iters must be >= 0");
-  if (prm->action_dim != 1 && (prm->action_dim != prm->nx || prm->nx != prm->ny))
-    return pdegym::fail(-2, "action_dim must be 1 or the edge length of a square grid");
-  C.nx = prm->nx;
-  C.ny = prm->ny;
-  C.nt = prm->nt;
-  C.iters = prm->iters;
-  C.action_dim = prm->action_dim;
-  for (int e = 0; e < 4; ++e)
-    for (int k = 0; k < 2; ++k) {
-      if (prm->bc[e][k] < 0 || prm->bc[e][k] > 2) return pdegym::fail(-2, "bad boundary condition code");
-      C.bc[e][k] = prm->bc[e][k];
-    }
-  // Python evaluates these scalar sub-expressions in double before they meet an array (navier_stokes2D.py:12,14,21,
-  // 103,108,144): 2*step, dx*dy, rho/dt, dt/rho
-  S.dt = (T)prm->dt;
-  S.two_dx = (T)(2 * prm->dx);
-  S.two_dy = (T)(2 * prm->dy);
-  S.dxdy = (T)(prm->dx * prm->dy);
-  S.nu = (T)prm->viscosity;
-  S.rho_over_dt = (T)(prm->density / prm->dt);
-  S.dt_over_rho = (T)(prm->dt / prm->density);
-  S.gamma_half = (T)(prm->gamma / 2);
-  S.inv_two_dx = (T)(1.0 / (2 * prm->dx));
-  S.inv_two_dy = (T)(1.0 / (2 * prm->dy));
-  S.inv_dxdy = (T)(1.0 / (prm->dx * prm->dy));
-  return 0;
-}
+// (fill: the launch constants of a parameter block, checked -- pdegym_ns_common.h)
 
 // LDS-resident Jacobi: every thread owns at most kLdsCPT cells.  A lone wave issues an instruction only every ~6.5 cycles,
 // so when the batch leaves CUs idle anyway (B <= 512: at most two workgroups per CU) one thread per cell (up to 512) cuts the

@@ -1,0 +1,182 @@
+"""GPU tests of the NavierStokes2D adjoint-optimisation baseline (csrc/pdegym_ns_adjoint.hip, pde_control_gym.NSAdjointOptimizer)
+against tests/golden/adjoint_ns.npz -- the reference's own script, bit for bit -- and the NumPy restatement of
+tests/adjoint_restatement.py (pinned to the same fixtures by tests/test_adjoint.py).
+
+A fixture case runs as row 1 of a batch of floor(64 / nx) + 1 instances: row 1 shares its wave with other instances, and the last
+row sits alone in a second wave.  The other rows hold scaled copies of the case's data."""
+import numpy as np
+import pytest
+
+from tests import adjoint_restatement as R
+from tests import poison
+
+pytestmark = pytest.mark.gpu
+torch = pytest.importorskip("torch")
+
+# kernel of csrc/pdegym_ns_adjoint.hip -> its output-contract tests (tests/test_adjoint.py checks the table against the source)
+KERNEL_CASES = {"ns_adjoint_march": ["test_outputs_are_fully_written_and_inputs_left_alone", "test_lam_is_optional"]}
+
+FULL = [n for n, c in R.CASES.items() if not c.get("sums_only")] + ["restatement_only/" + n for n in R.RESTATEMENT_ONLY]
+ROW = 1
+
+
+@pytest.fixture(scope="module")
+def fixture():
+    return R.load_fixture()
+
+
+def _dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def _scale(r):
+    return 1.0 if r == ROW else 1.0 + 0.125 * (r + 1)
+
+
+def _engine(c, B, U_ref):
+    from pdecontrolgym_amd.batch2d import NSBatch2D
+    return NSBatch2D(boundary_condition=R.BC, U_ref=U_ref, action_ref=2.0 * np.ones(c["T"] + 2), action_dim=1, gamma=0.1, num_envs=B,
+                     device="cuda", dtype=torch.float64, **R.case_params(c))
+
+
+def _batch(c):
+    return 64 // c.get("nx", c["n"]) + 1
+
+
+def _rollout_of(g, B):
+    """[T+1, B, ny, nx, 2]: row ROW holds the fixture's forward frames (slot 0, which the march never reads, its initial fields),
+    the other rows scaled copies."""
+    fr = np.concatenate([np.stack([g["u0"], g["v0"]], axis=-1)[None], np.stack([g["U"], g["V"]], axis=-1)])
+    return _dev(np.stack([fr * _scale(r) for r in range(B)], axis=1))
+
+
+def _same(t, a, what):
+    a = np.ascontiguousarray(a)
+    got = t.cpu().numpy()
+    assert got.shape == a.shape and got.dtype == a.dtype, what
+    assert got.tobytes() == a.tobytes(), f"{what}: {int((got != a).sum())} of {a.size} values differ, max |diff| {np.abs(got - a).max():.3e}"
+
+
+@pytest.mark.parametrize("name", FULL)
+def test_march_on_the_fixture_trajectory_is_bitwise(fixture, name):
+    from pde_control_gym import NSAdjointOptimizer
+    g, c = fixture[name], R.case_of(name)
+    B = _batch(c)
+    core = _engine(c, B, g["U_ref"])
+    actions, grad, lam = NSAdjointOptimizer(core).sweep(_rollout_of(g, B), keep_lam=True)
+    assert actions.shape == (c["T"], B, 1) and grad.shape == (c["T"], B)
+    _same(lam[:, ROW, ..., 0], g["lam1"], "lam1")
+    _same(lam[:, ROW, ..., 1], g["lam2"], "lam2")
+    _same(grad[:, ROW], g["grad"], "grad")
+    _same(actions[:, ROW, 0], g["actions"], "actions")
+
+
+@pytest.mark.parametrize("name", FULL)
+def test_march_on_the_device_rollout_is_bitwise_and_the_replay_keeps_the_rewards(fixture, name):
+    from pde_control_gym import NSAdjointOptimizer
+    g, c = fixture[name], R.case_of(name)
+    B, T = _batch(c), c["T"]
+    core = _engine(c, B, g["U_ref"])
+    opt = NSAdjointOptimizer(core)
+    init = [_dev(np.stack([g[k] * _scale(r) for r in range(B)])) for k in ("u0", "v0", "p0")]
+    a0 = _dev(np.repeat(g["actions0"][:, None, None], B, axis=1))
+    obs, rew0 = opt._rollout(*init, a0)
+    _same(obs[1:, ROW, ..., 0], g["U"], "forward U")
+    _same(obs[1:, ROW, ..., 1], g["V"], "forward V")
+    actions, grad, lam = opt.sweep(obs, keep_lam=True)
+    _same(lam[:, ROW, ..., 0], g["lam1"], "lam1")
+    _same(lam[:, ROW, ..., 1], g["lam2"], "lam2")
+    _same(grad[:, ROW], g["grad"], "grad")
+    _same(actions[:, ROW, 0], g["actions"], "actions")
+    obs2, rew1 = opt._rollout(*init, actions)
+    np.testing.assert_allclose(rew0[:, ROW].cpu().numpy(), g["rewards0"], rtol=1e-12)
+    np.testing.assert_allclose(rew1[:, ROW].cpu().numpy(), g["rewards"], rtol=1e-12)
+
+
+def test_shipped_shape_end_to_end_through_optimize(fixture):
+    """21 x 21, K = 2000, T = 199: the script's own shape, three instances (one wave)."""
+    from pde_control_gym import NSAdjointOptimizer
+    name = "shipped_n21_K2000_T199"
+    g, c = fixture[name], R.CASES[name]
+    inp = R.case_inputs(c)
+    B = 3
+    core = _engine(c, B, inp["U_ref"])
+    out = NSAdjointOptimizer(core).optimize(inp["u0"], inp["v0"], inp["p0"], inp["actions0"])
+    for b in range(B):
+        _same(out["grad"][:, b], g["grad"], f"grad[{b}]")
+        _same(out["actions"][:, b, 0], g["actions"], f"actions[{b}]")
+    np.testing.assert_allclose(out["reward_before"].cpu().numpy(), np.full(B, g["reward_sums"][0]), rtol=1e-12)
+    np.testing.assert_allclose(out["reward_after"].cpu().numpy(), np.full(B, g["reward_sums"][1]), rtol=1e-12)
+
+
+def test_batch_of_one_equals_every_position_of_a_batch_of_seven(fixture):
+    from pde_control_gym import NSAdjointOptimizer
+    name = "n21_K2_T6"
+    g, c = fixture[name], R.CASES[name]
+    obs7 = _rollout_of(g, 7)                   # seven different instances: three waves, the last holds one
+    a7, g7, l7 = NSAdjointOptimizer(_engine(c, 7, g["U_ref"])).sweep(obs7, keep_lam=True)
+    one = NSAdjointOptimizer(_engine(c, 1, g["U_ref"]))
+    for b in range(7):
+        a1, g1, l1 = one.sweep(obs7[:, b:b + 1].contiguous(), keep_lam=True)
+        poison.assert_bits_equal(l7[:, b:b + 1].contiguous(), l1, name=f"lam at position {b}")
+        poison.assert_bits_equal(g7[:, b:b + 1].contiguous(), g1, name=f"grad at position {b}")
+        poison.assert_bits_equal(a7[:, b:b + 1].contiguous(), a1, name=f"actions at position {b}")
+
+
+def test_time_offset_and_target_clamp_follow_the_restatement(fixture):
+    """t0 = 3 with T + 1 target frames: the target index t0 + s runs past the last frame and is clamped to it."""
+    name = "n11_K7_T9"
+    g, c = fixture[name], R.CASES[name]
+    B = _batch(c)
+    core = _engine(c, B, g["U_ref"])
+    obs = _rollout_of(g, B)
+    from pde_control_gym import NSAdjointOptimizer
+    actions, grad, lam = NSAdjointOptimizer(core, a_nom=np.linspace(1, 3, c["T"]), ratio=0.75, width=3.0).sweep(obs, t0=3, keep_lam=True)
+    wl, wg, wa = R.march(R.oracle_for(R.case_params(c), g["U_ref"]), obs.cpu().numpy(), g["U_ref"], np.linspace(1, 3, c["T"]),
+                         ratio=0.75, width=3.0, t0=3)
+    _same(lam, wl, "lam")
+    _same(grad, wg, "grad")
+    _same(actions[..., 0], wa, "actions")
+
+
+def _poisoned_call(g, c, with_lam):
+    B, T, ny, nx = _batch(c), c["T"], c["n"], c.get("nx", c["n"])
+    core = _engine(c, B, g["U_ref"])
+    arena = poison.Arena("cuda")
+    src_obs = _rollout_of(g, B)
+    obs = arena.like("obs", src_obs)
+    uref = arena.like("U_ref", core.t["U_ref"])
+    core.t["U_ref"] = uref
+    a_nom = arena.like("a_nom", torch.full((T,), 2.0, dtype=torch.float64, device="cuda"))
+    grad = poison.poison_(arena.new("grad", (T, B), torch.float64))
+    actions = poison.poison_(arena.new("actions", (T, B), torch.float64))
+    lam = poison.poison_(arena.new("lam", (T, B, ny, nx, 2), torch.float64)) if with_lam else None
+    core.backend.ns2d_adjoint(core.params, core.t, obs, a_nom, 1.0, 5.0, grad, actions, lam=lam, t0=0)
+    arena.check()
+    poison.assert_bits_equal(obs, src_obs, name="obs (input)")
+    poison.assert_bits_equal(uref, _dev(g["U_ref"]), name="U_ref (input)")
+    poison.assert_bits_equal(a_nom, torch.full((T,), 2.0, dtype=torch.float64, device="cuda"), name="a_nom (input)")
+    return grad, actions, lam
+
+
+@pytest.mark.parametrize("name", ["n21_K2_T6", "n8_K3_T1", "restatement_only/r8x64_K3_T3"])
+def test_outputs_are_fully_written_and_inputs_left_alone(fixture, name):
+    g, c = fixture[name], R.case_of(name)
+    grad, actions, lam = _poisoned_call(g, c, with_lam=True)
+    poison.assert_written(grad, name="grad")
+    poison.assert_written(actions, name="actions")
+    poison.assert_written(lam, name="lam")
+    _same(grad[:, ROW], g["grad"], "grad")
+    _same(lam[:, ROW, ..., 0], g["lam1"], "lam1")
+    assert not bool(lam[-1].any()) and not bool(grad[-1].any())          # time index T-1: the zero field
+
+
+def test_lam_is_optional(fixture):
+    name = "n21_K2_T6"
+    g, c = fixture[name], R.CASES[name]
+    grad, actions, lam = _poisoned_call(g, c, with_lam=False)
+    assert lam is None
+    poison.assert_written(grad, name="grad")
+    poison.assert_written(actions, name="actions")
+    _same(grad[:, ROW], g["grad"], "grad")
+    _same(actions[:, ROW], g["actions"], "actions")

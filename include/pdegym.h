@@ -35,7 +35,14 @@
  *     the library allocates nothing and keeps no state besides a thread-local error string;
  *   - calls only ENQUEUE work on `stream` (a hipStream_t passed as void*); they never synchronise;
  *   - return value 0 = success, negative = error (message via pdegym_last_error()); nothing throws;
- *   - arrays are C-contiguous; the grid axis is the fastest axis.
+ *   - arrays are C-contiguous; the grid axis is the fastest axis;
+ *   - non-finite data is ordinary data, as it is to the reference: a NaN command, observation or state cell propagates exactly as
+ *     NumPy / PyTorch propagate it there (a stencil spreads it to the cells that read it, norms and rewards become NaN, comparisons
+ *     with it are false), and every clamp (the action clips of the environments, the fused clamp of pdegym_mlp_forward, of the
+ *     in-kernel policies and of pdegym_backstep_control's out32, the tumour's clip to [0, k]) KEEPS a NaN like np.clip and
+ *     torch.clamp do -- a diverged policy shows up as NaN observations and rewards within a step, not as the lower action bound.
+ *     +-Inf is clamped to the bound.  relu keeps a NaN too (torch.relu).  Instances are independent in this as well: a non-finite
+ *     value in one instance changes no bit of another.  Clamp BOUNDS, sizes, strides and counts must be finite.
  */
 #ifndef PDEGYM_H
 #define PDEGYM_H
@@ -447,7 +454,12 @@ enum {
 };
 
 /* One day per call.  nx <= 4096.  An active instance with time_index >= nt-1 (its episode is over) keeps its state and out[b];
- * the call writes reward[b] = 0, terminated[b] = truncated[b] = 0 for it. */
+ * the call writes reward[b] = 0, terminated[b] = truncated[b] = 0 for it.
+ * Where the reference raises: a Therapy day on which the tumour is invisible on T2 has treatment radius 0, and the reference's toxicity
+ * reward evaluates 0.0 ** -0.685 (brain_tumor_reward.py:63, ZeroDivisionError) -- reached e.g. the day after a NaN or -Inf dosage, which
+ * turns the whole treated region into NaN.  The kernel cannot raise: it advances the state, the counters and the flags as on any day
+ * (nothing is irradiated), reports out[b] treatment radius 0 and T2 NaN, and returns reward[b] = NaN (116 * 0^-0.685 = +Inf makes the
+ * dose ratio Inf / Inf).  Other instances of the batch are not affected.  (The CPU double of the tests raises, like the reference.) */
 int pdegym_tumor_step(const pdegym_params_tumor* prm, const pdegym_bufs_tumor* buf, int32_t B, void* stream);
 /* Up to max_days days per participating instance inside ONE launch (row and stage machine stay on chip between days);
  * control is 0 on every day of modes 1-3; reward / flags / out are those of the LAST simulated day; instances that do not

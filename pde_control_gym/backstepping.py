@@ -115,7 +115,9 @@ class BacksteppingController:
 
     def forward_into(self, obs, out, clamp=None, noise=None):
         """out[b] = the command for observation row obs[b]: ``obs`` float32 [B, n]; ``out`` [B] or [B, 1], float64, or float32
-        (rounded once from the double, then ``noise`` [B] added, then clamped to ``clamp`` = (lo, hi)).  Returns ``out``."""
+        (rounded once from the double, then ``noise`` [B] added, then clamped to ``clamp`` = (lo, hi)).  Returns ``out``.
+        A NaN in an observation row makes that row's command NaN, as in the reference's dot product, and the clamp keeps it like
+        ``np.clip``; +-Inf is clamped to the bound (include/pdegym.h, conventions)."""
         x = obs.reshape(obs.shape[0], -1)
         self.backend.backstep_control(x, out, self.gain, self._length(int(x.shape[1])), self.scale, ordered=self.order == "ordered",
                                       gain_pool=self.pool_gain if self._reset_count is not None else None,

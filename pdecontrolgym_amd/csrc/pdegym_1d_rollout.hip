@@ -158,7 +158,7 @@ __global__ __launch_bounds__(kWave* pdegym_policy::kWaves) void rollout1d_policy
     else a = lane_value(pol::eval(N, St, pol_smem, xw, hw, n, lane), 0);      // neuron 0 of the last layer
     if (!active) continue;
     if (N.noise) a += N.noise[((size_t)t * B + inst) * N.noise_stride];
-    if (N.clamp) a = fminf(fmaxf(a, N.lo), N.hi);
+    if (N.clamp) a = pdegym::clip_keep_nan(a, N.lo, N.hi);
     if (lane == 0) Ro.actions[(size_t)t * B + inst] = a;
 
     pdegym_bufs1d S = Bf;
@@ -207,7 +207,7 @@ __global__ __launch_bounds__(kWave* pdegym_policy::kWaves) void rollout1d_policy
     else a = lane_value(pol::eval(N, St, pol_smem, xw, hw, od, lane), 0);
     if (!active) continue;
     if (N.noise) a += N.noise[((size_t)t * B + inst) * N.noise_stride];
-    if (N.clamp) a = fminf(fmaxf(a, N.lo), N.hi);
+    if (N.clamp) a = pdegym::clip_keep_nan(a, N.lo, N.hi);
     if (lane == 0) Ro.actions[(size_t)t * B + inst] = a;
     rollout1d_general_step<EPL, PARABOLIC, NEUMANN, BURGERS>(P, Bf, Ro, B, inst, lane, t, &a);
   }

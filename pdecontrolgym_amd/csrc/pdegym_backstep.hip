@@ -143,7 +143,7 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void backstep_control_kernel
   } else {
     float f = (float)act;
     if (A.noise) f += A.noise[inst];
-    if (A.clamp) f = fminf(fmaxf(f, A.lo), A.hi);
+    if (A.clamp) f = pdegym::clip_keep_nan(f, A.lo, A.hi);
     A.out32[inst] = f;
   }
 }

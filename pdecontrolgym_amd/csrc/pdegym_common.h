@@ -46,7 +46,14 @@ inline int simd_count() {
   return cus * 4;
 }
 
-// ---- device side: the wave64 primitives of every kernel family ------------------------------------------------------------------
+// ---- device side ------------------------------------------------------------------------------------------------------------------
+// min(max(x, lo), hi) as the reference's clamps evaluate it (np.clip, torch.clamp, Python's min(max(x, lo), hi) with x first): a NaN x
+// stays NaN -- the device's fmin / fmax return the operand that is NOT NaN, which would turn a diverged command into the lower bound.
+// Every other x keeps the bits the plain form gives (signed zeros and infinities included).  The bounds are finite by contract.
+__device__ __forceinline__ float clip_keep_nan(float x, float lo, float hi) { return x != x ? x : fminf(fmaxf(x, lo), hi); }
+__device__ __forceinline__ double clip_keep_nan(double x, double lo, double hi) { return x != x ? x : fmin(fmax(x, lo), hi); }
+
+// the wave64 primitives of every kernel family
 namespace wave {
 
 constexpr int kWave = 64;

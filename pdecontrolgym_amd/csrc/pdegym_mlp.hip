@@ -158,7 +158,7 @@ __global__ __launch_bounds__(64 * WV) void mlp_forward_kernel(pdegym_mlp N, cons
           float o = n < H ? activate(av[v] + bias_all[l][t], L.act) : 0.f;
           if (last) {
             if (N.noise && n < H && row0 + r < B) o += N.noise[(long long)(row0 + r) * N.noise_stride + n];
-            if (N.clamp) o = fminf(fmaxf(o, N.lo), N.hi);
+            if (N.clamp) o = pdegym::clip_keep_nan(o, N.lo, N.hi);
             if (n < H && row0 + r < B) y[(long long)(row0 + r) * y_stride + n] = (TY)o;
           } else {
             hout[r * kLdh + n] = o;

@@ -25,7 +25,7 @@ constexpr int kStage = 4;                   // k-blocks (of 16 inputs) per softw
 
 __device__ __forceinline__ float activate(float v, int act) {
   if (act == PDEGYM_MLP_TANH) return tanhf(v);
-  if (act == PDEGYM_MLP_RELU) return v > 0.f ? v : 0.f;
+  if (act == PDEGYM_MLP_RELU) return (v > 0.f || v != v) ? v : 0.f;      // torch.relu keeps a NaN
   return v;
 }
 

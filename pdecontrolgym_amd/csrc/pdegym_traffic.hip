@@ -39,12 +39,13 @@ inline TrafficConsts traffic_consts(const pdegym_params_traffic& P) {
   return K;
 }
 
-// The commands of a step: action clip (:151-156) -- np.clip(a, low, high) = min(max(a, low), high) -- and which end each one drives
+// The commands of a step: action clip (:151-156) -- np.clip(a, low, high): min(max(a, low), high) for every a but NaN, which np.clip
+// keeps (pdegym_common.h: clip_keep_nan) -- and which end each one drives
 __device__ __forceinline__ void traffic_commands(const pdegym_params_traffic& P, double qc, double qs, double a0, double a1, double& q_in,
                                                  double& q_out) {
   const double lo = qc * 0.8, hi = 1.2 * qc;
-  a0 = fmin(fmax(a0, lo), hi);
-  a1 = fmin(fmax(a1, lo), hi);
+  a0 = pdegym::clip_keep_nan(a0, lo, hi);
+  a1 = pdegym::clip_keep_nan(a1, lo, hi);
   if (P.sim == PDEGYM_TRAFFIC_BOTH) { q_in = a0; q_out = a1; }
   else if (P.sim == PDEGYM_TRAFFIC_INLET) { q_in = a0; q_out = qs; }
   else { q_in = qs; q_out = a0; }
@@ -293,8 +294,8 @@ __global__ __launch_bounds__(kWave* pdegym_policy::kWaves) void traffic_rollout_
         if (A > 1) c1 += nz[1];
       }
       if (N.clamp) {
-        c0 = fminf(fmaxf(c0, N.lo), N.hi);
-        c1 = fminf(fmaxf(c1, N.lo), N.hi);
+        c0 = pdegym::clip_keep_nan(c0, N.lo, N.hi);
+        c1 = pdegym::clip_keep_nan(c1, N.lo, N.hi);
       }
       a0 = (double)c0;
       a1 = (double)c1;

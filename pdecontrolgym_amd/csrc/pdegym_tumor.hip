@@ -36,7 +36,7 @@ __device__ __forceinline__ double fd_node(const pdegym_params_tumor& P, double u
   return uc + P.dt * s;
 }
 
-__device__ __forceinline__ double clip0k(double x, double k) { return fmin(fmax(x, 0.0), k); }
+__device__ __forceinline__ double clip0k(double x, double k) { return pdegym::clip_keep_nan(x, 0.0, k); }      // np.clip(nextU, 0, k) :244
 
 // mode: PDEGYM_TUMOR_RUN_*; every participating instance simulates at most max_days days.  The row ping-pongs between two
 // LDS copies owned by the wave (no workgroup barrier: waves of a block run different numbers of days), the scalars of the
@@ -201,7 +201,7 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void tumor_step_kernel(pdegy
       else {                                                           // brain_tumor_reward.py:59-73
         const double maxsafe = 116.0 * pow(treat_r, -0.685);
         const double ratio = (applied - maxsafe) / (P.total_dosage - maxsafe);
-        const double r = fmin(fmax(ratio, 0.0), 1.0);
+        const double r = pdegym::clip_keep_nan(ratio, 0.0, 1.0);      // Python min(max(ratio, 0.0), 1.0): NaN for a NaN ratio
         reward = -50.0 * pow(r, 1.0 / 3.0);
       }
     } else if (stage == PDEGYM_TUMOR_POST && (term || lethal)) {

@@ -116,7 +116,9 @@ class FusedMLP:
         or [B] when out_dim == 1, on the parameters' device.  float64 observations (traffic, tumour, float64 Navier-Stokes)
         are rounded to float32 as they are read and a float64 ``out`` receives the widened float32 result -- the casts SB3
         makes around its float32 policy.  ``noise`` (float32, same shape as the action): added to the network output before
-        the clamp -- the caller's pre-scaled exploration noise of a Gaussian policy.  Returns ``out``."""
+        the clamp -- the caller's pre-scaled exploration noise of a Gaussian policy.  Returns ``out``.
+        A NaN observation propagates as in PyTorch (the row's output is NaN) and the clamp keeps a NaN like ``torch.clamp`` /
+        ``np.clip``; +-Inf is clamped to the bound (include/pdegym.h, conventions)."""
         B = obs.shape[0]
         x = obs.reshape(B, -1)
         if x.shape[1] != self.in_dim:

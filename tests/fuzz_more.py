@@ -27,6 +27,16 @@ def bits_equal(a, b):
     return np.array_equal(a.view(ui)[fin], b.view(ui)[fin])
 
 
+def draw_plant(idx, salt):
+    """About one case in ten carries a non-finite value (tests/test_gpu_nonfinite.py holds the fixed cases): returns None, or a
+    generator of its own from which the case draws what to plant and where -- the case's main stream is left as it was."""
+    prng = np.random.default_rng([idx, salt])
+    return prng if prng.random() < 0.1 else None
+
+
+PLANTS = [float("nan"), float("inf"), float("-inf")]
+
+
 def ns_case(rng, idx):
     from pdecontrolgym_amd.batch2d import NSBatch2D
     n = int(rng.choice([3, 4, 5, 8, 16, 21, 32, 33, 40, 63, 64, 65, 70, 100, 128])) if rng.random() < 0.7 else int(rng.integers(3, 90))
@@ -55,10 +65,19 @@ def ns_case(rng, idx):
             return np.zeros((B, m, n))
         return rng.uniform(-1, 1, (B, m, n))
     u0, v0, p0 = field(), field(), field()
+    plant = draw_plant(idx, 1)
+    nan_cmd = None
+    if plant is not None:          # a NaN cell in the initial u or p of one instance, or a NaN command at the first step
+        what = int(plant.integers(3))
+        where = (int(plant.integers(B)), int(plant.integers(m)), int(plant.integers(n)))
+        if what < 2:
+            (u0, p0)[what][where] = np.nan
+        else:
+            nan_cmd = where[0]
     kw = dict(T=nt * dt, dt=dt, X=1, dx=dx, Y=Yl, dy=dy, boundary_condition=bc, U_ref=rng.uniform(-1, 1, (nt, m, n, 2)),
               action_ref=rng.uniform(1, 3, nt), gamma=float(rng.choice([0.1, 0.0, 2.0])), maximum_pressure_iteration=K, viscosity=nu,
               density=float(rng.choice([1.0, 2.0])))
-    desc = f"#{idx} ns nx={n} ny={m} K={K} B={B} adim={adim} nt={nt} inter={inter} ic={style} bc={bc}"
+    desc = f"#{idx} ns nx={n} ny={m} K={K} B={B} adim={adim} nt={nt} inter={inter} ic={style} bc={bc} plant={plant is not None}"
     # grids of 8 / 11 / 16 / 21 / 26 / 31 / 32 rows and up to 64 columns: half of the cases on the column-per-lane kernel (which float64
     # batches this small would not reach by themselves), half on the workgroup kernel -- the switch is read at every launch
     col = rng.random() < 0.5
@@ -70,11 +89,14 @@ def ns_case(rng, idx):
     env.reset(u0, v0, p0)
     for i in range(nt - 1):      # U_ref[t] is read after the increment: the reference cannot step further either
         a = rng.uniform(2, 4, (B, adim)) * float(rng.choice([1.0, 0.0, -1.0]))
-        o_ref, r_ref, te_ref, _ = orc.step(a)
+        if nan_cmd is not None and i == 0:
+            a[nan_cmd, 0] = np.nan
+        with np.errstate(invalid="ignore"):
+            o_ref, r_ref, te_ref, _ = orc.step(a)
         obs, r, te = env.step(a)
         assert bits_equal(obs.cpu().numpy(), o_ref), desc + f" step {i}: obs"
         assert bits_equal(env.p.cpu().numpy(), orc.p), desc + f" step {i}: p"
-        assert np.allclose(r.cpu().numpy(), r_ref, rtol=1e-12, atol=1e-300), desc + f" step {i}: reward {r.cpu().numpy()} {r_ref}"
+        assert np.allclose(r.cpu().numpy(), r_ref, rtol=1e-12, atol=1e-300, equal_nan=True), desc + f" step {i}: reward {r.cpu().numpy()} {r_ref}"
         assert np.array_equal(te.cpu().numpy().astype(bool), te_ref), desc + f" step {i}: terminate"
     _dbg("DEBUG_NS_COL_MIN_BATCH", -1)
     # the column kernel and the workgroup kernel: every output bit for bit, rewards included (one summation order)
@@ -193,7 +215,7 @@ def traffic_case(rng, idx):
     M = len(np.arange(0, X + dxs, dxs))
     if M > 1024:
         return None
-    desc = f"#{idx} traffic {sim} cf={cf} B={B} X={X} dx={dxs} dt={dt} T={T} limit={limit}"
+    desc = f"#{idx} traffic {sim} cf={cf} B={B} X={X} dx={dxs} dt={dt} T={T} limit={limit} plant={draw_plant(idx, 2) is not None}"
     orc = po.TrafficOracle(T, dt, X, dxs, sim, 40, 0.16, 60, limit, cf)
     env = TrafficBatch(T, dt, X, dxs, sim, 40, 0.16, 60, limit, cf, num_envs=B, device="cuda")
     rs = rng.choice([0.115, 0.12, 0.125, 0.1], B)
@@ -204,8 +226,11 @@ def traffic_case(rng, idx):
     o = env.reset(rs)
     assert bits_equal(o.cpu().numpy(), o_ref), desc + " reset"
     nact = 2 if sim == "both" else 1
+    plant = draw_plant(idx, 2)
     for k in range(int(rng.integers(3, 30))):
         a = rng.uniform(0.5, 1.5, (B, nact)) * orc.qs[:, None]
+        if plant is not None and k == 1:          # a NaN / +Inf / -Inf command of one instance
+            a[int(plant.integers(B)), int(plant.integers(nact))] = PLANTS[int(plant.integers(3))]
         with np.errstate(all="ignore"):
             o_ref, r_ref, d_ref, t_ref = orc.step(a)
         o, r, d, t = env.step(a)
@@ -236,6 +261,14 @@ def tumor_case(rng, idx):
     xs = np.linspace(0, X, orc.nx)
     init = (0.8 * kwp["k"] * np.exp(-0.25 * xs ** 2))[None] * rng.uniform(0.8, 1.0, (B, 1))
     tb = np.where(rng.random(B) < 0.3, np.nan, rng.integers(100, 400, B).astype(np.float64))
+    plant = draw_plant(idx, 3)
+    dose_day = -1
+    if plant is not None:          # a NaN cell in one initial profile, or a NaN / +Inf / -Inf request on one of the daily steps
+        if plant.random() < 0.5:
+            init[int(plant.integers(B)), int(plant.integers(orc.nx))] = np.nan
+        else:
+            dose_day = int(plant.integers(0, 5))
+        desc += " plant"
     eng.set_benchmark(tb)
     eng.reset(init)
     orc.reset(init, tb)
@@ -248,7 +281,8 @@ def tumor_case(rng, idx):
             if not part.any():
                 break
             keep = [np.copy(x) for x in (orc.u, orc.time_index, orc.stage, orc.remaining, orc.growthDays, orc.therapyDays, orc.postDays, orc.simulationDays, orc.cDeathDay)]
-            orc.step(np.zeros(B))
+            with np.errstate(invalid="ignore"):
+                orc.step(np.zeros(B))
             new = [orc.u, orc.time_index, orc.stage, orc.remaining, orc.growthDays, orc.therapyDays, orc.postDays, orc.simulationDays, orc.cDeathDay]
             merged = [np.where(part.reshape((-1,) + (1,) * (k.ndim - 1)), n_, k) for k, n_ in zip(keep, new)]
             (orc.u, orc.time_index, orc.stage, orc.remaining, orc.growthDays, orc.therapyDays, orc.postDays, orc.simulationDays, orc.cDeathDay) = merged
@@ -256,12 +290,15 @@ def tumor_case(rng, idx):
         assert np.array_equal(eng.t["time_index"].cpu().numpy(), orc.time_index) and np.array_equal(eng.t["stage"].cpu().numpy(), orc.stage), desc + " growth run: state"
     for n in range(int(rng.integers(5, 60))):
         a = rng.uniform(0, 1, B) * hi
+        if n == dose_day:
+            a[int(plant.integers(B))] = PLANTS[int(plant.integers(3))]
         try:
-            o, ro, teo, tro = orc.step(a)
+            with np.errstate(invalid="ignore", over="ignore"):
+                o, ro, teo, tro = orc.step(a)
         except ZeroDivisionError:      # treatment radius 0 (tumour invisible on T2): the reference's reward raises
             return desc + " (reference raises)"
         u, r, te, tr = eng.step(a)
-        assert np.allclose(u.cpu().numpy(), o, rtol=1e-12, atol=0), desc + f" day {n}: rows"
+        assert np.allclose(u.cpu().numpy(), o, rtol=1e-12, atol=0, equal_nan=True), desc + f" day {n}: rows"
         assert np.allclose(r.cpu().numpy(), ro, rtol=1e-11, atol=0, equal_nan=True), desc + f" day {n}: reward {r.cpu().numpy()} {ro}"
         assert np.array_equal(te.cpu().numpy().astype(bool), teo) and np.array_equal(tr.cpu().numpy().astype(bool), tro), desc + f" day {n}: flags"
         assert np.array_equal(eng.t["stage"].cpu().numpy(), orc.stage), desc + f" day {n}: stage"

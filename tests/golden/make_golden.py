@@ -882,15 +882,157 @@ def gen_sweep_tumor(src, out=HERE):
     assert ends["b_term_therapy"] == (1, True, False) and ends["c_term_post"] == (2, True, False) and ends["e_term_post"] == (2, True, False)
     np.savez_compressed(os.path.join(out, "sweep_tumor.npz"), **store)
 
+# ---- non-finite inputs: what the reference does with a NaN / +-Inf command, a NaN dosage, a NaN cell in a state ------------------
+# np.clip, np.linalg.norm, Python's min(x, ...) / max(x, ...) and the stencils all KEEP a NaN: the recorded observations, rewards
+# and flags are what the oracle (and through it every engine) has to reproduce, NaN positions included.  One reference instance per
+# run.  To keep the file small the constructor parameters of a family are stored once ("<family>_kw/..."), and the three plants of a
+# traffic configuration are stacked on a leading axis (their rows agree away from the driven end, which the compressor finds).
+# Where the reference raises, the exception class is recorded under "<case>/raises" (the generator fails if it stops raising) and
+# the action of that call is the last of "actions".
+NF_PLANTS = (("nan", float("nan")), ("pinf", float("inf")), ("ninf", float("-inf")))
+
+
+def gen_nonfinite(src, out=HERE):
+    import contextlib
+    import importlib
+    import io
+    import random
+    store = {}
+    rng = np.random.default_rng(20265)
+    # ---- traffic: X = 500, dx = 10 (M = 51), six steps, the plant in the command of step 1; 'both' also in the second column
+    P = dict(T=240, dt=0.25, X=500, dx=10, tau=60, v_max=40, ro_max=0.16, ro_steady=0.12)
+    Veq = src.TrafficPDE1D.Veq
+    v_steady = Veq(P["v_max"], P["ro_max"], P["ro_steady"])
+    _scalars(store, "traffic_kw", control_freq=1, limit=True, v_steady=v_steady, **P)
+    for sim, col in (("inlet", 0), ("outlet", 0), ("both", 0), ("both", 1)):
+        nact = 2 if sim == "both" else 1
+        base = rng.uniform(0.7, 1.3, (6, nact))
+        runs = []
+        for pname, pval in NF_PLANTS:
+            kw = dict(T=P["T"], dt=P["dt"], X=P["X"], dx=P["dx"], reward_class=src.TrafficARZReward(), simulation_type=sim,
+                      v_steady=v_steady, ro_steady=P["ro_steady"], v_max=P["v_max"], ro_max=P["ro_max"], tau=P["tau"],
+                      limit_pde_state_size=True, control_freq=1)
+            random.seed(11)
+            with contextlib.redirect_stdout(io.StringIO()):
+                env = src.TrafficPDE1D(**kw)
+                qs_clip = env.qs
+                random.seed(13)
+                obs0, _ = env.reset()
+            acts = base * env.qs
+            acts[1, col] = pval
+            obs, rew, done, trunc, tim = [np.array(obs0)], [], [], [], []
+            with np.errstate(all="ignore"):
+                for a in acts:
+                    with contextlib.redirect_stdout(io.StringIO()):
+                        o, r, d, t, _ = env.step(a.copy())
+                    obs.append(np.array(o))
+                    rew.append(r)
+                    done.append(bool(d))
+                    trunc.append(bool(t))
+                    tim.append(env.time_index)
+            runs.append(dict(obs=np.stack(obs), reward=np.array(rew, dtype=np.float64), done=np.array(done), trunc=np.array(trunc),
+                             time=np.array(tim, dtype=np.float64), actions=acts))
+            if pname == "nan":
+                assert np.isnan(obs[2]).sum() >= 2 and np.isnan(rew[1]) and not np.isnan(obs[1]).any(), (sim, col)
+        name = f"traffic_{sim}_c{col}"
+        pack(name, {k: np.stack([r_[k] for r_ in runs]) for k in runs[0]}, store)
+        pack(name, dict(rs=np.float64(env.rs), qs_clip=np.float64(qs_clip), sim=np.array(sim), plants=np.array([n_ for n_, _ in NF_PLANTS])),
+             store)
+    # ---- tumour: X = 100, dx = 1; set A of gen_sweep_tumor on a wide initial profile (therapy from day 21); a NaN cell in the
+    # initial profile; a NaN / +Inf / -Inf dosage on the second therapy day.  Rows sub-sampled (``keep``), the last ones all kept.
+    bt = importlib.import_module("pde_control_gym.src.environments1d.brain_tumor_env")
+    br = importlib.import_module("pde_control_gym.src.rewards.brain_tumor_reward")
+    A = dict(X=100, dx=1, D=0.1, rho=0.05, alpha=0.1, alpha_beta_ratio=3, k=1.0, t1_detection_threshold=0.6, t2_detection_threshold=0.3,
+             dosage_termination_threshold=1.0, t1_detection_radius=10, t1_death_radius=25, total_dosage=30.0)
+    T = 40
+    _scalars(store, "tumor_kw", T=T, dt=1, **A)
+    xs = np.linspace(0, A["X"], 101)
+    for name, cell, dose in (("tumor_cell_nan", 40, None),) + tuple((f"tumor_dose_{n}", None, v) for n, v in NF_PLANTS):
+        init = 0.8 * A["k"] * np.exp(-(xs / 11.0) ** 2)
+        if cell is not None:
+            init[cell] = np.nan
+        env = bt.BrainTumor1D(T=T, dt=1, normalize=True, reward_class=br.BrainTumorReward(), verbose=False,
+                              reset_init_condition_func=lambda X, n: init.copy(), **A)
+        env.t_benchmark = 30
+        env.reset()
+        acts, rew, term, trunc, stage, raised = [], [], [], [], [], ""
+        therapy_days = 0
+        with np.errstate(all="ignore"):
+            while len(acts) < T:
+                a = float(rng.uniform(0.02, 0.1))
+                if env.stage == "Therapy":
+                    therapy_days += 1
+                    if dose is not None and therapy_days == 2:
+                        a = dose
+                acts.append(a)
+                step = lambda: env.step(a)      # noqa: E731
+                if dose is not None and dose != float("inf") and therapy_days == 3:
+                    raised = _raises(step)      # the day after a NaN / -Inf dosage: the whole treated region is NaN, T2 radius None
+                    break
+                o, r, te, tr, info = step()
+                rew.append(float(r))
+                term.append(bool(te))
+                trunc.append(bool(tr))
+                stage.append({"Growth": 0, "Therapy": 1, "Post-Therapy": 2}[info["stage"]])
+                if te or tr:
+                    break
+        n = len(rew)
+        assert therapy_days >= 2, (name, therapy_days)
+        keep = np.unique(np.concatenate([np.arange(0, n + 1, 10), np.arange(max(0, n - 1), n + 1)]))
+        pack(name, dict(init=init, actions=np.array(acts), t_benchmark=np.float64(30), reward=np.array(rew), term=np.array(term),
+                        trunc=np.array(trunc), stage=np.array(stage), keep=keep, rows=env.u[keep].copy(),
+                        dosage=env.dosage_vs_time[: n + 1].copy(),
+                        days=np.array([env.growthDays, env.therapyDays, env.postTherapyDays, env.simulationDays,
+                                       -1 if env.cDeathDay is None else env.cDeathDay]),
+                        remaining=np.float64(env.remaining_dosage), raises=np.array(raised)), store)
+    # ---- Navier-Stokes: 11 x 11, K = 3, per-node commands on one Controllable edge (upper, u), three steps.  Fields in sixteenths.
+    n, K, nt = 11, 3, 5
+    bc = {"upper": ["Controllable", "Dirchilet"], "lower": ["Dirchilet", "Neumann"], "left": ["Neumann", "Dirchilet"],
+          "right": ["Dirchilet", "Neumann"]}
+    edges = ("upper", "lower", "left", "right")
+    dx = 1.0 / (n - 1)
+    dt = 0.2 * 0.5 * dx ** 2 / 0.1
+    base = [rng.integers(-16, 17, (n, n)) / 16.0 for _ in range(3)]
+    Uref = rng.integers(-16, 17, (nt, n, n, 2)) / 16.0
+    aref = rng.integers(16, 49, nt) / 16.0
+    acts0 = rng.integers(32, 65, (3, n)) / 16.0
+    pack("ns_kw", dict(u0=base[0], v0=base[1], p0=base[2], U_ref=Uref, action_ref=aref, actions=acts0,
+                       bc=np.array([bc[k][i] for k in edges for i in (0, 1)])), store)
+    _scalars(store, "ns_kw", T=nt * dt, dt=dt, X=1.0, dx=dx, Y=1.0, dy=dx, nt=nt, n=n, action_dim=n, gamma=0.1,
+             viscosity=0.1, density=1.0, maximum_pressure_iteration=K)
+    # (what is planted: "a" = actions[step, node], "u" / "p" = initial field [row, column])
+    for name, what, where, val in (("ns_cmd_nan", "a", (1, 4), float("nan")), ("ns_cmd_pinf", "a", (1, 4), float("inf")),
+                                   ("ns_u_nan", "u", (5, 5), float("nan")), ("ns_p_nan", "p", (5, 5), float("nan"))):
+        u0, v0, p0 = (b.copy() for b in base)
+        acts = acts0.copy()
+        {"a": acts, "u": u0, "p": p0}[what][where] = val
+        kw = dict(T=nt * dt, dt=dt, X=1, dx=dx, Y=1, dy=dx, action_dim=n, reward_class=src.NSReward(0.1), normalize=False,
+                  reset_init_condition_func=lambda X: (u0.copy(), v0.copy(), p0.copy()), boundary_condition=bc,
+                  U_ref=Uref, action_ref=aref, maximum_pressure_iteration=K, viscosity=0.1, density=1.0)
+        env = src.NavierStokes2D(**kw)
+        env.reset()
+        obs_l, p_l, r_l, te_l = [], [], [], []
+        with np.errstate(all="ignore"):
+            for a in acts:
+                obs, r, te, tr, _ = env.step(a.copy())
+                obs_l.append(np.array(obs))
+                p_l.append(np.array(env.p))
+                r_l.append(r)
+                te_l.append(bool(te))
+        pack(name, dict(plant_in=np.array(what), plant_at=np.array(where), plant=np.float64(val), obs=np.stack(obs_l), p=np.stack(p_l),
+                        rewards=np.array(r_l, dtype=np.float64), terminate=np.array(te_l)), store)
+        if val != val:
+            assert np.isnan(obs_l[-1]).sum() >= np.isnan(obs_l[1]).sum() > 0 and np.isnan(r_l[-1]), name
+    np.savez_compressed(os.path.join(out, "nonfinite.npz"), **store)
 
 FILES = {"transport": "transport.npz", "parabolic": "parabolic.npz", "kat": "kat.npz", "mixed": "mixed.npz", "ns": "ns2d.npz",
          "traffic": "traffic.npz", "tumor": "tumor.npz", "sweep_1d": "sweep_1d.npz", "sweep_ns": "sweep_ns.npz",
-         "sweep_traffic": "sweep_traffic.npz", "sweep_tumor": "sweep_tumor.npz"}
+         "sweep_traffic": "sweep_traffic.npz", "sweep_tumor": "sweep_tumor.npz", "nonfinite": "nonfinite.npz"}
 
 
 GEN = {"transport": gen_transport, "parabolic": gen_parabolic, "kat": gen_kat, "mixed": gen_mixed, "ns": gen_ns,
        "traffic": gen_traffic, "tumor": gen_tumor, "sweep_1d": gen_sweep_1d, "sweep_ns": gen_sweep_ns,
-       "sweep_traffic": gen_sweep_traffic, "sweep_tumor": gen_sweep_tumor}
+       "sweep_traffic": gen_sweep_traffic, "sweep_tumor": gen_sweep_tumor, "nonfinite": gen_nonfinite}
 
 
 def check(which=None):

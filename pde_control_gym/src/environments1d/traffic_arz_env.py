@@ -67,23 +67,19 @@ class TrafficPDE1D(PDEEnv1D):
         # one launch, ONE device-to-host copy and one synchronisation per step(): the command is read by the kernel from pinned host
         # memory in place; observation, fields, clock, reward and flags share one allocation (TrafficBatch.host_pack)
         from pdecontrolgym_amd.hostio import HostFetch, PinnedInputs
-        self._fetch, self._pins, self._views = HostFetch(self._core.device), PinnedInputs(self._core.device), None
+        self._fetch, self._pins = HostFetch(self._core.device), PinnedInputs(self._core.device)
         self._core.reset([self.rs])
         self._load_state()
         self.info["V"] = self.v
 
     def _load_state(self):
         """Observation, fields, clock, reward and flags of the last launch: ONE device-to-host copy of the engine's pack."""
-        core = self._core
-        raw = self._fetch([core.host_pack])[0]
-        if self._views is None or self._views[0] is not raw:
-            self._views = (raw, core.pack_layout.numpy_views(raw))
-        v = self._views[1]
+        v = self._core.host_views(self._fetch)
         self.r = v["r"][0].reshape(self.M, 1).copy()
         self.y = v["y"][0].reshape(self.M, 1).copy()
         self.v = self.y / self.r + TrafficPDE1D.Veq(self.vm, self.rm, self.r)
         self.time_index = float(v["time"][0])
-        return v["obs1" if core.t["obs"] is core._obs[1] else "obs0"][0].copy(), v
+        return v[self._core.obs_segment][0].copy(), v
 
     def terminate(self):
         return bool(self._done_flag)

@@ -36,6 +36,31 @@ def _on_device_of(key):
     return deco
 
 
+def _prepared(fn, pP, pB, B, dev, what, keep):
+    """A zero-argument callable that launches ``fn(pP, pB, B, stream)`` on the current stream of ``dev`` (made current first when
+    another device is) and raises on failure.  ``keep``: what the argument structures point into, kept alive with the call."""
+    import torch
+    current_stream, current_device = torch.cuda.current_stream, torch.cuda.current_device
+
+    def call(_keep=keep):
+        if current_device() != dev.index:
+            with torch.cuda.device(dev):
+                rc = fn(pP, pB, B, current_stream(dev).cuda_stream)
+        else:
+            rc = fn(pP, pB, B, current_stream(dev).cuda_stream)
+        if rc:
+            N.check(rc, what)
+    return call
+
+
+def _check_shapes(prefix, wanted):
+    """``wanted``: name -> (tensor | None, shape[, dtype]).  Every tensor given must be contiguous and have that shape (and dtype)."""
+    for name, (x, shape, *dtype) in wanted.items():
+        if x is not None and (tuple(x.shape) != tuple(shape) or not x.is_contiguous() or (dtype and x.dtype != dtype[0])):
+            kind = "contiguous " + str(dtype[0]).replace("torch.", "") if dtype else "contiguous"
+            raise N.NativeError(f"{prefix} {name} must be a {kind} {list(shape)} tensor, got {tuple(x.shape)}")
+
+
 class HipBackend:
     name = "hip-gfx950"
 
@@ -51,7 +76,7 @@ class HipBackend:
         if si is not None:       # the rows live in the (double-buffered) observation tensors: read from the previous one
             b.state_in, b.u = N.dptr(si, torch.float32), None
         else:
-            b.u = N.dptr(T["u"], torch.float32) if T.get("u") is not None else None
+            b.u = N.dptr(T.get("u"), torch.float32)
         b.beta = N.dptr(T["beta"])                 # float32, or float64 in the reference's mixed-precision mode (P.beta_f64)
         b.beta_stride = 0 if T["beta"].dim() == 1 else T["beta"].stride(0)
         b.action = N.dptr(T["action"])             # float32, or float64 when P.action_kind != ACTION_F32
@@ -64,14 +89,10 @@ class HipBackend:
         b.norm_back = N.dptr(T["norm_back"], torch.float32)
         b.terminated = N.dptr(T["terminated"], torch.uint8)
         b.truncated = N.dptr(T["truncated"], torch.uint8)
-        h = T.get("history")
-        b.history = N.dptr(h, torch.float32) if h is not None else None
-        ri, fo = T.get("reset_init"), T.get("final_obs")
-        b.reset_init = N.dptr(ri, torch.float32) if ri is not None else None
-        b.final_obs = N.dptr(fo, torch.float32) if fo is not None else None
-        rb, rc = T.get("reset_beta"), T.get("reset_count")
-        b.reset_beta = N.dptr(rb, T["beta"].dtype) if rb is not None else None
-        b.reset_count = N.dptr(rc, torch.int32) if rc is not None else None
+        b.history = N.dptr(T.get("history"), torch.float32)
+        ri, rb = T.get("reset_init"), T.get("reset_beta")
+        b.reset_init, b.final_obs = N.dptr(ri, torch.float32), N.dptr(T.get("final_obs"), torch.float32)
+        b.reset_beta, b.reset_count = N.dptr(rb, T["beta"].dtype), N.dptr(T.get("reset_count"), torch.int32)
         b.reset_pool_rows = int(ri.shape[0]) if ri is not None else 0
         if rb is not None and (T["beta"].dim() == 1 or rb.shape != ri.shape):
             raise N.NativeError("reset_beta needs a per-instance beta [B, n] and the shape of reset_init")
@@ -98,18 +119,7 @@ class HipBackend:
             raise N.NativeError(f"beta is {T['beta'].dtype} but params.beta_f64 = {P.beta_f64}")
         bufs = self._bufs1d(T)
         dev = T["bsum"].device                     # (outputs may live in pinned host memory: the state names the device)
-        pP, pB, what = C.byref(P), C.byref(bufs), f"pdegym_{kind}_step"
-        current_stream, current_device = torch.cuda.current_stream, torch.cuda.current_device
-
-        def call(_keep=(bufs, T)):
-            if current_device() != dev.index:
-                with torch.cuda.device(dev):
-                    rc = fn(pP, pB, B, current_stream(dev).cuda_stream)
-            else:
-                rc = fn(pP, pB, B, current_stream(dev).cuda_stream)
-            if rc:
-                N.check(rc, what)
-        return call
+        return _prepared(fn, C.byref(P), C.byref(bufs), B, dev, f"pdegym_{kind}_step", (bufs, T))
     prepare_step1d.device_guard_key = "bsum"     # the guard is inside the prepared call (the state's device made current)
 
     @_on_device_of("obs")
@@ -125,29 +135,24 @@ class HipBackend:
         steps = int(actions.shape[0])
         full = P.sensing == N.SENSE_FULL
         od = P.n if full else 1
-        if tuple(obs.shape) != (steps + 1, B, od) or not obs.is_contiguous():
-            raise N.NativeError(f"rollout obs must be a contiguous [{steps + 1}, {B}, {od}] tensor, got {tuple(obs.shape)}")
-        for name, x in (("actions", actions), ("rewards", rewards), ("terminated", terminated), ("truncated", truncated)):
-            if tuple(x.shape) != (steps, B) or not x.is_contiguous():
-                raise N.NativeError(f"rollout {name} must be a contiguous [{steps}, {B}] tensor, got {tuple(x.shape)}")
-        for name, x in (("obs_noise", obs_noise), ("obs_seen", obs_seen)):
-            if x is not None and (tuple(x.shape) != (steps, B, od) or not x.is_contiguous() or x.dtype != torch.float32):
-                raise N.NativeError(f"rollout {name} must be a contiguous float32 [{steps}, {B}, {od}] tensor, got {tuple(x.shape)}")
+        _check_shapes("rollout", {"obs": (obs, (steps + 1, B, od)), "actions": (actions, (steps, B)), "rewards": (rewards, (steps, B)),
+                                  "terminated": (terminated, (steps, B)), "truncated": (truncated, (steps, B)),
+                                  "obs_noise": (obs_noise, (steps, B, od), torch.float32),
+                                  "obs_seen": (obs_seen, (steps, B, od), torch.float32)})
         bufs = self._bufs1d({**T, "state_in": None, "u": None if full else T["u"], "history": None})
         ro = N.Rollout1D()
         ro.T = steps
         ro.obs, ro.actions, ro.rewards = N.dptr(obs, torch.float32), N.dptr(actions, torch.float32), N.dptr(rewards, torch.float32)
         ro.terminated, ro.truncated = N.dptr(terminated, torch.uint8), N.dptr(truncated, torch.uint8)
         ro.policy = C.addressof(policy) if policy is not None else None
-        ro.obs_noise = N.dptr(obs_noise, torch.float32) if obs_noise is not None else None
-        ro.obs_seen = N.dptr(obs_seen, torch.float32) if obs_seen is not None else None
+        ro.obs_noise, ro.obs_seen = N.dptr(obs_noise, torch.float32), N.dptr(obs_seen, torch.float32)
         N.check(fn(C.byref(P), C.byref(bufs), C.byref(ro), B, N.current_stream_ptr(obs.device)), f"pdegym_{kind}_rollout")
 
     @_on_device_of("bsum")
     def reset1d(self, P: N.Params1D, T: dict, init, mask, B: int):
         import torch
         bufs = self._bufs1d(T)
-        m = N.dptr(mask, torch.uint8) if mask is not None else None
+        m = N.dptr(mask, torch.uint8)
         N.check(self.lib.pdegym_reset1d_masked(C.byref(P), C.byref(bufs), N.dptr(init, torch.float32), m, B,
                                                N.current_stream_ptr(T["bsum"].device)), "pdegym_reset1d_masked")
 
@@ -166,8 +171,8 @@ class HipBackend:
         for k in ("p", "scratch", "action", "U_ref", "action_ref", "obs", "reward"):
             setattr(b, k, N.dptr(T[k], dtype))
         for k in ("u", "v", "state_in", "p_out", "reset_u0", "reset_v0", "reset_p0", "final_obs"):
-            setattr(b, k, N.dptr(T[k], dtype) if T.get(k) is not None else None)
-        b.reset_count = N.dptr(T["reset_count"], torch.int32) if T.get("reset_count") is not None else None
+            setattr(b, k, N.dptr(T.get(k), dtype))
+        b.reset_count = N.dptr(T.get("reset_count"), torch.int32)
         b.reset_pool_rows = int(T["reset_u0"].shape[0]) if T.get("reset_u0") is not None else 0
         b.time_index = N.dptr(T["time_index"], torch.int32)
         b.terminated = N.dptr(T["terminated"], torch.uint8)
@@ -188,23 +193,10 @@ class HipBackend:
 
     def prepare_ns2d_step(self, P: N.ParamsNS2D, T: dict, B: int):
         """pdegym_ns2d_step_* with its argument structures built once (see prepare_step1d): a zero-argument callable."""
-        import torch
         dtype = T["p"].dtype
         bufs = self._bufs_ns(T, dtype)
         fn = getattr(self.lib, "pdegym_ns2d_step_" + self._sfx(dtype))
-        dev = T["p"].device
-        pP, pB = C.byref(P), C.byref(bufs)
-        current_stream, current_device = torch.cuda.current_stream, torch.cuda.current_device
-
-        def call(_keep=(bufs, T)):
-            if current_device() != dev.index:
-                with torch.cuda.device(dev):
-                    rc = fn(pP, pB, B, current_stream(dev).cuda_stream)
-            else:
-                rc = fn(pP, pB, B, current_stream(dev).cuda_stream)
-            if rc:
-                N.check(rc, "pdegym_ns2d_step")
-        return call
+        return _prepared(fn, C.byref(P), C.byref(bufs), B, T["p"].device, "pdegym_ns2d_step", (bufs, T))
     prepare_ns2d_step.device_guard_key = "p"
 
     @_on_device_of("p")
@@ -214,10 +206,8 @@ class HipBackend:
         import torch
         dtype = T["p"].dtype
         steps = int(actions.shape[0])
-        want = {"obs": (steps + 1, B, P.ny, P.nx, 2), "actions": (steps, B, P.action_dim), "rewards": (steps, B), "terminated": (steps, B)}
-        for name, x in (("obs", obs), ("actions", actions), ("rewards", rewards), ("terminated", terminated)):
-            if tuple(x.shape) != want[name] or not x.is_contiguous():
-                raise N.NativeError(f"rollout {name} must be a contiguous {list(want[name])} tensor, got {tuple(x.shape)}")
+        _check_shapes("rollout", {"obs": (obs, (steps + 1, B, P.ny, P.nx, 2)), "actions": (actions, (steps, B, P.action_dim)),
+                                  "rewards": (rewards, (steps, B)), "terminated": (terminated, (steps, B))})
         bufs = self._bufs_ns({**T, "u": None, "v": None, "state_in": None, "p_out": None, "obs": obs[0], "action": actions[0],
                               "reward": rewards[0], "terminated": terminated[0]}, dtype)
         ro = N.RolloutNS2D()
@@ -233,7 +223,7 @@ class HipBackend:
         dtype = T["p"].dtype
         bufs = self._bufs_ns(T, dtype)
         fn = getattr(self.lib, "pdegym_ns2d_reset_masked_" + self._sfx(dtype))
-        m = N.dptr(mask, torch.uint8) if mask is not None else None
+        m = N.dptr(mask, torch.uint8)
         N.check(fn(C.byref(P), C.byref(bufs), N.dptr(u0, dtype), N.dptr(v0, dtype), N.dptr(p0, dtype), m, B,
                    N.current_stream_ptr(T["p"].device)), "pdegym_ns2d_reset_masked")
 
@@ -252,11 +242,8 @@ class HipBackend:
         import torch
         f64 = torch.float64
         steps, B = int(obs.shape[0]) - 1, int(obs.shape[1])
-        want = {"obs": (steps + 1, B, P.ny, P.nx, 2), "a_nom": (steps,), "grad": (steps, B), "actions": (steps, B),
-                "lam": (steps, B, P.ny, P.nx, 2)}
-        for name, x in (("obs", obs), ("a_nom", a_nom), ("grad", grad), ("actions", actions), ("lam", lam)):
-            if x is not None and (tuple(x.shape) != want[name] or not x.is_contiguous()):
-                raise N.NativeError(f"adjoint {name} must be a contiguous {list(want[name])} tensor, got {tuple(x.shape)}")
+        _check_shapes("adjoint", {"obs": (obs, (steps + 1, B, P.ny, P.nx, 2)), "a_nom": (a_nom, (steps,)), "grad": (grad, (steps, B)),
+                                  "actions": (actions, (steps, B)), "lam": (lam, (steps, B, P.ny, P.nx, 2))})
         a = N.AdjointNS2D()
         a.T, a.t0, a.ratio, a.width = steps, int(t0), float(ratio), float(width)
         a.obs, a.a_nom, a.grad, a.actions = N.dptr(obs, f64), N.dptr(a_nom, f64), N.dptr(grad, f64), N.dptr(actions, f64)
@@ -279,8 +266,7 @@ class HipBackend:
         if rr is not None:           # fused auto-reset (include/pdegym.h)
             b.reset_rs, b.reset_profile = N.dptr(rr, torch.float64), N.dptr(T["reset_profile"], torch.float64)
             b.reset_pool_rows = int(rr.shape[0])
-            b.final_obs = N.dptr(T["final_obs"], torch.float64) if T.get("final_obs") is not None else None
-            b.reset_count = N.dptr(T["reset_count"], torch.int32) if T.get("reset_count") is not None else None
+            b.final_obs, b.reset_count = N.dptr(T.get("final_obs"), torch.float64), N.dptr(T.get("reset_count"), torch.int32)
         return b
 
     @_on_device_of("r")
@@ -296,13 +282,10 @@ class HipBackend:
         import torch
         steps = int(actions.shape[0])
         A = int(actions.shape[2])
-        if tuple(obs.shape) != (steps + 1, B, 2 * P.M) or not obs.is_contiguous():
-            raise N.NativeError(f"rollout obs must be a contiguous [{steps + 1}, {B}, {2 * P.M}] tensor, got {tuple(obs.shape)}")
-        if tuple(actions.shape) != (steps, B, A) or A not in (1, 2) or not actions.is_contiguous():
+        if A not in (1, 2):
             raise N.NativeError(f"rollout actions must be a contiguous [{steps}, {B}, 1 or 2] tensor, got {tuple(actions.shape)}")
-        for name, x in (("rewards", rewards), ("done", done), ("truncated", truncated)):
-            if tuple(x.shape) != (steps, B) or not x.is_contiguous():
-                raise N.NativeError(f"rollout {name} must be a contiguous [{steps}, {B}] tensor, got {tuple(x.shape)}")
+        _check_shapes("rollout", {"obs": (obs, (steps + 1, B, 2 * P.M)), "actions": (actions, (steps, B, A)), "rewards": (rewards, (steps, B)),
+                                  "done": (done, (steps, B)), "truncated": (truncated, (steps, B))})
         bufs = self._bufs_traffic({**T, "action": actions[0]})
         ro = N.RolloutTraffic()
         ro.T = steps
@@ -316,7 +299,7 @@ class HipBackend:
     def traffic_reset(self, P: N.ParamsTraffic, T: dict, profile, mask, B: int):
         import torch
         bufs = self._bufs_traffic(T)
-        m = N.dptr(mask, torch.uint8) if mask is not None else None
+        m = N.dptr(mask, torch.uint8)
         N.check(self.lib.pdegym_traffic_reset_masked(C.byref(P), C.byref(bufs), N.dptr(profile, torch.float64), m, B,
                                                      N.current_stream_ptr(T["r"].device)), "pdegym_traffic_reset_masked")
 
@@ -327,14 +310,13 @@ class HipBackend:
         b = N.BufsTumor()
         for k in ("u", "xscale", "control", "remaining", "t_benchmark", "reward", "out"):
             setattr(b, k, N.dptr(T[k], torch.float64))
-        b.kill = N.dptr(T.get("kill"), torch.float64) if T.get("kill") is not None else None
+        b.kill = N.dptr(T.get("kill"), torch.float64)
         for k in ("time_index", "stage", "days"):
             setattr(b, k, N.dptr(T[k], torch.int32))
         b.terminated = N.dptr(T["terminated"], torch.uint8)
         b.truncated = N.dptr(T["truncated"], torch.uint8)
-        b.active = N.dptr(T.get("active"), torch.uint8) if T.get("active") is not None else None
-        b.history = N.dptr(T.get("history"), torch.float64) if T.get("history") is not None else None
-        b.t1_log = N.dptr(T.get("t1_log"), torch.float64) if T.get("t1_log") is not None else None
+        b.active = N.dptr(T.get("active"), torch.uint8)
+        b.history, b.t1_log = N.dptr(T.get("history"), torch.float64), N.dptr(T.get("t1_log"), torch.float64)
         return b
 
     @_on_device_of("u")
@@ -353,7 +335,7 @@ class HipBackend:
     def tumor_reset(self, P: N.ParamsTumor, T: dict, init, mask, B: int):
         import torch
         bufs = self._bufs_tumor(T)
-        m = N.dptr(mask, torch.uint8) if mask is not None else None
+        m = N.dptr(mask, torch.uint8)
         stride = 0 if init.dim() == 1 else init.shape[-1]
         N.check(self.lib.pdegym_tumor_reset_masked(C.byref(P), C.byref(bufs), N.dptr(init, torch.float64), stride, m, B,
                                                    N.current_stream_ptr(T["u"].device)), "pdegym_tumor_reset_masked")

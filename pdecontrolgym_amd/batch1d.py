@@ -85,10 +85,7 @@ class PDEBatch1D(EngineCheckpoint):
         self.sensing_loc, self.sensing_type, self.normalize = sensing_loc, sensing_type, bool(normalize)
         self.max_control_value, self.max_state_value = max_control_value, max_state_value
         self.limit_pde_state_size = limit_pde_state_size
-        if backend is None:
-            from .backend import default_backend
-            backend = default_backend()
-        self.backend = backend.bind(self) if hasattr(backend, "bind") else backend
+        self._bind_backend(backend)
 
         P = N.Params1D()
         P.n, P.nt, P.substeps = self.n, self.nt, self.substeps
@@ -136,7 +133,6 @@ class PDEBatch1D(EngineCheckpoint):
             "reset_beta": None,
             "reset_count": None,
         }
-        # observations are double-buffered: the tensor returned by step k stays valid during step k+1
         self._obs = [torch.zeros(B, self.obs_dim, dtype=f32, device=dev) for _ in range(2)]
         self._flip = 0
         self.t["obs"] = self._obs[0]
@@ -156,11 +152,6 @@ class PDEBatch1D(EngineCheckpoint):
     @property
     def time_index(self):
         return self.t["time_index"]
-
-    def _next_obs(self):
-        self._flip ^= 1
-        self.t["obs"] = self._obs[self._flip]
-        return self.t["obs"]
 
     # ---- API -----------------------------------------------------------------------------------------
     def set_beta(self, beta, dtype=None):
@@ -188,10 +179,9 @@ class PDEBatch1D(EngineCheckpoint):
         if init.shape != (self.num_envs, self.n):
             raise ValueError(f"init must be [{self.num_envs}, {self.n}], got {tuple(init.shape)}")
         if mask is not None:
-            mask = torch.as_tensor(mask, device=self.device).to(torch.uint8).contiguous()
-            # masked reset writes into the CURRENT obs buffer so untouched instances keep their observation
+            mask = self._as_mask(mask)     # a masked reset writes into the CURRENT obs buffer: untouched instances keep theirs
         else:
-            self._next_obs()
+            self._flip_obs()
         if self.state_in_obs:
             self.t["u"] = None                      # the reset rows go to the observation buffer only
         self.backend.reset1d(self.params, self.t, init, mask, self.num_envs)
@@ -210,26 +200,17 @@ class PDEBatch1D(EngineCheckpoint):
         pool = torch.as_tensor(init_pool, dtype=torch.float32, device=self.device).contiguous()
         if pool.dim() != 2 or pool.shape[1] != self.n or pool.shape[0] < self.num_envs:
             raise ValueError(f"init_pool must be [P >= {self.num_envs}, {self.n}], got {tuple(pool.shape)}")
-        self.t["reset_init"] = pool
-        self.t["reset_count"] = torch.zeros(self.num_envs, dtype=torch.int32, device=self.device)
-        self.t["reset_beta"] = None
+        bp = None
         if beta_pool is not None:
             if self.t["beta"].dim() == 1:        # a shared row cannot be redrawn per instance: give every instance its own
                 self.t["beta"] = self.t["beta"].unsqueeze(0).repeat(self.num_envs, 1).contiguous()
             bp = torch.as_tensor(beta_pool).to(device=self.device, dtype=self.t["beta"].dtype).contiguous()
             if bp.shape != pool.shape:
                 raise ValueError(f"beta_pool must have the shape of init_pool {tuple(pool.shape)}, got {tuple(bp.shape)}")
-            self.t["reset_beta"] = bp
-        self.t["final_obs"] = (torch.zeros(self.num_envs, self.obs_dim, dtype=torch.float32, device=self.device)
-                               if keep_final_obs else None)
-        self._drop_prepared_call()
+        self._set_auto_reset({"reset_init": pool, "reset_beta": bp}, keep_final_obs)
 
     def disable_auto_reset(self):
-        self.t["reset_init"] = None
-        self.t["final_obs"] = None
-        self.t["reset_beta"] = None
-        self.t["reset_count"] = None
-        self._drop_prepared_call()
+        self._clear_auto_reset(("reset_init", "reset_beta"))
 
     def step(self, action, out_obs=None, out_reward=None, out_terminated=None, out_truncated=None, action_kind=None):
         """Advance every instance by one env-step (S sub-steps). action: [B] tensor.
@@ -249,12 +230,7 @@ class PDEBatch1D(EngineCheckpoint):
         self.t["action"] = a
         self.params.action_kind = action_kind
         prev = self.t["obs"]
-        if out_obs is not None:
-            self.t["obs"] = out_obs.view(self.num_envs, self.obs_dim)
-        else:
-            self._next_obs()
-            if self.state_in_obs and self.t["obs"] is prev:   # never write the observation over the state it is computed from
-                self._next_obs()
+        self._flip_obs(out_obs, avoid=prev if self.state_in_obs else None)
         if self.state_in_obs:
             if self.t["obs"].data_ptr() == prev.data_ptr():
                 raise ValueError("out_obs must not be the tensor that holds the current observation (it is the state)")
@@ -269,14 +245,12 @@ class PDEBatch1D(EngineCheckpoint):
 
     # ---- batch-of-one face: command in / results out through ONE pinned host allocation ------------------------------
     def enable_host_io(self):
-        """Host-facing mode of a small batch (the single environments, ``num_envs=1``): the command and everything a host caller
-        reads after a step -- observation, reward, ||u||, terminated, truncated -- live in ONE pinned host allocation that is
-        mapped into the device's address space (hipHostMalloc).  The step kernel reads the command from it and writes its
-        results into it directly, so an env-step is ONE stream operation (the kernel launch) + ONE stream synchronisation: no
-        host-to-device copy of the command, no device-to-host copies of the results, no torch dispatch.  The plant state (row,
-        beta, ring, running sums, time index, history) stays in HBM.  Not for ``state_in_obs`` engines (their observation IS
-        the state).  Returns the NumPy views ``{"obs", "reward", "norm_now", "terminated", "truncated"}`` (valid after
-        ``step_host`` / ``sync_host``; overwritten by the next step)."""
+        """Host-facing mode of the single environments (``EngineCheckpoint._enable_host_io``): the command, observation, reward,
+        ||u||, terminated and truncated live in one pinned host allocation, so an env-step is ONE stream operation (the kernel
+        launch) + ONE stream synchronisation.  The plant state (row, beta, ring, running sums, time index, history) stays in HBM.
+        Not for ``state_in_obs`` engines (their observation IS the state).  Returns the NumPy views ``{"obs", "reward",
+        "norm_now", "terminated", "truncated"}`` (valid after ``step_host`` / ``sync_host``; overwritten by the next step)."""
+        import numpy as np
         import torch
         if self.state_in_obs:
             raise ValueError("host I/O needs the state in its own tensor (build the engine with state_in_obs=False)")
@@ -284,31 +258,15 @@ class PDEBatch1D(EngineCheckpoint):
             # (the command slot is 8 bytes wide so that one address serves float32 and float64 commands: an array of float32
             # commands would need 4-byte slots -- batches take the staged path of PDEVecEnv)
             raise ValueError("host I/O is the batch-of-one face (num_envs = 1)")
-        if getattr(self, "_hio", None) is not None:
+        if self._hio is not None:
             return self._hio["np"]
-        B, od = self.num_envs, self.obs_dim
-        sizes = (("action", 8 * B), ("obs", 4 * B * od), ("reward", 4 * B), ("norm_now", 4 * B), ("terminated", B), ("truncated", B))
-        pack = torch.zeros((sum(s for _, s in sizes) + 63) // 64 * 64, dtype=torch.uint8, pin_memory=self.device.type == "cuda")
-        raw, off, sl = pack.numpy(), 0, {}
-        for k, nb in sizes:
-            sl[k] = slice(off, off + nb)
-            off += nb
-        f32 = torch.float32
-        tv = {"action": pack[sl["action"]].view(torch.float64), "obs": pack[sl["obs"]].view(f32).view(B, od),
-              "reward": pack[sl["reward"]].view(f32), "norm_now": pack[sl["norm_now"]].view(f32),
-              "terminated": pack[sl["terminated"]], "truncated": pack[sl["truncated"]]}
-        import numpy as np
-        nv = {"obs": raw[sl["obs"]].view(np.float32).reshape(B, od), "reward": raw[sl["reward"]].view(np.float32),
-              "norm_now": raw[sl["norm_now"]].view(np.float32), "terminated": raw[sl["terminated"]],
-              "truncated": raw[sl["truncated"]]}
+        B, f32, u8 = self.num_envs, torch.float32, torch.uint8
+        nv = self._enable_host_io([("action", (B,), torch.float64), ("obs", (B, self.obs_dim), f32), ("reward", (B,), f32),
+                                   ("norm_now", (B,), f32), ("terminated", (B,), u8), ("truncated", (B,), u8)], align=1)
         # one 8-byte slot per instance: a float32 command occupies its first four bytes, a float64 one all eight (the kernel reads
         # the slot as params.action_kind says)
-        a64 = raw[sl["action"]].view(np.float64)
-        a32 = raw[sl["action"]].view(np.float32)[::2]
-        for k in ("obs", "reward", "norm_now", "terminated", "truncated"):
-            self.t[k] = tv[k]
-        self._obs = [tv["obs"], tv["obs"]]
-        self._hio = {"pack": pack, "action": tv["action"], "a32": a32, "a64": a64, "np": nv, "call": None, "key": None}
+        a64 = nv.pop("action")
+        self._hio.update(action=self.t["action"], a64=a64, a32=a64.view(np.float32)[::2], key=None)
         return nv
 
     def _host_call(self):
@@ -331,12 +289,6 @@ class PDEBatch1D(EngineCheckpoint):
                 io["call"] = call
             io["key"] = key
         return io["call"]
-
-    def sync_host(self):
-        """Wait until the results of the last launch are in the host views."""
-        if self.device.type == "cuda":
-            import torch
-            torch.cuda.current_stream(self.device).synchronize()
 
     def step_host(self, value: float, action_kind: int = N.ACTION_F32):
         """One env-step of a batch of one commanded from the host: ``value`` (a Python float) is written into the pinned command
@@ -361,22 +313,10 @@ class PDEBatch1D(EngineCheckpoint):
                     and self.n <= N.MAX_N1D_REG and hasattr(self.backend, "rollout1d"))
 
     def policy_fits_rollout(self, policy) -> bool:
-        """Whether ``policy`` (a ``FusedMLP``) can be evaluated inside the rollout kernel: the observation (the row of at most
-        513 nodes, or the one sensed value) as its input and one output.  Layers of at most 64 units: one neuron per lane, the
-        weights + 16 observation rows within 160 KB of LDS.  A layer of 65..256 units (SB3's 256-256 actors): the 16 waves of a
-        workgroup evaluate the network together on the matrix cores, weights streamed from L2 -- bit-identical to
-        ``pdegym_mlp_forward`` (16 observation rows + the hidden rows within 160 KB of LDS: any row the kernel takes)."""
-        if not (self.can_rollout() and hasattr(policy, "layers") and hasattr(policy, "_net")):
-            return False
-        dims = [(int(w.shape[1]), int(w.shape[0])) for w, _, _ in policy.layers]
-        if dims[0][0] != self.obs_dim or self.n > 513 or dims[-1][1] != 1 or any(o > 256 for _, o in dims):
-            return False
-        stride = lambda w: (w + 63) // 64 * 64 + 4                  # noqa: E731  (pdegym_mlp_tile.h: lds_stride)
-        if any(o > 64 for _, o in dims):
-            floats = 16 * (stride((self.obs_dim + 15) // 16 * 16) + 2 * stride(256)) + 32
-        else:
-            floats = sum((((i + 3) // 4) | 1) * 4 * o + 64 for i, o in dims) + 16 * (((self.obs_dim + 3) // 4) * 4 + 128)
-        return 4 * floats <= 160 * 1024
+        """Whether ``policy`` (a ``FusedMLP``) can be evaluated inside the rollout kernel (``FusedMLP.fits_rollout``): the
+        observation (the row of at most 513 nodes, or the one sensed value) as its input and one output."""
+        fits = getattr(policy, "fits_rollout", None)
+        return fits is not None and self.can_rollout() and fits(self.obs_dim, 1) and self.n <= 513
 
     def rollout(self, obs, actions, rewards, terminated, truncated, policy=None, clamp="default", noise=None, obs_noise=None,
                 obs_seen=None):
@@ -402,15 +342,7 @@ class PDEBatch1D(EngineCheckpoint):
         if policy is not None:
             if not self.policy_fits_rollout(policy):
                 raise ValueError("this policy cannot run inside the rollout kernel (see policy_fits_rollout)")
-            import torch
-            if not (obs.is_cuda and torch.cuda.is_current_stream_capturing()):
-                policy.refresh()             # pick up in-place parameter updates (as FusedMLP.forward_into does)
-            net = policy._net(policy.clamp if clamp == "default" else clamp)
-            if noise is not None:
-                import torch
-                if noise.dtype != torch.float32 or tuple(noise.shape) != tuple(actions.shape) or not noise.is_contiguous():
-                    raise ValueError("noise must be a contiguous float32 [T, B] tensor")
-                net.noise, net.noise_stride = noise.data_ptr(), 1
+            net = policy.rollout_net(obs, actions, clamp, noise)
         elif obs_noise is not None or obs_seen is not None:
             raise ValueError("obs_noise / obs_seen shape the policy's input: they need a policy")
         self.backend.rollout1d(self.kind, self.params, self.t, obs, actions, rewards, terminated, truncated, self.num_envs,

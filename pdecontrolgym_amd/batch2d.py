@@ -54,10 +54,7 @@ class NSBatch2D(EngineCheckpoint):
         self.ctor = dict(T=T, dt=dt, X=X, dx=dx, Y=Y, dy=dy, boundary_condition=boundary_condition, gamma=gamma,
                          viscosity=viscosity, density=density, maximum_pressure_iteration=self.iters,
                          stable_factor=stable_factor)
-        if backend is None:
-            from .backend import default_backend
-            backend = default_backend()
-        self.backend = backend.bind(self) if hasattr(backend, "bind") else backend
+        self._bind_backend(backend)
 
         P = N.ParamsNS2D()
         P.nx, P.ny, P.nt, P.iters, P.action_dim = self.nx, self.ny, self.nt, self.iters, self.action_dim
@@ -120,18 +117,6 @@ class NSBatch2D(EngineCheckpoint):
     def time_index(self):
         return self.t["time_index"]
 
-    def _next_obs(self, out_obs=None):
-        prev = self.t["obs"]
-        if self.interleaved_state:
-            self.t["state_in"] = prev               # the observation just produced is the next call's input state
-        if out_obs is not None:                     # the caller's buffer (e.g. slot t+1 of a rollout) receives the observation
-            self.t["obs"] = out_obs.view(self.num_envs, self.ny, self.nx, 2)
-            return
-        self._flip ^= 1
-        if self._obs[self._flip] is prev:           # never write the observation over the state it is computed from
-            self._flip ^= 1
-        self.t["obs"] = self._obs[self._flip]
-
     @contextmanager
     def single_pressure_buffer(self):
         """While steps are baked into a graph the pressure must stay in ONE tensor: inside this block the 256 x 256 engines do not
@@ -153,23 +138,17 @@ class NSBatch2D(EngineCheckpoint):
         for a in pools:
             if a.dim() != 3 or a.shape[0] < self.num_envs or tuple(a.shape[1:]) != (self.ny, self.nx) or a.shape != pools[0].shape:
                 raise ValueError(f"pools must be [P >= {self.num_envs}, {self.ny}, {self.nx}], got {tuple(a.shape)}")
-        self.t["reset_u0"], self.t["reset_v0"], self.t["reset_p0"] = pools
-        self.t["reset_count"] = torch.zeros(self.num_envs, dtype=torch.int32, device=self.device)
-        self.t["final_obs"] = (torch.zeros(self.num_envs, self.ny, self.nx, 2, dtype=self.dtype, device=self.device)
-                               if keep_final_obs else None)
-        self._drop_prepared_call()
+        self._set_auto_reset(dict(zip(("reset_u0", "reset_v0", "reset_p0"), pools)), keep_final_obs)
 
     def disable_auto_reset(self):
-        for k in ("reset_u0", "reset_v0", "reset_p0", "final_obs", "reset_count"):
-            self.t[k] = None
-        self._drop_prepared_call()
+        self._clear_auto_reset(("reset_u0", "reset_v0", "reset_p0"))
 
     def reset(self, u0, v0, p0, mask=None):
         import torch
         cvt = lambda a: torch.as_tensor(a, dtype=self.dtype, device=self.device).expand(self.num_envs, self.ny, self.nx).contiguous()
         u0, v0, p0 = cvt(u0), cvt(v0), cvt(p0)
         if mask is not None:
-            mask = torch.as_tensor(mask, device=self.device).to(torch.uint8).contiguous()
+            mask = self._as_mask(mask)
         # a reset writes the (new) state into the CURRENT observation buffer: untouched instances keep theirs
         self.backend.ns2d_reset(self.params, self.t, u0, v0, p0, mask, self.num_envs)
         return self.t["obs"]
@@ -180,7 +159,10 @@ class NSBatch2D(EngineCheckpoint):
         import torch
         a = torch.as_tensor(action, dtype=self.dtype, device=self.device).reshape(self.num_envs, self.action_dim).contiguous()
         self.t["action"] = a
-        self._next_obs(out_obs)
+        prev = self.t["obs"]
+        if self.interleaved_state:
+            self.t["state_in"] = prev               # the observation just produced is this call's input state
+        self._flip_obs(out_obs, avoid=prev)
         if out_reward is not None:
             self.t["reward"] = out_reward
         if out_terminated is not None:
@@ -192,42 +174,18 @@ class NSBatch2D(EngineCheckpoint):
 
     # ---- batch-of-one face: command in / results out through ONE pinned host allocation ------------------------------
     def enable_host_io(self):
-        """Host-facing mode of a small batch (the single environment): the command, the observation, the reward and the terminated
-        flag live in ONE pinned host allocation mapped into the device's address space -- the kernels read the command from it and
-        write their results into it, so an env-step is the step's launches + ONE stream synchronisation, no copies in either
-        direction.  Needs the velocity state in its own tensors (``interleaved_state=False``: the observation is a pure output).
-        Returns the NumPy views ``{"action", "obs", "reward", "terminated"}``."""
-        import numpy as np
+        """Host-facing mode of the single environment (``EngineCheckpoint._enable_host_io``): the command, the observation, the
+        reward and the terminated flag live in one pinned host allocation.  Needs the velocity state in its own tensors
+        (``interleaved_state=False``: the observation is a pure output).  Returns the NumPy views ``{"action", "obs", "reward",
+        "terminated"}``."""
         import torch
         if self.interleaved_state:
             raise ValueError("host I/O needs the velocity state in its own tensors (interleaved_state=False)")
-        if getattr(self, "_hio", None) is not None:
+        if self._hio is not None:
             return self._hio["np"]
-        B, ny, nx, A = self.num_envs, self.ny, self.nx, self.action_dim
-        w = 8 if self.dtype == torch.float64 else 4
-        sizes = (("action", w * B * A), ("obs", w * B * ny * nx * 2), ("reward", w * B), ("terminated", B))
-        pack = torch.zeros((sum((nb + 7) // 8 * 8 for _, nb in sizes) + 63) // 64 * 64, dtype=torch.uint8,
-                           pin_memory=self.device.type == "cuda")
-        raw, off, tv, nv = pack.numpy(), 0, {}, {}
-        npdt = np.float64 if w == 8 else np.float32
-        shapes = {"action": (B, A), "obs": (B, ny, nx, 2), "reward": (B,)}
-        for k, nb in sizes:
-            if k == "terminated":
-                tv[k], nv[k] = pack[off:off + nb], raw[off:off + nb]
-            else:
-                tv[k] = pack[off:off + nb].view(self.dtype).view(shapes[k])
-                nv[k] = raw[off:off + nb].view(npdt).reshape(shapes[k])
-            off += (nb + 7) // 8 * 8
-        for k in ("action", "obs", "reward", "terminated"):
-            self.t[k] = tv[k]
-        self._obs = [tv["obs"], tv["obs"]]
-        self._hio = {"pack": pack, "np": nv, "call": None}
-        return nv
-
-    def sync_host(self):
-        if self.device.type == "cuda":
-            import torch
-            torch.cuda.current_stream(self.device).synchronize()
+        B, dt_ = self.num_envs, self.dtype
+        return self._enable_host_io([("action", (B, self.action_dim), dt_), ("obs", (B, self.ny, self.nx, 2), dt_),
+                                     ("reward", (B,), dt_), ("terminated", (B,), torch.uint8)], align=8)
 
     def step_host(self):
         """One env-step commanded from the host: the caller has written the command into the ``"action"`` view; launches the step

@@ -10,6 +10,7 @@ import numpy as np
 
 from . import _native as N
 from .checkpoint import EngineCheckpoint
+from .hostio import PackLayout, as_kernel_input
 
 
 class TrafficBatch(EngineCheckpoint):
@@ -30,10 +31,7 @@ class TrafficBatch(EngineCheckpoint):
         self.num_envs = int(num_envs)
         self.device = torch.device(device)
         self.action_dim = 2 if simulation_type == "both" else 1
-        if backend is None:
-            from .backend import default_backend
-            backend = default_backend()
-        self.backend = backend.bind(self) if hasattr(backend, "bind") else backend
+        self._bind_backend(backend)
         P = N.ParamsTraffic()
         P.M, P.control_freq, P.sim, P.limit = self.M, control_freq, N.TRAFFIC_SIM[simulation_type], int(self.limit)
         P.dt, P.dx, P.T, P.vm, P.rm, P.tau = dt, dx, T, v_max, ro_max, tau
@@ -43,7 +41,6 @@ class TrafficBatch(EngineCheckpoint):
         self.profile = torch.as_tensor(np.sin(3 * self.x / X * np.pi) * 0.1 + np.ones(M), dtype=f64, device=dev)
         # everything a host-facing caller reads after a step lives in ONE allocation (hostio.PackLayout): the single environment
         # fetches observation, fields, clock, reward and flags with one device-to-host copy
-        from .hostio import PackLayout
         u8 = torch.uint8
         self.pack_layout = PackLayout([("obs0", (B, 2 * M), f64), ("obs1", (B, 2 * M), f64), ("r", (B, M), f64), ("y", (B, M), f64),
                                        ("time", (B,), f64), ("reward", (B,), f64), ("done", (B,), u8), ("truncated", (B,), u8)])
@@ -62,9 +59,10 @@ class TrafficBatch(EngineCheckpoint):
     def Veq(self, rho):
         return self.vm * (1 - rho / self.rm)
 
-    def _next_obs(self):
-        self._flip ^= 1
-        self.t["obs"] = self._obs[self._flip]
+    @property
+    def obs_segment(self) -> str:
+        """The segment of ``host_pack`` / ``pack_layout`` that holds the current observation."""
+        return "obs1" if self.t["obs"] is self._obs[1] else "obs0"
 
     def set_action_bounds(self, qs_clip):
         import torch
@@ -75,7 +73,7 @@ class TrafficBatch(EngineCheckpoint):
         import torch
         rs = torch.as_tensor(rs, dtype=torch.float64, device=self.device).reshape(self.num_envs).contiguous()
         if mask is not None:
-            mask = torch.as_tensor(mask, device=self.device).to(torch.uint8).contiguous()
+            mask = self._as_mask(mask)
             self.t["rs"] = torch.where(mask.bool(), rs, self.t["rs"]).contiguous()
         else:
             self.t["rs"] = rs
@@ -88,36 +86,21 @@ class TrafficBatch(EngineCheckpoint):
         k-th restart (``rs_pool`` [P]: the reference redraws it in 'outlet-train'); ``t['final_obs']`` keeps the last
         observation of the finished episode."""
         import torch
-        B, dev = self.num_envs, self.device
-        self.t["reset_rs"] = torch.as_tensor(rs_pool, dtype=torch.float64, device=dev).reshape(-1).contiguous()
-        self.t["reset_profile"] = self.profile
-        self.t["reset_count"] = torch.zeros(B, dtype=torch.int32, device=dev)
-        self.t["final_obs"] = torch.zeros(B, 2 * self.M, dtype=torch.float64, device=dev) if keep_final_obs else None
+        pool = torch.as_tensor(rs_pool, dtype=torch.float64, device=self.device).reshape(-1).contiguous()
+        self._set_auto_reset({"reset_rs": pool, "reset_profile": self.profile}, keep_final_obs)
 
     def disable_auto_reset(self):
-        for k in ("reset_rs", "reset_profile", "reset_count", "final_obs"):
-            self.t.pop(k, None)
+        self._clear_auto_reset(("reset_rs", "reset_profile"))
 
     def can_rollout(self) -> bool:
         """``rollout`` needs the register-resident kernel (freeways of up to 64 nodes: the reference's grid has 51)."""
         return self.M <= 64 and hasattr(self.backend, "traffic_rollout")
 
     def policy_fits_rollout(self, policy) -> bool:
-        """Whether ``policy`` (a ``FusedMLP``) can run inside the rollout kernel: 2M inputs, one output per command.  Layers of
-        at most 64 units: weights + 16 observation rows within 160 KB of LDS; a layer of 65 .. 256 units: evaluated by the
-        workgroup's 16 waves together on the matrix cores (bit-identical to ``FusedMLP`` itself), as in the 1D engines."""
-        if not (self.can_rollout() and hasattr(policy, "layers") and hasattr(policy, "_net")):
-            return False
-        dims = [(int(w.shape[1]), int(w.shape[0])) for w, _, _ in policy.layers]
-        D = 2 * self.M
-        if dims[0][0] != D or dims[-1][1] != self.action_dim or any(o > 256 for _, o in dims):
-            return False
-        if any(o > 64 for _, o in dims):
-            stride = lambda w: (w + 63) // 64 * 64 + 4                  # noqa: E731  (pdegym_mlp_tile.h: lds_stride)
-            floats = 16 * (stride((D + 15) // 16 * 16) + 2 * stride(256)) + 32
-        else:
-            floats = sum((((i + 3) // 4) | 1) * 4 * o + 64 for i, o in dims) + 16 * (((D + 3) // 4) * 4 + 128)
-        return 4 * floats <= 160 * 1024
+        """Whether ``policy`` (a ``FusedMLP``) can run inside the rollout kernel (``FusedMLP.fits_rollout``): 2M inputs, one
+        output per command."""
+        fits = getattr(policy, "fits_rollout", None)
+        return fits is not None and self.can_rollout() and fits(2 * self.M, self.action_dim)
 
     def rollout(self, obs, actions, rewards, done, truncated, policy=None, clamp="default", noise=None):
         """T env-steps in ONE launch (include/pdegym.h: pdegym_traffic_rollout): step t takes ``actions[t]`` ([T, B, action_dim]),
@@ -131,15 +114,7 @@ class TrafficBatch(EngineCheckpoint):
         if policy is not None:
             if not self.policy_fits_rollout(policy):
                 raise ValueError("this policy cannot run inside the rollout kernel (see policy_fits_rollout)")
-            import torch
-            if not (obs.is_cuda and torch.cuda.is_current_stream_capturing()):
-                policy.refresh()             # pick up in-place parameter updates (as FusedMLP.forward_into does)
-            net = policy._net(policy.clamp if clamp == "default" else clamp)
-            if noise is not None:
-                import torch
-                if noise.dtype != torch.float32 or tuple(noise.shape) != tuple(actions.shape) or not noise.is_contiguous():
-                    raise ValueError("noise must be a contiguous float32 tensor of the actions' shape")
-                net.noise, net.noise_stride = noise.data_ptr(), int(actions.shape[2])
+            net = policy.rollout_net(obs, actions, clamp, noise)
         self.backend.traffic_rollout(self.params, self.t, obs, actions, rewards, done, truncated, self.num_envs, policy=net)
         self.t["obs"].copy_(obs[-1])
         self.t["reward"].copy_(rewards[-1])
@@ -150,11 +125,10 @@ class TrafficBatch(EngineCheckpoint):
     def step(self, action):
         """action [B] / [B,1] (inlet, outlet) or [B,2] ('both'). Returns (obs [B,2M], reward, done, truncated)."""
         import torch
-        from .hostio import as_kernel_input
         a = as_kernel_input(action, torch.float64, self.device, (self.num_envs, -1))     # (a pinned host tensor is read in place)
         if a.shape[1] > 2 or (self.action_dim == 2 and a.shape[1] != 2):
             raise ValueError(f"action must be [B] / [B, 1] / [B, 2] ('both' needs two columns), got {tuple(a.shape)}")
         self.t["action"] = a.contiguous()       # used in place: the kernel takes the column count as the stride
-        self._next_obs()
+        self._flip_obs()
         self.backend.traffic_step(self.params, self.t, self.num_envs)
         return self.t["obs"], self.t["reward"], self.t["done"], self.t["truncated"]

@@ -10,6 +10,7 @@ import numpy as np
 
 from . import _native as N
 from .checkpoint import EngineCheckpoint
+from .hostio import PackLayout, as_kernel_input
 
 
 class TumorBatch(EngineCheckpoint):
@@ -29,10 +30,7 @@ class TumorBatch(EngineCheckpoint):
         self.device = torch.device(device)
         self.total_dosage = float(total_dosage)
         self.alpha, self.alpha_beta_ratio, self.k = alpha, alpha_beta_ratio, k
-        if backend is None:
-            from .backend import default_backend
-            backend = default_backend()
-        self.backend = backend.bind(self) if hasattr(backend, "bind") else backend
+        self._bind_backend(backend)
         P = N.ParamsTumor()
         P.nx, P.nt = self.nx, self.nt
         P.dt, P.dx, P.dx2 = dt, dx, dx ** 2
@@ -43,7 +41,6 @@ class TumorBatch(EngineCheckpoint):
         self.params = P
         B, dev, f64, i32 = self.num_envs, self.device, torch.float64, torch.int32
         # everything a host-facing caller reads after a day lives in ONE allocation (hostio.PackLayout): one device-to-host copy
-        from .hostio import PackLayout
         u8 = torch.uint8
         self.pack_layout = PackLayout([("u", (B, self.nx), f64), ("out", (B, 4), f64), ("remaining", (B,), f64), ("reward", (B,), f64),
                                        ("time_index", (B,), i32), ("stage", (B,), i32), ("days", (B, 5), i32),
@@ -72,12 +69,11 @@ class TumorBatch(EngineCheckpoint):
     def set_benchmark(self, t_benchmark):
         """Baseline survival days per patient (NaN = not set: every reward is 0, brain_tumor_reward.py:43-47)."""
         import torch
-        if torch.is_tensor(t_benchmark) and t_benchmark.dtype == torch.float64 and t_benchmark.numel() == self.num_envs and \
-                t_benchmark.device.type == "cpu" and self.device.type == "cuda" and t_benchmark.is_pinned():
-            self.t["t_benchmark"] = t_benchmark.reshape(self.num_envs)          # pinned host memory: read in place by the kernel
-            return
-        tb = torch.as_tensor(t_benchmark, dtype=torch.float64, device=self.device)
-        self.t["t_benchmark"] = tb.expand(self.num_envs).contiguous() if tb.dim() == 0 else tb.reshape(self.num_envs).contiguous()
+        if not torch.is_tensor(t_benchmark):
+            t_benchmark = torch.as_tensor(t_benchmark, dtype=torch.float64)
+        if t_benchmark.dim() == 0:
+            t_benchmark = t_benchmark.expand(self.num_envs)
+        self.t["t_benchmark"] = as_kernel_input(t_benchmark, torch.float64, self.device, (self.num_envs,))   # (pinned: in place)
 
     def reset(self, init, mask=None):
         """init [nx] (shared) or [B, nx]; where ``mask`` is given only those patients restart."""
@@ -88,7 +84,7 @@ class TumorBatch(EngineCheckpoint):
         else:
             assert init.shape == (self.nx,)
         if mask is not None:
-            mask = torch.as_tensor(mask, device=self.device).to(torch.uint8).contiguous()
+            mask = self._as_mask(mask)
         self.backend.tumor_reset(self.params, self.t, init, mask, self.num_envs)
         if self.t["history"] is not None:
             sel = slice(None) if mask is None else mask.bool()
@@ -98,9 +94,7 @@ class TumorBatch(EngineCheckpoint):
         return self.t["u"]
 
     def _set_active(self, active):
-        import torch
-        self.t["active"] = None if active is None else \
-            torch.as_tensor(active, device=self.device).to(torch.uint8).reshape(self.num_envs).contiguous()
+        self.t["active"] = None if active is None else self._as_mask(active).reshape(self.num_envs)
 
     def advance(self, mode: int, max_days: int = None, active=None):
         """Run whole stretches of days inside ONE launch (control 0 every day): ``N.TUMOR_RUN_GROWTH`` -- patients in Growth
@@ -116,7 +110,6 @@ class TumorBatch(EngineCheckpoint):
         ``1 - exp(-alpha*BED)`` evaluated by the caller (NumPy bit parity); by default the kernel evaluates it.
         Returns (u [B,nx] -- the live state, updated in place --, reward, terminated, truncated)."""
         import torch
-        from .hostio import as_kernel_input
         self.t["control"] = as_kernel_input(control, torch.float64, self.device, (self.num_envs,))   # (pinned host tensors: in place)
         self.t["kill"] = None if kill is None else as_kernel_input(kill, torch.float64, self.device, (self.num_envs,))
         self._set_active(active)

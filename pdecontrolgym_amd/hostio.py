@@ -5,7 +5,8 @@ until the copy has finished -- a single environment that reads seven scalars tha
 ``HostFetch`` copies any number of device tensors into pinned staging buffers asynchronously and synchronises once; ``PackLayout``
 lays several small tensors out in ONE allocation so that "any number" becomes one copy; ``PinnedInputs`` holds per-call inputs in pinned
 host memory that the kernels read in place (no upload).  (The transport / reaction-diffusion / Navier-Stokes single environments go one
-step further: their kernels also WRITE their results into pinned host memory, ``PDEBatch1D.enable_host_io``.)
+step further: their kernels also WRITE their results into pinned host memory, a ``PackLayout`` allocated with ``host=True`` by the
+engines' ``enable_host_io``.)
 """
 from __future__ import annotations
 
@@ -36,13 +37,15 @@ class HostFetch:
 
 
 class PackLayout:
-    """Several small per-instance tensors as views of ONE allocation, so that a host-facing caller fetches all of them with a
-    single device-to-host copy (``HostFetch``) and names them again on the host side with ``numpy_views``.  Segments start on
-    64-byte boundaries."""
+    """Several small per-instance tensors as views of ONE allocation: in HBM, so that a host-facing caller fetches all of them with
+    a single device-to-host copy (``HostFetch``) and names them again on the host side with ``numpy_views``; or in pinned host
+    memory that the kernels read and write in place (``allocate(host=True)``).  Segments start on ``align``-byte boundaries (64:
+    a cache line each; a smaller value packs the results of a batch-of-one face into as few lines as they need -- every segment
+    must still start on a multiple of its element size)."""
 
     _NP = {"float64": "f8", "float32": "f4", "int32": "i4", "uint8": "u1"}
 
-    def __init__(self, spec):
+    def __init__(self, spec, align: int = 64):
         """spec: [(name, shape, torch dtype)]"""
         self.items, off = [], 0
         for name, shape, dtype in spec:
@@ -51,17 +54,21 @@ class PackLayout:
                 n *= int(d)
             nbytes = n * {"float64": 8, "float32": 4, "int32": 4, "uint8": 1}[str(dtype).replace("torch.", "")]
             self.items.append((name, tuple(int(d) for d in shape), dtype, off, nbytes))
-            off += (nbytes + 63) // 64 * 64
-        self.nbytes = off
+            off += (nbytes + align - 1) // align * align
+        self.nbytes = (off + 63) // 64 * 64
 
-    def allocate(self, device):
-        """(pack, {name: tensor view}) -- zero-filled."""
+    def allocate(self, device, host: bool = False):
+        """(pack, {name: tensor view}) -- zero-filled, on ``device``; ``host=True``: in host memory instead, pinned (mapped into the
+        device's address space) when ``device`` is a GPU."""
         import torch
-        pack = torch.zeros(self.nbytes, dtype=torch.uint8, device=device)
+        if host:
+            pack = torch.zeros(self.nbytes, dtype=torch.uint8, pin_memory=torch.device(device).type == "cuda")
+        else:
+            pack = torch.zeros(self.nbytes, dtype=torch.uint8, device=device)
         return pack, {name: pack[off:off + nb].view(dtype).view(shape) for name, shape, dtype, off, nb in self.items}
 
     def numpy_views(self, raw):
-        """The same names on a uint8 NumPy array holding a copy of the pack."""
+        """The same names on a uint8 NumPy array: a copy of the pack, or the host pack itself (``pack.numpy()``)."""
         return {name: raw[off:off + nb].view(self._NP[str(dtype).replace("torch.", "")]).reshape(shape)
                 for name, shape, dtype, off, nb in self.items}
 

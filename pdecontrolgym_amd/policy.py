@@ -63,6 +63,13 @@ class FusedMLP:
             backend = default_backend()
         self.backend = backend
 
+    def _refresh_unless_capturing(self, x):
+        """Pick up in-place parameter updates before a launch that reads ``x`` -- except while a hipGraph is being captured
+        (``refresh`` launches copies of its own; ``DeviceRollout.run`` refreshes before it replays)."""
+        import torch
+        if not (x.is_cuda and torch.cuda.is_current_stream_capturing()):
+            self.refresh()
+
     @classmethod
     def from_sb3(cls, policy, clamp=None, backend=None):
         """The deterministic actor of a Stable-Baselines3 policy as a ``FusedMLP`` (duck-typed, SB3 itself is not imported):
@@ -111,6 +118,38 @@ class FusedMLP:
             L.in_dim, L.out_dim, L.act = int(w.shape[1]), int(w.shape[0]), act
         return net
 
+    # ---- the policy inside a rollout kernel (pdegym_*_rollout with ``policy`` set: 1D and traffic engines) ----------------------
+    def fits_rollout(self, in_dim: int, out_dim: int) -> bool:
+        """Whether a rollout kernel can evaluate this network on rows of ``in_dim`` values for ``out_dim`` commands (the engines'
+        ``policy_fits_rollout`` ask; having this method is their test for a ``FusedMLP``): those sizes, layers of at most 256
+        units.  Layers of at most 64 units: one neuron per lane, the weights + 16 observation rows within 160 KB of LDS.  A
+        layer of 65 .. 256 units (SB3's 256-256 actors): the 16 waves of a workgroup evaluate the network together on the matrix
+        cores, weights streamed from L2 -- bit-identical to ``pdegym_mlp_forward`` (16 observation rows + the hidden rows within
+        160 KB of LDS: any row the kernels take)."""
+        dims = [(int(w.shape[1]), int(w.shape[0])) for w, _, _ in self.layers]
+        if dims[0][0] != in_dim or dims[-1][1] != out_dim or any(o > 256 for _, o in dims):
+            return False
+        # the budget of csrc/pdegym_policy.h: wide_lds_floats (over pdegym_mlp_tile.h: lds_stride) / lds_floats <= kMaxLdsBytes
+        if any(o > 64 for _, o in dims):
+            stride = lambda w: (w + 63) // 64 * 64 + 4                  # noqa: E731
+            floats = 16 * (stride((in_dim + 15) // 16 * 16) + 2 * stride(256)) + 32
+        else:
+            floats = sum((((i + 3) // 4) | 1) * 4 * o + 64 for i, o in dims) + 16 * (((in_dim + 3) // 4) * 4 + 128)
+        return 4 * floats <= 160 * 1024
+
+    def rollout_net(self, obs, actions, clamp="default", noise=None) -> N.Mlp:
+        """The descriptor for a rollout that reads ``obs`` and writes ``actions`` ([T, B] or [T, B, A]): weights refreshed (unless
+        capturing), ``clamp`` (default: the policy's own), and ``noise`` -- float32, contiguous, the actions' shape -- added to
+        the network output of step t before the clamp."""
+        import torch
+        self._refresh_unless_capturing(obs)
+        net = self._net(self.clamp if clamp == "default" else clamp)
+        if noise is not None:
+            if noise.dtype != torch.float32 or tuple(noise.shape) != tuple(actions.shape) or not noise.is_contiguous():
+                raise ValueError("noise must be a contiguous float32 tensor of the actions' shape")
+            net.noise, net.noise_stride = noise.data_ptr(), (1 if actions.dim() == 2 else int(actions.shape[2]))
+        return net
+
     def forward_into(self, obs, out, clamp="default", noise=None):
         """out[b, :] = net(obs[b, :]); ``obs`` [B, in_dim] (any trailing shape that flattens to in_dim), ``out`` [B, out_dim]
         or [B] when out_dim == 1, on the parameters' device.  float64 observations (traffic, tumour, float64 Navier-Stokes)
@@ -127,8 +166,7 @@ class FusedMLP:
         if y.data_ptr() != out.data_ptr():
             raise ValueError("out must be viewable as [B, out_dim] without a copy")
         import torch
-        if not (x.is_cuda and torch.cuda.is_current_stream_capturing()):
-            self.refresh()
+        self._refresh_unless_capturing(x)
         for t_, name in ((x, "obs"), (y, "out")):
             if t_.dtype not in (torch.float32, torch.float64):
                 raise N.NativeError(f"FusedMLP: {name} must be float32 or float64, got {t_.dtype}")

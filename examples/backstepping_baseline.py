@@ -3,9 +3,10 @@
 The reference runs examples/transportPDE/transport1Dbackstepping.py and examples/reactionDiffusionPDE/reactionDiffusion1DBackstepping.py
 once per episode (one environment, NumPy gains, a Python dot product per step) and averages 50 episodes with random initial
 conditions.  Here every episode is one instance of a batch: the gains of all instances are computed by one kernel launch, the
-control law and the environment step are two launches per env-step, and nothing leaves the device until the rewards are summed.
+control law and the environment step are two launches per env-step -- or, with --one-launch, the whole episode is ONE kernel launch
+with the law evaluated inside it (the same bits) -- and nothing leaves the device until the rewards are summed.
 
-    python examples/backstepping_baseline.py [--episodes 50] [--gamma-spread 0.0] [--order tree]
+    python examples/backstepping_baseline.py [--episodes 50] [--gamma-spread 0.0] [--order tree] [--one-launch]
 
 Prints the mean episode reward per family.  The published means were drawn with other random initial conditions, so the number is
 printed, not compared.
@@ -31,7 +32,7 @@ def chebyshev(x, gamma, amp):
     return (amp * np.cos(np.asarray(gamma)[:, None] * np.arccos(x)[None])).astype(np.float32)
 
 
-def run(kind, episodes, spread, order, seed):
+def run(kind, episodes, spread, order, seed, one_launch=False):
     env_id, T, dt, dx, rate, gamma0, amp, ghost = FAMILIES[kind]
     rng = np.random.default_rng(seed)
     nx = int(round(1 / dx))
@@ -48,7 +49,8 @@ def run(kind, episodes, spread, order, seed):
     controller = BacksteppingController(kind, theta, dx, order=order).attach(venv)
     steps = int(round(T / rate))
     # the scripts hand the raw command to env.step: no action box
-    rollout = DeviceRollout(venv, controller, steps, use_graph=False, action_low=-float("inf"), action_high=float("inf")).run()
+    rollout = DeviceRollout(venv, controller, steps, use_graph=False, action_low=-float("inf"), action_high=float("inf"),
+                            one_launch=True if one_launch else None).run()
     done = (rollout.terminated | rollout.truncated).bool()
     alive = torch.cat([torch.ones_like(done[:1]), ~done[:-1].cumsum(0).bool()])     # steps up to and including the episode's last
     returns = (rollout.rewards.double() * alive).sum(0)
@@ -61,9 +63,10 @@ def main():
     ap.add_argument("--gamma-spread", type=float, default=0.0, help="each instance draws gamma within +- this of the scripts' value")
     ap.add_argument("--order", choices=("tree", "ordered"), default="tree")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--one-launch", action="store_true", help="evaluate the law inside the rollout kernel: one launch per episode")
     args = ap.parse_args()
     for kind in FAMILIES:
-        mean, std = run(kind, args.episodes, args.gamma_spread, args.order, args.seed)
+        mean, std = run(kind, args.episodes, args.gamma_spread, args.order, args.seed, args.one_launch)
         print(f"{kind:10s} backstepping, {args.episodes} episodes: mean episode reward {mean:.2f} (std {std:.2f})")
 
 

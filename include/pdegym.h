@@ -53,7 +53,7 @@
 extern "C" {
 #endif
 
-#define PDEGYM_ABI_VERSION 17
+#define PDEGYM_ABI_VERSION 18
 #define PDEGYM_RING 128          /* slots of the per-instance row-norm ring (look-back is 100 rows) */
 #define PDEGYM_LOOKBACK 100      /* tuned_reward_1d.py:25,40: int(1/0.01) rows */
 #define PDEGYM_MAX_N1D 2048      /* nodes per 1D row kept in registers by the wave-per-instance kernels */
@@ -551,6 +551,27 @@ typedef struct pdegym_backstep {
   int32_t reserved_;
 } pdegym_backstep;
 int pdegym_backstep_control(const pdegym_backstep* c, int32_t B, void* stream);
+
+/* The law INSIDE the one-launch rollout: T x (pdegym_backstep_control into actions[t], then one env-step) as ONE kernel launch, the
+ * row, beta, the norm ring, the sums and the instance's gain row held in registers throughout.  Every output -- obs slots 1 .. T,
+ * actions (WRITTEN: the command after noise and clamp), rewards, terminated, truncated -- and the engine state left behind (time_index,
+ * bsum, ring, norm_now, norm_back, beta, reset_count, final_obs) is BIT-IDENTICAL to that loop of two calls per env-step, in both
+ * orders of addition (the kernels share one copy of the dot product).  prm / buf / ro as for pdegym_*_rollout, in its register-resident
+ * corner only: Dirichlet actuation, full-state sensing, the linear flux, float32 beta and actions (beta_f64 == 0, action_kind ==
+ * PDEGYM_ACTION_F32), no history, the temporal reward horizon, substeps >= 1 and rows of at most 8 slots per lane: 3 <= n <= 512
+ * (transport) / 3 <= n <= 513 (parabolic: node 0 is held apart from the slots); ro->policy must be NULL.  ro->obs_noise /
+ * ro->obs_seen ([T, B, n], optional) shape the LAW's input as they do a policy's: the law of step t reads obs[t] + obs_noise[t], which
+ * obs_seen[t] receives, and the observation slots stay clean.  Everything else takes the two calls.
+ * From `law` the call reads gain0, gain_stride, gain_pool, reset_count, pool_rows, m; len (1 <= len <= min(m, n)), order, scale; noise
+ * -- here [T, B]: row t, instance b at noise[t * B + b] -- clamp, lo, hi.  law->obs, law->out64 and law->out32 must be NULL (the
+ * observation is the rollout's slot t, the command goes to actions[t] as out32 would receive it).  gain_row(b) follows the rule of
+ * pdegym_backstep_control; a restart made INSIDE the launch by the fused auto-reset switches the row before the next command, as the
+ * counter would between two launches.  law->reset_count, when both are given, must be buf->reset_count: controller and plant read the
+ * same counter (with buf->reset_count NULL the counter never moves, in either path). */
+int pdegym_transport_backstep_rollout(const pdegym_params1d* prm, const pdegym_bufs1d* buf, const pdegym_rollout1d* ro,
+                                      const pdegym_backstep* law, int32_t B, void* stream);
+int pdegym_parabolic_backstep_rollout(const pdegym_params1d* prm, const pdegym_bufs1d* buf, const pdegym_rollout1d* ro,
+                                      const pdegym_backstep* law, int32_t B, void* stream);
 
 /* ---- adjoint-optimisation baseline of NavierStokes2D (the model-based row of the reference's NS result table) ----------------
  * examples/NavierStokes/NS2Doptimization.py:83-107 for a whole batch in ONE launch, float64 (the script's arithmetic), on the grids of

@@ -6,6 +6,8 @@ The gain is a function of each instance's theta row (the plant parameter sampled
 row on the device at construction (``solveKernelFunction``), and the control law (``solveControl``: one dot product per instance)
 is one kernel launch per env-step.  ``DeviceRollout(venv, controller, T)`` drives it like a ``FusedMLP`` (control launch, then step
 launch); with ``pool_theta`` the gains follow the fused auto-reset, which redraws beta from a pool at every restart.
+``DeviceRollout(venv, controller.attach(venv), T, one_launch=True)`` evaluates the law INSIDE the one-launch rollout kernel instead
+(``rollout_law``: Dirichlet actuation, rows of up to 512 / 513 nodes): one launch per rollout, the same bits.
 """
 from __future__ import annotations
 
@@ -64,6 +66,7 @@ class BacksteppingController:
                 raise ValueError("pool_theta redraws the gain per instance: theta must be [B, m] as well")
             self.pool_gain = self._gains(pool)
         self._reset_count = None
+        self._core = None       # the engine attach() bound this controller to
 
     def _gains(self, theta):
         import torch
@@ -97,7 +100,42 @@ class BacksteppingController:
             raise ValueError(f"the environment redraws beta from a pool of {rows} rows at every restart and pool_theta was not "
                              "given (0 rows): the gains would be stale after the first restart")
         self._reset_count = count if self.pool_gain is not None else None
+        self._core = core
         return self
+
+    # ---- the law inside the one-launch rollout kernel (pdegym_*_backstep_rollout) --------------------------------------------------------
+    def rollout_gap(self, core):
+        """What keeps this controller out of ``core``'s one-launch rollout, as a sentence -- or None when nothing does (the engines'
+        ``law_rollout_gap`` ask, after their own checks): the law needs the checks of ``attach`` and, with ``pool_theta``, the
+        engine's restart counters."""
+        if self._core is None:
+            return "the controller is not attached to the environment (controller.attach(venv) first)"
+        if self._core is not core:
+            return (f"the {self.kind} controller is attached to another environment than this {getattr(core, 'kind', '?')} one "
+                    "(controller.attach(venv) binds it to the one it drives)")
+        return None
+
+    def rollout_law(self, actions, clamp=None, noise=None):
+        """The ``pdegym_backstep`` descriptor of a rollout that writes its commands into ``actions`` [T, B]: gains (with the pool
+        and the restart counters ``attach`` took), length, order and scale of the attached environment; ``noise`` -- float32,
+        contiguous, the actions' shape -- added to the command of step t before the clamp to ``clamp`` = (lo, hi).  The
+        observation and output pointers stay unset: the rollout's own buffers are used."""
+        import torch
+        from pdecontrolgym_amd import _native as N
+        if self._core is None:
+            raise ValueError("rollout_law needs an attached controller (controller.attach(venv) first)")
+        c = N.Backstep()
+        c.gain0, c.gain_stride, c.m = self.gain.data_ptr(), (0 if self.gain.dim() == 1 else self.gain.stride(0)), self.m
+        if self._reset_count is not None:
+            c.gain_pool, c.pool_rows, c.reset_count = self.pool_gain.data_ptr(), int(self.pool_gain.shape[0]), self._reset_count.data_ptr()
+        c.len, c.order, c.scale = self._length(self._core.n), (N.BACKSTEP_ORDERED if self.order == "ordered" else N.BACKSTEP_TREE), self.scale
+        if noise is not None:
+            if noise.dtype != torch.float32 or tuple(noise.shape) != tuple(actions.shape) or not noise.is_contiguous():
+                raise ValueError("noise must be a contiguous float32 tensor of the actions' shape")
+            c.noise = noise.data_ptr()
+        if clamp is not None:
+            c.clamp, c.lo, c.hi = 1, float(clamp[0]), float(clamp[1])
+        return c
 
     def _length(self, n):
         """Terms of the dot product for rows of n nodes: transport1Dbackstepping.py:33-35 runs over len(u);

@@ -14,7 +14,11 @@ class DeviceRollout:
     torch module, or a ``pdecontrolgym_amd.FusedMLP`` (Linear/Tanh/ReLU stack evaluated, clamped and stored in ONE launch).
     Buffers: ``obs[T+1, B, D]``, ``actions[T, B]`` (``[T, B, action_dim]`` for Navier-Stokes and two-command traffic), ``rewards[T, B]``, ``terminated[T, B]``, ``truncated[T, B]``; with
     ``action_noise=True`` also ``action_noise[T, B]`` (float32), added to the policy output of step t before the clamp.
-    ``one_launch``: see the constructor (1D engines with full-state sensing + a small ``FusedMLP``: the rollout is ONE kernel)."""
+    ``one_launch``: see the constructor (1D engines with full-state sensing + a small ``FusedMLP``: the rollout is ONE kernel).
+    ``one_launch=True`` with an attached ``BacksteppingController`` on a transport / reaction-diffusion environment (Dirichlet
+    actuation, full-state sensing, rows of up to 512 (transport) / 513 (parabolic) nodes): the law runs inside the rollout kernel as
+    well -- one launch per ``run()``, results bit-identical to the default two launches per env-step, and faster at all three
+    measured shapes."""
 
     def __init__(self, venv, policy, n_steps: int, use_graph: bool = True, action_low: float = -1.0, action_high: float = 1.0,
                  action_noise: bool = False, one_launch=None, sensing_noise: bool = False):
@@ -40,7 +44,15 @@ class DeviceRollout:
         # transport / reaction-diffusion (any control / sensing combination), or traffic, and a FusedMLP of <= 256-unit layers: the WHOLE rollout is one
         # kernel launch (pdegym_*_rollout with the policy inside: no kernel boundary between env-steps, none between policy and step).
         # one_launch=None: whenever it applies; True: required; False: T x (policy launch + step launch) as for the others.
+        # A controller with a rollout descriptor (BacksteppingController) inside the launch is opt-in, one_launch=True only:
+        # pdegym_*_backstep_rollout, bit-identical to T x (control launch + step launch); timings: DESIGN.md section 4.7.
+        # one_launch=None keeps the two launches per env-step for it.
         fits = bool(venv.one_launch_fits(policy))
+        if one_launch and not fits and hasattr(policy, "rollout_law"):
+            gap = venv.one_launch_law_gap(policy)
+            if gap is not None:
+                raise ValueError("one_launch=True cannot take this controller into the rollout kernel: " + gap)
+            fits = True
         if one_launch and not fits:
             raise ValueError("one_launch=True needs a transport / reaction-diffusion engine whose state has one home (any control / "
                              "sensing combination, no history, float32 operands) or a traffic engine of <= 64 nodes, and a FusedMLP "

@@ -132,6 +132,8 @@ class BatchedVecEnv(VecEnv):
     #   adopt_rollout_obs(buf)    after a graph replay (PDEVecEnv below)
     #   one_launch_fits(policy)   whether the whole rollout with the policy inside is ONE kernel launch, rollout_one_launch(*buffers,
     #                             policy=, clamp=, noise=[, obs_noise=, obs_seen=]); one_launch_obs_noise: it takes pre-drawn sensing noise
+    #   one_launch_law_fits(law)  the same question for a controller evaluated inside the launch (BacksteppingController: opt-in,
+    #                             DeviceRollout(one_launch=True)); one_launch_law_gap(law): what is missing, or None
     _rollout_state_keys = None
     rollout_action_shape = ()
     one_launch_obs_noise = True
@@ -158,6 +160,12 @@ class BatchedVecEnv(VecEnv):
 
     def one_launch_fits(self, policy):
         return False
+
+    def one_launch_law_gap(self, law):
+        return f"{type(self).__name__} has no rollout kernel with a control law inside"
+
+    def one_launch_law_fits(self, law):
+        return self.one_launch_law_gap(law) is None
 
     def rollout_one_launch(self, *buffers, **kw):
         self.core.rollout(*buffers, **kw)
@@ -521,6 +529,9 @@ class PDEVecEnv1D(PDEVecEnv):
 
     def one_launch_fits(self, policy):
         return self.core.policy_fits_rollout(policy)
+
+    def one_launch_law_gap(self, law):
+        return self.core.law_rollout_gap(law)
 
 
 class NSVecEnv(PDEVecEnv):

@@ -11,7 +11,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "lib", "libpdegym_hip.so")
 
-ABI_VERSION = 17
+ABI_VERSION = 18
 RING = 128
 LOOKBACK = 100
 MAX_N1D = 8192
@@ -34,7 +34,7 @@ EXPORTS = [
     "pdegym_tumor_step", "pdegym_tumor_advance", "pdegym_tumor_reset_masked", "pdegym_mlp_forward",
     "pdegym_transport_rollout", "pdegym_parabolic_rollout", "pdegym_traffic_rollout", "pdegym_debug_set",
     "pdegym_backstep_gain_parabolic", "pdegym_backstep_gain_transport", "pdegym_backstep_control",
-    "pdegym_ns2d_adjoint_f64",
+    "pdegym_ns2d_adjoint_f64", "pdegym_transport_backstep_rollout", "pdegym_parabolic_backstep_rollout",
 ]
 # keys of pdegym_debug_set (test-only dispatch overrides, include/pdegym.h)
 DEBUG_NS_GENERIC, DEBUG_NS_NO_COL, DEBUG_NS_COL_MIN_BATCH, DEBUG_NS_NO_LDS_JACOBI = range(4)
@@ -219,6 +219,9 @@ def load():
         f.restype = C.c_int
     lib.pdegym_backstep_control.argtypes = [C.POINTER(Backstep), C.c_int32, C.c_void_p]
     lib.pdegym_backstep_control.restype = C.c_int
+    for f in (lib.pdegym_transport_backstep_rollout, lib.pdegym_parabolic_backstep_rollout):
+        f.argtypes = [C.POINTER(Params1D), C.POINTER(Bufs1D), C.POINTER(Rollout1D), C.POINTER(Backstep), C.c_int32, C.c_void_p]
+        f.restype = C.c_int
     lib.pdegym_ns2d_adjoint_f64.argtypes = [C.POINTER(ParamsNS2D), C.c_void_p, C.c_int32, C.POINTER(AdjointNS2D), C.c_int32, C.c_void_p]
     lib.pdegym_ns2d_adjoint_f64.restype = C.c_int
     lib.pdegym_debug_set.argtypes = [C.c_int32, C.c_int32]

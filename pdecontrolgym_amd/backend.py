@@ -401,6 +401,28 @@ class HipBackend:
             c.clamp, c.lo, c.hi = 1, float(clamp[0]), float(clamp[1])
         N.check(self.lib.pdegym_backstep_control(C.byref(c), B, N.current_stream_ptr(obs.device)), "pdegym_backstep_control")
 
+    @_on_device_of("obs")
+    def backstep_rollout1d(self, kind: str, P: N.Params1D, T: dict, obs, actions, rewards, terminated, truncated, B: int, law: N.Backstep,
+                           obs_noise=None, obs_seen=None):
+        """T env-steps with the backstepping law inside, in one launch (pdegym_*_backstep_rollout): the buffers of ``rollout1d``
+        (full-state sensing: ``obs`` [T+1, B, n]); ``actions`` is an output.  ``law``: an ``N.Backstep`` descriptor with gains,
+        length, order, scale, ``noise`` [T, B], clamp (``BacksteppingController.rollout_law``; obs / out64 / out32 unset)."""
+        import torch
+        fn = self.lib.pdegym_transport_backstep_rollout if kind == "transport" else self.lib.pdegym_parabolic_backstep_rollout
+        steps = int(actions.shape[0])
+        _check_shapes("backstep rollout", {"obs": (obs, (steps + 1, B, P.n)), "actions": (actions, (steps, B)), "rewards": (rewards, (steps, B)),
+                                           "terminated": (terminated, (steps, B)), "truncated": (truncated, (steps, B)),
+                                           "obs_noise": (obs_noise, (steps, B, P.n), torch.float32),
+                                           "obs_seen": (obs_seen, (steps, B, P.n), torch.float32)})
+        bufs = self._bufs1d({**T, "state_in": None, "u": None, "history": None})
+        ro = N.Rollout1D()
+        ro.T = steps
+        ro.obs, ro.actions, ro.rewards = N.dptr(obs, torch.float32), N.dptr(actions, torch.float32), N.dptr(rewards, torch.float32)
+        ro.terminated, ro.truncated = N.dptr(terminated, torch.uint8), N.dptr(truncated, torch.uint8)
+        ro.obs_noise, ro.obs_seen = N.dptr(obs_noise, torch.float32), N.dptr(obs_seen, torch.float32)
+        N.check(fn(C.byref(P), C.byref(bufs), C.byref(ro), C.byref(law), B, N.current_stream_ptr(obs.device)),
+                f"pdegym_{kind}_backstep_rollout")
+
 
 _default = None
 

@@ -318,6 +318,32 @@ class PDEBatch1D(EngineCheckpoint):
         fits = getattr(policy, "fits_rollout", None)
         return fits is not None and self.can_rollout() and fits(self.obs_dim, 1) and self.n <= 513
 
+    def law_rollout_gap(self, law):
+        """What keeps ``law`` (a ``BacksteppingController``) out of the one-launch rollout kernel with the control law inside
+        (pdegym_*_backstep_rollout), as a sentence; None when it fits: the register-resident corner of ``rollout`` -- Dirichlet
+        actuation, full-state sensing, the linear flux, rows of at most 512 (transport) / 513 (parabolic) nodes -- and a controller attached to this engine
+        (asked of the controller: ``rollout_gap``)."""
+        if not hasattr(law, "rollout_law") or not hasattr(law, "rollout_gap"):
+            return "the policy is not a controller with a rollout descriptor (BacksteppingController.rollout_law)"
+        if not hasattr(self.backend, "backstep_rollout1d"):
+            return "the backend has no backstep_rollout1d"
+        if self.control_type != "Dirchilet":
+            return f"{self.control_type} actuation (the kernel covers Dirichlet actuation; others take the two-launch path)"
+        if self.sensing != N.SENSE_FULL:
+            return "scalar sensing (the law reads the whole row: sensing_loc='full')"
+        if self.flux != "linear":
+            return f"the {self.flux} flux (the law exists for the linear transport term)"
+        most = 513 if self.kind == "parabolic" else 512          # 8 slots per lane (node 0 of a parabolic row is not a slot)
+        if self.n > most:
+            return f"rows of {self.n} nodes (the kernel keeps {self.kind} rows of up to {most} nodes in registers)"
+        if not self.can_rollout():
+            return "the engine cannot roll out in one launch (state with one home: state_in_obs, no history; float32 beta; temporal reward horizon)"
+        return law.rollout_gap(self)
+
+    def law_fits_rollout(self, law) -> bool:
+        """Whether ``rollout(..., policy=law)`` can evaluate the controller inside the launch (``law_rollout_gap`` says why not)."""
+        return self.law_rollout_gap(law) is None
+
     def rollout(self, obs, actions, rewards, terminated, truncated, policy=None, clamp="default", noise=None, obs_noise=None,
                 obs_seen=None):
         """T env-steps in ONE launch (include/pdegym.h: pdegym_*_rollout): step t takes the commands from ``actions[t]`` and
@@ -334,11 +360,27 @@ class PDEBatch1D(EngineCheckpoint):
         own MFMA reduction order: commands -- hence whole trajectories -- are bit-identical to the two-launch loop
         (``forward_into`` + ``step``).  A policy whose layers all have <= 64 units sums each neuron in one fmaf chain instead:
         its commands agree with ``forward_into`` to float32 rounding (rtol ~2e-5), NOT bit for bit, and trajectories drift apart
-        accordingly -- the environment arithmetic is bit-identical to step calls either way (given the same commands)."""
+        accordingly -- the environment arithmetic is bit-identical to step calls either way (given the same commands).
+
+        ``policy`` may also be an attached ``BacksteppingController`` that fits (``law_fits_rollout``): the law is evaluated inside the
+        launch on ``obs[t]`` (+ ``obs_noise[t]``), ``actions[t]`` receives the command after ``noise[t]`` and the clamp (``clamp``:
+        (lo, hi) or None; "default" = none), and everything is bit-identical to ``controller.forward_into`` + ``step`` per env-step,
+        in both summation orders, with gains that follow the restarts the fused auto-reset makes inside the launch."""
         if not self.can_rollout():
             raise ValueError("rollout needs a state with one home (full-state sensing: state_in_obs; no history) and float32 operands")
         self.params.action_kind = N.ACTION_F32
         net = None
+        if hasattr(policy, "rollout_law"):          # a controller: its descriptor travels with the launch (pdegym_*_backstep_rollout)
+            gap = self.law_rollout_gap(policy)
+            if gap is not None:
+                raise ValueError("this controller cannot run inside the rollout kernel: " + gap)
+            law = policy.rollout_law(actions, None if clamp == "default" else clamp, noise)
+            self.backend.backstep_rollout1d(self.kind, self.params, self.t, obs, actions, rewards, terminated, truncated, self.num_envs,
+                                            law, obs_noise=obs_noise, obs_seen=obs_seen)
+            self.t["obs"].copy_(obs[-1])
+            if self.state_in_obs:
+                self.t["u"] = self.t["obs"]
+            return obs, rewards, terminated, truncated
         if policy is not None:
             if not self.policy_fits_rollout(policy):
                 raise ValueError("this policy cannot run inside the rollout kernel (see policy_fits_rollout)")

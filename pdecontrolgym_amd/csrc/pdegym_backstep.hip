@@ -13,18 +13,13 @@
 #include <type_traits>
 
 #include "pdegym.h"
+#include "pdegym_backstep_law.h"
 #include "pdegym_common.h"
 
 namespace {
 
 using namespace pdegym::wave;      // kWave, kWavesPerBlock, lane shifts, wave_sum, lane_value, wave_lds_sync, pool_row
-
-// s + p[0] + p[1] + ... + p[cnt - 1] over the lanes of `p`, added one after the other in that order (cnt wave-uniform, <= 64):
-// the left-to-right chain of a Python loop / the builtin sum.  Result in every lane.
-__device__ __forceinline__ double chain_add(double s, double p, int cnt) {
-  for (int l = 0; l < cnt; ++l) s += lane_value(p, l);
-  return s;
-}
+using pdegym_backstep_law::chain_add;      // the ordered chain: shared with the control law's dot product (pdegym_backstep_law.h)
 
 // ---- parabolic gain: the last row k[m-1][:] of the reference's m x m kernel matrix ------------------------------------------------
 // The reference marches in i: row i+1 from rows i and i-1 at columns j-1, j, j+1 (the shape of the 1D steppers).  Lane l holds the
@@ -125,17 +120,8 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void backstep_control_kernel
   // the row pool_row() named when the counter still read c - 1
   if (A.gain_pool && A.reset_count[inst] > 0) g = A.gain_pool + (size_t)pool_row(A.pool_rows, A.reset_count, inst, B, -1) * A.m;
   const float* o = A.obs + (size_t)inst * A.obs_stride;
-  double s = 0.0;
-  if (ORDERED) {
-    for (int base = 0; base < A.len; base += kWave) {
-      const int i = base + lane;
-      const double p = i < A.len ? g[i] * (double)o[i] : 0.0;
-      s = chain_add(s, p, min(kWave, A.len - base));
-    }
-  } else {
-    for (int i = lane; i < A.len; i += kWave) s += g[i] * (double)o[i];
-    s = wave_sum(s);
-  }
+  // both orders of addition: pdegym_backstep_law.h (the one-launch rollout kernel evaluates the same function)
+  const double s = pdegym_backstep_law::dot<ORDERED>(A.len, lane, [&](int, int i) { return g[i] * (double)o[i]; });
   const double act = s * A.scale;
   if (lane != 0) return;
   if (A.out64) {

@@ -31,7 +31,7 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void step1d_kernel(pdegym_pa
   const int lane = threadIdx.x & (kWave - 1);
   const int inst = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
   if (inst >= B) return;  // wave-uniform
-  step1d_body<EPL, PARABOLIC, NEUMANN, HIST, BURGERS, M64, false, false, FULL, HFAST>(P, Bf, B, inst, lane);
+  step1d_body<EPL, PARABOLIC, NEUMANN, HIST, BURGERS, M64, false, false, FULL, HFAST, true>(P, Bf, B, inst, lane);
 }
 
 // Rows of more than 2048 nodes: the register-resident layout would not fit, so the row ping-pongs between two LDS copies

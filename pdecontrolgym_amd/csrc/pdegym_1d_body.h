@@ -17,9 +17,6 @@ namespace {
 
 using namespace pdegym::wave;      // kWave, kWavesPerBlock, lane shifts, wave_reduce / wave_sum, lane_value, drain_vmem, pool_row
 
-__device__ __forceinline__ float wave_max(float v) {      // callers pass magnitudes: 0 is the identity
-  return wave_reduce(v, [](float a, float b) { return fmaxf(a, b); });
-}
 // max of two magnitudes (sign bit clear) that propagates NaN like np.max: non-negative floats order as their bit patterns,
 // and every NaN pattern lies above +inf.  The Linf reward norms use it (np.linalg.norm(row, ord=inf) of a row holding NaN is NaN).
 __device__ __forceinline__ float mag_max(float a, float b) {
@@ -29,6 +26,9 @@ __device__ __forceinline__ float mag_max(float a, float b) {
 __device__ __forceinline__ float wave_mag_max(float v) {
   return wave_reduce(v, [](float a, float b) { return mag_max(a, b); });
 }
+// The overflow pre-check's name for it (step1d_body, carry_refresh_beta; one v_max_u32 with a DPP operand per stage): a NaN that comes
+// through makes the pre-check's comparison fail, and the wave takes the exact loop.
+__device__ __forceinline__ float wave_max(float v) { return wave_mag_max(v); }
 
 // value of slot s when lane l holds slots [l*EPL, l*EPL+EPL)
 template <int EPL>
@@ -96,6 +96,35 @@ __device__ __forceinline__ void store_slots(float* base, const float (&x)[EPL], 
 #pragma unroll
     for (int e = 0; e < EPL; ++e)
       if (s0 + e < ns) base[s0 + e] = x[e];
+  }
+}
+// The row store of a lane with FOUR slots as write-through (sc1): one dwordx4 per lane, so one instruction of the wave covers 1 KB
+// without gaps and every line it touches leaves the XCD's L2 once, as the store is issued, where a plain store leaves the line dirty
+// until the release at the end of the kernel writes all of them back at once (4.4 MB at B = 4096, nx = 256).  Only this layout: with
+// more slots per lane each dwordx4 of the wave covers 16 of every 32 (or more) bytes and every line goes out several times as a
+// masked write (EPL = 8 measured: WRITE_SIZE of transport_c3 35.2 -> 68.9 MB per step for no gain, profiles/r07_ab_notes.txt), and
+// narrower write-through stores are a fabric write each.  `row` = the row's node 0, the slots start J0 floats in: the byte offset is
+// the instruction's immediate, as in the compiler's own stores.  The compiler does not look inside the statement: the dwordx4 store
+// ends with the two wait states that must separate it from a write of its data registers, and its vmcnt is not in the compiler's
+// books -- which only makes the waits the compiler inserts stricter (the counter is in order); drain_vmem() waits for these stores
+// like for any other.  The guarded dwords of a lane that straddles the row's end stay plain stores.
+typedef float pdegym_f4 __attribute__((ext_vector_type(4)));
+template <int BYTES>
+__device__ __forceinline__ void store_wt(float* p, pdegym_f4 v) {
+  asm volatile("global_store_dwordx4 %0, %1, off offset:%2 sc1\n\ts_nop 1" : : "v"(p), "v"(v), "n"(BYTES) : "memory");
+}
+template <int BYTES>
+__device__ __forceinline__ void store_wt(float* p, float v) {      // (node 0 of a parabolic row: one lane)
+  asm volatile("global_store_dword %0, %1, off offset:%2 sc1" : : "v"(p), "v"(v), "n"(BYTES) : "memory");
+}
+template <int J0>
+__device__ __forceinline__ void store_slots_wt(float* row, const float (&x)[4], int s0, int ns) {
+  if (s0 + 4 <= ns) {
+    store_wt<4 * J0>(row + s0, pdegym_f4{x[0], x[1], x[2], x[3]});
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (s0 + e < ns) row[J0 + s0 + e] = x[e];
   }
 }
 template <int EPL>
@@ -552,10 +581,11 @@ __device__ __forceinline__ void load_row(Row<EPL>& R, float (&beta)[EPL], const 
 // ring loads at the head of the step.  What a step stores is what a caller can see of it afterwards: observation slot t + 1 and
 // row t of the reward / flag arrays always; the per-instance state words that every step would overwrite (norm_now, norm_back,
 // time_index, bsum -- and the ring, kept in registers) only when store_state says this is the launch's last step.
+// STEP_KERNEL (round 7): the caller is step1d_kernel -- one env-step per launch, nothing in the launch reads what the step stored (kObsEarly).
 // HFAST (round 6, with HIST): the fast sub-step loop storing every row into the trajectory buffer (bufs.history must be given; the
 // launcher keeps the NormReward "differential" / "t-horizon" requests on the select form).
 template <int EPL, bool PARABOLIC, bool NEUMANN, bool HIST, bool BURGERS = false, bool M64 = false, bool ROLL = false,
-          bool CARRY = false, bool FULL = false, bool HFAST = false>
+          bool CARRY = false, bool FULL = false, bool HFAST = false, bool STEP_KERNEL = false>
 __device__ __forceinline__ void step1d_body(const pdegym_params1d& P, const pdegym_bufs1d& Bf, const int B, const int inst,
                                             const int lane, const float* command = nullptr, Carry<EPL>* carry = nullptr,
                                             const bool store_state = true) {
@@ -564,6 +594,15 @@ __device__ __forceinline__ void step1d_body(const pdegym_params1d& P, const pdeg
   constexpr bool kFast = !NEUMANN && !M64 && (!HIST || HFAST);
   static_assert(!CARRY || kFast, "the carried state is the float32 Dirichlet rollout path");
   static_assert(!FULL || kFast, "FULL rows: the float32 Dirichlet fast path only");
+  // The fast-path step kernels with four slots per lane (nx = 256: the headline shape; not the carried rollouts, whose launches are
+  // bound by HBM, and not the trajectory mode) with state_in -- the row's only home is obs, which is never the buffer being read --
+  // store the row right after the sub-step loop, beside the norm chain instead of behind it, and write-through (store_slots_wt: why
+  // four slots).  The rare paths that change what obs must hold (exact redo, auto-reset) drain the wave's stores and store again, with
+  // plain stores like every store at the end of the step: write-through pays only together with the early position
+  // (profiles/r07_ab_notes.txt: at the end of the wave it costs 0.37 us at S = 1).  STEP_KERNEL: step1d_kernel alone asks for it -- the
+  // general rollout kernels instantiate this body without CARRY too, and a rollout step may re-read, behind a workgroup-scope fence,
+  // a row that an earlier step stored: not one stored by a statement the compiler does not track.
+  constexpr bool kObsEarly = STEP_KERNEL && kFast && !CARRY && !HFAST && EPL == 4;
   const int n = FULL ? kWave * EPL + J0 : P.n, ns = n - J0, s0 = lane * EPL;
   // state_in given: the row comes from the previous call's observation and goes to obs only (include/pdegym.h)
   const float* urow_in = (Bf.state_in ? Bf.state_in : Bf.u) + (size_t)inst * n;
@@ -647,6 +686,8 @@ __device__ __forceinline__ void step1d_body(const pdegym_params1d& P, const pdeg
     }
   }
   float norm_now;
+  bool obs_early = false;      // wave-uniform: the fast loop's row is already on its way to obs
+  bool obs_final = false;      // ... and it is the row obs must hold unless an auto-reset follows
   if constexpr (kFast) {
     // The fast loop freezes the controlled boundary slot with zero coefficients: x + 0*t keeps every x except -0.0
     // (-0.0 + +0.0 = +0.0), so a commanded boundary value of exactly -0.0 takes the exact loop (wave-uniform test).
@@ -687,9 +728,18 @@ __device__ __forceinline__ void step1d_body(const pdegym_params1d& P, const pdeg
     norm_now = 0.f;
     if (!exact) {
       run_substeps<EPL, PARABOLIC, false, true, HFAST, BURGERS, false, ROLL, RingT, FULL>(R, beta, P, nsub, a, ring, hist, lane);
+      if constexpr (kObsEarly) {
+        if (Bf.state_in && P.sensing == PDEGYM_SENSE_FULL) {
+          float* orow = Bf.obs + (size_t)inst * n;
+          if (PARABOLIC && lane == 0) store_wt<0>(orow, R.bl);
+          store_slots_wt<J0>(orow, R.x, s0, ns);
+          obs_early = true;
+        }
+      }
       norm_now = sqrtf(slots_sumsq<EPL>(R.x, s0, ns) + R.bl * R.bl);
       // inf/NaN somewhere (or a squared overflow): 0*inf may have leaked into a frozen slot -> redo exactly
       exact = !(fabsf(norm_now) <= 3.4028234663852886e38f);
+      obs_final = obs_early && !exact;
       if (exact) {
         if constexpr (CARRY) {
           // the carried input was overwritten: observation slot t holds the row (each lane re-reads the slots it stored),
@@ -821,7 +871,10 @@ __device__ __forceinline__ void step1d_body(const pdegym_params1d& P, const pdeg
       if (PARABOLIC && lane == 0) urow[0] = R.bl;
       store_slots<EPL>(urow + J0, R.x, s0, ns);
     }
-    emit_obs(Bf.obs);
+    if (!obs_final) {
+      if (obs_early) drain_vmem();      // the exact redo's row goes over the fast loop's
+      emit_obs(Bf.obs);
+    }
     if (lane == 0 && store_state) {
       Bf.time_index[inst] = t;
       Bf.bsum[inst] = R.bsum;
@@ -867,6 +920,7 @@ __device__ __forceinline__ void step1d_body(const pdegym_params1d& P, const pdeg
     }
     const float n0 = sqrtf(slots_sumsq<EPL>(R.x, s0, ns) + R.bl * R.bl);
     const float last = node(n - 1);
+    if (obs_early) drain_vmem();        // the pool row goes over the terminal row stored after the fast loop
     emit_obs(Bf.obs);
     if (lane == 0 && store_state) {
       Bf.time_index[inst] = 0;

@@ -19,6 +19,8 @@
  *   pdegym_backstep_gain_transport / _parabolic  replace solveKernelFunction   examples/transportPDE/transport1Dbackstepping.py:22-29,
  *                                                examples/reactionDiffusionPDE/reactionDiffusion1DBackstepping.py:22-35
  *   pdegym_backstep_control replaces solveControl                 transport1Dbackstepping.py:32-36, reactionDiffusion1DBackstepping.py:38-39
+ *   pdegym_traffic_backstep_control replaces bcksController       examples/TrafficPDE1D/Backstepping control.ipynb, cell 5
+ *   pdegym_traffic_backstep_rollout replaces runSingleEpisode's loop around it (same cell)
  *   pdegym_ns2d_adjoint_f64 replaces the backward march and the control read-off of the adjoint-optimisation baseline
  *                                                examples/NavierStokes/NS2Doptimization.py:83-107
  *
@@ -53,7 +55,7 @@
 extern "C" {
 #endif
 
-#define PDEGYM_ABI_VERSION 18
+#define PDEGYM_ABI_VERSION 19
 #define PDEGYM_RING 128          /* slots of the per-instance row-norm ring (look-back is 100 rows) */
 #define PDEGYM_LOOKBACK 100      /* tuned_reward_1d.py:25,40: int(1/0.01) rows */
 #define PDEGYM_MAX_N1D 2048      /* nodes per 1D row kept in registers by the wave-per-instance kernels */
@@ -572,6 +574,47 @@ int pdegym_transport_backstep_rollout(const pdegym_params1d* prm, const pdegym_b
                                       const pdegym_backstep* law, int32_t B, void* stream);
 int pdegym_parabolic_backstep_rollout(const pdegym_params1d* prm, const pdegym_bufs1d* buf, const pdegym_rollout1d* ro,
                                       const pdegym_backstep* law, int32_t B, void* stream);
+
+/* ---- backstepping baseline of TrafficPDE1D (the model-based row of the reference's traffic result table) -------------------------
+ * pdegym_traffic_backstep_control replaces bcksController, examples/TrafficPDE1D/Backstepping control.ipynb cell 5, for a whole batch:
+ *   'inlet'   the constant qs;      'outlet'  q_out;      'both'  (qs, q_out);      the train types are refused (no ps, normalised obs)
+ *   q_out = (qs + rs*Iv) + Iq,  Iv = np.trapz(cv*(v - vs), dx=dx),  Iq = np.trapz(cq*(r*v - qs), dx=dx)
+ * with (r, v) the two halves of the float64 observation row, vs = vm*(1 - rs/rm) and qs = rs*vs formed as the step kernels form them.
+ * The weight rows cv, cq [M] hold NumPy's exp and are formed by the caller on the host, in the notebook's order of operations:
+ *   K = -(1/(gamma*ps))*(-1/tau)*exp(-x/(tau*vs)), Mk = -K, E = exp(x/(vs*tau)), cv = Mk + (l2/l1)*K*E, cq = ((l1 - l2)/l1)*K*E,
+ *   ps = vm/rm*qs/vs, l1 = vs, l2 = vs + rs*(-vm/rm), gamma = 1, x = np.arange(0, X + dx, dx).
+ * The device forms the products at the nodes, the terms t_i = (dx*(p[i+1] + p[i]))/2.0, i < n = M - 1, and adds them in one of two orders: */
+enum {
+  PDEGYM_TRAFFIC_BACKSTEP_TREE = 0,   /* lane l adds t_l, t_{l+64}, ... in ascending order, then the wave reduction: any M, the batch default */
+  PDEGYM_TRAFFIC_BACKSTEP_NUMPY = 1   /* np.add.reduce's order for n <= 128 (n < 8: one chain from 0.0; else eight accumulators a_k = t_k
+                                         taking t_{k+8}, ... over the first n - n%8 terms, ((a0+a1)+(a2+a3))+((a4+a5)+(a6+a7)), then the
+                                         last n%8 terms in turn): commands BIT-IDENTICAL to the notebook's.  M <= 129               */
+};
+#define PDEGYM_TRAFFIC_BACKSTEP_NUMPY_MAX_M 129
+/* The two orders differ by at most 2^-52 * [(n + 2)*(|rs|*sum|tv_i| + sum|tq_i|) + |rs*Iv| + |qs + rs*Iv| + |q_out|]. */
+typedef struct pdegym_traffic_backstep {
+  const double* weights_v;  /* cv: [B, M] rows weight_stride apart, or one shared row with weight_stride = 0 (unused by 'inlet')   */
+  const double* weights_q;  /* cq: the same layout                                                                                */
+  int64_t weight_stride;    /* doubles between the rows of consecutive instances, 0 = shared                                      */
+  int32_t order;            /* PDEGYM_TRAFFIC_BACKSTEP_*                                                                          */
+  int32_t clamp;            /* nonzero: every command is clamped to [lo, hi] (np.clip: a NaN stays NaN)                           */
+  const float* noise;       /* optional float32 [B, commands] (control) / [T, B, commands] (rollout), widened and added first      */
+  int64_t noise_stride;     /* floats between the rows of consecutive instances (>= the number of commands: 1, 'both' 2)          */
+  double lo, hi;
+} pdegym_traffic_backstep;
+/* obs [B, obs_stride >= 2M] float64, rs [B], out [B, out_stride >= commands] float64: out[b, 0] (and out[b, 1] for 'both').
+ * 4 <= M <= PDEGYM_TRAFFIC_MAX_M.  'inlet' reads neither obs nor the weights. */
+int pdegym_traffic_backstep_control(const pdegym_params_traffic* prm, const pdegym_traffic_backstep* law, const double* obs,
+                                    int64_t obs_stride, const double* rs, double* out, int32_t out_stride, int32_t B, void* stream);
+/* The law INSIDE the one-launch rollout (the loop of runSingleEpisode around bcksController, same cell): T x
+ * (pdegym_traffic_backstep_control on observation slot t into actions[t], then pdegym_traffic_step) as ONE launch, 4 <= M <= 64.
+ * prm / buf / ro as for pdegym_traffic_rollout; ro->policy must be NULL, ro->T >= 1, buf->action_stride the number of commands
+ * (1; 2 or 0 for 'both').  Slot 0 of ro->obs is the caller's current observation; actions is WRITTEN (the command after noise and
+ * clamp).  The law reads rs as the plant holds it, also after a restart by the fused auto-reset -- the weight rows do not follow a
+ * restart, so a pool of other densities needs new weights (the Python layer refuses it).  Every output and the state left behind
+ * are BIT-IDENTICAL to that loop of two calls per env-step, in both orders. */
+int pdegym_traffic_backstep_rollout(const pdegym_params_traffic* prm, const pdegym_bufs_traffic* buf, const pdegym_rollout_traffic* ro,
+                                    const pdegym_traffic_backstep* law, int32_t B, void* stream);
 
 /* ---- adjoint-optimisation baseline of NavierStokes2D (the model-based row of the reference's NS result table) ----------------
  * examples/NavierStokes/NS2Doptimization.py:83-107 for a whole batch in ONE launch, float64 (the script's arithmetic), on the grids of

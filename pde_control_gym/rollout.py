@@ -18,7 +18,10 @@ class DeviceRollout:
     ``one_launch=True`` with an attached ``BacksteppingController`` on a transport / reaction-diffusion environment (Dirichlet
     actuation, full-state sensing, rows of up to 512 (transport) / 513 (parabolic) nodes): the law runs inside the rollout kernel as
     well -- one launch per ``run()``, results bit-identical to the default two launches per env-step, and faster at all three
-    measured shapes."""
+    measured shapes.  ``one_launch=True`` also takes an attached ``TrafficBacksteppingController`` on a
+    TrafficPDE1D environment of up to 64 nodes into the traffic rollout kernel: opt-in, results bit-identical to the two launches per
+    env-step (timings: DESIGN.md section 4.9); ``sensing_noise=True`` keeps its two launches (the traffic kernels take no observation
+    noise)."""
 
     def __init__(self, venv, policy, n_steps: int, use_graph: bool = True, action_low: float = -1.0, action_high: float = 1.0,
                  action_noise: bool = False, one_launch=None, sensing_noise: bool = False):

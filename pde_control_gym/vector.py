@@ -715,10 +715,23 @@ class TrafficVecEnv(PDEVecEnv):
     def one_launch_fits(self, policy):
         return self.core.policy_fits_rollout(policy)
 
-    def rollout_one_launch(self, obs, actions, *outputs, noise=None, **kw):
+    def one_launch_law_gap(self, law):
+        return self.core.law_rollout_gap(law)
+
+    def refresh_pool(self, init_pool=None, beta_pool=None):
+        super().refresh_pool(init_pool, beta_pool)
+        self.core.pool_refreshed()
+
+    def rollout_one_launch(self, obs, actions, *outputs, noise=None, policy=None, clamp="default", **kw):
         if actions.dim() == 2:                 # the traffic kernel takes [T, B, action_dim]
             actions, noise = actions.unsqueeze(2), (noise.unsqueeze(2) if noise is not None else None)
-        self.core.rollout(obs, actions, *outputs, noise=noise, **kw)
+        if hasattr(policy, "rollout_law"):     # a controller: its descriptor travels with the launch (pdegym_traffic_backstep_rollout)
+            gap = self.core.law_rollout_gap(policy)
+            if gap is not None:
+                raise ValueError("this controller cannot run inside the rollout kernel: " + gap)
+            law = policy.rollout_law(actions, None if clamp == "default" else clamp, noise)
+            return self.core.rollout(obs, actions, *outputs, law=law, **kw)
+        self.core.rollout(obs, actions, *outputs, policy=policy, clamp=clamp, noise=noise, **kw)
 
 
 _FAMILIES = {"transport": PDEVecEnv1D, "burgers": PDEVecEnv1D, "parabolic": PDEVecEnv1D, "ns2d": NSVecEnv, "traffic": TrafficVecEnv}

@@ -11,7 +11,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "lib", "libpdegym_hip.so")
 
-ABI_VERSION = 18
+ABI_VERSION = 19
 RING = 128
 LOOKBACK = 100
 MAX_N1D = 8192
@@ -35,12 +35,15 @@ EXPORTS = [
     "pdegym_transport_rollout", "pdegym_parabolic_rollout", "pdegym_traffic_rollout", "pdegym_debug_set",
     "pdegym_backstep_gain_parabolic", "pdegym_backstep_gain_transport", "pdegym_backstep_control",
     "pdegym_ns2d_adjoint_f64", "pdegym_transport_backstep_rollout", "pdegym_parabolic_backstep_rollout",
+    "pdegym_traffic_backstep_control", "pdegym_traffic_backstep_rollout",
 ]
 # keys of pdegym_debug_set (test-only dispatch overrides, include/pdegym.h)
 DEBUG_NS_GENERIC, DEBUG_NS_NO_COL, DEBUG_NS_COL_MIN_BATCH, DEBUG_NS_NO_LDS_JACOBI = range(4)
 MLP_MAX_LAYERS, MLP_MAX_WIDTH, MLP_MAX_INPUT = 4, 256, 8192
 MLP_IDENTITY, MLP_TANH, MLP_RELU = 0, 1, 2
 BACKSTEP_TREE, BACKSTEP_ORDERED = 0, 1
+TRAFFIC_BACKSTEP_TREE, TRAFFIC_BACKSTEP_NUMPY = 0, 1
+TRAFFIC_BACKSTEP_NUMPY_MAX_M = 129      # the longest row whose np.trapz sum is un-recursed (128 terms)
 
 
 class Params1D(C.Structure):
@@ -147,6 +150,11 @@ class Backstep(C.Structure):
                 ("clamp", C.c_int32), ("lo", C.c_float), ("hi", C.c_float), ("reserved_", C.c_int32)]
 
 
+class TrafficBackstep(C.Structure):
+    _fields_ = [("weights_v", C.c_void_p), ("weights_q", C.c_void_p), ("weight_stride", C.c_int64), ("order", C.c_int32),
+                ("clamp", C.c_int32), ("noise", C.c_void_p), ("noise_stride", C.c_int64), ("lo", C.c_double), ("hi", C.c_double)]
+
+
 class AdjointNS2D(C.Structure):
     _fields_ = [("T", C.c_int32), ("t0", C.c_int32), ("obs", C.c_void_p), ("a_nom", C.c_void_p), ("ratio", C.c_double),
                 ("width", C.c_double), ("grad", C.c_void_p), ("actions", C.c_void_p), ("lam", C.c_void_p)]
@@ -222,6 +230,12 @@ def load():
     for f in (lib.pdegym_transport_backstep_rollout, lib.pdegym_parabolic_backstep_rollout):
         f.argtypes = [C.POINTER(Params1D), C.POINTER(Bufs1D), C.POINTER(Rollout1D), C.POINTER(Backstep), C.c_int32, C.c_void_p]
         f.restype = C.c_int
+    lib.pdegym_traffic_backstep_control.argtypes = [C.POINTER(ParamsTraffic), C.POINTER(TrafficBackstep), C.c_void_p, C.c_int64, C.c_void_p,
+                                                    C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+    lib.pdegym_traffic_backstep_control.restype = C.c_int
+    lib.pdegym_traffic_backstep_rollout.argtypes = [C.POINTER(ParamsTraffic), C.POINTER(BufsTraffic), C.POINTER(RolloutTraffic),
+                                                    C.POINTER(TrafficBackstep), C.c_int32, C.c_void_p]
+    lib.pdegym_traffic_backstep_rollout.restype = C.c_int
     lib.pdegym_ns2d_adjoint_f64.argtypes = [C.POINTER(ParamsNS2D), C.c_void_p, C.c_int32, C.POINTER(AdjointNS2D), C.c_int32, C.c_void_p]
     lib.pdegym_ns2d_adjoint_f64.restype = C.c_int
     lib.pdegym_debug_set.argtypes = [C.c_int32, C.c_int32]

@@ -295,6 +295,43 @@ class HipBackend:
         N.check(self.lib.pdegym_traffic_rollout(C.byref(P), C.byref(bufs), C.byref(ro), B, N.current_stream_ptr(obs.device)),
                 "pdegym_traffic_rollout")
 
+    @_on_device_of("obs")
+    def traffic_backstep_control(self, P: N.ParamsTraffic, obs, rs, out, law: N.TrafficBackstep):
+        """out[b] = the backstepping command(s) for observation row obs[b] (pdegym_traffic_backstep_control): ``obs`` float64
+        [B, 2M] (row stride = stride(0)), ``rs`` float64 [B], ``out`` float64 [B] / [B, 1] ([B, 2] for 'both'); ``law``: an
+        ``N.TrafficBackstep`` descriptor with the weight rows, the order, ``noise`` [B, commands] and the clamp
+        (what ``TrafficBacksteppingController.forward_into`` builds)."""
+        import torch
+        if obs.dim() != 2 or obs.stride(1) != 1 or obs.dtype != torch.float64 or not obs.is_cuda or obs.shape[1] != 2 * P.M:
+            raise N.NativeError(f"traffic_backstep_control: obs must be a float64 HIP tensor [B, {2 * P.M}] with unit inner stride")
+        B = int(obs.shape[0])
+        ncmd = 2 if P.sim == N.TRAFFIC_SIM["both"] else 1
+        if out.dtype != torch.float64 or out.numel() != B * ncmd or not out.is_contiguous():
+            raise N.NativeError(f"traffic_backstep_control: out must be a contiguous float64 tensor of {B} x {ncmd} commands")
+        if rs.numel() != B:
+            raise N.NativeError(f"traffic_backstep_control: rs must have {B} elements")
+        N.check(self.lib.pdegym_traffic_backstep_control(C.byref(P), C.byref(law), obs.data_ptr(), obs.stride(0), N.dptr(rs, torch.float64),
+                                                         N.dptr(out, torch.float64), ncmd, B, N.current_stream_ptr(obs.device)),
+                "pdegym_traffic_backstep_control")
+
+    @_on_device_of("r")
+    def traffic_backstep_rollout(self, P: N.ParamsTraffic, T: dict, obs, actions, rewards, done, truncated, B: int, law: N.TrafficBackstep):
+        """T env-steps with the backstepping law inside, in one launch (pdegym_traffic_backstep_rollout): the buffers of
+        ``traffic_rollout`` with ``actions`` [T, B, commands] an output; ``law``: an ``N.TrafficBackstep`` descriptor
+        (``TrafficBacksteppingController.rollout_law``; its ``noise`` [T, B, commands])."""
+        import torch
+        steps = int(actions.shape[0])
+        A = 2 if P.sim == N.TRAFFIC_SIM["both"] else 1
+        _check_shapes("backstep rollout", {"obs": (obs, (steps + 1, B, 2 * P.M)), "actions": (actions, (steps, B, A)),
+                                           "rewards": (rewards, (steps, B)), "done": (done, (steps, B)), "truncated": (truncated, (steps, B))})
+        bufs = self._bufs_traffic({**T, "action": actions[0]})
+        ro = N.RolloutTraffic()
+        ro.T = steps
+        ro.obs, ro.actions, ro.rewards = N.dptr(obs, torch.float64), N.dptr(actions, torch.float64), N.dptr(rewards, torch.float64)
+        ro.done, ro.truncated = N.dptr(done, torch.uint8), N.dptr(truncated, torch.uint8)
+        N.check(self.lib.pdegym_traffic_backstep_rollout(C.byref(P), C.byref(bufs), C.byref(ro), C.byref(law), B,
+                                                         N.current_stream_ptr(obs.device)), "pdegym_traffic_backstep_rollout")
+
     @_on_device_of("r")
     def traffic_reset(self, P: N.ParamsTraffic, T: dict, profile, mask, B: int):
         import torch

@@ -54,6 +54,7 @@ class TrafficBatch(EngineCheckpoint):
         }
         self._obs = [pv["obs0"], pv["obs1"]]
         self._flip = 0
+        self.rs_version, self._rs_host = 0, None      # counts the changes of rs and of the reset pool (reset, *_auto_reset, pool_refreshed)
         self.t["obs"] = self._obs[0]
 
     def Veq(self, rho):
@@ -71,12 +72,22 @@ class TrafficBatch(EngineCheckpoint):
     def reset(self, rs, mask=None):
         """rs [B]: steady-state density per instance; where ``mask`` is given only those instances restart."""
         import torch
+        host = None if torch.is_tensor(rs) else np.asarray(rs, dtype=np.float64).reshape(self.num_envs).copy()
         rs = torch.as_tensor(rs, dtype=torch.float64, device=self.device).reshape(self.num_envs).contiguous()
         if mask is not None:
             mask = self._as_mask(mask)
             self.t["rs"] = torch.where(mask.bool(), rs, self.t["rs"]).contiguous()
+            if host is not None and self._rs_host is not None:
+                host = np.where(mask.bool().cpu().numpy(), host, self._rs_host)
+            else:
+                host = None
         else:
             self.t["rs"] = rs
+        # rs_version: what a controller built from the densities compares (TrafficBacksteppingController); a reset that hands over
+        # the densities the engine already holds (every restart of the non-train types) leaves it alone
+        if host is None or self._rs_host is None or not np.array_equal(host, self._rs_host):
+            self.rs_version += 1
+        self._rs_host = host
         self.backend.traffic_reset(self.params, self.t, self.profile, mask, self.num_envs)
         return self.t["obs"]
 
@@ -88,9 +99,15 @@ class TrafficBatch(EngineCheckpoint):
         import torch
         pool = torch.as_tensor(rs_pool, dtype=torch.float64, device=self.device).reshape(-1).contiguous()
         self._set_auto_reset({"reset_rs": pool, "reset_profile": self.profile}, keep_final_obs)
+        self.rs_version += 1
+
+    def pool_refreshed(self):
+        """The caller rewrote ``t['reset_rs']`` in place: the densities of coming episodes may have changed."""
+        self.rs_version += 1
 
     def disable_auto_reset(self):
         self._clear_auto_reset(("reset_rs", "reset_profile"))
+        self.rs_version += 1
 
     def can_rollout(self) -> bool:
         """``rollout`` needs the register-resident kernel (freeways of up to 64 nodes: the reference's grid has 51)."""
@@ -102,20 +119,37 @@ class TrafficBatch(EngineCheckpoint):
         fits = getattr(policy, "fits_rollout", None)
         return fits is not None and self.can_rollout() and fits(2 * self.M, self.action_dim)
 
-    def rollout(self, obs, actions, rewards, done, truncated, policy=None, clamp="default", noise=None):
+    def law_rollout_gap(self, controller):
+        """What keeps ``controller`` (a ``TrafficBacksteppingController``) out of the one-launch rollout kernel with the control
+        law inside (pdegym_traffic_backstep_rollout), as a sentence; None when it fits: freeways of at most 64 nodes and a
+        controller attached to this engine (asked of the controller: ``rollout_gap``)."""
+        if not hasattr(controller, "rollout_law") or not hasattr(controller, "rollout_gap"):
+            return "the policy is not a controller with a rollout descriptor (TrafficBacksteppingController.rollout_law)"
+        if not hasattr(self.backend, "traffic_backstep_rollout"):
+            return "the backend has no traffic_backstep_rollout"
+        if self.M > 64:
+            return f"freeways of {self.M} nodes (the kernel keeps freeways of up to 64 nodes in registers)"
+        return controller.rollout_gap(self)
+
+    def rollout(self, obs, actions, rewards, done, truncated, policy=None, clamp="default", noise=None, law=None):
         """T env-steps in ONE launch (include/pdegym.h: pdegym_traffic_rollout): step t takes ``actions[t]`` ([T, B, action_dim]),
         writes ``obs[t + 1]`` ([T+1, B, 2M]), ``rewards[t]``, ``done[t]``, ``truncated[t]`` -- bit-identical to T ``step`` calls.
         With ``policy`` (a ``FusedMLP``) the commands are computed inside the launch from ``obs[t]`` (``obs[0]`` = the current
         observation, supplied by the caller) and written to ``actions``; ``noise`` [T, B, action_dim] float32 is added before
-        the clamp.  The engine's own observation / reward / flag tensors receive the values of the last step."""
+        the clamp.  With ``law`` (an ``N.TrafficBackstep`` descriptor: ``TrafficBacksteppingController.rollout_law``) the
+        backstepping law forms the commands inside the launch instead (pdegym_traffic_backstep_rollout), bit-identical to control
+        launch + ``step`` per env-step.  The engine's own observation / reward / flag tensors receive the values of the last step."""
         if not self.can_rollout():
             raise ValueError("rollout needs freeways of at most 64 nodes")
-        net = None
-        if policy is not None:
-            if not self.policy_fits_rollout(policy):
-                raise ValueError("this policy cannot run inside the rollout kernel (see policy_fits_rollout)")
-            net = policy.rollout_net(obs, actions, clamp, noise)
-        self.backend.traffic_rollout(self.params, self.t, obs, actions, rewards, done, truncated, self.num_envs, policy=net)
+        if law is not None and policy is not None:
+            raise ValueError("rollout takes a policy or a law, not both")
+        if policy is not None and not self.policy_fits_rollout(policy):
+            raise ValueError("this policy cannot run inside the rollout kernel (see policy_fits_rollout)")
+        if law is not None:
+            self.backend.traffic_backstep_rollout(self.params, self.t, obs, actions, rewards, done, truncated, self.num_envs, law)
+        else:
+            net = policy.rollout_net(obs, actions, clamp, noise) if policy is not None else None
+            self.backend.traffic_rollout(self.params, self.t, obs, actions, rewards, done, truncated, self.num_envs, policy=net)
         self.t["obs"].copy_(obs[-1])
         self.t["reward"].copy_(rewards[-1])
         self.t["done"].copy_(done[-1])

@@ -18,6 +18,28 @@
 //       transport  environments1d/hyperbolic.py:143-155
 //       parabolic  environments1d/parabolic.py:138-150
 //       reward     rewards/tuned_reward_1d.py:25-40 (streaming form, see docs/HISTORY.md section 3.3)
+#ifdef PDEGYM_HEAD_STAMPS
+// Diagnostic build (tools/head_stamps.py; 1 = the kernels as launched, 2 = every launch through step1d_kernel): three 100 MHz
+// real-time stamps per wave -- 0 at wave entry, 1 when the head's pointers are in SGPRs, 2 when the row, beta and the per-instance
+// words have arrived -- parked in LDS by lane 0 (no store joins the vector-memory queue the head waits on) and copied out as the
+// wave ends.  Stamp 2 waits for all of the wave's outstanding loads first.
+#include <hip/hip_runtime.h>
+__shared__ unsigned long long pdegym_stamp_lds[4][3];
+__device__ unsigned long long pdegym_head_stamp_buf[3 * 65536];
+#define PDEGYM_HEAD_STAMP(k)                                                      \
+  do {                                                                            \
+    if ((k) == 2) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");     \
+    const unsigned long long stamp_ = __builtin_amdgcn_s_memrealtime();           \
+    if ((threadIdx.x & 63) == 0) pdegym_stamp_lds[threadIdx.x >> 6][k] = stamp_;  \
+  } while (0)
+#define PDEGYM_HEAD_STAMPS_OUT(inst)                                                                             \
+  do {                                                                                                           \
+    if ((threadIdx.x & 63) == 0 && (inst) < 65536)                                                               \
+      for (int k_ = 0; k_ < 3; ++k_) pdegym_head_stamp_buf[3 * (inst) + k_] = pdegym_stamp_lds[threadIdx.x >> 6][k_]; \
+  } while (0)
+#else
+#define PDEGYM_HEAD_STAMPS_OUT(inst)
+#endif
 #include "pdegym_1d_body.h"
 
 namespace {
@@ -30,8 +52,51 @@ template <int EPL, bool PARABOLIC, bool NEUMANN, bool HIST, bool BURGERS = false
 __global__ __launch_bounds__(kWave* kWavesPerBlock) void step1d_kernel(pdegym_params1d P, pdegym_bufs1d Bf, int B) {
   const int lane = threadIdx.x & (kWave - 1);
   const int inst = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+  PDEGYM_HEAD_STAMP(0);
   if (inst >= B) return;  // wave-uniform
+#ifdef PDEGYM_HEAD_STAMPS
+  asm volatile("" : : "s"(Bf.u), "s"(Bf.state_in), "s"(Bf.beta), "s"(Bf.beta_stride), "s"(Bf.time_index), "s"(Bf.action), "s"(Bf.bsum),
+               "s"(Bf.ring) : "memory");
+#endif
+  PDEGYM_HEAD_STAMP(1);
   step1d_body<EPL, PARABOLIC, NEUMANN, HIST, BURGERS, M64, false, false, FULL, HFAST, true>(P, Bf, B, inst, lane);
+  PDEGYM_HEAD_STAMPS_OUT(inst);
+}
+
+// The head of the fast-path launch (round 8).  What a wave needs before its first vector load leaves -- the input row's base, beta and
+// its stride, the per-instance words, the batch size -- are the kernel's LEADING parameters: 14 dwords, the first 56 bytes of the
+// argument block, so one scalar fetch of one cache line stands in front of the loads where step1d_kernel has two dependent ones on
+// two lines (B at the block's end, then the pointers in the middle of pdegym_bufs1d).  The structs follow by value as in
+// step1d_kernel and the body runs on a copy of the bufs whose fields are overwritten with the leading values, so the compiler drops
+// the struct's loads of them.  beta_stride travels as 32 bits (launch_epl keeps wider strides on step1d_kernel).  The unit is built
+// with kernel-argument preloading (build.py: FILE_OPTS), which hands exactly these 14 dwords to the wave in SGPRs at launch: then
+// not even that fetch stands in front of the loads (C2 15.59 -> 15.22 us, S = 1 4.52 -> 4.15 us: profiles/r08_ab_notes.txt).
+struct HeadArgs {};      // names the overload: step1d_kernel<HeadArgs, ...> is the fast path with leading head arguments
+template <typename LEAD, int EPL, bool PARABOLIC, bool BURGERS, bool FULL>
+__global__ __launch_bounds__(kWave* kWavesPerBlock) void step1d_kernel(const float* row_in, const void* beta, int32_t* time_index,
+                                                                             const void* action, double* bsum, float* ring,
+                                                                             int beta_stride, int B, pdegym_params1d P, pdegym_bufs1d Bf) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int inst = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+  PDEGYM_HEAD_STAMP(0);
+  if (inst >= B) return;  // wave-uniform
+#ifdef PDEGYM_HEAD_STAMPS
+  asm volatile("" : : "s"(row_in), "s"(beta), "s"(beta_stride), "s"(time_index), "s"(action), "s"(bsum), "s"(ring) : "memory");
+#endif
+  PDEGYM_HEAD_STAMP(1);
+  __builtin_assume(row_in != nullptr);
+  pdegym_bufs1d L = Bf;
+  const bool in_obs = Bf.state_in != nullptr;      // (which of the two the row came from: only the stores at the end ask)
+  L.state_in = in_obs ? row_in : nullptr;
+  L.u = in_obs ? Bf.u : const_cast<float*>(row_in);
+  L.beta = beta;
+  L.beta_stride = beta_stride;
+  L.time_index = time_index;
+  L.action = action;
+  L.bsum = bsum;
+  L.ring = ring;
+  step1d_body<EPL, PARABOLIC, false, false, BURGERS, false, false, false, FULL, false, true>(P, L, B, inst, lane);
+  PDEGYM_HEAD_STAMPS_OUT(inst);
 }
 
 // Rows of more than 2048 nodes: the register-resident layout would not fit, so the row ping-pongs between two LDS copies
@@ -333,7 +398,19 @@ __global__ __launch_bounds__(256) void reset_history_kernel(pdegym_params1d P, f
     h[q] = (q < (size_t)P.n) ? src[q] : 0.f;
 }
 
-__global__ __launch_bounds__(kWave* kWavesPerBlock) void rownorm2_kernel(const float* rows, float* out, int n, int B) {
+// (The unit is compiled with kernel-argument preloading, which takes leading scalar / pointer parameters -- build.py.  Only the head
+// of step1d_kernel<HeadArgs, ...> is meant: the two small kernels below take their arguments as one structure of several members, which is
+// not preloaded (a structure of one pointer is): the same instructions as with the flat list, rownorm2_kernel with its two argument
+// fetches scheduled apart.)
+struct RowNorm2Args {
+  const float* rows;
+  float* out;
+  int n, B;
+};
+__global__ __launch_bounds__(kWave* kWavesPerBlock) void rownorm2_kernel(RowNorm2Args A) {
+  const float* rows = A.rows;
+  float* out = A.out;
+  const int n = A.n, B = A.B;
   const int lane = threadIdx.x & (kWave - 1);
   const int inst = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
   if (inst >= B) return;
@@ -344,7 +421,19 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void rownorm2_kernel(const f
   if (lane == 0) out[inst] = sqrtf(ss);
 }
 
-__global__ void selftest_quotient_kernel(const float* a, float dx, double rdx, unsigned int* mismatches, int n) {
+struct SelftestQuotientArgs {
+  const float* a;
+  float dx;
+  double rdx;
+  unsigned int* mismatches;
+  int n;
+};
+__global__ void selftest_quotient_kernel(SelftestQuotientArgs A) {
+  const float* a = A.a;
+  const float dx = A.dx;
+  const double rdx = A.rdx;
+  unsigned int* mismatches = A.mismatches;
+  const int n = A.n;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
     const float x = a[i];
     const float q_fast = (float)((double)x * rdx);
@@ -377,7 +466,22 @@ int launch_epl(const pdegym_params1d& P, const pdegym_bufs1d& Bf, int B, hipStre
       hipLaunchKernelGGL((step1d_kernel<EPL, PARABOLIC, false, true, BURGERS>), grid, block, lds, st, P, Bf, B);
   } else {
     constexpr bool kHasFull = EPL == 1 || EPL == 2 || EPL == 4 || EPL == 8;      // rows of 64 / 128 / 256 / 512 slots
-    if (kHasFull && P.n - (PARABOLIC ? 1 : 0) == kWave * EPL)
+    const bool full = kHasFull && P.n - (PARABOLIC ? 1 : 0) == kWave * EPL;
+#if defined(PDEGYM_HEAD_STAMPS) && PDEGYM_HEAD_STAMPS == 2
+    constexpr bool kHead = false;
+#else
+    constexpr bool kHead = true;
+#endif
+    if (kHead && Bf.beta_stride >= 0 && Bf.beta_stride <= INT32_MAX) {      // step1d_kernel<HeadArgs, ...>: the head's arguments lead
+      const float* row_in = Bf.state_in ? Bf.state_in : Bf.u;
+      const int bstride = (int)Bf.beta_stride;
+      if (full)
+        hipLaunchKernelGGL((step1d_kernel<HeadArgs, EPL, PARABOLIC, BURGERS, kHasFull>), grid, block, lds, st, row_in, Bf.beta, Bf.time_index,
+                           Bf.action, Bf.bsum, Bf.ring, bstride, B, P, Bf);
+      else
+        hipLaunchKernelGGL((step1d_kernel<HeadArgs, EPL, PARABOLIC, BURGERS, false>), grid, block, lds, st, row_in, Bf.beta, Bf.time_index,
+                           Bf.action, Bf.bsum, Bf.ring, bstride, B, P, Bf);
+    } else if (full)
       hipLaunchKernelGGL((step1d_kernel<EPL, PARABOLIC, false, false, BURGERS, false, kHasFull>), grid, block, lds, st, P, Bf, B);
     else
       hipLaunchKernelGGL((step1d_kernel<EPL, PARABOLIC, false, false, BURGERS>), grid, block, lds, st, P, Bf, B);
@@ -486,7 +590,7 @@ int pdegym_reset1d_masked(const pdegym_params1d* prm, const pdegym_bufs1d* buf, 
 int pdegym_selftest_quotient(const float* a, float dx, double rdx, uint32_t* mismatches, int32_t n, void* stream) {
   if (!a || !mismatches) return pdegym::fail(-1, "null pointer");
   if (n <= 0) return 0;
-  hipLaunchKernelGGL(selftest_quotient_kernel, dim3(1024), dim3(256), 0, (hipStream_t)stream, a, dx, rdx, mismatches, n);
+  hipLaunchKernelGGL(selftest_quotient_kernel, dim3(1024), dim3(256), 0, (hipStream_t)stream, SelftestQuotientArgs{a, dx, rdx, mismatches, n});
   return pdegym::check_launch("selftest_quotient");
 }
 
@@ -494,8 +598,14 @@ int pdegym_rownorm2_f32(const float* rows, float* out, int32_t n, int32_t B, voi
   if (!rows || !out) return pdegym::fail(-1, "null pointer");
   if (B <= 0) return 0;
   const dim3 grid((B + kWavesPerBlock - 1) / kWavesPerBlock), block(kWave * kWavesPerBlock);
-  hipLaunchKernelGGL(rownorm2_kernel, grid, block, 0, (hipStream_t)stream, rows, out, n, B);
+  hipLaunchKernelGGL(rownorm2_kernel, grid, block, 0, (hipStream_t)stream, RowNorm2Args{rows, out, n, B});
   return pdegym::check_launch("rownorm2");
 }
+
+#ifdef PDEGYM_HEAD_STAMPS
+int pdegym_head_stamps_read(unsigned long long* out, int32_t waves) {      // diagnostic build only: not part of include/pdegym.h
+  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(pdegym_head_stamp_buf), (size_t)waves * 3 * sizeof(unsigned long long));
+}
+#endif
 
 }  // extern "C"

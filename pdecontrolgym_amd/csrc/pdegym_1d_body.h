@@ -13,6 +13,12 @@
 #include "pdegym.h"
 #include "pdegym_common.h"
 
+// Hook of the launch-head diagnostic (tools/head_stamps.py builds pdegym_1d.hip with PDEGYM_HEAD_STAMPS into a library of its own,
+// never the shipped one): empty in every other build, so no stamp executes in a product kernel.
+#ifndef PDEGYM_HEAD_STAMP
+#define PDEGYM_HEAD_STAMP(k)
+#endif
+
 namespace {
 
 using namespace pdegym::wave;      // kWave, kWavesPerBlock, lane shifts, wave_reduce / wave_sum, lane_value, drain_vmem, pool_row
@@ -685,6 +691,7 @@ __device__ __forceinline__ void step1d_body(const pdegym_params1d& P, const pdeg
       ring.put(t_in & (PDEGYM_RING - 1), nk0, lane);
     }
   }
+  PDEGYM_HEAD_STAMP(2);      // (diagnostic build only: the row, beta and the per-instance words have arrived)
   float norm_now;
   bool obs_early = false;      // wave-uniform: the fast loop's row is already on its way to obs
   bool obs_final = false;      // ... and it is the row obs must hold unless an auto-reset follows

@@ -55,7 +55,7 @@
 extern "C" {
 #endif
 
-#define PDEGYM_ABI_VERSION 19
+#define PDEGYM_ABI_VERSION 20
 #define PDEGYM_RING 128          /* slots of the per-instance row-norm ring (look-back is 100 rows) */
 #define PDEGYM_LOOKBACK 100      /* tuned_reward_1d.py:25,40: int(1/0.01) rows */
 #define PDEGYM_MAX_N1D 2048      /* nodes per 1D row kept in registers by the wave-per-instance kernels */
@@ -472,6 +472,65 @@ int pdegym_tumor_advance(const pdegym_params_tumor* prm, const pdegym_bufs_tumor
  * remaining = total_dosage, days = (0,0,0,0,-1). */
 int pdegym_tumor_reset_masked(const pdegym_params_tumor* prm, const pdegym_bufs_tumor* buf, const double* init,
                               int64_t init_stride, const uint8_t* mask, int32_t B, void* stream);
+
+/* ---- TherapyWrapper(BrainTumor1D) for every patient: one wrapper step, or T of them with the policy inside, in ONE launch
+ * (brain_tumor_env.py:385-505; the notebook's PPO("MlpPolicy", TherapyWrapper(gym.make("PDEControlGym-BrainTumor1D")))).
+ * The wrapper's own state, per patient; in/out arrays are read once and written once per launch.                           */
+typedef struct pdegym_wrap_tumor {
+  int32_t weekends;                     /* nonzero: two untreated days after five consecutive treatment days      :458-472 */
+  int32_t reserved_;
+  const double* init;                   /* initial row(s) a finished patient restarts from                        :409-428 */
+  int64_t init_stride;                  /* doubles between the rows of consecutive patients: 0 = one shared [nx] row, nx = [B, nx] */
+  int32_t* consecutive;                 /* [B] in/out consecutive treatment days (used with weekends; 0 after a restart)   */
+  int64_t* treatment_calls;             /* [B] in/out Therapy-stage wrapper steps                                          */
+  int64_t* soft_constraint_violations;  /* [B] in/out Therapy-stage wrapper steps whose reward was negative                */
+  double* final_obs;                    /* [B, nx] or NULL: the last row of an episode that ended in this launch (rows of
+                                           other patients are left untouched)                                              */
+  double* obs;                          /* pdegym_tumor_therapy_step only: [B, nx] receives the returned observation, or NULL:
+                                           the observation is buf->u (not with weekends)                                   */
+} pdegym_wrap_tumor;
+
+/* One wrapper step (TherapyWrapper.step, brain_tumor_env.py:385-505) of every patient in one launch, per patient in this order:
+ *  1. stage Post-Therapy: days with control 0 until terminated or truncated; reward / flags / out of the last simulated day.
+ *  2. stage Therapy: one day with buf->control[b] (the kill fraction is evaluated in the kernel: buf->kill is ignored, as are
+ *     buf->active and the launch's days are not recorded: history / t1_log must be NULL); treatment_calls += 1,
+ *     soft_constraint_violations += (reward < 0).  With weekends: consecutive = control > 0 ? consecutive + 1 : 0; if it reaches 5 and
+ *     the day did not end the episode, consecutive = 0 and two more days with control 0 follow (each as pdegym_tumor_step: none once
+ *     time_index has reached nt-1); the state, the day counters and out keep them, reward and flags stay the treatment day's.
+ *  3. terminated | truncated: the live row goes to final_obs, the patient restarts from init (pdegym_tumor_reset_masked),
+ *     consecutive = 0, and the growth stage runs until the stage changes or the episode ends (PDEGYM_TUMOR_RUN_GROWTH).
+ *  4. the observation is the live row -- for a patient that took weekend days and is not finished: the treatment day's row.
+ * A patient found in Growth (its growth run hit the time limit) is outside the wrapper's contract: reward 0, no flag, state
+ * untouched.  A patient past its last day (time_index >= nt-1) simulates nothing: Therapy reports reward 0 and no flag, Post-Therapy
+ * reports buf->reward / terminated / truncated as it found them.
+ * buf->reward / terminated / truncated receive the step's reported values (before the restart), buf->out the last simulated day's.
+ * Bit-identical to the launches TumorVecEnv.step_tensor composes the step from.                                                  */
+int pdegym_tumor_therapy_step(const pdegym_params_tumor* prm, const pdegym_bufs_tumor* buf, const pdegym_wrap_tumor* wrap, int32_t B,
+                              void* stream);
+
+/* T wrapper steps (brain_tumor_env.py:385-505, the loop SB3 runs around TherapyWrapper.step) in ONE launch: step t takes the command
+ * from actions row t and writes observation slot t + 1, rewards / terminated / truncated row t; the state, the wrapper's counters
+ * and the engine's [B] outputs are read once and written back at the end (reward / terminated / truncated: the last step's;
+ * buf->control and wrap->obs are ignored).  Bit-identical to T pdegym_tumor_therapy_step calls.  With a policy (HOST pointer;
+ * nx inputs, one output; layers of <= 256 units -- more than 64: evaluated cooperatively with pdegym_mlp_forward's MFMA reduction,
+ * bit-identical to it, see pdegym_rollout1d.policy) the command of step t is computed inside the launch from observation slot t
+ * (slot 0 = the caller's current observation) rounded to float32, plus noise [T, B] (row stride noise_stride), clamped, widened
+ * and stored to actions -- the contract of pdegym_rollout_traffic.policy.  The policy's LDS plus two float64 rows for each of the
+ * workgroup's 16 patients must fit into 160 KB (nx = 201: a 64-64 actor and a 256-256 actor both fit); history / t1_log recording
+ * is refused.                                                                                                                     */
+typedef struct pdegym_rollout_tumor {
+  int32_t T;
+  int32_t reserved_;
+  double* obs;              /* [T + 1, B, nx]  slot 0 is read only by a policy; slots 1 .. T are written        */
+  double* actions;          /* [T, B]  read, or written when a policy is given                                  */
+  double* rewards;          /* [T, B]                                                                           */
+  uint8_t* terminated;      /* [T, B]                                                                           */
+  uint8_t* truncated;       /* [T, B]                                                                           */
+  const struct pdegym_mlp_s* policy;
+} pdegym_rollout_tumor;
+
+int pdegym_tumor_rollout(const pdegym_params_tumor* prm, const pdegym_bufs_tumor* buf, const pdegym_wrap_tumor* wrap,
+                         const pdegym_rollout_tumor* ro, int32_t B, void* stream);
 
 /* ---- policy network on the device (the caller of env.step inside an on-device rollout) ------------------------------
  * The reference evaluates an SB3 "MlpPolicy" (two hidden layers of 64 tanh units by default) between two env.step calls:

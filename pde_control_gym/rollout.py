@@ -21,7 +21,9 @@ class DeviceRollout:
     measured shapes.  ``one_launch=True`` also takes an attached ``TrafficBacksteppingController`` on a
     TrafficPDE1D environment of up to 64 nodes into the traffic rollout kernel: opt-in, results bit-identical to the two launches per
     env-step (timings: DESIGN.md section 4.9); ``sensing_noise=True`` keeps its two launches (the traffic kernels take no observation
-    noise)."""
+    noise).  ``one_launch=True`` on a BrainTumor1D environment (``TumorVecEnv``) runs the T ``TherapyWrapper`` steps -- treatment
+    days, weekend days, post-therapy and growth runs, restarts -- and a ``FusedMLP`` that fits, or commands given ahead
+    (``policy=None``, fill ``ro.actions``), in one launch: opt-in, bit-identical to the default path."""
 
     def __init__(self, venv, policy, n_steps: int, use_graph: bool = True, action_low: float = -1.0, action_high: float = 1.0,
                  action_noise: bool = False, one_launch=None, sensing_noise: bool = False):
@@ -55,6 +57,14 @@ class DeviceRollout:
             gap = venv.one_launch_law_gap(policy)
             if gap is not None:
                 raise ValueError("one_launch=True cannot take this controller into the rollout kernel: " + gap)
+            fits = True
+        # BrainTumor1D (TumorVecEnv): the wrapper steps and the policy inside pdegym_tumor_rollout, opt-in like the control laws --
+        # one_launch=True with a FusedMLP that fits or with policy=None (commands given ahead in ``actions``); one_launch=None keeps
+        # the launches of step_tensor.  Bit-identical to them; timings: DESIGN.md section 4.10.
+        if one_launch and not fits and getattr(venv, "one_launch_opt_in", False):
+            gap = venv.one_launch_gap(policy)
+            if gap is not None:
+                raise ValueError("one_launch=True cannot take this rollout into the rollout kernel: " + gap)
             fits = True
         if one_launch and not fits:
             raise ValueError("one_launch=True needs a transport / reaction-diffusion engine whose state has one home (any control / "

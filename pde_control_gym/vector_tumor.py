@@ -6,6 +6,10 @@ synchronisation: the agent only sees treatment days; growth (at reset) and post-
 in-kernel day loops (``pdegym_tumor_advance``), finished patients restart inside the same ``step`` (SB3 auto-reset
 semantics: ``infos[i]["terminal_observation"]``).  Per-patient semantics follow brain_tumor_env.py:385-505 including
 the ``weekends`` option (two untreated days after five consecutive treatment days).
+
+``fused_step=True``: the whole wrapper step is ONE launch (``pdegym_tumor_therapy_step``), bit-identical to the sequence above;
+``DeviceRollout(venv, policy, T, one_launch=True)`` goes further and runs T wrapper steps with the policy inside one launch
+(``pdegym_tumor_rollout``).  Both are opt-in: the default stays the launch sequence.
 """
 from __future__ import annotations
 
@@ -18,7 +22,11 @@ from pde_control_gym.vector import BatchedVecEnv
 class TumorVecEnv(BatchedVecEnv):
     _checkpoint_attrs = ("_consecutive", "treatment_calls", "soft_constraint_violations")
 
-    def __init__(self, num_envs: int, weekends: bool = False, device="cuda", backend=None, t_benchmark=None, **kw):
+    one_launch_opt_in = True               # DeviceRollout(one_launch=True) asks one_launch_gap; one_launch=None keeps step_tensor
+    one_launch_obs_noise = False           # (the tumour rollout kernel has no obs_noise input)
+
+    def __init__(self, num_envs: int, weekends: bool = False, device="cuda", backend=None, t_benchmark=None, fused_step: bool = False,
+                 **kw):
         import torch
         from pdecontrolgym_amd.batch_tumor import TumorBatch
         from pdecontrolgym_amd import _native as N
@@ -43,7 +51,27 @@ class TumorVecEnv(BatchedVecEnv):
             self.t_benchmark = t_benchmark
             c.set_benchmark(t_benchmark)
         self._actions = None
+        # fused_step: step_tensor is one pdegym_tumor_therapy_step launch.  The wrapper's state travels as one dictionary: the
+        # counters above (in place), the initial row(s), and two buffers the kernels write -- the last row of every episode that
+        # ended (terminal_obs) and, with weekends, the returned observation (a resting patient returns the treatment day's row)
+        self.fused_step = bool(fused_step)
+        if self.fused_step:
+            gap = c.rollout_gap()
+            if gap is not None:
+                raise ValueError("fused_step=True is not available: " + gap)
+        self._wrap_state = None
         self._finish_vec_env_init()
+
+    def _wrapper_state(self):
+        import torch
+        if self._wrap_state is None:
+            B, nx = self.num_envs, self.core.nx
+            self._final_obs = torch.zeros(B, nx, dtype=torch.float64, device=self.device)
+            self._fused_obs = torch.zeros(B, nx, dtype=torch.float64, device=self.device) if self.weekends else None
+            self._wrap_state = {"weekends": self.weekends, "init": self._init_rows.contiguous(), "consecutive": self._consecutive,
+                                "treatment_calls": self.treatment_calls, "soft_constraint_violations": self.soft_constraint_violations,
+                                "final_obs": self._final_obs, "obs": self._fused_obs}
+        return self._wrap_state
 
     # ---- TherapyWrapper.benchmark / reset -------------------------------------------------------------------------
     def benchmark(self):
@@ -83,6 +111,11 @@ class TumorVecEnv(BatchedVecEnv):
         import torch
         N, c = self._N, self.core
         a = torch.as_tensor(actions, dtype=torch.float64, device=self.device).reshape(self.num_envs)
+        if self.fused_step:                                          # the same step as ONE launch (pdegym_tumor_therapy_step)
+            W = self._wrapper_state()
+            obs, rew, term, trunc = c.therapy_step(a, W)
+            self.terminal_obs = W["final_obs"]                       # (rows of patients whose episode ended in this step)
+            return obs, rew.clone(), term.bool(), trunc.bool()
         stage = c.t["stage"]
         in_post = stage == N.TUMOR_POST
         in_therapy = stage == N.TUMOR_THERAPY                       # Growth cannot be observed here (reset runs it)
@@ -118,6 +151,32 @@ class TumorVecEnv(BatchedVecEnv):
 
     def rollout_obs(self):          # (DeviceRollout: the observation IS the engine's one live row)
         return self.core.t["u"]
+
+    def one_launch_gap(self, policy):
+        """What keeps ``DeviceRollout(self, policy, T, one_launch=True)`` out of pdegym_tumor_rollout, as a sentence; None when it
+        fits: a ``FusedMLP`` of nx inputs and one output that fits the kernel's LDS next to the rows, or ``policy=None`` (commands
+        given ahead in ``DeviceRollout.actions``)."""
+        gap = self.core.rollout_gap()
+        if gap is not None:
+            return gap
+        if policy is None:
+            return None
+        if not hasattr(policy, "fits_rollout"):
+            return "the policy is not a FusedMLP (or None: commands given ahead in the rollout's actions buffer)"
+        if not self.core.policy_fits_rollout(policy):
+            return (f"the policy does not fit the rollout kernel: {self.core.nx} inputs, one output, layers of <= 256 units, and its LDS plus "
+                    f"two float64 rows of {self.core.nx} nodes for 16 patients within 160 KB (TumorBatch.policy_fits_rollout)")
+        return None
+
+    def rollout_one_launch(self, obs, actions, rewards, terminated, truncated, policy=None, clamp="default", noise=None, **kw):
+        """T wrapper steps (and the policy) in ONE launch; ``terminal_obs`` holds the last row of every episode that ended in it
+        (the latest one per patient)."""
+        if kw:
+            raise ValueError(f"the tumour rollout kernel takes no {sorted(kw)}")
+        W = self._wrapper_state()
+        self.core.rollout(obs, actions, rewards, terminated, truncated, policy=policy, clamp=clamp,
+                          noise=noise if policy is not None else None, wrap_state=W)
+        self.terminal_obs = W["final_obs"]
 
     # ---- SB3 VecEnv face ------------------------------------------------------------------------------------------------
     def step_wait(self):

@@ -11,7 +11,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "lib", "libpdegym_hip.so")
 
-ABI_VERSION = 19
+ABI_VERSION = 20
 RING = 128
 LOOKBACK = 100
 MAX_N1D = 8192
@@ -35,7 +35,7 @@ EXPORTS = [
     "pdegym_transport_rollout", "pdegym_parabolic_rollout", "pdegym_traffic_rollout", "pdegym_debug_set",
     "pdegym_backstep_gain_parabolic", "pdegym_backstep_gain_transport", "pdegym_backstep_control",
     "pdegym_ns2d_adjoint_f64", "pdegym_transport_backstep_rollout", "pdegym_parabolic_backstep_rollout",
-    "pdegym_traffic_backstep_control", "pdegym_traffic_backstep_rollout",
+    "pdegym_traffic_backstep_control", "pdegym_traffic_backstep_rollout", "pdegym_tumor_therapy_step", "pdegym_tumor_rollout",
 ]
 # keys of pdegym_debug_set (test-only dispatch overrides, include/pdegym.h)
 DEBUG_NS_GENERIC, DEBUG_NS_NO_COL, DEBUG_NS_COL_MIN_BATCH, DEBUG_NS_NO_LDS_JACOBI = range(4)
@@ -132,6 +132,17 @@ class BufsTumor(C.Structure):
                                           "t1_log")]
 
 
+class WrapTumor(C.Structure):
+    _fields_ = [("weekends", C.c_int32), ("reserved_", C.c_int32), ("init", C.c_void_p), ("init_stride", C.c_int64),
+                ("consecutive", C.c_void_p), ("treatment_calls", C.c_void_p), ("soft_constraint_violations", C.c_void_p),
+                ("final_obs", C.c_void_p), ("obs", C.c_void_p)]
+
+
+class RolloutTumor(C.Structure):
+    _fields_ = [("T", C.c_int32), ("reserved_", C.c_int32), ("obs", C.c_void_p), ("actions", C.c_void_p),
+                ("rewards", C.c_void_p), ("terminated", C.c_void_p), ("truncated", C.c_void_p), ("policy", C.c_void_p)]
+
+
 class MlpLayer(C.Structure):
     _fields_ = [("w", C.c_void_p), ("b", C.c_void_p), ("in_dim", C.c_int32), ("out_dim", C.c_int32), ("act", C.c_int32),
                 ("reserved_", C.c_int32)]
@@ -220,6 +231,11 @@ def load():
     lib.pdegym_tumor_reset_masked.argtypes = [C.POINTER(ParamsTumor), C.POINTER(BufsTumor), C.c_void_p, C.c_int64, C.c_void_p,
                                               C.c_int32, C.c_void_p]
     lib.pdegym_tumor_reset_masked.restype = C.c_int
+    lib.pdegym_tumor_therapy_step.argtypes = [C.POINTER(ParamsTumor), C.POINTER(BufsTumor), C.POINTER(WrapTumor), C.c_int32, C.c_void_p]
+    lib.pdegym_tumor_therapy_step.restype = C.c_int
+    lib.pdegym_tumor_rollout.argtypes = [C.POINTER(ParamsTumor), C.POINTER(BufsTumor), C.POINTER(WrapTumor), C.POINTER(RolloutTumor),
+                                         C.c_int32, C.c_void_p]
+    lib.pdegym_tumor_rollout.restype = C.c_int
     lib.pdegym_mlp_forward.argtypes = [C.POINTER(Mlp), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
     lib.pdegym_mlp_forward.restype = C.c_int
     for f in (lib.pdegym_backstep_gain_parabolic, lib.pdegym_backstep_gain_transport):

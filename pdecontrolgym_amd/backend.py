@@ -377,6 +377,54 @@ class HipBackend:
         N.check(self.lib.pdegym_tumor_reset_masked(C.byref(P), C.byref(bufs), N.dptr(init, torch.float64), stride, m, B,
                                                    N.current_stream_ptr(T["u"].device)), "pdegym_tumor_reset_masked")
 
+    @staticmethod
+    def _wrap_tumor(T, W: dict, B: int) -> N.WrapTumor:
+        """``W``: the wrapper's state -- ``weekends``, ``init`` [nx] or [B, nx], ``consecutive`` int32 [B], ``treatment_calls`` /
+        ``soft_constraint_violations`` int64 [B], optional ``final_obs`` / ``obs`` [B, nx]."""
+        import torch
+        nx = int(T["u"].shape[1])
+        init = W["init"]
+        if tuple(init.shape) not in ((nx,), (B, nx)):
+            raise N.NativeError(f"tumor wrapper: init must be [{nx}] or [{B}, {nx}], got {tuple(init.shape)}")
+        _check_shapes("tumor wrapper", {"consecutive": (W["consecutive"], (B,)), "treatment_calls": (W["treatment_calls"], (B,)),
+                                        "soft_constraint_violations": (W["soft_constraint_violations"], (B,)),
+                                        "final_obs": (W.get("final_obs"), (B, nx)), "obs": (W.get("obs"), (B, nx))})
+        w = N.WrapTumor()
+        w.weekends = int(bool(W["weekends"]))
+        w.init, w.init_stride = N.dptr(init, torch.float64), (0 if init.dim() == 1 else nx)
+        w.consecutive = N.dptr(W["consecutive"], torch.int32)
+        w.treatment_calls = N.dptr(W["treatment_calls"], torch.int64)
+        w.soft_constraint_violations = N.dptr(W["soft_constraint_violations"], torch.int64)
+        w.final_obs, w.obs = N.dptr(W.get("final_obs"), torch.float64), N.dptr(W.get("obs"), torch.float64)
+        return w
+
+    @_on_device_of("u")
+    def tumor_therapy_step(self, P: N.ParamsTumor, T: dict, W: dict, B: int):
+        """One TherapyWrapper step of every patient in one launch (pdegym_tumor_therapy_step): the command is ``T["control"]``, the
+        wrapper's state ``W`` (``_wrap_tumor``); ``W["obs"]`` receives the returned observation."""
+        bufs = self._bufs_tumor({**T, "kill": None, "active": None})
+        wrap = self._wrap_tumor(T, W, B)
+        N.check(self.lib.pdegym_tumor_therapy_step(C.byref(P), C.byref(bufs), C.byref(wrap), B, N.current_stream_ptr(T["u"].device)),
+                "pdegym_tumor_therapy_step")
+
+    @_on_device_of("u")
+    def tumor_rollout(self, P: N.ParamsTumor, T: dict, W: dict, obs, actions, rewards, terminated, truncated, B: int, policy=None):
+        """T wrapper steps in one launch (pdegym_tumor_rollout): ``obs`` [T+1, B, nx], ``actions`` [T, B] (an output when ``policy`` --
+        an ``N.Mlp`` descriptor, its ``noise`` [T, B] -- is given), ``rewards`` / ``terminated`` / ``truncated`` [T, B]."""
+        import torch
+        steps = int(actions.shape[0])
+        _check_shapes("rollout", {"obs": (obs, (steps + 1, B, P.nx)), "actions": (actions, (steps, B)), "rewards": (rewards, (steps, B)),
+                                  "terminated": (terminated, (steps, B)), "truncated": (truncated, (steps, B))})
+        bufs = self._bufs_tumor({**T, "kill": None, "active": None})
+        wrap = self._wrap_tumor(T, {**W, "obs": None}, B)
+        ro = N.RolloutTumor()
+        ro.T = steps
+        ro.obs, ro.actions, ro.rewards = N.dptr(obs, torch.float64), N.dptr(actions, torch.float64), N.dptr(rewards, torch.float64)
+        ro.terminated, ro.truncated = N.dptr(terminated, torch.uint8), N.dptr(truncated, torch.uint8)
+        ro.policy = C.addressof(policy) if policy is not None else None
+        N.check(self.lib.pdegym_tumor_rollout(C.byref(P), C.byref(bufs), C.byref(wrap), C.byref(ro), B, N.current_stream_ptr(obs.device)),
+                "pdegym_tumor_rollout")
+
     # ---- policy network ----------------------------------------------------------------------------
     @_on_device_of("x")
     def mlp_forward(self, net: N.Mlp, x, y, B: int):

@@ -115,3 +115,62 @@ class TumorBatch(EngineCheckpoint):
         self._set_active(active)
         self.backend.tumor_step(self.params, self.t, self.num_envs)
         return self.t["u"], self.t["reward"], self.t["terminated"], self.t["truncated"]
+
+    # ---- TherapyWrapper steps inside one launch (include/pdegym.h: pdegym_tumor_therapy_step / pdegym_tumor_rollout) -------------
+    def rollout_gap(self):
+        """What keeps this engine out of the wrapper-step kernels, as a sentence; None when nothing does."""
+        if not hasattr(self.backend, "tumor_rollout") or not hasattr(self.backend, "tumor_therapy_step"):
+            return "the backend has no tumor_therapy_step / tumor_rollout"
+        if self.t["history"] is not None:
+            return "record_history=True (the wrapper-step kernels do not record the trajectory)"
+        return None
+
+    def can_rollout(self) -> bool:
+        """``therapy_step`` / ``rollout`` need a backend with the entry points and an engine that does not record its history."""
+        return self.rollout_gap() is None
+
+    def policy_fits_rollout(self, policy) -> bool:
+        """Whether ``policy`` (a ``FusedMLP``) can run inside the rollout kernel: nx inputs, one output, layers of at most 256 units
+        (``FusedMLP.fits_rollout``), and the policy's LDS plus this engine's two float64 rows for each of a workgroup's 16 patients
+        within the kernel's 160 KB."""
+        fits = getattr(policy, "fits_rollout", None)
+        if fits is None or not self.can_rollout() or not fits(self.nx, 1):
+            return False
+        rows = 16 * 2 * self.nx * 8
+        return (policy.rollout_lds_bytes(self.nx) + 15) // 16 * 16 + rows <= policy.ROLLOUT_LDS_BYTES
+
+    def _wrap(self, wrap_state):
+        gap = self.rollout_gap()
+        if gap is not None:
+            raise ValueError("the wrapper step cannot run inside one launch: " + gap)
+        missing = {"weekends", "init", "consecutive", "treatment_calls", "soft_constraint_violations"} - set(wrap_state)
+        if missing:
+            raise ValueError(f"wrap_state lacks {sorted(missing)}")
+        return wrap_state
+
+    def therapy_step(self, control, wrap_state):
+        """One ``TherapyWrapper.step`` of every patient in ONE launch (brain_tumor_env.py:385-505): post-therapy run or treatment day
+        (+ weekend days), counters, kept last row, restart and growth run of finished patients.  ``control`` [B]; ``wrap_state``: a
+        dict with ``weekends``, ``init`` ([nx] or [B, nx]), the in/out tensors ``consecutive`` (int32), ``treatment_calls`` and
+        ``soft_constraint_violations`` (int64) [B], and optionally ``final_obs`` / ``obs`` [B, nx] (``obs`` is required with
+        weekends; without it the observation is the live row).  Returns (observation, reward, terminated, truncated): the engine's
+        own tensors, reward and flags being the step's reported ones."""
+        import torch
+        W = self._wrap(wrap_state)
+        self.t["control"] = as_kernel_input(control, torch.float64, self.device, (self.num_envs,))
+        self.backend.tumor_therapy_step(self.params, self.t, W, self.num_envs)
+        obs = W.get("obs")
+        return (self.t["u"] if obs is None else obs), self.t["reward"], self.t["terminated"], self.t["truncated"]
+
+    def rollout(self, obs, actions, rewards, terminated, truncated, policy=None, clamp="default", noise=None, wrap_state=None):
+        """T wrapper steps in ONE launch (pdegym_tumor_rollout): step t takes ``actions[t]`` ([T, B]) and writes ``obs[t + 1]``
+        ([T+1, B, nx]), ``rewards[t]``, ``terminated[t]``, ``truncated[t]`` -- bit-identical to T ``therapy_step`` calls.  With
+        ``policy`` (a ``FusedMLP``) the commands are computed inside the launch from ``obs[t]`` (``obs[0]`` = the current
+        observation, supplied by the caller) and written to ``actions``; ``noise`` [T, B] float32 is added before the clamp.
+        ``wrap_state`` as for ``therapy_step`` (its ``obs`` is not used)."""
+        W = self._wrap(wrap_state if wrap_state is not None else {})
+        if policy is not None and not self.policy_fits_rollout(policy):
+            raise ValueError("this policy cannot run inside the rollout kernel (see policy_fits_rollout)")
+        net = policy.rollout_net(obs, actions, clamp, noise) if policy is not None else None
+        self.backend.tumor_rollout(self.params, self.t, W, obs, actions, rewards, terminated, truncated, self.num_envs, policy=net)
+        return obs, rewards, terminated, truncated

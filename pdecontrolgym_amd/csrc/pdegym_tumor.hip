@@ -13,30 +13,11 @@
 
 #include "pdegym.h"
 #include "pdegym_common.h"
+#include "pdegym_tumor_body.h"
 
 namespace {
 
-using namespace pdegym::wave;      // kWave, kWavesPerBlock, wave_lds_sync
-constexpr int kMaxNx = 4096;
-
-// index of the highest lane set in a chunk's ballot (chunks are visited left to right, so a later hit wins)
-__device__ __forceinline__ int rightmost(unsigned long long ballot, int chunk_base, int so_far) {
-  return ballot ? chunk_base + 63 - __builtin_clzll(ballot) : so_far;
-}
-
-// brain_tumor_env.py:221-245, one interior node.
-__device__ __forceinline__ double fd_node(const pdegym_params_tumor& P, double ul, double uc, double ur, double R, bool rad) {
-  double lap = (ur - 2.0 * uc) + ul;
-  if (P.dx2 != 1.0) lap = lap / P.dx2;                                 // x / 1.0 == x: skip the f64 division when dx = 1
-  const double diffusion = P.D * lap;
-  const double logistic = 1.0 - (uc / P.k);
-  const double proliferation = (P.rho * uc) * logistic;
-  double s = diffusion + proliferation;
-  if (rad) s = s - (R * uc) * logistic;
-  return uc + P.dt * s;
-}
-
-__device__ __forceinline__ double clip0k(double x, double k) { return pdegym::clip_keep_nan(x, 0.0, k); }      // np.clip(nextU, 0, k) :244
+using namespace pdegym_tumor;      // kWave, wave_lds_sync, rightmost, fd_node, clip0k, check (pdegym_tumor_body.h)
 
 // mode: PDEGYM_TUMOR_RUN_*; every participating instance simulates at most max_days days.  The row ping-pongs between two
 // LDS copies owned by the wave (no workgroup barrier: waves of a block run different numbers of days), the scalars of the
@@ -252,15 +233,6 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void tumor_reset_kernel(pdeg
     days[0] = days[1] = days[2] = days[3] = 0;
     days[PDEGYM_TUMOR_DAY_DEATH] = -1;
   }
-}
-
-int check(const pdegym_params_tumor* prm, const pdegym_bufs_tumor* buf) {
-  if (!prm || !buf) return pdegym::fail(-1, "null params/bufs");
-  if (prm->nx < 3 || prm->nx > kMaxNx) return pdegym::fail(-2, "tumor: nx must be in [3, 4096]");
-  if (prm->nt < 2) return pdegym::fail(-2, "tumor: nt must be >= 2");
-  if (!buf->u || !buf->time_index || !buf->stage || !buf->remaining || !buf->days)
-    return pdegym::fail(-3, "null device buffer");
-  return 0;
 }
 
 }  // namespace

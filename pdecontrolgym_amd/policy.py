@@ -129,13 +129,21 @@ class FusedMLP:
         dims = [(int(w.shape[1]), int(w.shape[0])) for w, _, _ in self.layers]
         if dims[0][0] != in_dim or dims[-1][1] != out_dim or any(o > 256 for _, o in dims):
             return False
-        # the budget of csrc/pdegym_policy.h: wide_lds_floats (over pdegym_mlp_tile.h: lds_stride) / lds_floats <= kMaxLdsBytes
+        return self.rollout_lds_bytes(in_dim) <= self.ROLLOUT_LDS_BYTES
+
+    ROLLOUT_LDS_BYTES = 160 * 1024      # csrc/pdegym_policy.h: kMaxLdsBytes
+
+    def rollout_lds_bytes(self, in_dim: int) -> int:
+        """LDS bytes the in-kernel evaluation takes per workgroup of 16 instances (csrc/pdegym_policy.h: wide_lds_floats, over
+        pdegym_mlp_tile.h: lds_stride, for a layer of more than 64 units; lds_floats otherwise).  An engine whose rollout kernel keeps
+        LDS rows of its own (the brain-tumour engine) adds them to this figure."""
+        dims = [(int(w.shape[1]), int(w.shape[0])) for w, _, _ in self.layers]
         if any(o > 64 for _, o in dims):
             stride = lambda w: (w + 63) // 64 * 64 + 4                  # noqa: E731
             floats = 16 * (stride((in_dim + 15) // 16 * 16) + 2 * stride(256)) + 32
         else:
             floats = sum((((i + 3) // 4) | 1) * 4 * o + 64 for i, o in dims) + 16 * (((in_dim + 3) // 4) * 4 + 128)
-        return 4 * floats <= 160 * 1024
+        return 4 * floats
 
     def rollout_net(self, obs, actions, clamp="default", noise=None) -> N.Mlp:
         """The descriptor for a rollout that reads ``obs`` and writes ``actions`` ([T, B] or [T, B, A]): weights refreshed (unless

@@ -122,6 +122,18 @@ class HipBackend:
         return _prepared(fn, C.byref(P), C.byref(bufs), B, dev, f"pdegym_{kind}_step", (bufs, T))
     prepare_step1d.device_guard_key = "bsum"     # the guard is inside the prepared call (the state's device made current)
 
+    @staticmethod
+    def _rollout1d_desc(obs, actions, rewards, terminated, truncated, obs_noise=None, obs_seen=None, policy=None) -> N.Rollout1D:
+        """The descriptor of a 1D rollout over ``actions.shape[0]`` env-steps, from tensors whose shapes the caller has checked."""
+        import torch
+        ro = N.Rollout1D()
+        ro.T = int(actions.shape[0])
+        ro.obs, ro.actions, ro.rewards = N.dptr(obs, torch.float32), N.dptr(actions, torch.float32), N.dptr(rewards, torch.float32)
+        ro.terminated, ro.truncated = N.dptr(terminated, torch.uint8), N.dptr(truncated, torch.uint8)
+        ro.policy = C.addressof(policy) if policy is not None else None
+        ro.obs_noise, ro.obs_seen = N.dptr(obs_noise, torch.float32), N.dptr(obs_seen, torch.float32)
+        return ro
+
     @_on_device_of("obs")
     def rollout1d(self, kind: str, P: N.Params1D, T: dict, obs, actions, rewards, terminated, truncated, B: int, policy=None,
                   obs_noise=None, obs_seen=None):
@@ -140,12 +152,7 @@ class HipBackend:
                                   "obs_noise": (obs_noise, (steps, B, od), torch.float32),
                                   "obs_seen": (obs_seen, (steps, B, od), torch.float32)})
         bufs = self._bufs1d({**T, "state_in": None, "u": None if full else T["u"], "history": None})
-        ro = N.Rollout1D()
-        ro.T = steps
-        ro.obs, ro.actions, ro.rewards = N.dptr(obs, torch.float32), N.dptr(actions, torch.float32), N.dptr(rewards, torch.float32)
-        ro.terminated, ro.truncated = N.dptr(terminated, torch.uint8), N.dptr(truncated, torch.uint8)
-        ro.policy = C.addressof(policy) if policy is not None else None
-        ro.obs_noise, ro.obs_seen = N.dptr(obs_noise, torch.float32), N.dptr(obs_seen, torch.float32)
+        ro = self._rollout1d_desc(obs, actions, rewards, terminated, truncated, obs_noise, obs_seen, policy)
         N.check(fn(C.byref(P), C.byref(bufs), C.byref(ro), B, N.current_stream_ptr(obs.device)), f"pdegym_{kind}_rollout")
 
     @_on_device_of("bsum")
@@ -275,11 +282,21 @@ class HipBackend:
         N.check(self.lib.pdegym_traffic_step(C.byref(P), C.byref(bufs), B, N.current_stream_ptr(T["r"].device)),
                 "pdegym_traffic_step")
 
+    @staticmethod
+    def _rollout_traffic_desc(obs, actions, rewards, done, truncated, policy=None) -> N.RolloutTraffic:
+        """The descriptor of a traffic rollout over ``actions.shape[0]`` env-steps, from tensors whose shapes the caller has checked."""
+        import torch
+        ro = N.RolloutTraffic()
+        ro.T = int(actions.shape[0])
+        ro.obs, ro.actions, ro.rewards = N.dptr(obs, torch.float64), N.dptr(actions, torch.float64), N.dptr(rewards, torch.float64)
+        ro.done, ro.truncated = N.dptr(done, torch.uint8), N.dptr(truncated, torch.uint8)
+        ro.policy = C.addressof(policy) if policy is not None else None
+        return ro
+
     @_on_device_of("r")
     def traffic_rollout(self, P: N.ParamsTraffic, T: dict, obs, actions, rewards, done, truncated, B: int, policy=None):
         """T env-steps in one launch (pdegym_traffic_rollout): ``obs`` [T+1, B, 2M], ``actions`` [T, B, A] (A = 1 or 2; an output
         when ``policy`` -- an ``N.Mlp`` descriptor, its ``noise`` [T, B, A] -- is given), ``rewards`` / ``done`` / ``truncated`` [T, B]."""
-        import torch
         steps = int(actions.shape[0])
         A = int(actions.shape[2])
         if A not in (1, 2):
@@ -287,11 +304,7 @@ class HipBackend:
         _check_shapes("rollout", {"obs": (obs, (steps + 1, B, 2 * P.M)), "actions": (actions, (steps, B, A)), "rewards": (rewards, (steps, B)),
                                   "done": (done, (steps, B)), "truncated": (truncated, (steps, B))})
         bufs = self._bufs_traffic({**T, "action": actions[0]})
-        ro = N.RolloutTraffic()
-        ro.T = steps
-        ro.obs, ro.actions, ro.rewards = N.dptr(obs, torch.float64), N.dptr(actions, torch.float64), N.dptr(rewards, torch.float64)
-        ro.done, ro.truncated = N.dptr(done, torch.uint8), N.dptr(truncated, torch.uint8)
-        ro.policy = C.addressof(policy) if policy is not None else None
+        ro = self._rollout_traffic_desc(obs, actions, rewards, done, truncated, policy)
         N.check(self.lib.pdegym_traffic_rollout(C.byref(P), C.byref(bufs), C.byref(ro), B, N.current_stream_ptr(obs.device)),
                 "pdegym_traffic_rollout")
 
@@ -319,16 +332,12 @@ class HipBackend:
         """T env-steps with the backstepping law inside, in one launch (pdegym_traffic_backstep_rollout): the buffers of
         ``traffic_rollout`` with ``actions`` [T, B, commands] an output; ``law``: an ``N.TrafficBackstep`` descriptor
         (``TrafficBacksteppingController.rollout_law``; its ``noise`` [T, B, commands])."""
-        import torch
         steps = int(actions.shape[0])
         A = 2 if P.sim == N.TRAFFIC_SIM["both"] else 1
         _check_shapes("backstep rollout", {"obs": (obs, (steps + 1, B, 2 * P.M)), "actions": (actions, (steps, B, A)),
                                            "rewards": (rewards, (steps, B)), "done": (done, (steps, B)), "truncated": (truncated, (steps, B))})
         bufs = self._bufs_traffic({**T, "action": actions[0]})
-        ro = N.RolloutTraffic()
-        ro.T = steps
-        ro.obs, ro.actions, ro.rewards = N.dptr(obs, torch.float64), N.dptr(actions, torch.float64), N.dptr(rewards, torch.float64)
-        ro.done, ro.truncated = N.dptr(done, torch.uint8), N.dptr(truncated, torch.uint8)
+        ro = self._rollout_traffic_desc(obs, actions, rewards, done, truncated)
         N.check(self.lib.pdegym_traffic_backstep_rollout(C.byref(P), C.byref(bufs), C.byref(ro), C.byref(law), B,
                                                          N.current_stream_ptr(obs.device)), "pdegym_traffic_backstep_rollout")
 
@@ -500,11 +509,7 @@ class HipBackend:
                                            "obs_noise": (obs_noise, (steps, B, P.n), torch.float32),
                                            "obs_seen": (obs_seen, (steps, B, P.n), torch.float32)})
         bufs = self._bufs1d({**T, "state_in": None, "u": None, "history": None})
-        ro = N.Rollout1D()
-        ro.T = steps
-        ro.obs, ro.actions, ro.rewards = N.dptr(obs, torch.float32), N.dptr(actions, torch.float32), N.dptr(rewards, torch.float32)
-        ro.terminated, ro.truncated = N.dptr(terminated, torch.uint8), N.dptr(truncated, torch.uint8)
-        ro.obs_noise, ro.obs_seen = N.dptr(obs_noise, torch.float32), N.dptr(obs_seen, torch.float32)
+        ro = self._rollout1d_desc(obs, actions, rewards, terminated, truncated, obs_noise, obs_seen)
         N.check(fn(C.byref(P), C.byref(bufs), C.byref(ro), C.byref(law), B, N.current_stream_ptr(obs.device)),
                 f"pdegym_{kind}_backstep_rollout")
 

@@ -4,30 +4,16 @@
 // iterations of one loop, with the row, beta, the norm ring, the running sums AND the instance's gain row held in registers for the whole
 // rollout.  Every value is bit-identical to the two-launch path: the env-step is step1d_body of pdegym_1d_body.h as the carried policy
 // kernel instantiates it (pdegym_1d_rollout.hip: rollout1d_policy_kernel), the dot product is pdegym_backstep_law.h, the function the
-// control kernel calls, on the same operands.
+// control kernel calls, on the same operands.  What the kernel shares with the other 1D rollout kernels is pdegym_1d_rollout.h.
 // Output contract (poisoned buffers, guard bands): tests/test_gpu_backstep_rollout.py, KERNEL_CASES there; tests/test_backstep_rollout.py
 // fails when a kernel launched here is missing from that table.
-#include "pdegym_1d_body.h"
+#include "pdegym_1d_rollout.h"
 #include "pdegym_backstep_law.h"
 
 namespace {
 
 constexpr int kMaxRow = 513;                     // the longest row: 8 slots per lane + node 0 of a parabolic row (transport: 512)
 constexpr int kStrip = (kMaxRow + 3) / 4 * 4;    // floats of one wave's LDS strip
-
-// Pre-drawn additive sensing noise with the semantics of sense_noise in pdegym_1d_rollout.hip: the wave's LDS copy of observation t
-// becomes obs + obs_noise[t], which is what the law reads and what obs_seen[t] receives; the observation slots stay clean.
-__device__ __forceinline__ void law_sense_noise(const float* obs_noise, float* obs_seen, float* xw, int od, int B, int inst, int lane, int t) {
-  if (!obs_noise && !obs_seen) return;     // wave-uniform
-  const size_t base = ((size_t)t * B + inst) * od;
-  for (int j = lane; j < od; j += kWave) {
-    float v = xw[j];
-    if (obs_noise) v += obs_noise[base + j];
-    xw[j] = v;
-    if (obs_seen) obs_seen[base + j] = v;
-  }
-  wave_lds_sync();
-}
 
 // One wave per instance, kWavesPerBlock waves per workgroup (rollout1d_kernel's shape).  Dirichlet actuation, full-state sensing,
 // float32 operands, no history, temporal reward horizon, at most 8 slots per lane (n <= 512 transport / 513 parabolic): the corner
@@ -45,9 +31,7 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void backstep_rollout1d_kern
   if (inst >= B) return;  // wave-uniform; the kernel has no workgroup barrier
   constexpr int J0 = PARABOLIC ? 1 : 0;
   constexpr int NK = EPL + J0;
-  // (the staging loops take the row length from the kernel argument even when FULL makes it a compile-time constant for the env-step,
-  // as the policy kernel does)
-  const int n = P.n, ns = n - J0, s0 = lane * EPL;
+  const int n = P.n;      // (the kernel argument even under FULL: stage_carried_row)
   const size_t slot = (size_t)B * n;
   float* const xw = strips[wave];
 
@@ -67,28 +51,15 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void backstep_rollout1d_kern
   Carry<EPL> C;       // the state stays in registers over the T env-steps (see rollout1d_kernel)
   carry_load<EPL, PARABOLIC, FULL>(C, P, Bf, Ro.obs, inst, lane);      // ends with drain_vmem(): the gains have landed too
   for (int t = 0; t < Ro.T; ++t) {
-    // observation of this instance -> LDS, straight from the carried row (slot t of Ro.obs holds the same values)
-    if (PARABOLIC && lane == 0) xw[0] = C.bl;
-#pragma unroll
-    for (int e = 0; e < EPL; ++e)
-      if (s0 + e < ns) xw[J0 + s0 + e] = C.x[e];
-    wave_lds_sync();
-    law_sense_noise(Ro.obs_noise, Ro.obs_seen, xw, n, B, inst, lane, t);
+    stage_carried_row<EPL, PARABOLIC>(C, xw, n, lane);
+    sense_noise(Ro.obs_noise, Ro.obs_seen, xw, n, B, inst, lane, t);
     const double s = pdegym_backstep_law::dot<ORDERED, NK>(L.len, lane, [&](int k, int i) { return gain[k] * (double)xw[i]; });
     float a = (float)(s * L.scale);      // rounded once, as the control kernel's out32
     if (L.noise) a += L.noise[(size_t)t * B + inst];
     if (L.clamp) a = pdegym::clip_keep_nan(a, L.lo, L.hi);
     if (lane == 0) Ro.actions[(size_t)t * B + inst] = a;
 
-    pdegym_bufs1d S = Bf;
-    S.u = nullptr;
-    S.history = nullptr;
-    S.state_in = Ro.obs + (size_t)t * slot;
-    S.obs = Ro.obs + (size_t)(t + 1) * slot;
-    S.action = Ro.actions + (size_t)t * B;
-    S.reward = Ro.rewards + (size_t)t * B;
-    S.terminated = Ro.terminated + (size_t)t * B;
-    S.truncated = Ro.truncated + (size_t)t * B;
+    const pdegym_bufs1d S = rollout_step_view(Bf, Ro, B, slot, t);
     step1d_body<EPL, PARABOLIC, false, false, false, false, true, true, FULL>(P, S, B, inst, lane, &a, &C, t == Ro.T - 1);
     // The auto-reset branch of step1d_body is the only place that leaves the carried time index at 0 (a step from index 0 advances it:
     // substeps >= 1, nt >= 2, checked by the entry point): the instance restarted, and its next command takes the next gain row.
@@ -108,24 +79,16 @@ int launch_backstep_rollout(const pdegym_params1d* prm, const pdegym_bufs1d* buf
   if (B <= 0 || ro->T <= 0) return 0;
   const pdegym_params1d& P = *prm;
   const pdegym_backstep& L = *law;
-  // the plant: the checks of launch_rollout (pdegym_1d_rollout.hip), narrowed to the corner this kernel covers
-  if (P.n < 3) return pdegym::fail(-2, "backstep rollout: n must be >= 3");
+  // the plant: the checks of every 1D rollout, then what narrows them to the corner this kernel covers
+  if (const int rc = check_rollout_plant(P, *buf, *ro, "backstep rollout")) return rc;
   // at most 8 slots per lane (the widest instantiation): 512 nodes of a transport row, 513 of a parabolic one (node 0 is not a slot)
   if (P.n - (PARABOLIC ? 1 : 0) > 8 * kWave)
     return pdegym::fail(-2, PARABOLIC ? "backstep rollout: rows of up to 513 nodes (longer rows: pdegym_backstep_control + pdegym_parabolic_step)"
                                       : "backstep rollout: rows of up to 512 nodes (longer rows: pdegym_backstep_control + pdegym_transport_step)");
-  if (P.nt < 2) return pdegym::fail(-2, "nt must be >= 2");
   if (P.substeps < 1) return pdegym::fail(-2, "backstep rollout: substeps must be >= 1");
   if (P.sensing != PDEGYM_SENSE_FULL) return pdegym::fail(-2, "backstep rollout: the law reads the whole row (full-state sensing only)");
   if (P.control_type != PDEGYM_CONTROL_DIRICHLET) return pdegym::fail(-2, "backstep rollout: Dirichlet actuation only (Neumann: pdegym_backstep_control + pdegym_*_step)");
   if (P.flux != PDEGYM_FLUX_LINEAR) return pdegym::fail(-2, "backstep rollout: the law exists for the linear transport term only");
-  if (P.beta_f64 || P.action_kind != PDEGYM_ACTION_F32) return pdegym::fail(-2, "backstep rollout: float32 beta and actions only");
-  if (buf->history) return pdegym::fail(-2, "backstep rollout cannot record a history buffer");
-  if (P.reward_horizon != PDEGYM_HORIZON_TEMPORAL) return pdegym::fail(-2, "backstep rollout: only the temporal reward horizon is evaluated in the rollout kernels");
-  if (!buf->beta || !buf->time_index || !buf->bsum || !buf->ring || !buf->norm_now || !buf->norm_back)
-    return pdegym::fail(-3, "null device buffer");
-  if (!ro->obs || !ro->actions || !ro->terminated || !ro->truncated) return pdegym::fail(-3, "null rollout buffer");
-  if (P.reward_kind != PDEGYM_REWARD_NONE && !ro->rewards) return pdegym::fail(-3, "null reward buffer");
   if (ro->policy) return pdegym::fail(-2, "backstep rollout: the law replaces the policy (rollout.policy must be NULL)");
   // the law: the checks of pdegym_backstep_control
   if (!L.gain0) return pdegym::fail(-3, "null gain0");
@@ -144,9 +107,9 @@ int launch_backstep_rollout(const pdegym_params1d* prm, const pdegym_bufs1d* buf
   const int epl = (nslots + kWave - 1) / kWave;      // the slots-per-lane choice of launch_step / launch_rollout: rewards depend on it
   const bool ordered = L.order == PDEGYM_BACKSTEP_ORDERED;
   const dim3 grid((B + kWavesPerBlock - 1) / kWavesPerBlock), block(kWave * kWavesPerBlock);
-  auto go = [&](auto tag) {
+  with_rollout_epl<8>(epl, [&](auto tag) {      // (more than 8 was refused above)
     constexpr int E = decltype(tag)::value;
-    constexpr bool kHasFull = E == 1 || E == 2 || E == 4 || E == 8;      // rows of 64 / 128 / 256 / 512 slots
+    constexpr bool kHasFull = epl_has_full(E);
     if (kHasFull && nslots == kWave * E) {
       if (ordered) backstep_rollout1d_kernel<E, PARABOLIC, true, kHasFull><<<grid, block, 0, st>>>(P, *buf, *ro, L, B);
       else backstep_rollout1d_kernel<E, PARABOLIC, false, kHasFull><<<grid, block, 0, st>>>(P, *buf, *ro, L, B);
@@ -154,14 +117,7 @@ int launch_backstep_rollout(const pdegym_params1d* prm, const pdegym_bufs1d* buf
       if (ordered) backstep_rollout1d_kernel<E, PARABOLIC, true, false><<<grid, block, 0, st>>>(P, *buf, *ro, L, B);
       else backstep_rollout1d_kernel<E, PARABOLIC, false, false><<<grid, block, 0, st>>>(P, *buf, *ro, L, B);
     }
-  };
-  if (epl <= 1) go(std::integral_constant<int, 1>{});
-  else if (epl <= 2) go(std::integral_constant<int, 2>{});
-  else if (epl <= 3) go(std::integral_constant<int, 3>{});
-  else if (epl <= 4) go(std::integral_constant<int, 4>{});
-  else if (epl <= 5) go(std::integral_constant<int, 5>{});
-  else if (epl <= 6) go(std::integral_constant<int, 6>{});
-  else go(std::integral_constant<int, 8>{});      // epl 7 or 8 (more was refused above)
+  });
   return pdegym::check_launch("backstep_rollout1d");
 }
 

@@ -36,7 +36,8 @@ KERNEL_CASES = {
     "selftest_quotient_kernel": ["test_selftest_quotient_counter_only"],
     "rollout1d_kernel": ["test_1d_rollout_contract"],
     "rollout1d_general_kernel": ["test_1d_rollout_contract"],
-    "kernel": ["test_1d_rollout_contract"],          # pdegym_1d_rollout.hip: the in-kernel policy launch through a chosen pointer
+    "rollout1d_policy_kernel": ["test_1d_rollout_contract"],
+    "rollout1d_policy_general_kernel": ["test_1d_rollout_contract"],
     "mlp_forward_kernel": ["test_mlp_forward_contract_vs_float64"],
     "ns256_fused_step": ["test_ns256_contract"],
     "ns256_split_obs": ["test_ns256_contract"],

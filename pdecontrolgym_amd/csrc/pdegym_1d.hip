@@ -142,7 +142,6 @@ __global__ __launch_bounds__(kWave) void step1d_wide_kernel(pdegym_params1d P, p
   const float norm_back_pre = from_ring ? ring[src_row & (PDEGYM_RING - 1)] : 0.f;
   const int back_row = (!zero_row && !from_ring) ? src_row : -1;
   float back_norm = 0.f;
-  const bool rec_all = P.nt <= PDEGYM_RING;
   const float dx = P.dx, dt = P.dt, F = P.F;
   // transport/Neumann reads u[t][-2] of the NEW (still zero) row, hyperbolic.py:144
   float bval = boundary_value<M64>(P, a, a64, 0.0f, neumann);
@@ -165,7 +164,7 @@ __global__ __launch_bounds__(kWave) void step1d_wide_kernel(pdegym_params1d P, p
     }
     return row_norm(row);
   };
-  const int thor_k = (P.reward_horizon == PDEGYM_HORIZON_T && P.reward_kind >= PDEGYM_REWARD_NORM_L1) ? P.reward_t_horizon : 0;
+  const int thor_k = thor_length(P);
   wave_lds_sync();
   if (thor_k > 0) {
     const float nk0 = kind_norm_row(cur);
@@ -226,7 +225,7 @@ __global__ __launch_bounds__(kWave) void step1d_wide_kernel(pdegym_params1d P, p
       float* hrow = hist + (size_t)t * n;
       for (int j = lane; j < n; j += kWave) hrow[j] = cur[j];
     }
-    if (s + 1 < nsub && (rec_all || k == 0 || t + PDEGYM_LOOKBACK == P.nt - 1)) {   // tuned_reward_1d.py:40 look-back rows
+    if (s + 1 < nsub && ring_records(P, k, t)) {
       const float nr = row_norm(cur);
       if (lane == 0) ring[t & (PDEGYM_RING - 1)] = nr;
       if (t == back_row) back_norm = nr;
@@ -238,11 +237,9 @@ __global__ __launch_bounds__(kWave) void step1d_wide_kernel(pdegym_params1d P, p
   }
   if (!neumann) bsum += (double)nsub * (double)fabsf(bval);
   const float norm_now = row_norm(cur);
-  if (nsub > 0 && (rec_all || k == 0 || t + PDEGYM_LOOKBACK == P.nt - 1)) {
-    if (lane == 0) ring[t & (PDEGYM_RING - 1)] = norm_now;
-  }
-  const bool terminate = t >= P.nt - 1;
-  const bool truncate = P.limit_state && (norm_now >= P.max_state);
+  if (nsub > 0 && ring_records(P, k, t) && lane == 0) ring[t & (PDEGYM_RING - 1)] = norm_now;
+  const bool terminate = step_terminates(P, t);
+  const bool truncate = step_truncates(P, norm_now);
   float nr_alt = norm_now;
   // "differential" horizon (norm_reward.py:55-59): after the last swap nxt still holds the row before the last sub-step
   const bool nr_diff = P.reward_horizon == PDEGYM_HORIZON_DIFFERENTIAL && P.reward_kind >= PDEGYM_REWARD_NORM_L1 && nsub > 0;
@@ -290,21 +287,10 @@ __global__ __launch_bounds__(kWave) void step1d_wide_kernel(pdegym_params1d P, p
       float* orow = obs_base + (size_t)inst * n;
       for (int j = lane; j < n; j += kWave) orow[j] = row[j];
     } else if (lane == 0) {
-      float o;
-      if (P.sensing == PDEGYM_SENSE_LAST) o = row[n - 1];
-      else if (P.sensing == PDEGYM_SENSE_LAST_DERIV) o = (row[n - 1] - row[n - 2]) / P.dx;
-      else if (P.sensing == PDEGYM_SENSE_FIRST_DERIV) o = (row[1] - row[0]) / P.dx;
-      else o = row[0];
-      obs_base[inst] = o;
+      obs_base[inst] = sensed_value(P, n, [&](int j) { return row[j]; });
     }
   };
-  if (lane == 0) {
-    if (P.reward_kind != PDEGYM_REWARD_NONE) Bf.reward[inst] = reward;
-    Bf.norm_now[inst] = norm_now;
-    Bf.norm_back[inst] = norm_back;
-    Bf.terminated[inst] = terminate ? 1 : 0;
-    Bf.truncated[inst] = truncate ? 1 : 0;
-  }
+  store_step_words(P, Bf, inst, lane, reward, norm_now, norm_back, terminate, truncate, true);
   if (!auto_reset) {
     if (nsub > 0 && urow)
       for (int j = lane; j < n; j += kWave) urow[j] = cur[j];
@@ -335,8 +321,7 @@ __global__ __launch_bounds__(kWave) void step1d_wide_kernel(pdegym_params1d P, p
       nxt[j] = v;
       if (urow) urow[j] = v;
     }
-    if (hist)
-      for (size_t q = lane; q < (size_t)P.nt * n; q += kWave) hist[q] = (q < (size_t)n) ? irow[q] : 0.f;
+    if (hist) wipe_history(hist, irow, P.nt, n, lane);
     wave_lds_sync();
     const float n0 = row_norm(nxt);
     emit_obs(Bf.obs, nxt);
@@ -375,14 +360,7 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void reset1d_kernel(pdegym_p
     Bf.norm_back[inst] = 0.f;
     Bf.terminated[inst] = 0;
     Bf.truncated[inst] = 0;
-    if (P.sensing != PDEGYM_SENSE_FULL) {
-      float o;
-      if (P.sensing == PDEGYM_SENSE_LAST) o = last;
-      else if (P.sensing == PDEGYM_SENSE_LAST_DERIV) o = (last - src[n - 2]) / P.dx;
-      else if (P.sensing == PDEGYM_SENSE_FIRST_DERIV) o = (src[1] - src[0]) / P.dx;
-      else o = src[0];
-      Bf.obs[inst] = o;
-    }
+    if (P.sensing != PDEGYM_SENSE_FULL) Bf.obs[inst] = sensed_value(P, n, [&](int j) { return src[j]; });
   }
 }
 
@@ -465,7 +443,7 @@ int launch_epl(const pdegym_params1d& P, const pdegym_bufs1d& Bf, int B, hipStre
     else
       hipLaunchKernelGGL((step1d_kernel<EPL, PARABOLIC, false, true, BURGERS>), grid, block, lds, st, P, Bf, B);
   } else {
-    constexpr bool kHasFull = EPL == 1 || EPL == 2 || EPL == 4 || EPL == 8;      // rows of 64 / 128 / 256 / 512 slots
+    constexpr bool kHasFull = epl_has_full(EPL);
     const bool full = kHasFull && P.n - (PARABOLIC ? 1 : 0) == kWave * EPL;
 #if defined(PDEGYM_HEAD_STAMPS) && PDEGYM_HEAD_STAMPS == 2
     constexpr bool kHead = false;
@@ -524,7 +502,7 @@ int launch_step(const pdegym_params1d* prm, const pdegym_bufs1d* buf, int B, voi
         else if (hist) hipLaunchKernelGGL((step1d_kernel<E, PARABOLIC, false, true, false, true>), grid, block, 0, st, P, *buf, B);
         else hipLaunchKernelGGL((step1d_kernel<E, PARABOLIC, false, false, false, true>), grid, block, 0, st, P, *buf, B);
       };
-      switch (epl64) {
+      switch (epl64) {      // not with_epl: this mode has only the power-of-two layouts {1, 2, 4, 8}, so 3 slots per lane run on 4 and 5 ... 7 on 8
         case 1: go(std::integral_constant<int, 1>{}); break;
         case 2: go(std::integral_constant<int, 2>{}); break;
         case 3: case 4: go(std::integral_constant<int, 4>{}); break;
@@ -541,19 +519,9 @@ int launch_step(const pdegym_params1d* prm, const pdegym_bufs1d* buf, int B, voi
   }
   const int nslots = P.n - (PARABOLIC ? 1 : 0);  // parabolic node 0 lives in a wave-uniform register
   const int epl = (nslots + kWave - 1) / kWave;
-  switch (epl) {
-    case 1: return launch_epl<1, PARABOLIC, BURGERS>(P, *buf, B, st);
-    case 2: return launch_epl<2, PARABOLIC, BURGERS>(P, *buf, B, st);
-    case 3: return launch_epl<3, PARABOLIC, BURGERS>(P, *buf, B, st);
-    case 4: return launch_epl<4, PARABOLIC, BURGERS>(P, *buf, B, st);
-    case 5: return launch_epl<5, PARABOLIC, BURGERS>(P, *buf, B, st);
-    case 6: return launch_epl<6, PARABOLIC, BURGERS>(P, *buf, B, st);
-    case 7: case 8: return launch_epl<8, PARABOLIC, BURGERS>(P, *buf, B, st);
-    case 9: case 10: case 11: case 12: return launch_epl<12, PARABOLIC, BURGERS>(P, *buf, B, st);
-    case 13: case 14: case 15: case 16: return launch_epl<16, PARABOLIC, BURGERS>(P, *buf, B, st);
-    case 17: case 18: case 19: case 20: case 21: case 22: case 23: case 24: return launch_epl<24, PARABOLIC, BURGERS>(P, *buf, B, st);
-    default: return launch_epl<32, PARABOLIC, BURGERS>(P, *buf, B, st);
-  }
+  int rc = 0;
+  with_epl<32>(epl, [&](auto tag) { rc = launch_epl<decltype(tag)::value, PARABOLIC, BURGERS>(P, *buf, B, st); });
+  return rc;
 }
 
 }  // namespace

@@ -29,12 +29,11 @@ __device__ __forceinline__ float mag_max(float a, float b) {
   const unsigned int ua = __float_as_uint(a), ub = __float_as_uint(b);
   return __uint_as_float(ua > ub ? ua : ub);
 }
+// (The overflow pre-check of step1d_body / carry_refresh_beta uses it too -- one v_max_u32 with a DPP operand per stage: a NaN that comes
+// through makes the pre-check's comparison fail, and the wave takes the exact loop.)
 __device__ __forceinline__ float wave_mag_max(float v) {
   return wave_reduce(v, [](float a, float b) { return mag_max(a, b); });
 }
-// The overflow pre-check's name for it (step1d_body, carry_refresh_beta; one v_max_u32 with a DPP operand per stage): a NaN that comes
-// through makes the pre-check's comparison fail, and the wave takes the exact loop.
-__device__ __forceinline__ float wave_max(float v) { return wave_mag_max(v); }
 
 // value of slot s when lane l holds slots [l*EPL, l*EPL+EPL)
 template <int EPL>
@@ -212,10 +211,52 @@ __device__ __forceinline__ void carry_refresh_beta(Carry<EPL>& C, const pdegym_p
   float cm = 0.f;
 #pragma unroll
   for (int e = 0; e < EPL; ++e) cm = fmaxf(cm, fabsf(P.dt * C.beta[e]));
-  C.cm = wave_max(cm);
+  C.cm = wave_mag_max(cm);
   C.glog = __log2f(growth_bound(P, C.cm));
   (void)s0;
   (void)ns;
+}
+
+// ---- step bookkeeping: the pieces around the sub-step loop that step1d_body (rows in registers) and step1d_wide_kernel (pdegym_1d.hip:
+// rows in LDS) both call.  Only pieces whose call leaves every register-resident kernel's instructions as they were; the look-back
+// plan, the reward selection, the NormReward norms and the beta redraw stay written out in both (docs/HISTORY.md, section 3).
+// rows whose norm a later reward call looks back at (tuned_reward_1d.py:40): r+100 is a step end
+__device__ __forceinline__ bool ring_records(const pdegym_params1d& P, int k, int t) {
+  return P.nt <= PDEGYM_RING || k == 0 || t + PDEGYM_LOOKBACK == P.nt - 1;
+}
+// NormReward "t-horizon" (norm_reward.py:60-73): the length that applies (0: another reward)
+__device__ __forceinline__ int thor_length(const pdegym_params1d& P) {
+  return (P.reward_horizon == PDEGYM_HORIZON_T && P.reward_kind >= PDEGYM_REWARD_NORM_L1) ? P.reward_t_horizon : 0;
+}
+__device__ __forceinline__ bool step_terminates(const pdegym_params1d& P, int t) { return t >= P.nt - 1; }   // hyperbolic.py:171-180
+__device__ __forceinline__ bool step_truncates(const pdegym_params1d& P, float norm_now) {                   // hyperbolic.py:182-194
+  return P.limit_state && (norm_now >= P.max_state);
+}
+// The scalar observation of sensing_update (hyperbolic.py:72-116) from a node accessor: node(j) = u[j] of the row's n nodes
+// (the memory-resident forms: step1d_wide_kernel, reset1d_kernel; step1d_body's, whose accessor shuffles, is written out there).
+template <typename NodeF>
+__device__ __forceinline__ float sensed_value(const pdegym_params1d& P, int n, NodeF&& node) {
+  if (P.sensing == PDEGYM_SENSE_LAST) return node(n - 1);
+  if (P.sensing == PDEGYM_SENSE_LAST_DERIV) return (node(n - 1) - node(n - 2)) / P.dx;
+  if (P.sensing == PDEGYM_SENSE_FIRST_DERIV) return (node(1) - node(0)) / P.dx;
+  return node(0);
+}
+// What lane 0 stores of every step: reward, flags, and (store_state: not overwritten by a later step of the same launch) the norms.
+__device__ __forceinline__ void store_step_words(const pdegym_params1d& P, const pdegym_bufs1d& Bf, int inst, int lane, float reward,
+                                                 float norm_now, float norm_back, bool terminate, bool truncate, bool store_state) {
+  if (lane == 0) {
+    if (P.reward_kind != PDEGYM_REWARD_NONE) Bf.reward[inst] = reward;
+    if (store_state) {
+      Bf.norm_now[inst] = norm_now;
+      Bf.norm_back[inst] = norm_back;
+    }
+    Bf.terminated[inst] = terminate ? 1 : 0;
+    Bf.truncated[inst] = truncate ? 1 : 0;
+  }
+}
+// Fused auto-reset: the trajectory restarts -- history = zeros((nt, n)); history[0] = the pool row (hyperbolic.py:214-217)
+__device__ __forceinline__ void wipe_history(float* hist, const float* irow, int nt, int n, int lane) {
+  for (size_t q = lane; q < (size_t)nt * n; q += kWave) hist[q] = (q < (size_t)n) ? irow[q] : 0.f;
 }
 
 // The reward's own norm of a register-resident row (NormReward kinds; same expressions as the epilogue of step1d_body), for the
@@ -684,7 +725,7 @@ __device__ __forceinline__ void step1d_body(const pdegym_params1d& P, const pdeg
   // NormReward "t-horizon" (norm_reward.py:60-73): the ring holds the reward's own norm of the rows the mean looks back at --
   // the row this call starts from (recorded here: independent of how the previous call or the reset left the slot), the last
   // rows of the sub-step loop, the final row (epilogue).  Select-form instantiations only, like "differential".
-  const int thor_k = (!kFast && P.reward_horizon == PDEGYM_HORIZON_T && P.reward_kind >= PDEGYM_REWARD_NORM_L1) ? P.reward_t_horizon : 0;
+  const int thor_k = kFast ? 0 : thor_length(P);
   if constexpr (!kFast) {
     if (thor_k > 0) {
       const float nk0 = kind_norm<EPL>(R.x, R.bl, s0, ns, P.reward_kind);
@@ -719,8 +760,8 @@ __device__ __forceinline__ void step1d_body(const pdegym_params1d& P, const pdeg
           mx = fmaxf(mx, fabsf(R.x[e]));
           cm = fmaxf(cm, fabsf(P.dt * beta[e]));
         }
-        mx = wave_max(mx);
-        cm = wave_max(cm);
+        mx = wave_mag_max(mx);
+        cm = wave_mag_max(cm);
       }
       if constexpr (CARRY) {
         // log2 g is carried, and log2 mx is only formed when the bound could matter: mx <= 2^40 and nsub log2 g <= 80 give
@@ -778,12 +819,9 @@ __device__ __forceinline__ void step1d_body(const pdegym_params1d& P, const pdeg
   const int t = R.t;
 
   // ---- epilogue: norms, flags, reward, observation ------------------------------------------------
-  const bool rec_all = P.nt <= PDEGYM_RING;
-  if (nsub > 0 && (rec_all || R.k == 0 || t + PDEGYM_LOOKBACK == P.nt - 1)) {
-    ring.put(t & (PDEGYM_RING - 1), norm_now, lane);
-  }
-  const bool terminate = t >= P.nt - 1;                                 // hyperbolic.py:171-180
-  const bool truncate = P.limit_state && (norm_now >= P.max_state);     // hyperbolic.py:182-194
+  if (nsub > 0 && ring_records(P, R.k, t)) ring.put(t & (PDEGYM_RING - 1), norm_now, lane);
+  const bool terminate = step_terminates(P, t);
+  const bool truncate = step_truncates(P, norm_now);
   // NormReward variants need wave-wide reductions: do them before the single-lane tail
   float nr_alt = norm_now;
   bool nr_diff = false;
@@ -864,15 +902,7 @@ __device__ __forceinline__ void step1d_body(const pdegym_params1d& P, const pdeg
       if (lane == 0) obs_base[inst] = o;
     }
   };
-  if (lane == 0) {
-    if (P.reward_kind != PDEGYM_REWARD_NONE) Bf.reward[inst] = reward;
-    if (store_state) {
-      Bf.norm_now[inst] = norm_now;
-      Bf.norm_back[inst] = norm_back;
-    }
-    Bf.terminated[inst] = terminate ? 1 : 0;
-    Bf.truncated[inst] = truncate ? 1 : 0;
-  }
+  store_step_words(P, Bf, inst, lane, reward, norm_now, norm_back, terminate, truncate, store_state);
   if (!auto_reset) {
     if (nsub > 0 && urow) {
       if (PARABOLIC && lane == 0) urow[0] = R.bl;
@@ -922,8 +952,7 @@ __device__ __forceinline__ void step1d_body(const pdegym_params1d& P, const pdeg
       if (s0 + e < ns && urow) urow[J0 + s0 + e] = R.x[e];
     }
     if constexpr (HIST) {
-      if (hist)
-        for (size_t q = lane; q < (size_t)P.nt * n; q += kWave) hist[q] = (q < (size_t)n) ? irow[q] : 0.f;
+      if (hist) wipe_history(hist, irow, P.nt, n, lane);
     }
     const float n0 = sqrtf(slots_sumsq<EPL>(R.x, s0, ns) + R.bl * R.bl);
     const float last = node(n - 1);
@@ -979,6 +1008,28 @@ __device__ __forceinline__ void carry_store_ring(const Carry<EPL>& C, const pdeg
   ring[lane] = C.ring.lo;
   ring[kWave + lane] = C.ring.hi;
 }
+
+// ---- host side: the slots-per-lane ladder, once: f(std::integral_constant<int, E>) for the E that serves a float32 row of epl =
+// ceil(slots / 64) slots per lane.  The step launcher and every rollout launcher pick through it: the norm reductions, hence the
+// rewards, depend on the layout.  MAX_E = 32: every row; MAX_E = 8: the kernels that carry a controller (longer rows were refused).
+template <int MAX_E, typename F>
+inline void with_epl(int epl, F&& f) {
+  if (epl <= 1) f(std::integral_constant<int, 1>{});
+  else if (epl <= 2) f(std::integral_constant<int, 2>{});
+  else if (epl <= 3) f(std::integral_constant<int, 3>{});
+  else if (epl <= 4) f(std::integral_constant<int, 4>{});
+  else if (epl <= 5) f(std::integral_constant<int, 5>{});
+  else if (epl <= 6) f(std::integral_constant<int, 6>{});
+  else if (MAX_E == 8 || epl <= 8) f(std::integral_constant<int, 8>{});
+  else if constexpr (MAX_E == 32) {
+    if (epl <= 12) f(std::integral_constant<int, 12>{});
+    else if (epl <= 16) f(std::integral_constant<int, 16>{});
+    else if (epl <= 24) f(std::integral_constant<int, 24>{});
+    else f(std::integral_constant<int, 32>{});
+  }
+}
+// E with a FULL instantiation: rows of exactly 64 / 128 / 256 / 512 slots, whose slot masks fold away
+constexpr bool epl_has_full(int E) { return E == 1 || E == 2 || E == 4 || E == 8; }
 
 }  // namespace
 #endif

@@ -1,6 +1,7 @@
 // pdegym_1d_rollout.h -- what the one-launch 1D rollout units share (pdegym_1d_rollout.hip: open loop and with the MLP policy inside;
 // pdegym_backstep_rollout.hip: with the backstepping law inside), one copy of each: the sensing noise, the carried row's way to LDS, the
-// per-step view of the rollout arrays, the checks of the plant, the slots-per-lane ladder.  Kernels and launches stay in the .hip files.
+// per-step view of the rollout arrays, the checks of the plant.  (The slots-per-lane ladder, with_epl / epl_has_full, is the step launcher's
+// too: pdegym_1d_body.h.)  Kernels and launches stay in the .hip files.
 #pragma once
 #include <cstdio>
 
@@ -68,27 +69,5 @@ inline int check_rollout_plant(const pdegym_params1d& P, const pdegym_bufs1d& bu
   if (P.reward_kind != PDEGYM_REWARD_NONE && !ro.rewards) return fail(-3, "null reward buffer");
   return 0;
 }
-
-// The slots-per-lane ladder, once: f(std::integral_constant<int, E>) for the E launch_step (pdegym_1d.hip) picks for a row of epl =
-// ceil(slots / 64) slots per lane -- the norm reductions, hence the rewards, depend on the layout, so another E would not reproduce the step
-// calls.  MAX_E = 32: every row; MAX_E = 8: the kernels that carry a controller, whose entry points have refused longer rows.
-template <int MAX_E, typename F>
-inline void with_rollout_epl(int epl, F&& f) {
-  if (epl <= 1) f(std::integral_constant<int, 1>{});
-  else if (epl <= 2) f(std::integral_constant<int, 2>{});
-  else if (epl <= 3) f(std::integral_constant<int, 3>{});
-  else if (epl <= 4) f(std::integral_constant<int, 4>{});
-  else if (epl <= 5) f(std::integral_constant<int, 5>{});
-  else if (epl <= 6) f(std::integral_constant<int, 6>{});
-  else if (MAX_E == 8 || epl <= 8) f(std::integral_constant<int, 8>{});
-  else if constexpr (MAX_E == 32) {
-    if (epl <= 12) f(std::integral_constant<int, 12>{});
-    else if (epl <= 16) f(std::integral_constant<int, 16>{});
-    else if (epl <= 24) f(std::integral_constant<int, 24>{});
-    else f(std::integral_constant<int, 32>{});
-  }
-}
-// E with a FULL instantiation: rows of exactly 64 / 128 / 256 / 512 slots, whose slot masks fold away
-constexpr bool epl_has_full(int E) { return E == 1 || E == 2 || E == 4 || E == 8; }
 
 }  // namespace

@@ -208,7 +208,7 @@ int launch_rollout(const pdegym_params1d* prm, const pdegym_bufs1d* buf, const p
     };
     constexpr std::true_type yes{};
     constexpr std::false_type no{};
-    with_rollout_epl<8>(epl, [&](auto tag) {
+    with_epl<8>(epl, [&](auto tag) {
       constexpr int E = decltype(tag)::value;
       auto carried = [&](auto wide_tag, auto full_tag) {
         constexpr bool W = decltype(wide_tag)::value, F = decltype(full_tag)::value;
@@ -236,7 +236,7 @@ int launch_rollout(const pdegym_params1d* prm, const pdegym_bufs1d* buf, const p
   }
   const dim3 grid((B + kWavesPerBlock - 1) / kWavesPerBlock), block(kWave * kWavesPerBlock);
   // the same slots-per-lane choice as launch_step: the norm reductions (hence rewards) depend on the layout
-  with_rollout_epl<32>(epl, [&](auto tag) {
+  with_epl<32>(epl, [&](auto tag) {
     constexpr int E = decltype(tag)::value;
     if constexpr (epl_has_full(E)) {
       if (!general && nslots == kWave * E) {

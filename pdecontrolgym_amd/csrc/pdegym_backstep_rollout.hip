@@ -107,7 +107,7 @@ int launch_backstep_rollout(const pdegym_params1d* prm, const pdegym_bufs1d* buf
   const int epl = (nslots + kWave - 1) / kWave;      // the slots-per-lane choice of launch_step / launch_rollout: rewards depend on it
   const bool ordered = L.order == PDEGYM_BACKSTEP_ORDERED;
   const dim3 grid((B + kWavesPerBlock - 1) / kWavesPerBlock), block(kWave * kWavesPerBlock);
-  with_rollout_epl<8>(epl, [&](auto tag) {      // (more than 8 was refused above)
+  with_epl<8>(epl, [&](auto tag) {      // (more than 8 was refused above)
     constexpr int E = decltype(tag)::value;
     constexpr bool kHasFull = epl_has_full(E);
     if (kHasFull && nslots == kWave * E) {

@@ -2,9 +2,12 @@
 """Differential fuzz of the 1D step kernels against the NumPy oracle (test infrastructure; run on a GPU box):
 random grid sizes, sub-step counts, episode lengths (incl. nt <= 128 and episodes that end mid-step), control / sensing
 modes, normalisation, truncation thresholds, shared or per-instance beta, zero / tiny / large states, history recording and
-the fused auto-reset.  Rows, observations and flags must agree bit for bit, rewards to rtol 1e-6.
+the fused auto-reset.  Rows, observations and flags must agree bit for bit, rewards to rtol 2e-6.
 
     python tests/fuzz_1d.py [seconds] [seed]
+
+draw_case draws a case into a plain dict, run_case runs such a dict against the oracle (tests/test_gpu_1d_wide_bookkeeping.py
+runs dicts it writes out itself); one_case is the two in a row.
 """
 import os
 import sys
@@ -19,7 +22,9 @@ from pdecontrolgym_amd import _native as N  # noqa: E402
 from pdecontrolgym_amd.batch1d import PDEBatch1D, RewardSpec  # noqa: E402
 
 
-def one_case(rng, idx):
+def draw_case(rng, idx):
+    """One random case as a dict (None: no case for this draw).  The control inputs are not in it: run_case draws them step by step
+    from the same generator, so the stream after a case that ends early (reference look-back raises) stays what it always was."""
     kind = rng.choice(["parabolic", "transport", "burgers"])
     flux = "burgers" if kind == "burgers" else "linear"
     base = "parabolic" if kind == "parabolic" else "transport"
@@ -74,31 +79,50 @@ def one_case(rng, idx):
     rargs = (nt - 1, float(rng.choice([-1e3, -1e-4])), float(rng.choice([3e2, 1e2])))
     # reward evaluated in the kernel epilogue: TunedReward1D, or NormReward "temporal" with the 1 / 2 / inf norm
     rkind = str(rng.choice(["tuned", "tuned", "tuned", "n1", "n2", "ninf"]))
-    rcode = {"tuned": N.REWARD_TUNED1D, "n1": N.REWARD_NORM_L1, "n2": N.REWARD_NORM_L2, "ninf": N.REWARD_NORM_LINF}[rkind]
     # ... or its "differential" horizon on every other NormReward case (no extra draw: the case stream stays what it was)
     # ... and "t-horizon" (mean of the last k row norms, k from the case index) on every fourth
     hz = "temporal" if rkind == "tuned" else ("t-horizon" if idx % 4 == 3 else ("differential" if idx % 2 == 1 else "temporal"))
-    hcode = {"temporal": N.HORIZON_TEMPORAL, "differential": N.HORIZON_DIFFERENTIAL, "t-horizon": N.HORIZON_T}[hz]
     klen = (1, 3, 7, 40, 128)[(idx // 4) % 5]
-    mk_reward = (lambda: po.TunedReward1DOracle(*rargs)) if rkind == "tuned" else \
-        (lambda: po.NormRewardOracle(rargs[0], {"n1": "1", "n2": "2", "ninf": "inf"}[rkind], rargs[1], rargs[2], hz, klen))
     # the reference's mixed-precision modes: float64 plant parameter, float64 / Python-scalar control input
     beta64 = bool(rng.random() < 0.2)
     akind = str(rng.choice(["f32", "f32", "f32", "f64", "weak"]))
-    acode = {"f32": N.ACTION_F32, "f64": N.ACTION_F64, "weak": N.ACTION_WEAK}[akind]
     if beta64:
         beta = amp * rng.uniform(0, 1) * np.cos(rng.uniform(1, 8.5, (1 if shared else B, 1)) * np.arccos(x))
     hist = bool(rng.random() < 0.25)
     auto = bool(rng.random() < 0.35)          # fused VecEnv auto-reset from a pool of initial rows
-    ocls = {"parabolic": po.ParabolicOracle, "transport": po.TransportOracle, "burgers": po.BurgersOracle}[kind]
-    okw = {k: kw[k] for k in ("T", "dt", "X", "dx", "control_sample_rate", "control_type", "sensing_loc", "sensing_type", "normalize",
-                              "max_control_value", "limit_pde_state_size", "max_state_value")}
     P = B * int(rng.choice([1, 1, 2, 3]))           # pool rows: the k-th restart of instance b takes row (b + k*B) mod P
     pool = (rng.uniform(0.1, 3, (P, 1)) * np.ones((1, n))).astype(np.float32)
     use_bpool = auto and (not shared) and bool(rng.random() < 0.5)
     bpool = (amp * rng.uniform(0, 1) * np.cos(rng.uniform(1, 8.5, (P, 1)) * np.arccos(x)))
     bpool = bpool if beta64 else bpool.astype(np.float32)
-    desc = f"#{idx} P={P} bpool={use_bpool} reward={rkind}/{hz}{klen if hz == 't-horizon' else ''} beta64={beta64} act={akind} auto={auto} {kind} nx={nx} S={S} nt={nt} B={B} {ctrl} {sloc}/{kw['sensing_type']} norm={normalize} limit={limit}/{max_state} ic={style} hist={hist} shared_beta={shared}"
+    case = dict(idx=idx, kind=kind, kw=kw, nx=nx, S=S, nt=nt, B=B, nsteps=nsteps, ic=style, init=init, beta=beta, shared=shared, rargs=rargs,
+                rkind=rkind, hz=hz, klen=klen, beta64=beta64, akind=akind, hist=hist, auto=auto, P=P, pool=pool, use_bpool=use_bpool,
+                bpool=bpool, actions=None)
+    return case
+
+
+def describe(c):
+    kw = c["kw"]
+    return f"#{c['idx']} P={c['P']} bpool={c['use_bpool']} reward={c['rkind']}/{c['hz']}{c['klen'] if c['hz'] == 't-horizon' else ''} beta64={c['beta64']} act={c['akind']} auto={c['auto']} {c['kind']} nx={c['nx']} S={c['S']} nt={c['nt']} B={c['B']} {kw['control_type']} {kw['sensing_loc']}/{kw['sensing_type']} norm={kw['normalize']} limit={kw['limit_pde_state_size']}/{kw['max_state_value']} ic={c['ic']} hist={c['hist']} shared_beta={c['shared']}"
+
+
+def run_case(c, rng=None, record=None):
+    """Run a case dict on the GPU and against the oracle; returns its description (ending in ")" when the reference refuses the
+    options or its look-back raises).  c["actions"]: the control input of each of the nsteps + 1 steps, or None to draw them from rng.
+    record: a list that receives every tensor the engine hands out, step by step, as NumPy arrays (for library A/B runs)."""
+    kind, kw, B, nsteps, init, beta, shared, rargs = c["kind"], c["kw"], c["B"], c["nsteps"], c["init"], c["beta"], c["shared"], c["rargs"]
+    rkind, hz, klen, akind, hist, auto, P, pool, use_bpool, bpool = (c[k] for k in ("rkind", "hz", "klen", "akind", "hist", "auto", "P", "pool", "use_bpool", "bpool"))
+    flux = "burgers" if kind == "burgers" else "linear"
+    base = "parabolic" if kind == "parabolic" else "transport"
+    rcode = {"tuned": N.REWARD_TUNED1D, "n1": N.REWARD_NORM_L1, "n2": N.REWARD_NORM_L2, "ninf": N.REWARD_NORM_LINF}[rkind]
+    hcode = {"temporal": N.HORIZON_TEMPORAL, "differential": N.HORIZON_DIFFERENTIAL, "t-horizon": N.HORIZON_T}[hz]
+    acode = {"f32": N.ACTION_F32, "f64": N.ACTION_F64, "weak": N.ACTION_WEAK}[akind]
+    mk_reward = (lambda: po.TunedReward1DOracle(*rargs)) if rkind == "tuned" else \
+        (lambda: po.NormRewardOracle(rargs[0], {"n1": "1", "n2": "2", "ninf": "inf"}[rkind], rargs[1], rargs[2], hz, klen))
+    ocls = {"parabolic": po.ParabolicOracle, "transport": po.TransportOracle, "burgers": po.BurgersOracle}[kind]
+    okw = {k: kw[k] for k in ("T", "dt", "X", "dx", "control_sample_rate", "control_type", "sensing_loc", "sensing_type", "normalize",
+                              "max_control_value", "limit_pde_state_size", "max_state_value")}
+    desc = describe(c)
     try:
         orc = ocls(reward=mk_reward(), keep_history=True, **okw)
     except Exception as ex:      # invalid option combination: the product must refuse it too
@@ -116,8 +140,11 @@ def one_case(rng, idx):
         env.enable_auto_reset(torch.tensor(pool), keep_final_obs=True, beta_pool=torch.tensor(bpool) if use_bpool else None)
         cnt = np.zeros(B, dtype=np.int64)
     for i in range(nsteps + 1):
-        a = rng.uniform(-1, 1, B) * float(rng.choice([1.0, 0.0, 10.0]))
-        a = a.astype(np.float32) if akind == "f32" else a
+        if c["actions"] is not None:
+            a = c["actions"][i]
+        else:
+            a = rng.uniform(-1, 1, B) * float(rng.choice([1.0, 0.0, 10.0]))
+            a = a.astype(np.float32) if akind == "f32" else a
         try:
             with np.errstate(all="ignore"):
                 o_ref, r_ref, te_ref, tr_ref = orc.step(a, action_kind=akind)
@@ -150,6 +177,10 @@ def one_case(rng, idx):
                 orf = orf.copy()
                 orf[done] = fresh_obs[done]
         row_g, row_o = env.u.cpu().numpy(), orc.row
+        if record is not None:
+            record += [og.copy(), r_gpu.cpu().numpy(), te_gpu.cpu().numpy(), tr_gpu.cpu().numpy(), row_g.copy(), env.time_index.cpu().numpy()]
+            record += [env.t[k].cpu().numpy() for k in ("norm_now", "norm_back", "bsum", "ring")]
+            record += [env.t["final_obs"].cpu().numpy()] if auto else []
         if not np.array_equal(row_g.view(np.uint32), row_o.view(np.uint32)):
             bad = np.argwhere(row_g.view(np.uint32) != row_o.view(np.uint32))
             # NaN payloads may differ; anything else is a failure
@@ -170,7 +201,14 @@ def one_case(rng, idx):
         hg, ho = env.t["history"].cpu().numpy(), orc.hist
         fin = ~(np.isnan(hg) & np.isnan(ho))
         assert np.array_equal(hg.view(np.uint32)[fin], ho.view(np.uint32)[fin]), desc + ": history differs"
+        if record is not None:
+            record.append(hg.copy())
     return desc
+
+
+def one_case(rng, idx):
+    c = draw_case(rng, idx)
+    return None if c is None else run_case(c, rng)
 
 
 if __name__ == "__main__":

@@ -25,11 +25,12 @@ from tests import poison as PZ
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-# kernel (template name as launched) -> tests of this module that reach at least one of its instantiations
+# kernel (template name as launched) -> tests that reach at least one of its instantiations: of this module, or "module::test" of
+# another module under tests/
 KERNEL_CASES = {
     "step1d_kernel": ["test_1d_step_contract", "test_1d_full_rows", "test_1d_m64_contract", "test_1d_state_in_leaves_u_alone",
                       "test_1d_auto_reset_final_obs_and_pools", "test_1d_reward_none_leaves_reward_alone"],
-    "step1d_wide_kernel": ["test_1d_wide_kernels"],
+    "step1d_wide_kernel": ["test_1d_wide_kernels", "test_gpu_1d_wide_bookkeeping::test_wide_kernel_bookkeeping_matches_oracle"],
     "reset1d_kernel": ["test_1d_masked_reset_leaves_others_alone", "test_1d_reset_initialises_poisoned_state"],
     "reset_history_kernel": ["test_1d_masked_reset_leaves_others_alone", "test_1d_step_contract"],
     "rownorm2_kernel": ["test_rownorm2_ragged"],

@@ -1,4 +1,4 @@
-"""The slots-per-lane ladder of the one-launch 1D rollouts (csrc/pdegym_1d_rollout.h: with_rollout_epl) against the step launcher's.
+"""The slots-per-lane ladder of the one-launch 1D rollouts (csrc/pdegym_1d_body.h: with_epl, which the step launcher picks through too) against the step launcher's.
 
 The reward is a wave reduction whose bits depend on how many slots a lane holds, so a rollout kernel has to be instantiated with the
 slots-per-lane count the step launcher picks for the same row length: one rollout call equals the step calls BIT FOR BIT --

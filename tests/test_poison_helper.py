@@ -123,5 +123,10 @@ def test_every_launched_kernel_is_in_the_contract_suite():
     assert not missing, f"kernels without a case in test_gpu_buffer_contract.KERNEL_CASES: {missing}"
     stale = sorted(set(C.KERNEL_CASES) - launched)
     assert not stale, f"KERNEL_CASES names kernels nothing launches: {stale}"
+    import importlib
+
+    def named(t):      # "test" of the contract module, or "module::test" of another module under tests/
+        mod, _, name = t.rpartition("::")
+        return getattr(importlib.import_module("tests." + mod) if mod else C, name, None)
     for k, tests in C.KERNEL_CASES.items():
-        assert tests and all(callable(getattr(C, t, None)) for t in tests), (k, tests)
+        assert tests and all(callable(named(t)) for t in tests), (k, tests)

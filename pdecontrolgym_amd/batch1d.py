@@ -21,6 +21,7 @@ from dataclasses import dataclass
 
 from . import _native as N
 from .checkpoint import EngineCheckpoint
+from .policy import fits_rollout_kernel
 
 
 @dataclass
@@ -315,8 +316,7 @@ class PDEBatch1D(EngineCheckpoint):
     def policy_fits_rollout(self, policy) -> bool:
         """Whether ``policy`` (a ``FusedMLP``) can be evaluated inside the rollout kernel (``FusedMLP.fits_rollout``): the
         observation (the row of at most 513 nodes, or the one sensed value) as its input and one output."""
-        fits = getattr(policy, "fits_rollout", None)
-        return fits is not None and self.can_rollout() and fits(self.obs_dim, 1) and self.n <= 513
+        return self.can_rollout() and self.n <= 513 and fits_rollout_kernel(policy, self.obs_dim, 1)
 
     def law_rollout_gap(self, law):
         """What keeps ``law`` (a ``BacksteppingController``) out of the one-launch rollout kernel with the control law inside

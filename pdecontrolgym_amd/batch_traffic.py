@@ -11,6 +11,7 @@ import numpy as np
 from . import _native as N
 from .checkpoint import EngineCheckpoint
 from .hostio import PackLayout, as_kernel_input
+from .policy import fits_rollout_kernel
 
 
 class TrafficBatch(EngineCheckpoint):
@@ -116,8 +117,7 @@ class TrafficBatch(EngineCheckpoint):
     def policy_fits_rollout(self, policy) -> bool:
         """Whether ``policy`` (a ``FusedMLP``) can run inside the rollout kernel (``FusedMLP.fits_rollout``): 2M inputs, one
         output per command."""
-        fits = getattr(policy, "fits_rollout", None)
-        return fits is not None and self.can_rollout() and fits(2 * self.M, self.action_dim)
+        return self.can_rollout() and fits_rollout_kernel(policy, 2 * self.M, self.action_dim)
 
     def law_rollout_gap(self, controller):
         """What keeps ``controller`` (a ``TrafficBacksteppingController``) out of the one-launch rollout kernel with the control

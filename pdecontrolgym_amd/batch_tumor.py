@@ -11,6 +11,7 @@ import numpy as np
 from . import _native as N
 from .checkpoint import EngineCheckpoint
 from .hostio import PackLayout, as_kernel_input
+from .policy import fits_rollout_kernel
 
 
 class TumorBatch(EngineCheckpoint):
@@ -133,11 +134,7 @@ class TumorBatch(EngineCheckpoint):
         """Whether ``policy`` (a ``FusedMLP``) can run inside the rollout kernel: nx inputs, one output, layers of at most 256 units
         (``FusedMLP.fits_rollout``), and the policy's LDS plus this engine's two float64 rows for each of a workgroup's 16 patients
         within the kernel's 160 KB."""
-        fits = getattr(policy, "fits_rollout", None)
-        if fits is None or not self.can_rollout() or not fits(self.nx, 1):
-            return False
-        rows = 16 * 2 * self.nx * 8
-        return (policy.rollout_lds_bytes(self.nx) + 15) // 16 * 16 + rows <= policy.ROLLOUT_LDS_BYTES
+        return self.can_rollout() and fits_rollout_kernel(policy, self.nx, 1, extra_lds_bytes=16 * 2 * self.nx * 8)
 
     def _wrap(self, wrap_state):
         gap = self.rollout_gap()

@@ -79,44 +79,12 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void rollout1d_general_kerne
 
 
 // ================================================================================================
-// ---- the policy inside the rollout kernel (pdegym_policy.h) -----------------------------------------------------------------
-// What a wave of a policy kernel keeps for the T evaluations: the staged network (narrow) and its strips of LDS -- xw, the policy's input
-// (od values, zero-padded to a multiple of four), and hw, the hidden activations.  (WIDE: the cooperative set-up, pdegym_policy::Wide, stays an
-// object of its own: eval_wide indexes its H[] at run time, which keeps it in scratch, and what shared its aggregate would live there too.)
-struct PolicyWave {
-  pdegym_policy::Staged St;
-  float *xw, *hw;
-};
-
-// Prologue of the two policy kernels; false for a wave that has nothing more to do: a narrow network's wave without an instance.  WIDE: a layer of
-// more than 64 units, evaluated by the 16 waves together (eval_wide) -- every wave, with or without an instance, runs all T iterations (barriers).
-template <bool WIDE>
-__device__ __forceinline__ bool policy_prologue(PolicyWave& W, pdegym_policy::Wide& Wd, const pdegym_mlp& N, float* smem, int od, bool active,
-                                                int wave, int lane) {
-  namespace pol = pdegym_policy;
-  const int xpad = pol::xpad(od);
-  if constexpr (WIDE) Wd = pol::wide_setup(N, smem, od, wave, lane);
-  else W.St = pol::stage(N, smem);      // the launch's only barrier
-  if (!WIDE && !active) return false;
-  W.xw = WIDE ? Wd.X + wave * Wd.ldx : smem + W.St.end + wave * (xpad + 2 * pol::kMaxWidth);
-  W.hw = W.xw + xpad;
-  if (!WIDE)
-    for (int j = od + lane; j < xpad; j += kWave) W.xw[j] = 0.f;     // zero padding to a multiple of four: written once
-  return true;
-}
-
-// The network on the wave's input row: neuron 0 of the last layer (every wave of a WIDE workgroup calls it: barriers inside).
-template <bool WIDE>
-__device__ __forceinline__ float policy_eval(const PolicyWave& W, const pdegym_policy::Wide& Wd, const pdegym_mlp& N, const float* smem, int od,
-                                             int wave, int lane) {
-  if constexpr (WIDE) return pdegym_policy::eval_wide(N, Wd, od, wave, lane);
-  else return lane_value(pdegym_policy::eval(N, W.St, smem, W.xw, W.hw, od, lane), 0);
-}
-
-// ... and its way to a command: + noise[t, b], clamped, stored to actions[t, b].
+// ---- the policy inside the rollout kernel (pdegym_policy.h: prologue, evaluate, command, shaped) ----------------------------------
+// A wave without an instance of a WIDE workgroup stays in the loop of T iterations and `continue`s behind the evaluation (not
+// pdegym_policy::attend, the traffic and tumor kernels' way: here the loop's form is the quicker one, profiles/policy_host_resources.txt).
+// The network's output on its way to the command of step t: + noise[t, b], clamped, stored to actions[t, b].
 __device__ __forceinline__ float policy_command(float a, const pdegym_mlp& N, const pdegym_rollout1d& Ro, int B, int inst, int lane, int t) {
-  if (N.noise) a += N.noise[((size_t)t * B + inst) * N.noise_stride];
-  if (N.clamp) a = pdegym::clip_keep_nan(a, N.lo, N.hi);
+  a = pdegym_policy::shaped(a, N, t, B, inst, 0);
   if (lane == 0) Ro.actions[(size_t)t * B + inst] = a;
   return a;
 }
@@ -124,14 +92,15 @@ __device__ __forceinline__ float policy_command(float a, const pdegym_mlp& N, co
 template <int EPL, bool PARABOLIC, bool BURGERS, bool WIDE, bool FULL>
 __global__ __launch_bounds__(kWave* pdegym_policy::kWaves) void rollout1d_policy_kernel(pdegym_params1d P, pdegym_bufs1d Bf,
                                                                                         pdegym_rollout1d Ro, pdegym_mlp N, int B) {
+  namespace pol = pdegym_policy;
   extern __shared__ __attribute__((aligned(16))) float pol_smem[];
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
-  const int inst = blockIdx.x * pdegym_policy::kWaves + wave;
+  const int inst = blockIdx.x * pol::kWaves + wave;
   const bool active = inst < B;           // wave-uniform
   const int n = P.n;                      // (the kernel argument even under FULL: stage_carried_row)
-  PolicyWave W;
-  pdegym_policy::Wide Wd;
-  if (!policy_prologue<WIDE>(W, Wd, N, pol_smem, n, active, wave, lane)) return;
+  pol::PolicyWave W;
+  pol::Wide Wd;
+  if (!pol::prologue<WIDE>(W, Wd, N, pol_smem, n, active, wave, lane)) return;
   const size_t slot = (size_t)B * n;
   Carry<EPL> C;       // the state stays in registers over the T env-steps (see rollout1d_kernel)
   if (active) carry_load<EPL, PARABOLIC, FULL>(C, P, Bf, Ro.obs, inst, lane);
@@ -140,7 +109,7 @@ __global__ __launch_bounds__(kWave* pdegym_policy::kWaves) void rollout1d_policy
       stage_carried_row<EPL, PARABOLIC>(C, W.xw, n, lane);
       sense_noise(Ro.obs_noise, Ro.obs_seen, W.xw, n, B, inst, lane, t);
     }
-    float a = policy_eval<WIDE>(W, Wd, N, pol_smem, n, wave, lane);
+    float a = pol::command<WIDE>(pol::evaluate<WIDE>(W, Wd, N, pol_smem, n, wave, lane), Wd, wave, 0);
     if (!active) continue;
     a = policy_command(a, N, Ro, B, inst, lane, t);
     const pdegym_bufs1d S = rollout_step_view(Bf, Ro, B, slot, t);
@@ -154,14 +123,15 @@ __global__ __launch_bounds__(kWave* pdegym_policy::kWaves) void rollout1d_policy
 template <int EPL, bool PARABOLIC, bool NEUMANN, bool BURGERS, bool WIDE>
 __global__ __launch_bounds__(kWave* pdegym_policy::kWaves) void rollout1d_policy_general_kernel(pdegym_params1d P, pdegym_bufs1d Bf,
                                                                                                 pdegym_rollout1d Ro, pdegym_mlp N, int B) {
+  namespace pol = pdegym_policy;
   extern __shared__ __attribute__((aligned(16))) float pol_smem[];
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
-  const int inst = blockIdx.x * pdegym_policy::kWaves + wave;
+  const int inst = blockIdx.x * pol::kWaves + wave;
   const bool active = inst < B;           // wave-uniform
   const int od = P.sensing == PDEGYM_SENSE_FULL ? P.n : 1;
-  PolicyWave W;
-  pdegym_policy::Wide Wd;
-  if (!policy_prologue<WIDE>(W, Wd, N, pol_smem, od, active, wave, lane)) return;
+  pol::PolicyWave W;
+  pol::Wide Wd;
+  if (!pol::prologue<WIDE>(W, Wd, N, pol_smem, od, active, wave, lane)) return;
   for (int t = 0; t < Ro.T; ++t) {
     if (active) {
       const float* orow = Ro.obs + ((size_t)t * B + inst) * od;
@@ -169,7 +139,7 @@ __global__ __launch_bounds__(kWave* pdegym_policy::kWaves) void rollout1d_policy
       wave_lds_sync();
       sense_noise(Ro.obs_noise, Ro.obs_seen, W.xw, od, B, inst, lane, t);
     }
-    float a = policy_eval<WIDE>(W, Wd, N, pol_smem, od, wave, lane);
+    float a = pol::command<WIDE>(pol::evaluate<WIDE>(W, Wd, N, pol_smem, od, wave, lane), Wd, wave, 0);
     if (!active) continue;
     a = policy_command(a, N, Ro, B, inst, lane, t);
     rollout1d_general_step<EPL, PARABOLIC, NEUMANN, BURGERS>(P, Bf, Ro, B, inst, lane, t, &a);
@@ -192,35 +162,30 @@ int launch_rollout(const pdegym_params1d* prm, const pdegym_bufs1d* buf, const p
   if (ro->policy) {
     const pdegym_mlp& N = *ro->policy;
     const int od = P.sensing == PDEGYM_SENSE_FULL ? P.n : 1;
-    if (const char* why = pdegym_policy::check(N, od, 1, true)) return pdegym::fail(-2, why);
+    const pdegym_policy::Plan pl = pdegym_policy::plan(&N, od, 1, B);
+    if (pl.why) return pdegym::fail(-2, pl.why);
     if (N.x_f64 || N.y_f64) return pdegym::fail(-2, "policy inside the 1D rollout kernel: float32 observations and commands");
     if (epl > 8) return pdegym::fail(-2, "policy inside the rollout kernel: rows of up to 513 nodes");
-    const dim3 pgrid((B + pdegym_policy::kWaves - 1) / pdegym_policy::kWaves), pblock(kWave * pdegym_policy::kWaves);
-    bool ok = true;
     // (round 5, measured again after the loop lost its waits: the cooperative MFMA evaluation forced onto a 64-64 network is slower
     // than one fma chain per neuron -- 0.99 against 0.73 ms per 100 env-steps at S = 1, 0.55 against 0.45 ms per 25 at S = 100: four
     // workgroup barriers per env-step and twelve of sixteen waves without an output tile)
-    const bool wide = pdegym_policy::is_wide(N);
-    const int lds_bytes = pdegym_policy::lds_floats(N, od) * (int)sizeof(float);
-    // each kernel is named where it is launched (tests/test_poison_helper.py reads the names there); attr: a static of each instantiation
-    auto raised = [&](auto kernel, signed char (&attr)[pdegym::kMaxDevices]) {
-      return ok = pdegym::raise_dynamic_lds_limit(reinterpret_cast<const void*>(kernel), pdegym_policy::kMaxLdsBytes, attr);
-    };
+    const bool wide = pl.wide;
+    int rc = 0;
+    const char* const failure = "cannot raise the dynamic LDS limit of rollout1d_policy_kernel";
     constexpr std::true_type yes{};
     constexpr std::false_type no{};
+    // each kernel is named where it is launched (tests/test_poison_helper.py reads the names there)
     with_epl<8>(epl, [&](auto tag) {
       constexpr int E = decltype(tag)::value;
       auto carried = [&](auto wide_tag, auto full_tag) {
         constexpr bool W = decltype(wide_tag)::value, F = decltype(full_tag)::value;
-        static signed char attr[pdegym::kMaxDevices] = {};
-        if (raised(&rollout1d_policy_kernel<E, PARABOLIC, BURGERS, W, F>, attr))
-          hipLaunchKernelGGL((rollout1d_policy_kernel<E, PARABOLIC, BURGERS, W, F>), pgrid, pblock, lds_bytes, st, P, *buf, *ro, N, B);
+        if (pdegym_policy::lds_limit_raised<&rollout1d_policy_kernel<E, PARABOLIC, BURGERS, W, F>>(failure, rc))
+          hipLaunchKernelGGL((rollout1d_policy_kernel<E, PARABOLIC, BURGERS, W, F>), pl.grid, pl.block, pl.lds_bytes, st, P, *buf, *ro, N, B);
       };
       auto in_general = [&](auto neumann_tag, auto wide_tag) {
         constexpr bool NEU = decltype(neumann_tag)::value, W = decltype(wide_tag)::value;
-        static signed char attr[pdegym::kMaxDevices] = {};
-        if (raised(&rollout1d_policy_general_kernel<E, PARABOLIC, NEU, BURGERS, W>, attr))
-          hipLaunchKernelGGL((rollout1d_policy_general_kernel<E, PARABOLIC, NEU, BURGERS, W>), pgrid, pblock, lds_bytes, st, P, *buf, *ro, N, B);
+        if (pdegym_policy::lds_limit_raised<&rollout1d_policy_general_kernel<E, PARABOLIC, NEU, BURGERS, W>>(failure, rc))
+          hipLaunchKernelGGL((rollout1d_policy_general_kernel<E, PARABOLIC, NEU, BURGERS, W>), pl.grid, pl.block, pl.lds_bytes, st, P, *buf, *ro, N, B);
       };
       if (general) {
         if (neumann) return wide ? in_general(yes, yes) : in_general(yes, no);
@@ -231,8 +196,7 @@ int launch_rollout(const pdegym_params1d* prm, const pdegym_bufs1d* buf, const p
       }
       return wide ? carried(yes, no) : carried(no, no);
     });
-    if (!ok) return pdegym::fail(-4, "cannot raise the dynamic LDS limit of rollout1d_policy_kernel");
-    return pdegym::check_launch("rollout1d_policy");
+    return rc ? rc : pdegym::check_launch("rollout1d_policy");
   }
   const dim3 grid((B + kWavesPerBlock - 1) / kWavesPerBlock), block(kWave * kWavesPerBlock);
   // the same slots-per-lane choice as launch_step: the norm reductions (hence rewards) depend on the layout

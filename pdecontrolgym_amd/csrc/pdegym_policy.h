@@ -17,6 +17,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "pdegym.h"
 #include "pdegym_common.h"
 #include "pdegym_mlp_tile.h"
@@ -237,6 +239,99 @@ __device__ __forceinline__ float eval_wide(const pdegym_mlp& N, const Wide& W, i
 }
 
 __device__ __forceinline__ float wide_out(const Wide& W, int wave, int k) { return W.act[wave * kWideOut + k]; }
+
+// ---- hosting an evaluator inside a rollout kernel: what every kernel with a policy inside does around eval / eval_wide ----------
+// The kernel's own: how the policy's input row gets into xw (and wave_lds_sync() after it), and where the command is stored.
+//
+// What a wave keeps for the T evaluations: the staged network (narrow) and its strips of LDS -- xw, the policy's input (n_in values,
+// zero-padded to a multiple of four), and hw, the hidden activations.  (WIDE: the cooperative set-up, Wide, stays an object of its own:
+// eval_wide indexes its H[] at run time, which keeps it in scratch, and what shared its aggregate would live there too.)
+struct PolicyWave {
+  Staged St;
+  float *xw, *hw;
+};
+
+// Prologue of a kernel with a policy inside (all threads of the workgroup: the narrow form's only barrier); false for a wave that has
+// nothing more to do: a narrow network's wave without an instance (`active` false, wave-uniform).  WIDE: every wave, with or without an
+// instance, has the barriers of all T evaluations ahead of it -- attend() is the way of a wave without one.
+template <bool WIDE>
+__device__ __forceinline__ bool prologue(PolicyWave& W, Wide& Wd, const pdegym_mlp& N, float* smem, int n_in, bool active, int wave, int lane) {
+  const int xp = xpad(n_in);
+  if constexpr (WIDE) Wd = wide_setup(N, smem, n_in, wave, lane);
+  else W.St = stage(N, smem);
+  if (!WIDE && !active) return false;
+  W.xw = WIDE ? Wd.X + wave * Wd.ldx : smem + W.St.end + wave * (xp + 2 * kMaxWidth);
+  W.hw = W.xw + xp;
+  if (!WIDE)
+    for (int j = n_in + lane; j < xp; j += kWave) W.xw[j] = 0.f;     // zero padding to a multiple of four: written once
+  return true;
+}
+
+// All a wave without an instance does in a WIDE workgroup after the prologue: it attends the barriers of the T evaluations (its input
+// row stays zero, it stores nothing) and returns, so the kernel loads no instance state for it.
+__device__ __forceinline__ void attend(const pdegym_mlp& N, const Wide& Wd, int n_in, int T, int wave, int lane) {
+  for (int t = 0; t < T; ++t) eval_wide(N, Wd, n_in, wave, lane);
+}
+
+// The network on the wave's input row, once per step (WIDE: barriers inside, so every wave of the workgroup is in here or in attend()
+// T times).  Returns what command() takes the outputs from.
+template <bool WIDE>
+__device__ __forceinline__ float evaluate(const PolicyWave& W, const Wide& Wd, const pdegym_mlp& N, const float* smem, int n_in, int wave,
+                                          int lane) {
+  if constexpr (WIDE) return eval_wide(N, Wd, n_in, wave, lane);
+  else return eval(N, W.St, smem, W.xw, W.hw, n_in, lane);
+}
+
+// Output neuron k (< kWideOut) of the last layer for this wave's row, wave-uniform; o: evaluate()'s value, which serves every k.
+template <bool WIDE>
+__device__ __forceinline__ float command(float o, const Wide& Wd, int wave, int k) {
+  if constexpr (WIDE) return k == 0 ? o : wide_out(Wd, wave, k);
+  else return pdegym::wave::lane_value(o, k);
+}
+
+// ... and its way to the command of instance `inst` at step t: + noise[t, inst, k], clamped (a NaN stays).
+__device__ __forceinline__ float shaped(float c, const pdegym_mlp& N, int t, int B, int inst, int k) {
+  if (N.noise) c += N.noise[((size_t)t * B + inst) * N.noise_stride + k];
+  if (N.clamp) c = pdegym::clip_keep_nan(c, N.lo, N.hi);
+  return c;
+}
+
+// ---- ... and launching such a kernel (host) -----------------------------------------------------------------------------------------
+// Workgroups of 16 waves, one instance per wave; in LDS the policy's floats come first, the kernel's own `extra_lds_bytes` (per
+// workgroup) start at extra_off, the next 16-byte boundary.  why: the reason a policy is refused (check), or nullptr.
+// policy == nullptr: the same workgroups without a policy.
+struct Plan {
+  const char* why;
+  bool wide;
+  size_t extra_off, lds_bytes;
+  dim3 grid, block;
+};
+inline Plan plan(const pdegym_mlp* policy, int n_in, int n_out, int B, size_t extra_lds_bytes = 0) {
+  Plan P = {nullptr, false, 0, extra_lds_bytes, dim3((B + kWaves - 1) / kWaves), dim3(kWave * kWaves)};
+  if (!policy) return P;
+  if ((P.why = check(*policy, n_in, n_out, true))) return P;
+  P.wide = is_wide(*policy);
+  P.extra_off = ((size_t)lds_floats(*policy, n_in) * sizeof(float) + 15) & ~(size_t)15;
+  P.lds_bytes = P.extra_off + extra_lds_bytes;
+  return P;
+}
+
+// f(wide_tag, policy_tag) with the std::bool_constant pair of a launch
+template <class F>
+inline void dispatch(bool policy, bool wide, F&& f) {
+  if (wide) f(std::true_type{}, std::true_type{});
+  else if (policy) f(std::false_type{}, std::true_type{});
+  else f(std::false_type{}, std::false_type{});
+}
+
+// Raise Kernel's dynamic-LDS limit to kMaxLdsBytes (once per kernel and device); on failure rc = -4 with `failure` as the message.
+template <auto Kernel>
+inline bool lds_limit_raised(const char* failure, int& rc) {
+  static signed char attr[pdegym::kMaxDevices] = {};
+  if (pdegym::raise_dynamic_lds_limit(reinterpret_cast<const void*>(Kernel), kMaxLdsBytes, attr)) return true;
+  rc = pdegym::fail(-4, failure);
+  return false;
+}
 
 }  // namespace pdegym_policy
 #endif

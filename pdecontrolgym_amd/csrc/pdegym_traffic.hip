@@ -8,8 +8,6 @@
 // fields are bit-identical to NumPy; the reward norms are wave reductions (rtol 1e-14 vs BLAS ddot).
 #include <hip/hip_runtime.h>
 
-#include <type_traits>
-
 #include "pdegym.h"
 #include "pdegym_common.h"
 #include "pdegym_policy.h"
@@ -66,8 +64,8 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void traffic_step_kernel(pde
 // caller's business in this engine).  With a policy (pdegym_policy.h) the command of step t is computed inside the launch
 // from observation slot t rounded to float32 -- the cast SB3 makes in front of its float32 network -- widened back to
 // float64, plus noise, clamped, and stored to actions row t.
-// WIDE: a policy with a layer of more than 64 units -- the 16 waves of the workgroup evaluate it together (pdegym_policy.h: eval_wide),
-// so every wave, with or without a freeway, runs all T iterations (barriers).
+// WIDE: a policy with a layer of more than 64 units -- the 16 waves of the workgroup evaluate it together; a wave without a freeway
+// only attends their barriers (pdegym_policy.h: attend) and loads nothing.
 // POLICY: compiled apart, so that the commands-given-ahead form carries none of the policy's loads (a load under a run-time branch
 // leaves the compiler's wait-count pass with "may be pending" registers at every join of the loop).
 template <bool WIDE, bool POLICY>
@@ -79,17 +77,18 @@ __global__ __launch_bounds__(kWave* pdegym_policy::kWaves) void traffic_rollout_
   namespace pol = pdegym_policy;
   extern __shared__ __attribute__((aligned(16))) float pol_smem[];
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
-  const int inst_raw = blockIdx.x * pol::kWaves + wave;
-  const int M = P.M, D = 2 * M, xpad = pol::xpad(D);
-  pol::Staged St = {};
+  const int inst = blockIdx.x * pol::kWaves + wave;
+  const int M = P.M, D = 2 * M;
+  const bool active = inst < B;      // wave-uniform
+  pol::PolicyWave W;
   pol::Wide Wd;
-  if constexpr (WIDE) Wd = pol::wide_setup(N, pol_smem, D, wave, lane);
-  else if constexpr (has_policy) St = pol::stage(N, pol_smem);        // the launch's only barrier (uniform over the grid)
-  const bool active = inst_raw < B;      // wave-uniform
-  if (!WIDE && !active) return;
-  const int inst = active ? inst_raw : 0;      // a wave without a freeway only attends the barriers: it reads instance 0, stores nothing
-  float* const xw = WIDE ? Wd.X + wave * Wd.ldx : pol_smem + St.end + wave * (xpad + 2 * pol::kMaxWidth);
-  float* const hw = xw + xpad;
+  if constexpr (has_policy) {
+    if (!pol::prologue<WIDE>(W, Wd, N, pol_smem, D, active, wave, lane)) return;
+  }
+  if (!active) {
+    if constexpr (WIDE) pol::attend(N, Wd, D, Ro.T, wave, lane);
+    return;
+  }
   const bool in = lane < M;
   double r = in ? Bf.r[(size_t)inst * M + lane] : 1.0;
   double y = in ? Bf.y[(size_t)inst * M + lane] : 0.0;
@@ -121,32 +120,11 @@ __global__ __launch_bounds__(kWave* pdegym_policy::kWaves) void traffic_rollout_
     }
     if constexpr (has_policy) {
       const double* xrow = Ro.obs + (size_t)t * slot + (size_t)inst * D;
-      float c0, c1;
-      if constexpr (WIDE) {
-        if (active)
-          for (int j = lane; j < D; j += kWave) xw[j] = (float)xrow[j];
-        pol::eval_wide(N, Wd, D, wave, lane);
-        if (!active) continue;
-        c0 = pol::wide_out(Wd, wave, 0);
-        c1 = A > 1 ? pol::wide_out(Wd, wave, 1) : 0.f;
-      } else {
-        for (int j = lane; j < xpad; j += kWave) xw[j] = j < D ? (float)xrow[j] : 0.f;
-        wave_lds_sync();
-        const float o = pol::eval(N, St, pol_smem, xw, hw, D, lane);
-        c0 = lane_value(o, 0);
-        c1 = A > 1 ? lane_value(o, 1) : 0.f;
-      }
-      if (N.noise) {
-        const float* nz = N.noise + ((size_t)t * B + inst) * N.noise_stride;
-        c0 += nz[0];
-        if (A > 1) c1 += nz[1];
-      }
-      if (N.clamp) {
-        c0 = pdegym::clip_keep_nan(c0, N.lo, N.hi);
-        c1 = pdegym::clip_keep_nan(c1, N.lo, N.hi);
-      }
-      a0 = (double)c0;
-      a1 = (double)c1;
+      for (int j = lane; j < D; j += kWave) W.xw[j] = (float)xrow[j];
+      wave_lds_sync();
+      const float o = pol::evaluate<WIDE>(W, Wd, N, pol_smem, D, wave, lane);      // one evaluation, both commands
+      a0 = (double)pol::shaped(pol::command<WIDE>(o, Wd, wave, 0), N, t, B, inst, 0);
+      if (A > 1) a1 = (double)pol::shaped(pol::command<WIDE>(o, Wd, wave, 1), N, t, B, inst, 1);
       if (lane == 0) {
         arow[0] = a0;
         if (A > 1) arow[1] = a1;
@@ -175,6 +153,8 @@ __global__ __launch_bounds__(kWave* pdegym_policy::kWaves) void traffic_rollout_
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     }
   }
+  // (never taken; without it the compiler inverts the exit test of the open-loop form's loop, which otherwise is the parent form's
+  // instruction for instruction: profiles/policy_host_resources.txt)
   if (!active) return;
   if (in) {
     Bf.r[(size_t)inst * M + lane] = r;
@@ -366,30 +346,17 @@ int pdegym_traffic_rollout(const pdegym_params_traffic* prm, const pdegym_bufs_t
   if (!ro->obs || !ro->actions || !ro->rewards || !ro->done || !ro->truncated) return pdegym::fail(-3, "null rollout buffer");
   const int A = buf->action_stride > 0 ? buf->action_stride : 2;
   if (A > 2) return pdegym::fail(-2, "action_stride must be 1 or 2");
-  pdegym_mlp net = {};
-  size_t lds_bytes = 0;
-  bool wide = false;
-  if (ro->policy) {
-    net = *ro->policy;
-    if (A > pdegym_policy::kWideOut) return pdegym::fail(-2, "policy: at most two commands");
-    if (const char* why = pdegym_policy::check(net, 2 * prm->M, A, true)) return pdegym::fail(-2, why);
-    wide = pdegym_policy::is_wide(net);
-    lds_bytes = (size_t)pdegym_policy::lds_floats(net, 2 * prm->M) * sizeof(float);
-  }
-  const dim3 grid((B + pdegym_policy::kWaves - 1) / pdegym_policy::kWaves), block(kWave * pdegym_policy::kWaves);
-  bool ok = true;
-  auto launch = [&](auto wide_tag, auto policy_tag) {
+  if (ro->policy && A > pdegym_policy::kWideOut) return pdegym::fail(-2, "policy: at most two commands");
+  const pdegym_policy::Plan pl = pdegym_policy::plan(ro->policy, 2 * prm->M, A, B);
+  if (pl.why) return pdegym::fail(-2, pl.why);
+  const pdegym_mlp net = ro->policy ? *ro->policy : pdegym_mlp{};
+  int rc = 0;
+  pdegym_policy::dispatch(ro->policy != nullptr, pl.wide, [&](auto wide_tag, auto policy_tag) {
     constexpr bool W = decltype(wide_tag)::value, Pol = decltype(policy_tag)::value;
-    static signed char attr[pdegym::kMaxDevices] = {};      // one per kernel: a static of each instantiation of this lambda
-    if constexpr (Pol) ok = pdegym::raise_dynamic_lds_limit(reinterpret_cast<const void*>(&traffic_rollout_kernel<W, Pol>), pdegym_policy::kMaxLdsBytes, attr);
-    if (ok)
-      hipLaunchKernelGGL((traffic_rollout_kernel<W, Pol>), grid, block, lds_bytes, (hipStream_t)stream, *prm, *buf, *ro, net, traffic_consts(*prm), B);
-  };
-  if (wide) launch(std::true_type{}, std::true_type{});
-  else if (ro->policy) launch(std::false_type{}, std::true_type{});
-  else launch(std::false_type{}, std::false_type{});
-  if (!ok) return pdegym::fail(-4, "cannot raise the dynamic LDS limit of traffic_rollout_kernel");
-  return pdegym::check_launch("traffic_rollout");
+    if (!Pol || pdegym_policy::lds_limit_raised<&traffic_rollout_kernel<W, Pol>>("cannot raise the dynamic LDS limit of traffic_rollout_kernel", rc))
+      hipLaunchKernelGGL((traffic_rollout_kernel<W, Pol>), pl.grid, pl.block, pl.lds_bytes, (hipStream_t)stream, *prm, *buf, *ro, net, traffic_consts(*prm), B);
+  });
+  return rc ? rc : pdegym::check_launch("traffic_rollout");
 }
 
 int pdegym_traffic_reset_masked(const pdegym_params_traffic* prm, const pdegym_bufs_traffic* buf, const double* profile,

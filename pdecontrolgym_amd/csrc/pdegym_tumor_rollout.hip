@@ -14,8 +14,6 @@
 // in a 300-day run makes the others wait -- and none returns before the last step.
 #include <hip/hip_runtime.h>
 
-#include <type_traits>
-
 #include "pdegym.h"
 #include "pdegym_common.h"
 #include "pdegym_policy.h"
@@ -25,9 +23,6 @@ namespace {
 
 using namespace pdegym_tumor;      // tumor_stage_row, tumor_day, tumor_reset_scalars, tumor_store_scalars (pdegym_tumor_body.h)
 namespace pol = pdegym_policy;
-
-// the policy's floats come first in the workgroup's LDS; the rows start on the next 16-byte boundary
-__host__ __device__ inline size_t rows_offset(size_t policy_floats) { return (policy_floats * sizeof(float) + 15) & ~(size_t)15; }
 
 // obs0: observation slot 0 (read by a policy only); obs1: slot 1 (slot t + 1 = obs1 + t * B * nx) or nullptr (the observation is
 // the live row, written once at the end); actions / rewards / terminated / truncated: rows of B, row t per wrapper step.
@@ -48,24 +43,18 @@ __global__ __launch_bounds__(kWave* pol::kWaves) void tumor_rollout_kernel(pdegy
   extern __shared__ __attribute__((aligned(16))) float pol_smem[];
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
   const int wpb = blockDim.x >> 6;      // 16 with a policy; 4, 2 or 1 without (the host's choice by nx)
-  const int inst_raw = __builtin_amdgcn_readfirstlane(blockIdx.x * wpb + wave);
-  const int nx = P.nx, xpad = pol::xpad(nx);
-  pol::Staged St = {};
-  pol::Wide Wd = {};
-  if constexpr (WIDE) Wd = pol::wide_setup(N, pol_smem, nx, wave, lane);
-  else if constexpr (POLICY) St = pol::stage(N, pol_smem);        // the only barrier of the neuron-per-lane form (uniform over the grid)
-  const bool active = inst_raw < B;      // wave-uniform
-  if constexpr (WIDE) {
-    if (!active) {      // a wave without a patient: its policy row stays zero, it attends the barriers of every step and stores nothing
-      for (int t = 0; t < Ro.T; ++t) pol::eval_wide(N, Wd, nx, wave, lane);
-      return;
-    }
-  } else {
-    if (!active) return;
+  const int inst = __builtin_amdgcn_readfirstlane(blockIdx.x * wpb + wave);
+  const int nx = P.nx;
+  const bool active = inst < B;      // wave-uniform
+  pol::PolicyWave W;
+  pol::Wide Wd;
+  if constexpr (POLICY) {
+    if (!pol::prologue<WIDE>(W, Wd, N, pol_smem, nx, active, wave, lane)) return;
   }
-  const int inst = inst_raw;
-  float* const xw = WIDE ? Wd.X + wave * Wd.ldx : pol_smem + St.end + wave * (xpad + 2 * pol::kMaxWidth);      // (a policy's only)
-  float* const hw = xw + xpad;
+  if (!active) {      // (WIDE: a wave without a patient attends the barriers of every step)
+    if constexpr (WIDE) pol::attend(N, Wd, nx, Ro.T, wave, lane);
+    return;
+  }
   double* cur = reinterpret_cast<double*>(reinterpret_cast<char*>(pol_smem) + rows_off) + (size_t)(2 * wave) * nx;
   double* nxt = cur + nx;
   double* g = Bf.u + (size_t)inst * nx;
@@ -98,11 +87,7 @@ __global__ __launch_bounds__(kWave* pol::kWaves) void tumor_rollout_kernel(pdegy
   const size_t slot = (size_t)B * nx;
   if constexpr (POLICY) {      // the policy row of step 0: the caller's observation slot 0, rounded to float32
     const double* x0 = Ro.obs0 + (size_t)inst * nx;
-    if constexpr (WIDE) {
-      for (int j = lane; j < nx; j += kWave) xw[j] = (float)x0[j];
-    } else {
-      for (int j = lane; j < xpad; j += kWave) xw[j] = j < nx ? (float)x0[j] : 0.f;
-    }
+    for (int j = lane; j < nx; j += kWave) W.xw[j] = (float)x0[j];
   }
   // The days of a wrapper step are ONE loop over phases with ONE copy of the simulated day in it (the day is ~1500 instructions):
   // a post-therapy run, or the treatment day and the two weekend days; then, for a finished patient, the growth run.
@@ -111,16 +96,8 @@ __global__ __launch_bounds__(kWave* pol::kWaves) void tumor_rollout_kernel(pdegy
     // ---- today's command
     double a;
     if constexpr (POLICY) {
-      float c;
-      if constexpr (WIDE) {
-        c = lane_value(pol::eval_wide(N, Wd, nx, wave, lane), 0);      // (the barrier inside publishes the policy rows)
-      } else {
-        wave_lds_sync();
-        c = lane_value(pol::eval(N, St, pol_smem, xw, hw, nx, lane), 0);
-      }
-      if (N.noise) c += N.noise[((size_t)t * B + inst) * N.noise_stride];
-      if (N.clamp) c = pdegym::clip_keep_nan(c, N.lo, N.hi);
-      a = (double)c;
+      wave_lds_sync();      // the policy row written by the step before (emit_row) or above
+      a = (double)pol::shaped(pol::command<WIDE>(pol::evaluate<WIDE>(W, Wd, N, pol_smem, nx, wave, lane), Wd, wave, 0), N, t, B, inst, 0);
       if (lane == 0) Ro.actions[(size_t)t * B + inst] = a;
     } else {
       a = Ro.actions[(size_t)t * B + inst];
@@ -132,7 +109,7 @@ __global__ __launch_bounds__(kWave* pol::kWaves) void tumor_rollout_kernel(pdegy
       for (int i = lane; i < nx; i += kWave) {
         const double v = cur[i];
         if (oslot) oslot[i] = v;
-        if constexpr (POLICY) xw[i] = (float)v;
+        if constexpr (POLICY) W.xw[i] = (float)v;
       }
     };
     // ---- TherapyWrapper.step :430-486
@@ -244,34 +221,23 @@ int check_wrap(const pdegym_params_tumor* prm, const pdegym_bufs_tumor* buf, con
 int launch(const pdegym_params_tumor* prm, const pdegym_bufs_tumor* buf, const pdegym_wrap_tumor* wrap, const Slots& ro, const pdegym_mlp* policy,
            int32_t B, void* stream, const char* what) {
   const int nx = prm->nx;
-  pdegym_mlp net = {};
-  bool wide = false;
-  int wpb = nx <= 1024 ? 4 : (nx <= 2048 ? 2 : 1);      // no policy: two LDS rows per wave, at most 64 KB per workgroup
-  size_t policy_floats = 0;
+  const size_t row_bytes = (size_t)2 * nx * sizeof(double);      // two LDS rows per wave, after the policy's floats
+  const int wpb = nx <= 1024 ? 4 : (nx <= 2048 ? 2 : 1);      // no policy: at most 64 KB of rows per workgroup
+  pol::Plan pl = {nullptr, false, 0, wpb * row_bytes, dim3((B + wpb - 1) / wpb), dim3(kWave * wpb)};
   if (policy) {
-    net = *policy;
-    if (const char* why = pol::check(net, nx, 1, true)) return pdegym::fail(-2, why);
-    wide = pol::is_wide(net);
-    policy_floats = (size_t)pol::lds_floats(net, nx);
-    wpb = pol::kWaves;
+    pl = pol::plan(policy, nx, 1, B, pol::kWaves * row_bytes);
+    if (pl.why) return pdegym::fail(-2, pl.why);
+    if (pl.lds_bytes > (size_t)pol::kMaxLdsBytes)
+      return pdegym::fail(-2, "tumor rollout: the policy's LDS and two float64 rows for each of 16 patients do not fit into 160 KB of LDS");
   }
-  const size_t rows_off = rows_offset(policy_floats);
-  const size_t lds_bytes = rows_off + (size_t)2 * wpb * nx * sizeof(double);
-  if (policy && lds_bytes > (size_t)pol::kMaxLdsBytes)
-    return pdegym::fail(-2, "tumor rollout: the policy's LDS and two float64 rows for each of 16 patients do not fit into 160 KB of LDS");
-  const dim3 grid((B + wpb - 1) / wpb), block(kWave * wpb);
-  bool ok = true;
-  auto go = [&](auto wide_tag, auto policy_tag) {
+  const pdegym_mlp net = policy ? *policy : pdegym_mlp{};
+  int rc = 0;
+  pol::dispatch(policy != nullptr, pl.wide, [&](auto wide_tag, auto policy_tag) {
     constexpr bool W = decltype(wide_tag)::value, Pol = decltype(policy_tag)::value;
-    static signed char attr[pdegym::kMaxDevices] = {};      // one per kernel: a static of each instantiation of this lambda
-    if constexpr (Pol) ok = pdegym::raise_dynamic_lds_limit(reinterpret_cast<const void*>(&tumor_rollout_kernel<W, Pol>), pol::kMaxLdsBytes, attr);
-    if (ok) tumor_rollout_kernel<W, Pol><<<grid, block, lds_bytes, (hipStream_t)stream>>>(*prm, *buf, *wrap, ro, net, (int)rows_off, B);
-  };
-  if (wide) go(std::true_type{}, std::true_type{});
-  else if (policy) go(std::false_type{}, std::true_type{});
-  else go(std::false_type{}, std::false_type{});
-  if (!ok) return pdegym::fail(-4, "cannot raise the dynamic LDS limit of tumor_rollout_kernel");
-  return pdegym::check_launch(what);
+    if (!Pol || pol::lds_limit_raised<&tumor_rollout_kernel<W, Pol>>("cannot raise the dynamic LDS limit of tumor_rollout_kernel", rc))
+      tumor_rollout_kernel<W, Pol><<<pl.grid, pl.block, pl.lds_bytes, (hipStream_t)stream>>>(*prm, *buf, *wrap, ro, net, (int)pl.extra_off, B);
+  });
+  return rc ? rc : pdegym::check_launch(what);
 }
 
 }  // namespace

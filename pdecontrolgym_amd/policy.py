@@ -15,6 +15,14 @@ from __future__ import annotations
 from . import _native as N
 
 
+def fits_rollout_kernel(policy, in_dim: int, out_dim: int, extra_lds_bytes: int = 0) -> bool:
+    """Whether ``policy`` fits a rollout kernel with ``in_dim`` inputs, ``out_dim`` outputs and ``extra_lds_bytes`` of the engine's
+    own LDS per workgroup: what the engines' ``policy_fits_rollout`` add their own conditions to.  Duck-typed: an object without
+    ``fits_rollout`` (anything but a ``FusedMLP``) does not fit."""
+    fits = getattr(policy, "fits_rollout", None)
+    return fits is not None and fits(in_dim, out_dim, extra_lds_bytes)
+
+
 class FusedMLP:
     """``policy = FusedMLP(torch_module)``; ``policy(obs)`` -> ``[B, out_dim]`` float32 actions on the same device.
 
@@ -118,18 +126,19 @@ class FusedMLP:
             L.in_dim, L.out_dim, L.act = int(w.shape[1]), int(w.shape[0]), act
         return net
 
-    # ---- the policy inside a rollout kernel (pdegym_*_rollout with ``policy`` set: 1D and traffic engines) ----------------------
-    def fits_rollout(self, in_dim: int, out_dim: int) -> bool:
+    # ---- the policy inside a rollout kernel (pdegym_*_rollout with ``policy`` set: 1D, traffic and brain-tumour engines) ---------
+    def fits_rollout(self, in_dim: int, out_dim: int, extra_lds_bytes: int = 0) -> bool:
         """Whether a rollout kernel can evaluate this network on rows of ``in_dim`` values for ``out_dim`` commands (the engines'
-        ``policy_fits_rollout`` ask; having this method is their test for a ``FusedMLP``): those sizes, layers of at most 256
-        units.  Layers of at most 64 units: one neuron per lane, the weights + 16 observation rows within 160 KB of LDS.  A
-        layer of 65 .. 256 units (SB3's 256-256 actors): the 16 waves of a workgroup evaluate the network together on the matrix
-        cores, weights streamed from L2 -- bit-identical to ``pdegym_mlp_forward`` (16 observation rows + the hidden rows within
-        160 KB of LDS: any row the kernels take)."""
+        ``policy_fits_rollout`` ask through ``fits_rollout_kernel``; having this method is the test for a ``FusedMLP``): those
+        sizes, layers of at most 256 units.  Layers of at most 64 units: one neuron per lane, the weights + 16 observation rows
+        within 160 KB of LDS.  A layer of 65 .. 256 units (SB3's 256-256 actors): the 16 waves of a workgroup evaluate the network
+        together on the matrix cores, weights streamed from L2 -- bit-identical to ``pdegym_mlp_forward`` (16 observation rows +
+        the hidden rows within 160 KB of LDS: any row the kernels take).  ``extra_lds_bytes``: LDS of the engine's own per
+        workgroup of 16 instances, which starts on the 16-byte boundary after the policy's (csrc/pdegym_policy.h: plan)."""
         dims = [(int(w.shape[1]), int(w.shape[0])) for w, _, _ in self.layers]
         if dims[0][0] != in_dim or dims[-1][1] != out_dim or any(o > 256 for _, o in dims):
             return False
-        return self.rollout_lds_bytes(in_dim) <= self.ROLLOUT_LDS_BYTES
+        return (self.rollout_lds_bytes(in_dim) + 15) // 16 * 16 + extra_lds_bytes <= self.ROLLOUT_LDS_BYTES
 
     ROLLOUT_LDS_BYTES = 160 * 1024      # csrc/pdegym_policy.h: kMaxLdsBytes
 

@@ -246,7 +246,7 @@ def test_one_launch_rollout_does_not_claim_the_controller():
     from pdecontrolgym_amd.batch1d import PDEBatch1D
     c = _ctrl()
     assert hasattr(c, "forward_into") and not hasattr(c, "layers") and not hasattr(c, "_net")
-    core = types.SimpleNamespace(can_rollout=lambda: True)
+    core = types.SimpleNamespace(can_rollout=lambda: True, n=65, obs_dim=65)
     assert PDEBatch1D.policy_fits_rollout(core, c) is False
 
 

@@ -438,6 +438,36 @@ def test_policy_fits_rollout_limits_on_cpu_double():
     assert wide.M == 101 and not wide.can_rollout()
 
 
+def test_the_rollout_units_host_the_policy_through_the_shared_header():
+    """csrc/pdegym_policy.h hosts the in-kernel evaluation for all three rollout units (prologue, attend, evaluate, command, shaped;
+    plan, dispatch, lds_limit_raised): no unit defines one of these, calls an evaluator or derives the LDS layout itself, and the
+    engines ask one function whether a policy fits."""
+    import os
+    import re
+    from pdecontrolgym_amd import build
+    code = lambda f: re.sub(r"//[^\n]*", "", open(os.path.join(build.CSRC, f)).read())      # noqa: E731
+    hdr = code("pdegym_policy.h")
+    shared = ("prologue", "attend", "evaluate", "command", "shaped", "plan", "dispatch", "lds_limit_raised")
+    defined = lambda name, src: re.findall(r"^(?:__device__ __forceinline__|inline)\s+[\w:]+\s+" + name + r"\(", src, re.M)      # noqa: E731
+    for name in shared:
+        assert len(defined(name, hdr)) == 1, name
+    assert len(re.findall(r"^struct PolicyWave \{", hdr, re.M)) == 1
+    direct = re.compile(r"(?<!\w)(stage|wide_setup|eval|eval_wide|wide_out|lds_floats|is_wide|raise_dynamic_lds_limit)\(")
+    for unit in ("pdegym_1d_rollout.hip", "pdegym_traffic.hip", "pdegym_tumor_rollout.hip"):
+        src = code(unit)
+        assert '#include "pdegym_policy.h"' in src
+        assert not direct.findall(src), (unit, direct.findall(src))
+        assert "struct PolicyWave" not in src and "+ 15) & ~" not in src, unit       # (the 16-byte round-up of the row offset)
+        assert not [n for n in shared if defined(n, src)], unit
+        for name in ("prologue", "evaluate", "command", "shaped", "plan", "lds_limit_raised"):
+            assert re.search(r"(?:pol|pdegym_policy)::" + name + r"[<(]", src), (unit, name)
+        # a wave without an instance of a cooperative workgroup: attend(), except where the 1D unit says why its loop stays
+        assert all(re.search(r"(?:pol|pdegym_policy)::" + name + r"\(", src) for name in ("attend", "dispatch")) or unit == "pdegym_1d_rollout.hip", unit
+    for mod in ("batch1d.py", "batch_traffic.py", "batch_tumor.py"):
+        src = open(os.path.join(build.HERE, mod)).read()
+        assert "fits_rollout_kernel(policy, " in src and 'getattr(policy, "fits_rollout"' not in src and "rollout_lds_bytes" not in src, mod
+
+
 def test_from_sb3_duck_typed_policies():
     """FusedMLP.from_sb3 picks the deterministic actor out of SB3-shaped policy objects (PPO: mlp_extractor.policy_net +
     action_net; SAC: actor.latent_pi + actor.mu + tanh) and shares their parameters."""

@@ -1,0 +1,151 @@
+#!/usr/bin/env python3
+"""SAC on a batched PDEControlGym environment with NOTHING on the host inside a rollout.
+
+The reference trains every environment family with SAC as well as PPO (examples/transportPDE/transport1Dsac.py,
+examples/ReactionDiffusionPDE/reactionDiffusion1Dsac.py: SAC("MlpPolicy", env)).  This is the same algorithm in plain torch on the
+batched engine, on the plant of examples/train_ppo_device.py:
+
+  * rollout  -- ``DeviceRollout`` with ``FusedMLP.squashed_gaussian``: per env-step the actor samples
+                a = tanh(mu(s) + exp(clip(log_std(s), -20, 2)) * eps) inside the rollout kernel and rescales it to the action box --
+                the whole T-step rollout is ONE launch (``one_launch=False``: one policy launch + one env-step launch per step in a
+                hipGraph); ``eps`` is drawn ahead with ``normal_()``, no ``mul_``: the standard deviation depends on the state;
+  * replay   -- a device tensor filled from the rollout's buffers (the stored action is SB3's scaled action,
+                2 (c - lo) / (hi - lo) - 1, recovered from the command c);
+  * update   -- twin Q critics, target networks, automatic entropy coefficient; the actor update is ordinary autograd on the same
+                ``latent`` / ``mu`` / ``log_std`` modules the rollout evaluates (``FusedMLP`` picks the new weights up at the next
+                ``run()``).
+
+    python examples/train_sac_device.py [iterations] [num_envs] [hidden units per layer: 64]
+"""
+import copy
+import math
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from pde_control_gym import DeviceRollout, FusedMLP  # noqa: E402
+from train_ppo_device import make_env  # noqa: E402
+
+LOG_STD_MIN, LOG_STD_MAX = -20.0, 2.0
+
+
+def mlp(sizes):
+    mods = []
+    for i in range(len(sizes) - 1):
+        mods.append(torch.nn.Linear(sizes[i], sizes[i + 1]))
+        if i < len(sizes) - 2:
+            mods.append(torch.nn.ReLU())
+    return torch.nn.Sequential(*mods)
+
+
+def sample(latent, mu, log_std, obs):
+    """Reparameterised action in [-1, 1] and its log-probability (the update's own forward pass, under autograd)."""
+    h = latent(obs)
+    mean, ls = mu(h), log_std(h).clamp(LOG_STD_MIN, LOG_STD_MAX)
+    z = mean + ls.exp() * torch.randn_like(mean)
+    a = torch.tanh(z)
+    logp = (-0.5 * ((z - mean) / ls.exp()) ** 2 - ls - 0.5 * math.log(2 * math.pi)).sum(-1) - torch.log(1 - a * a + 1e-6).sum(-1)
+    return a, logp
+
+
+def main(iterations=30, num_envs=1024, n_steps=32, hidden=64, one_launch=None, quiet=False, updates=8, batch=2048):
+    dev = torch.device("cuda", 0)
+    torch.manual_seed(0)
+    B, T = num_envs, n_steps
+    venv = make_env(B, horizon=64)
+    D = venv.reset_tensor().shape[1]
+    venv.enable_fused_auto_reset()
+    lo, hi = -10.0, 10.0                                 # the plant's max_control_value
+    latent = torch.nn.Sequential(torch.nn.Linear(D, hidden), torch.nn.ReLU(), torch.nn.Linear(hidden, hidden), torch.nn.ReLU()).to(dev)
+    mu, log_std = torch.nn.Linear(hidden, 1).to(dev), torch.nn.Linear(hidden, 1).to(dev)
+    q1, q2 = mlp([D + 1, hidden, hidden, 1]).to(dev), mlp([D + 1, hidden, hidden, 1]).to(dev)
+    with torch.no_grad():
+        for first in (latent[0], q1[0], q2[0]):
+            first.weight.mul_(0.1)                       # observations are O(10)
+        mu.weight.mul_(0.01)
+        log_std.weight.mul_(0.01)
+        log_std.bias.fill_(-1.0)
+    q1_t, q2_t = copy.deepcopy(q1).requires_grad_(False), copy.deepcopy(q2).requires_grad_(False)
+    log_alpha = torch.zeros(1, device=dev, requires_grad=True)
+    actor_params = list(latent.parameters()) + list(mu.parameters()) + list(log_std.parameters())
+    opt_actor = torch.optim.Adam(actor_params, lr=3e-4)
+    opt_q = torch.optim.Adam(list(q1.parameters()) + list(q2.parameters()), lr=3e-4)
+    opt_alpha = torch.optim.Adam([log_alpha], lr=3e-4)
+    start = {k: [p.detach().clone() for p in ps] for k, ps in (("actor", actor_params), ("q1", list(q1.parameters())), ("q2", list(q2.parameters())))}
+    rollout = DeviceRollout(venv, FusedMLP.squashed_gaussian(latent, mu, log_std, (LOG_STD_MIN, LOG_STD_MAX)), T,
+                            action_low=lo, action_high=hi, action_noise=True, one_launch=one_launch)
+    # the replay buffer: device tensors, a ring of `cap` transitions filled T * B at a time
+    cap = max(16 * T * B, batch)
+    buf = {k: torch.zeros(cap, n, device=dev) for k, n in (("obs", D), ("next", D), ("act", 1), ("rew", 1), ("term", 1))}
+    head, filled = 0, 0
+    gamma, tau, target_entropy = 0.99, 0.005, -1.0
+    history = {"q_loss": [], "actor_loss": [], "alpha": [], "mean_reward": [], "mean_norm": []}
+    t_roll = t_upd = 0.0
+    for it in range(iterations):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        rollout.action_noise.normal_()                   # eps: standard normal, scaled by the state's sigma inside the kernel
+        rollout.run()
+        torch.cuda.synchronize()
+        t_roll += time.perf_counter() - t0
+        t0 = time.perf_counter()
+        idx = (head + torch.arange(T * B, device=dev)) % cap
+        # (after a restart obs[t + 1] is the new episode's first row: the bootstrap of such a transition is cut like a termination's,
+        # the engines keep no terminal-observation buffer)
+        ended = (rollout.terminated | rollout.truncated).reshape(-1, 1).float()
+        buf["obs"][idx] = rollout.obs[:T].reshape(-1, D)
+        buf["next"][idx] = rollout.obs[1:].reshape(-1, D)
+        buf["act"][idx] = (2.0 * (rollout.actions.reshape(-1, 1) - lo) / (hi - lo) - 1.0).clamp(-1.0, 1.0)
+        buf["rew"][idx] = rollout.rewards.reshape(-1, 1)
+        buf["term"][idx] = ended
+        head, filled = (head + T * B) % cap, min(filled + T * B, cap)
+        for _ in range(updates):
+            mb = torch.randint(0, filled, (min(batch, filled),), device=dev)
+            o, o2, a, r, d = (buf[k][mb] for k in ("obs", "next", "act", "rew", "term"))
+            alpha = log_alpha.exp().detach()
+            with torch.no_grad():
+                a2, logp2 = sample(latent, mu, log_std, o2)
+                q_next = torch.min(q1_t(torch.cat([o2, a2], 1)), q2_t(torch.cat([o2, a2], 1))) - alpha * logp2.unsqueeze(1)
+                target = r + gamma * (1.0 - d) * q_next
+            oa = torch.cat([o, a], 1)
+            q_loss = (q1(oa) - target).pow(2).mean() + (q2(oa) - target).pow(2).mean()
+            opt_q.zero_grad(set_to_none=True)
+            q_loss.backward()
+            opt_q.step()
+            a_pi, logp = sample(latent, mu, log_std, o)
+            oa_pi = torch.cat([o, a_pi], 1)
+            actor_loss = (alpha * logp.unsqueeze(1) - torch.min(q1(oa_pi), q2(oa_pi))).mean()
+            opt_actor.zero_grad(set_to_none=True)
+            actor_loss.backward()
+            opt_actor.step()
+            alpha_loss = -(log_alpha * (logp.detach() + target_entropy).mean())
+            opt_alpha.zero_grad(set_to_none=True)
+            alpha_loss.backward()
+            opt_alpha.step()
+            with torch.no_grad():
+                for net, tgt in ((q1, q1_t), (q2, q2_t)):
+                    for p, pt in zip(net.parameters(), tgt.parameters()):
+                        pt.lerp_(p, tau)
+        torch.cuda.synchronize()
+        t_upd += time.perf_counter() - t0
+        for k, v in (("q_loss", q_loss), ("actor_loss", actor_loss), ("alpha", log_alpha.exp()), ("mean_reward", rollout.rewards.mean()),
+                     ("mean_norm", rollout.obs[:T].norm(dim=2).mean())):
+            history[k].append(float(v.detach()))
+        if not quiet and (it % 5 == 0 or it == iterations - 1):
+            print(f"iter {it:3d}  mean reward {history['mean_reward'][-1]:+8.4f}  mean ||u|| {history['mean_norm'][-1]:7.3f}  "
+                  f"Q loss {history['q_loss'][-1]:9.4g}  actor loss {history['actor_loss'][-1]:+9.4g}  alpha {history['alpha'][-1]:.3f}")
+    now = {"actor": actor_params, "q1": list(q1.parameters()), "q2": list(q2.parameters())}
+    history["moved"] = {k: all(not torch.equal(p.detach(), s) for p, s in zip(now[k], start[k])) for k in now}
+    history["one_launch"] = rollout.one_launch
+    if not quiet:
+        print(f"{iterations} iterations x {T} steps x {B} envs: rollouts {t_roll:.2f} s ({iterations * T * B / t_roll:.3g} env-steps/s incl. policy, "
+              f"one launch: {rollout.one_launch}), updates {t_upd:.2f} s")
+    return history
+
+
+if __name__ == "__main__":
+    main(int(sys.argv[1]) if len(sys.argv) > 1 else 30, int(sys.argv[2]) if len(sys.argv) > 2 else 1024,
+         hidden=int(sys.argv[3]) if len(sys.argv) > 3 else 64)

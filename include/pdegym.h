@@ -55,7 +55,7 @@
 extern "C" {
 #endif
 
-#define PDEGYM_ABI_VERSION 20
+#define PDEGYM_ABI_VERSION 21
 #define PDEGYM_RING 128          /* slots of the per-instance row-norm ring (look-back is 100 rows) */
 #define PDEGYM_LOOKBACK 100      /* tuned_reward_1d.py:25,40: int(1/0.01) rows */
 #define PDEGYM_MAX_N1D 2048      /* nodes per 1D row kept in registers by the wave-per-instance kernels */
@@ -564,8 +564,43 @@ typedef struct pdegym_mlp_s {
   const float* noise;  /* [B, out_dim] float32 or NULL: added to the last layer's output before the clamp -- the exploration
                           noise of a stochastic policy (SB3's Gaussian MlpPolicy samples mean + std * eps), drawn by the caller */
   int64_t noise_stride; /* floats between consecutive rows of noise                                                     */
-  pdegym_mlp_layer layer[PDEGYM_MLP_MAX_LAYERS];
+  /* The head's fields (ABI 21) occupy the reserved words of layer[0], layer[1] and layer[2]: the descriptor keeps the size and every
+   * offset of ABI 20 (168 bytes, layer[] at 40), and a zero-initialised descriptor means the plain head.                          */
+  union {
+    pdegym_mlp_layer layer[PDEGYM_MLP_MAX_LAYERS];
+    struct {
+      char in_layer0_[28];
+      int32_t head;        /* PDEGYM_MLP_HEAD_*: what becomes of the last layer's output (0: PLAIN)                              */
+      char in_layer1_[28];
+      float log_std_min;   /* SQUASHED_GAUSSIAN: the clip of log_std (SB3's SAC: -20, 2), min <= max                             */
+      char in_layer2_[28];
+      float log_std_max;
+    };
+  };
 } pdegym_mlp;
+
+/* The head.  PLAIN: y = clamp(last layer + noise), as described at the fields above.
+ * SQUASHED_GAUSSIAN: the actor SB3's SAC samples while it learns, a = tanh(mu(s) + exp(clip(log_std(s), min, max)) * eps), rescaled
+ * from [-1, 1] to the action box.  The last layer has 2A outputs and the IDENTITY activation: neurons 0 .. A-1 are mu, neurons
+ * A .. 2A-1 are log_std (the rows [mu; log_std] of the two torch.nn.Linear heads, one above the other).  y, the actions of a rollout
+ * and noise have A columns; noise holds STANDARD-NORMAL draws eps (not pre-scaled noise: the standard deviation depends on the state),
+ * noise_stride >= A.  clamp must be set with lo < hi -- the action box -- and log_std_min <= log_std_max; anything else is -2.
+ * pdegym_mlp_forward takes A <= 8 (mu and log_std of a row then sit in one row of 16 lanes of the matrix-core result, one DPP row shift
+ * apart); the rollout kernels take their own A (1, or 2 for two-command traffic).  Arithmetic, per output, float32, every operation
+ * rounded on its own (no fused multiply-add), in the order of SB3's torch ops -- expf and tanhf are the only places where the result
+ * can differ from torch float32:
+ *     s = clip_keep_nan(log_std, log_std_min, log_std_max)
+ *     z = noise ? mu + (expf(s) * eps) : mu            noise == NULL: the deterministic actor; log_std is not looked at at all
+ *     u = tanhf(z)
+ *     c = lo + ((0.5f * (u + 1.0f)) * (hi - lo))       SB3's unscale_action, in its order
+ *     c = clip_keep_nan(c, lo, hi)                     the box contract survives the last rounding
+ * One device function (pdegym_mlp_tile.h: squashed_gaussian) serves pdegym_mlp_forward and both evaluators inside the rollout
+ * kernels: equal pre-activations give equal bits everywhere.  Non-finite data (conventions above): a NaN in mu, or with noise a NaN
+ * in log_std or in eps, gives a NaN command; mu = -Inf gives lo, mu = +Inf gives lo + (hi - lo) clipped to the box (hi itself
+ * whenever that sum is exact, e.g. for dyadic bounds; otherwise within one rounding of it); log_std = +-Inf is clipped like any
+ * other value; eps = +-Inf gives hi / lo (NaN when sigma underflowed to 0: 0 * Inf).  A replay buffer that stores SB3's scaled
+ * action recovers it as 2 (c - lo) / (hi - lo) - 1.  Log-probabilities are not computed (SAC recomputes them under autograd). */
+enum { PDEGYM_MLP_HEAD_PLAIN = 0, PDEGYM_MLP_HEAD_SQUASHED_GAUSSIAN = 1 };
 
 /* y[b, :] = net(x[b, :]) for b < B; x_stride / y_stride = ELEMENTS between consecutive rows (>= the row lengths). */
 int pdegym_mlp_forward(const pdegym_mlp* net, const void* x, int64_t x_stride, void* y, int64_t y_stride, int32_t B,

@@ -14,6 +14,11 @@ class DeviceRollout:
     torch module, or a ``pdecontrolgym_amd.FusedMLP`` (Linear/Tanh/ReLU stack evaluated, clamped and stored in ONE launch).
     Buffers: ``obs[T+1, B, D]``, ``actions[T, B]`` (``[T, B, action_dim]`` for Navier-Stokes and two-command traffic), ``rewards[T, B]``, ``terminated[T, B]``, ``truncated[T, B]``; with
     ``action_noise=True`` also ``action_noise[T, B]`` (float32), added to the policy output of step t before the clamp.
+    With a squashed-Gaussian policy (``FusedMLP.squashed_gaussian`` / ``FusedMLP.from_sb3(policy, stochastic=True)``: SAC's sampling
+    actor) ``action_low`` / ``action_high`` are the action BOX the squashed sample is rescaled to, ``action_noise=True`` allocates the
+    standard-normal draws ``eps`` (fill with ``ro.action_noise.normal_()``, no ``mul_``: the deviation depends on the state),
+    ``action_noise=False`` gives the deterministic actor, and ``actions[t]`` holds the command ``c`` in ``[lo, hi]``; SB3's scaled
+    action, which a replay buffer stores, is ``2 (c - lo) / (hi - lo) - 1``.  Step loop, hipGraph and ``one_launch`` all take it.
     ``one_launch``: see the constructor (1D engines with full-state sensing + a small ``FusedMLP``: the rollout is ONE kernel).
     ``one_launch=True`` with an attached ``BacksteppingController`` on a transport / reaction-diffusion environment (Dirichlet
     actuation, full-state sensing, rows of up to 512 (transport) / 513 (parabolic) nodes): the law runs inside the rollout kernel as

@@ -11,7 +11,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "lib", "libpdegym_hip.so")
 
-ABI_VERSION = 20
+ABI_VERSION = 21
 RING = 128
 LOOKBACK = 100
 MAX_N1D = 8192
@@ -41,6 +41,7 @@ EXPORTS = [
 DEBUG_NS_GENERIC, DEBUG_NS_NO_COL, DEBUG_NS_COL_MIN_BATCH, DEBUG_NS_NO_LDS_JACOBI = range(4)
 MLP_MAX_LAYERS, MLP_MAX_WIDTH, MLP_MAX_INPUT = 4, 256, 8192
 MLP_IDENTITY, MLP_TANH, MLP_RELU = 0, 1, 2
+MLP_HEAD_PLAIN, MLP_HEAD_SQUASHED_GAUSSIAN = 0, 1
 BACKSTEP_TREE, BACKSTEP_ORDERED = 0, 1
 TRAFFIC_BACKSTEP_TREE, TRAFFIC_BACKSTEP_NUMPY = 0, 1
 TRAFFIC_BACKSTEP_NUMPY_MAX_M = 129      # the longest row whose np.trapz sum is un-recursed (128 terms)
@@ -148,10 +149,22 @@ class MlpLayer(C.Structure):
                 ("reserved_", C.c_int32)]
 
 
+class _MlpHead(C.Structure):
+    """The head's fields (ABI 21) in the reserved words of layer[0 .. 2]: the descriptor keeps the size and offsets of ABI 20."""
+    _fields_ = [("in_layer0_", C.c_char * 28), ("head", C.c_int32), ("in_layer1_", C.c_char * 28), ("log_std_min", C.c_float),
+                ("in_layer2_", C.c_char * 28), ("log_std_max", C.c_float)]
+
+
+class _MlpLayers(C.Union):
+    _fields_ = [("layer", MlpLayer * MLP_MAX_LAYERS), ("head_", _MlpHead)]
+    _anonymous_ = ("head_",)
+
+
 class Mlp(C.Structure):
     _fields_ = [("n_layers", C.c_int32), ("clamp", C.c_int32), ("lo", C.c_float), ("hi", C.c_float),
                 ("x_f64", C.c_int32), ("y_f64", C.c_int32), ("noise", C.c_void_p), ("noise_stride", C.c_int64),
-                ("layer", MlpLayer * MLP_MAX_LAYERS)]
+                ("layers_", _MlpLayers)]
+    _anonymous_ = ("layers_",)
 
 
 class Backstep(C.Structure):

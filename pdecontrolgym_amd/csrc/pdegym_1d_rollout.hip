@@ -82,14 +82,21 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void rollout1d_general_kerne
 // ---- the policy inside the rollout kernel (pdegym_policy.h: prologue, evaluate, command, shaped) ----------------------------------
 // A wave without an instance of a WIDE workgroup stays in the loop of T iterations and `continue`s behind the evaluation (not
 // pdegym_policy::attend, the traffic and tumor kernels' way: here the loop's form is the quicker one, profiles/policy_host_resources.txt).
-// The network's output on its way to the command of step t: + noise[t, b], clamped, stored to actions[t, b].
-__device__ __forceinline__ float policy_command(float a, const pdegym_mlp& N, const pdegym_rollout1d& Ro, int B, int inst, int lane, int t) {
-  a = pdegym_policy::shaped(a, N, t, B, inst, 0);
+// The network's output on its way to the command of step t (either head), stored to actions[t, b].
+template <bool WIDE, bool GAUSS>
+__device__ __forceinline__ float policy_command(float o, const pdegym_mlp& N, const pdegym_policy::Wide& Wd, const pdegym_rollout1d& Ro, int B,
+                                                int inst, int wave, int lane, int t) {
+  namespace pol = pdegym_policy;
+  float a;
+  if constexpr (GAUSS)      // the squashed-Gaussian head: neuron 0 is mu, neuron 1 log_std
+    a = pol::shaped_gaussian(pol::command<WIDE>(o, Wd, wave, 0), pol::command<WIDE>(o, Wd, wave, 1), N, t, B, inst, 0);
+  else
+    a = pol::shaped(pol::command<WIDE>(o, Wd, wave, 0), N, t, B, inst, 0);
   if (lane == 0) Ro.actions[(size_t)t * B + inst] = a;
   return a;
 }
 
-template <int EPL, bool PARABOLIC, bool BURGERS, bool WIDE, bool FULL>
+template <int EPL, bool PARABOLIC, bool BURGERS, bool WIDE, bool FULL, bool GAUSS>
 __global__ __launch_bounds__(kWave* pdegym_policy::kWaves) void rollout1d_policy_kernel(pdegym_params1d P, pdegym_bufs1d Bf,
                                                                                         pdegym_rollout1d Ro, pdegym_mlp N, int B) {
   namespace pol = pdegym_policy;
@@ -109,9 +116,9 @@ __global__ __launch_bounds__(kWave* pdegym_policy::kWaves) void rollout1d_policy
       stage_carried_row<EPL, PARABOLIC>(C, W.xw, n, lane);
       sense_noise(Ro.obs_noise, Ro.obs_seen, W.xw, n, B, inst, lane, t);
     }
-    float a = pol::command<WIDE>(pol::evaluate<WIDE>(W, Wd, N, pol_smem, n, wave, lane), Wd, wave, 0);
+    const float o = pol::evaluate<WIDE, GAUSS>(W, Wd, N, pol_smem, n, wave, lane);
     if (!active) continue;
-    a = policy_command(a, N, Ro, B, inst, lane, t);
+    float a = policy_command<WIDE, GAUSS>(o, N, Wd, Ro, B, inst, wave, lane, t);
     const pdegym_bufs1d S = rollout_step_view(Bf, Ro, B, slot, t);
     step1d_body<EPL, PARABOLIC, false, false, BURGERS, false, true, true, FULL>(P, S, B, inst, lane, &a, &C, t == Ro.T - 1);
   }
@@ -120,7 +127,7 @@ __global__ __launch_bounds__(kWave* pdegym_policy::kWaves) void rollout1d_policy
 
 // The policy in front of the general step (Neumann actuation / scalar sensing): its input is observation slot t as stored -- od = n
 // values, or the one sensed value -- read back from memory after the previous iteration's fence.
-template <int EPL, bool PARABOLIC, bool NEUMANN, bool BURGERS, bool WIDE>
+template <int EPL, bool PARABOLIC, bool NEUMANN, bool BURGERS, bool WIDE, bool GAUSS>
 __global__ __launch_bounds__(kWave* pdegym_policy::kWaves) void rollout1d_policy_general_kernel(pdegym_params1d P, pdegym_bufs1d Bf,
                                                                                                 pdegym_rollout1d Ro, pdegym_mlp N, int B) {
   namespace pol = pdegym_policy;
@@ -139,9 +146,9 @@ __global__ __launch_bounds__(kWave* pdegym_policy::kWaves) void rollout1d_policy
       wave_lds_sync();
       sense_noise(Ro.obs_noise, Ro.obs_seen, W.xw, od, B, inst, lane, t);
     }
-    float a = pol::command<WIDE>(pol::evaluate<WIDE>(W, Wd, N, pol_smem, od, wave, lane), Wd, wave, 0);
+    const float o = pol::evaluate<WIDE, GAUSS>(W, Wd, N, pol_smem, od, wave, lane);
     if (!active) continue;
-    a = policy_command(a, N, Ro, B, inst, lane, t);
+    float a = policy_command<WIDE, GAUSS>(o, N, Wd, Ro, B, inst, wave, lane, t);
     rollout1d_general_step<EPL, PARABOLIC, NEUMANN, BURGERS>(P, Bf, Ro, B, inst, lane, t, &a);
   }
 }
@@ -175,17 +182,19 @@ int launch_rollout(const pdegym_params1d* prm, const pdegym_bufs1d* buf, const p
     constexpr std::true_type yes{};
     constexpr std::false_type no{};
     // each kernel is named where it is launched (tests/test_poison_helper.py reads the names there)
-    with_epl<8>(epl, [&](auto tag) {
+    // the head is compiled in (a run-time branch on it cost the plain head 1 % at C2: DESIGN.md section 4.11)
+    auto with_head = [&](auto tag, auto gauss_tag) {
       constexpr int E = decltype(tag)::value;
+      constexpr bool G = decltype(gauss_tag)::value;
       auto carried = [&](auto wide_tag, auto full_tag) {
         constexpr bool W = decltype(wide_tag)::value, F = decltype(full_tag)::value;
-        if (pdegym_policy::lds_limit_raised<&rollout1d_policy_kernel<E, PARABOLIC, BURGERS, W, F>>(failure, rc))
-          hipLaunchKernelGGL((rollout1d_policy_kernel<E, PARABOLIC, BURGERS, W, F>), pl.grid, pl.block, pl.lds_bytes, st, P, *buf, *ro, N, B);
+        if (pdegym_policy::lds_limit_raised<&rollout1d_policy_kernel<E, PARABOLIC, BURGERS, W, F, G>>(failure, rc))
+          hipLaunchKernelGGL((rollout1d_policy_kernel<E, PARABOLIC, BURGERS, W, F, G>), pl.grid, pl.block, pl.lds_bytes, st, P, *buf, *ro, N, B);
       };
       auto in_general = [&](auto neumann_tag, auto wide_tag) {
         constexpr bool NEU = decltype(neumann_tag)::value, W = decltype(wide_tag)::value;
-        if (pdegym_policy::lds_limit_raised<&rollout1d_policy_general_kernel<E, PARABOLIC, NEU, BURGERS, W>>(failure, rc))
-          hipLaunchKernelGGL((rollout1d_policy_general_kernel<E, PARABOLIC, NEU, BURGERS, W>), pl.grid, pl.block, pl.lds_bytes, st, P, *buf, *ro, N, B);
+        if (pdegym_policy::lds_limit_raised<&rollout1d_policy_general_kernel<E, PARABOLIC, NEU, BURGERS, W, G>>(failure, rc))
+          hipLaunchKernelGGL((rollout1d_policy_general_kernel<E, PARABOLIC, NEU, BURGERS, W, G>), pl.grid, pl.block, pl.lds_bytes, st, P, *buf, *ro, N, B);
       };
       if (general) {
         if (neumann) return wide ? in_general(yes, yes) : in_general(yes, no);
@@ -195,7 +204,8 @@ int launch_rollout(const pdegym_params1d* prm, const pdegym_bufs1d* buf, const p
         if (nslots == kWave * E) return wide ? carried(yes, yes) : carried(no, yes);
       }
       return wide ? carried(yes, no) : carried(no, no);
-    });
+    };
+    with_epl<8>(epl, [&](auto tag) { return pdegym_policy::is_gaussian(N) ? with_head(tag, yes) : with_head(tag, no); });
     return rc ? rc : pdegym::check_launch("rollout1d_policy");
   }
   const dim3 grid((B + kWavesPerBlock - 1) / kWavesPerBlock), block(kWave * kWavesPerBlock);

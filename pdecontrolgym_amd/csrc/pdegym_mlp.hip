@@ -36,7 +36,8 @@ constexpr int kXChunk = 512;                // observation entries per row stage
 // units, 8 up to 128, 16 up to 256.  The reduction is bound by the latency of the weight stream, and more waves keep more
 // loads in flight per CU than fewer waves with more tiles each (257-256-256-1 at B = 4096: 27.7 us with 4 waves x 4 tiles,
 // 21.4 with 8 x 2, 19.2 with 16 x 1).
-template <int NT, int WV, typename TX, typename TY>
+// GAUSS: the squashed-Gaussian head's epilogue, compiled apart -- as a run-time branch it cost the plain head 1 %
+template <int NT, int WV, typename TX, typename TY, bool GAUSS>
 __global__ __launch_bounds__(64 * WV) void mlp_forward_kernel(pdegym_mlp N, const TX* __restrict__ x, long long x_stride,
                                                           TY* __restrict__ y, long long y_stride, int B, int ldx) {
   // LDS: activations ping-pong between hb0 and hb1; the staged observation chunk shares its space with hb1 (first written
@@ -156,7 +157,15 @@ __global__ __launch_bounds__(64 * WV) void mlp_forward_kernel(pdegym_mlp N, cons
         for (int v = 0; v < 4; ++v) {
           const int r = 4 * lg + v;
           float o = n < H ? activate(av[v] + bias_all[l][t], L.act) : 0.f;
-          if (last) {
+          if (GAUSS && last) {
+            // H = 2A <= 16: tile 0 of wave 0, all of whose lanes are here; lane li = a holds mu[a] of row r and lane A + a of the
+            // same row of 16 lanes its log_std[a].  Only the mu lanes store, into the A columns of y.
+            const int A = H >> 1;
+            const float log_std = row_lane_plus(o, A);
+            const bool mine = n < A && row0 + r < B;
+            const float eps = (N.noise && mine) ? N.noise[(long long)(row0 + r) * N.noise_stride + n] : 0.f;
+            if (mine) y[(long long)(row0 + r) * y_stride + n] = (TY)squashed_gaussian(o, log_std, N.noise != nullptr, eps, N);
+          } else if (last) {
             if (N.noise && n < H && row0 + r < B) o += N.noise[(long long)(row0 + r) * N.noise_stride + n];
             if (N.clamp) o = pdegym::clip_keep_nan(o, N.lo, N.hi);
             if (n < H && row0 + r < B) y[(long long)(row0 + r) * y_stride + n] = (TY)o;
@@ -172,23 +181,29 @@ __global__ __launch_bounds__(64 * WV) void mlp_forward_kernel(pdegym_mlp N, cons
 
 }  // namespace
 
-template <int NT, int WV, typename TX, typename TY>
+template <int NT, int WV, typename TX, typename TY, bool GAUSS>
 static void launch_mlp_nt(const pdegym_mlp* net, const TX* xp, long long xs, TY* yp, long long ys, int B, hipStream_t st) {
   const int kin = net->layer[0].in_dim < kXChunk ? net->layer[0].in_dim : kXChunk;
   const int ldh = lds_stride(16 * WV * NT);
   const int ldx = lds_stride(kin) > ldh ? lds_stride(kin) : ldh;
   const size_t lds_bytes = (size_t)kRows * (ldh + ldx) * sizeof(float);         // <= 50 KB: below the 64 KB that need no opt-in
-  hipLaunchKernelGGL((mlp_forward_kernel<NT, WV, TX, TY>), dim3((B + kRows - 1) / kRows), dim3(64 * WV), lds_bytes, st, *net, xp, xs, yp, ys,
+  hipLaunchKernelGGL((mlp_forward_kernel<NT, WV, TX, TY, GAUSS>), dim3((B + kRows - 1) / kRows), dim3(64 * WV), lds_bytes, st, *net, xp, xs, yp, ys,
                      B, ldx);
+}
+
+template <typename TX, typename TY, bool GAUSS>
+static void launch_mlp_head(const pdegym_mlp* net, const TX* xp, long long xs, TY* yp, long long ys, int B, int width, hipStream_t st) {
+  if (width <= 64) launch_mlp_nt<1, 4, TX, TY, GAUSS>(net, xp, xs, yp, ys, B, st);
+  else if (width <= 128) launch_mlp_nt<1, 8, TX, TY, GAUSS>(net, xp, xs, yp, ys, B, st);
+  else launch_mlp_nt<1, 16, TX, TY, GAUSS>(net, xp, xs, yp, ys, B, st);
 }
 
 template <typename TX, typename TY>
 static void launch_mlp(const pdegym_mlp* net, const void* x, long long xs, void* y, long long ys, int B, int width, hipStream_t st) {
   const TX* xp = static_cast<const TX*>(x);
   TY* yp = static_cast<TY*>(y);
-  if (width <= 64) launch_mlp_nt<1, 4, TX, TY>(net, xp, xs, yp, ys, B, st);
-  else if (width <= 128) launch_mlp_nt<1, 8, TX, TY>(net, xp, xs, yp, ys, B, st);
-  else launch_mlp_nt<1, 16, TX, TY>(net, xp, xs, yp, ys, B, st);
+  if (net->head == PDEGYM_MLP_HEAD_SQUASHED_GAUSSIAN) launch_mlp_head<TX, TY, true>(net, xp, xs, yp, ys, B, width, st);
+  else launch_mlp_head<TX, TY, false>(net, xp, xs, yp, ys, B, width, st);
 }
 
 extern "C" int pdegym_mlp_forward(const pdegym_mlp* net, const void* x, int64_t x_stride, void* y, int64_t y_stride, int32_t B,
@@ -205,10 +220,20 @@ extern "C" int pdegym_mlp_forward(const pdegym_mlp* net, const void* x, int64_t 
     if (l > 0 && L.in_dim != net->layer[l - 1].out_dim) return pdegym::fail(-2, "layer input size does not match the previous layer");
     if (L.act < PDEGYM_MLP_IDENTITY || L.act > PDEGYM_MLP_RELU) return pdegym::fail(-2, "unknown activation");
   }
-  if (x_stride < net->layer[0].in_dim || y_stride < net->layer[net->n_layers - 1].out_dim)
-    return pdegym::fail(-2, "row stride shorter than the row");
+  int n_out = net->layer[net->n_layers - 1].out_dim;      // columns of y and of noise
+  if (net->head == PDEGYM_MLP_HEAD_SQUASHED_GAUSSIAN) {
+    if (n_out % 2) return pdegym::fail(-2, "squashed-Gaussian head: the last layer holds [mu; log_std], an even number of outputs");
+    if (net->layer[net->n_layers - 1].act != PDEGYM_MLP_IDENTITY) return pdegym::fail(-2, "squashed-Gaussian head: the last layer's activation must be IDENTITY");
+    if (n_out > 16) return pdegym::fail(-2, "squashed-Gaussian head: pdegym_mlp_forward takes at most 8 actions");
+    if (!net->clamp || !(net->lo < net->hi)) return pdegym::fail(-2, "squashed-Gaussian head: clamp must be set with lo < hi (the action box)");
+    if (!(net->log_std_min <= net->log_std_max)) return pdegym::fail(-2, "squashed-Gaussian head: log_std_min <= log_std_max");
+    n_out /= 2;
+  } else if (net->head != PDEGYM_MLP_HEAD_PLAIN) {
+    return pdegym::fail(-2, "unknown head");
+  }
+  if (x_stride < net->layer[0].in_dim || y_stride < n_out) return pdegym::fail(-2, "row stride shorter than the row");
   if (net->clamp && !(net->lo <= net->hi)) return pdegym::fail(-2, "clamp bounds must satisfy lo <= hi");
-  if (net->noise && net->noise_stride < net->layer[net->n_layers - 1].out_dim) return pdegym::fail(-2, "noise row stride shorter than the row");
+  if (net->noise && net->noise_stride < n_out) return pdegym::fail(-2, "noise row stride shorter than the row");
   if (B == 0) return 0;
   int width = 0;
   for (int l = 0; l < net->n_layers; ++l) width = net->layer[l].out_dim > width ? net->layer[l].out_dim : width;

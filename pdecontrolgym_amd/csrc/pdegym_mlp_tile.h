@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include "pdegym.h"
+#include "pdegym_common.h"
 
 namespace pdegym_mlp_tile {
 
@@ -27,6 +28,37 @@ __device__ __forceinline__ float activate(float v, int act) {
   if (act == PDEGYM_MLP_TANH) return tanhf(v);
   if (act == PDEGYM_MLP_RELU) return (v > 0.f || v != v) ? v : 0.f;      // torch.relu keeps a NaN
   return v;
+}
+
+// The squashed-Gaussian head (include/pdegym.h: PDEGYM_MLP_HEAD_SQUASHED_GAUSSIAN), the ONE copy of its arithmetic: pdegym_mlp_forward's
+// epilogue and both evaluators inside the rollout kernels call it, so equal pre-activations give equal bits everywhere.  Every
+// operation is rounded on its own (hipcc contracts a * b + c by default: the _rn intrinsics do not contract), in the order of SB3's
+// torch ops.  noisy false: the deterministic actor, log_std is not looked at.
+__device__ __forceinline__ float squashed_gaussian(float mu, float log_std, bool noisy, float eps, const pdegym_mlp& N) {
+  float z = mu;
+  if (noisy) z = __fadd_rn(mu, __fmul_rn(expf(pdegym::clip_keep_nan(log_std, N.log_std_min, N.log_std_max)), eps));
+  const float u = tanhf(z);
+  const float c = __fadd_rn(N.lo, __fmul_rn(__fmul_rn(0.5f, __fadd_rn(u, 1.0f)), __fsub_rn(N.hi, N.lo)));
+  return pdegym::clip_keep_nan(c, N.lo, N.hi);
+}
+
+// lane i <- lane i + A of its row of 16 lanes, A = 1 .. 8 wave-uniform (DPP row_shl:A, one v_mov_b32_dpp: no LDS round trip as a
+// ds_bpermute would be); lanes i + A >= 16 of a row get 0.  Every lane of the wave must be active (pdegym_common.h, at pinned_from_left).
+__device__ __forceinline__ float row_lane_plus(float v, int A) {
+  using pdegym::wave::dpp_move;
+  float r = 0.f;
+  switch (A) {
+    case 1: r = dpp_move<0x101, 0xf, true>(v); break;
+    case 2: r = dpp_move<0x102, 0xf, true>(v); break;
+    case 3: r = dpp_move<0x103, 0xf, true>(v); break;
+    case 4: r = dpp_move<0x104, 0xf, true>(v); break;
+    case 5: r = dpp_move<0x105, 0xf, true>(v); break;
+    case 6: r = dpp_move<0x106, 0xf, true>(v); break;
+    case 7: r = dpp_move<0x107, 0xf, true>(v); break;
+    default: r = dpp_move<0x108, 0xf, true>(v); break;
+  }
+  asm volatile("" : "+v"(r));
+  return r;
 }
 
 // weights of k-blocks kb0 .. kb0 + kStage - 1 for this lane: group g = 4 kb + l / 16 of the blocked matrix, neuron n (already

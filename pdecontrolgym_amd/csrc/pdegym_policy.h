@@ -47,11 +47,17 @@ __host__ __device__ inline bool is_wide(const pdegym_mlp& N) {
 // 16 commands; row strides as in pdegym_mlp_forward
 __host__ __device__ inline int wide_ldx(int n_in) { return pdegym_mlp_tile::lds_stride((n_in + 15) & ~15); }
 constexpr int kWideLdh = pdegym_mlp_tile::lds_stride(kWideMax);
-constexpr int kWideOut = 2;            // outputs kept per row (neurons 0 and 1 of the last layer: the traffic engine's two commands)
-__host__ __device__ inline int wide_lds_floats(int n_in) { return kWaves * (wide_ldx(n_in) + 2 * kWideLdh) + kWideOut * kWaves; }
+constexpr int kWideOut = 2;            // commands per row at most (the traffic engine's two)
+__host__ __device__ inline bool is_gaussian(const pdegym_mlp& N) { return N.head == PDEGYM_MLP_HEAD_SQUASHED_GAUSSIAN; }
+// outputs kept per row: neurons 0 and 1 of the last layer for the plain head, 0 .. 3 for the squashed-Gaussian head ([mu; log_std] of
+// two commands) -- a second block of kWideOut per row BEHIND the first, so that the plain head's layout and size stay what they were
+__host__ __device__ inline int wide_kept(const pdegym_mlp& N) { return is_gaussian(N) ? 2 * kWideOut : kWideOut; }
+__host__ __device__ inline int wide_lds_floats(const pdegym_mlp& N, int n_in) {
+  return kWaves * (wide_ldx(n_in) + 2 * kWideLdh) + wide_kept(N) * kWaves;
+}
 // floats of LDS: per layer its weights and a bias row of 64, then per wave the padded observation row and two hidden rows of 64
 __host__ __device__ inline int lds_floats(const pdegym_mlp& N, int n_in) {
-  if (is_wide(N)) return wide_lds_floats(n_in);
+  if (is_wide(N)) return wide_lds_floats(N, n_in);
   int f = 0;
   for (int l = 0; l < N.n_layers; ++l) f += groups(N.layer[l].in_dim) * 4 * N.layer[l].out_dim + kMaxWidth;
   return f + kWaves * (xpad(n_in) + 2 * kMaxWidth);
@@ -69,7 +75,15 @@ inline const char* check(const pdegym_mlp& N, int n_in, int n_out, bool allow_wi
       return allow_wide ? "policy inside the rollout kernel: layers of 1..256 units" : "policy inside the rollout kernel: layers of 1..64 units";
     if (L.act < PDEGYM_MLP_IDENTITY || L.act > PDEGYM_MLP_RELU) return "policy: unknown activation";
   }
-  if (N.layer[N.n_layers - 1].out_dim != n_out) return "policy: the last layer must produce one command per actuator";
+  if (N.head != PDEGYM_MLP_HEAD_PLAIN && !is_gaussian(N)) return "policy: unknown head";
+  if (is_gaussian(N)) {
+    if (N.layer[N.n_layers - 1].out_dim != 2 * n_out) return "policy: a squashed-Gaussian head's last layer must produce mu and log_std per actuator";
+    if (N.layer[N.n_layers - 1].act != PDEGYM_MLP_IDENTITY) return "policy: a squashed-Gaussian head's last layer must have the IDENTITY activation";
+    if (!N.clamp || !(N.lo < N.hi)) return "policy: a squashed-Gaussian head needs clamp set with lo < hi (the action box)";
+    if (!(N.log_std_min <= N.log_std_max)) return "policy: a squashed-Gaussian head needs log_std_min <= log_std_max";
+  } else if (N.layer[N.n_layers - 1].out_dim != n_out) {
+    return "policy: the last layer must produce one command per actuator";
+  }
   if (N.clamp && !(N.lo <= N.hi)) return "policy: clamp bounds must satisfy lo <= hi";
   if (N.noise && N.noise_stride < n_out) return "policy: noise row stride shorter than the command";
   if (lds_floats(N, n_in) * (int)sizeof(float) > kMaxLdsBytes)
@@ -165,7 +179,7 @@ __device__ __forceinline__ float eval(const pdegym_mlp& N, const Staged& S, cons
 struct Wide {
   float* X;       // [16][ldx] observation rows (row = wave), zero beyond n_in up to a multiple of 16
   float* H[2];    // [16][kWideLdh] hidden activations, ping-pong
-  float* act;     // [16][kWideOut] neurons 0 .. kWideOut - 1 of the last layer per row
+  float* act;     // [16][kWideOut] neurons 0, 1 of the last layer per row; squashed-Gaussian head: [16][kWideOut] more, neurons 2, 3
   int ldx;
 };
 
@@ -184,7 +198,9 @@ __device__ __forceinline__ Wide wide_setup(const pdegym_mlp& N, float* smem, int
 
 // ALL 16 waves of the workgroup call this in every env-step (waves without an instance too: their row stays zero), having written
 // their observation row into W.X[wave]; returns the value of neuron 0 of the last layer for row `wave` (wide_out: the others).
-// Barriers: one ahead of the first layer, one per layer.
+// Barriers: one ahead of the first layer, one per layer.  GAUSS: the squashed-Gaussian head, whose neurons 2, 3 are kept as well -- a
+// template parameter, so that the plain head's code is what it was (measured: DESIGN.md section 4.11).
+template <bool GAUSS = false>
 __device__ __forceinline__ float eval_wide(const pdegym_mlp& N, const Wide& W, int n_in, int wave, int lane) {
   namespace mt = pdegym_mlp_tile;
   const int li = lane & 15, lg = lane >> 4;
@@ -228,6 +244,9 @@ __device__ __forceinline__ float eval_wide(const pdegym_mlp& N, const Wide& W, i
         const float o = n < H ? mt::activate(av[v] + bias, L.act) : 0.f;
         if (last) {
           if (n < kWideOut) W.act[r * kWideOut + n] = o;
+          else if constexpr (GAUSS) {
+            if (n < 2 * kWideOut) W.act[(kWaves + r) * kWideOut + n - kWideOut] = o;
+          }
         } else {
           hout[r * kWideLdh + n] = o;
         }
@@ -238,7 +257,10 @@ __device__ __forceinline__ float eval_wide(const pdegym_mlp& N, const Wide& W, i
   return W.act[wave * kWideOut];
 }
 
-__device__ __forceinline__ float wide_out(const Wide& W, int wave, int k) { return W.act[wave * kWideOut + k]; }
+// neuron k (< wide_kept) of the last layer for row `wave`
+__device__ __forceinline__ float wide_out(const Wide& W, int wave, int k) {
+  return k < kWideOut ? W.act[wave * kWideOut + k] : W.act[(kWaves + wave) * kWideOut + k - kWideOut];
+}
 
 // ---- hosting an evaluator inside a rollout kernel: what every kernel with a policy inside does around eval / eval_wide ----------
 // The kernel's own: how the policy's input row gets into xw (and wave_lds_sync() after it), and where the command is stored.
@@ -269,20 +291,21 @@ __device__ __forceinline__ bool prologue(PolicyWave& W, Wide& Wd, const pdegym_m
 
 // All a wave without an instance does in a WIDE workgroup after the prologue: it attends the barriers of the T evaluations (its input
 // row stays zero, it stores nothing) and returns, so the kernel loads no instance state for it.
-__device__ __forceinline__ void attend(const pdegym_mlp& N, const Wide& Wd, int n_in, int T, int wave, int lane) {
-  for (int t = 0; t < T; ++t) eval_wide(N, Wd, n_in, wave, lane);
+template <bool GAUSS = false>
+__device__ __forceinline__ void attend(const pdegym_mlp& N, const Wide& Wd, int n_in, int T, int wave, int lane, std::bool_constant<GAUSS> = {}) {
+  for (int t = 0; t < T; ++t) eval_wide<GAUSS>(N, Wd, n_in, wave, lane);
 }
 
 // The network on the wave's input row, once per step (WIDE: barriers inside, so every wave of the workgroup is in here or in attend()
 // T times).  Returns what command() takes the outputs from.
-template <bool WIDE>
+template <bool WIDE, bool GAUSS = false>
 __device__ __forceinline__ float evaluate(const PolicyWave& W, const Wide& Wd, const pdegym_mlp& N, const float* smem, int n_in, int wave,
                                           int lane) {
-  if constexpr (WIDE) return eval_wide(N, Wd, n_in, wave, lane);
+  if constexpr (WIDE) return eval_wide<GAUSS>(N, Wd, n_in, wave, lane);
   else return eval(N, W.St, smem, W.xw, W.hw, n_in, lane);
 }
 
-// Output neuron k (< kWideOut) of the last layer for this wave's row, wave-uniform; o: evaluate()'s value, which serves every k.
+// Output neuron k (< wide_kept) of the last layer for this wave's row, wave-uniform; o: evaluate()'s value, which serves every k.
 template <bool WIDE>
 __device__ __forceinline__ float command(float o, const Wide& Wd, int wave, int k) {
   if constexpr (WIDE) return k == 0 ? o : wide_out(Wd, wave, k);
@@ -294,6 +317,13 @@ __device__ __forceinline__ float shaped(float c, const pdegym_mlp& N, int t, int
   if (N.noise) c += N.noise[((size_t)t * B + inst) * N.noise_stride + k];
   if (N.clamp) c = pdegym::clip_keep_nan(c, N.lo, N.hi);
   return c;
+}
+
+// The squashed-Gaussian head's companion of shaped(): mu and log_std of actuator k -> the command in the action box, with
+// eps = noise[t, inst, k] (pdegym_mlp_tile.h: squashed_gaussian, the function pdegym_mlp_forward's epilogue calls).
+__device__ __forceinline__ float shaped_gaussian(float mu, float log_std, const pdegym_mlp& N, int t, int B, int inst, int k) {
+  const float eps = N.noise ? N.noise[((size_t)t * B + inst) * N.noise_stride + k] : 0.f;
+  return pdegym_mlp_tile::squashed_gaussian(mu, log_std, N.noise != nullptr, eps, N);
 }
 
 // ---- ... and launching such a kernel (host) -----------------------------------------------------------------------------------------
@@ -316,12 +346,15 @@ inline Plan plan(const pdegym_mlp* policy, int n_in, int n_out, int B, size_t ex
   return P;
 }
 
-// f(wide_tag, policy_tag) with the std::bool_constant pair of a launch
+// f(wide_tag, policy_tag, gaussian_tag) with the std::bool_constant triple of a launch (the head is compiled in: a run-time branch on
+// it cost the plain head 0.5 - 1 % at C2)
 template <class F>
-inline void dispatch(bool policy, bool wide, F&& f) {
-  if (wide) f(std::true_type{}, std::true_type{});
-  else if (policy) f(std::false_type{}, std::true_type{});
-  else f(std::false_type{}, std::false_type{});
+inline void dispatch(const pdegym_mlp* policy, bool wide, F&& f) {
+  constexpr std::true_type yes{};
+  constexpr std::false_type no{};
+  if (!policy) return f(no, no, no);
+  if (is_gaussian(*policy)) return wide ? f(yes, yes, yes) : f(no, yes, yes);
+  return wide ? f(yes, yes, no) : f(no, yes, no);
 }
 
 // Raise Kernel's dynamic-LDS limit to kMaxLdsBytes (once per kernel and device); on failure rc = -4 with `failure` as the message.

@@ -68,7 +68,7 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void traffic_step_kernel(pde
 // only attends their barriers (pdegym_policy.h: attend) and loads nothing.
 // POLICY: compiled apart, so that the commands-given-ahead form carries none of the policy's loads (a load under a run-time branch
 // leaves the compiler's wait-count pass with "may be pending" registers at every join of the loop).
-template <bool WIDE, bool POLICY>
+template <bool WIDE, bool POLICY, bool GAUSS = false>
 __global__ __launch_bounds__(kWave* pdegym_policy::kWaves) void traffic_rollout_kernel(pdegym_params_traffic P, pdegym_bufs_traffic Bf,
                                                                                        pdegym_rollout_traffic Ro, pdegym_mlp N, TrafficConsts K,
                                                                                        int B) {
@@ -86,7 +86,7 @@ __global__ __launch_bounds__(kWave* pdegym_policy::kWaves) void traffic_rollout_
     if (!pol::prologue<WIDE>(W, Wd, N, pol_smem, D, active, wave, lane)) return;
   }
   if (!active) {
-    if constexpr (WIDE) pol::attend(N, Wd, D, Ro.T, wave, lane);
+    if constexpr (WIDE) pol::attend(N, Wd, D, Ro.T, wave, lane, std::bool_constant<GAUSS>{});
     return;
   }
   const bool in = lane < M;
@@ -122,9 +122,14 @@ __global__ __launch_bounds__(kWave* pdegym_policy::kWaves) void traffic_rollout_
       const double* xrow = Ro.obs + (size_t)t * slot + (size_t)inst * D;
       for (int j = lane; j < D; j += kWave) W.xw[j] = (float)xrow[j];
       wave_lds_sync();
-      const float o = pol::evaluate<WIDE>(W, Wd, N, pol_smem, D, wave, lane);      // one evaluation, both commands
-      a0 = (double)pol::shaped(pol::command<WIDE>(o, Wd, wave, 0), N, t, B, inst, 0);
-      if (A > 1) a1 = (double)pol::shaped(pol::command<WIDE>(o, Wd, wave, 1), N, t, B, inst, 1);
+      const float o = pol::evaluate<WIDE, GAUSS>(W, Wd, N, pol_smem, D, wave, lane);      // one evaluation, both commands
+      if constexpr (GAUSS) {      // the squashed-Gaussian head: neurons 0 .. A-1 are mu, A .. 2A-1 log_std
+        a0 = (double)pol::shaped_gaussian(pol::command<WIDE>(o, Wd, wave, 0), pol::command<WIDE>(o, Wd, wave, A), N, t, B, inst, 0);
+        if (A > 1) a1 = (double)pol::shaped_gaussian(pol::command<WIDE>(o, Wd, wave, 1), pol::command<WIDE>(o, Wd, wave, A + 1), N, t, B, inst, 1);
+      } else {
+        a0 = (double)pol::shaped(pol::command<WIDE>(o, Wd, wave, 0), N, t, B, inst, 0);
+        if (A > 1) a1 = (double)pol::shaped(pol::command<WIDE>(o, Wd, wave, 1), N, t, B, inst, 1);
+      }
       if (lane == 0) {
         arow[0] = a0;
         if (A > 1) arow[1] = a1;
@@ -351,10 +356,10 @@ int pdegym_traffic_rollout(const pdegym_params_traffic* prm, const pdegym_bufs_t
   if (pl.why) return pdegym::fail(-2, pl.why);
   const pdegym_mlp net = ro->policy ? *ro->policy : pdegym_mlp{};
   int rc = 0;
-  pdegym_policy::dispatch(ro->policy != nullptr, pl.wide, [&](auto wide_tag, auto policy_tag) {
-    constexpr bool W = decltype(wide_tag)::value, Pol = decltype(policy_tag)::value;
-    if (!Pol || pdegym_policy::lds_limit_raised<&traffic_rollout_kernel<W, Pol>>("cannot raise the dynamic LDS limit of traffic_rollout_kernel", rc))
-      hipLaunchKernelGGL((traffic_rollout_kernel<W, Pol>), pl.grid, pl.block, pl.lds_bytes, (hipStream_t)stream, *prm, *buf, *ro, net, traffic_consts(*prm), B);
+  pdegym_policy::dispatch(ro->policy, pl.wide, [&](auto wide_tag, auto policy_tag, auto gauss_tag) {
+    constexpr bool W = decltype(wide_tag)::value, Pol = decltype(policy_tag)::value, G = decltype(gauss_tag)::value;
+    if (!Pol || pdegym_policy::lds_limit_raised<&traffic_rollout_kernel<W, Pol, G>>("cannot raise the dynamic LDS limit of traffic_rollout_kernel", rc))
+      hipLaunchKernelGGL((traffic_rollout_kernel<W, Pol, G>), pl.grid, pl.block, pl.lds_bytes, (hipStream_t)stream, *prm, *buf, *ro, net, traffic_consts(*prm), B);
   });
   return rc ? rc : pdegym::check_launch("traffic_rollout");
 }

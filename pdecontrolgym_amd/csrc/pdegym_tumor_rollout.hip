@@ -36,7 +36,7 @@ struct Slots {
   uint8_t* truncated;
 };
 
-template <bool WIDE, bool POLICY>
+template <bool WIDE, bool POLICY, bool GAUSS = false>
 __global__ __launch_bounds__(kWave* pol::kWaves) void tumor_rollout_kernel(pdegym_params_tumor P, pdegym_bufs_tumor Bf, pdegym_wrap_tumor Wr,
                                                                            Slots Ro, pdegym_mlp N, int rows_off, int B) {
   static_assert(POLICY || !WIDE, "the cooperative evaluation belongs to a policy");
@@ -52,7 +52,7 @@ __global__ __launch_bounds__(kWave* pol::kWaves) void tumor_rollout_kernel(pdegy
     if (!pol::prologue<WIDE>(W, Wd, N, pol_smem, nx, active, wave, lane)) return;
   }
   if (!active) {      // (WIDE: a wave without a patient attends the barriers of every step)
-    if constexpr (WIDE) pol::attend(N, Wd, nx, Ro.T, wave, lane);
+    if constexpr (WIDE) pol::attend(N, Wd, nx, Ro.T, wave, lane, std::bool_constant<GAUSS>{});
     return;
   }
   double* cur = reinterpret_cast<double*>(reinterpret_cast<char*>(pol_smem) + rows_off) + (size_t)(2 * wave) * nx;
@@ -97,7 +97,11 @@ __global__ __launch_bounds__(kWave* pol::kWaves) void tumor_rollout_kernel(pdegy
     double a;
     if constexpr (POLICY) {
       wave_lds_sync();      // the policy row written by the step before (emit_row) or above
-      a = (double)pol::shaped(pol::command<WIDE>(pol::evaluate<WIDE>(W, Wd, N, pol_smem, nx, wave, lane), Wd, wave, 0), N, t, B, inst, 0);
+      const float o = pol::evaluate<WIDE, GAUSS>(W, Wd, N, pol_smem, nx, wave, lane);
+      if constexpr (GAUSS)      // the squashed-Gaussian head: neuron 0 is mu, neuron 1 log_std
+        a = (double)pol::shaped_gaussian(pol::command<WIDE>(o, Wd, wave, 0), pol::command<WIDE>(o, Wd, wave, 1), N, t, B, inst, 0);
+      else
+        a = (double)pol::shaped(pol::command<WIDE>(o, Wd, wave, 0), N, t, B, inst, 0);
       if (lane == 0) Ro.actions[(size_t)t * B + inst] = a;
     } else {
       a = Ro.actions[(size_t)t * B + inst];
@@ -232,10 +236,10 @@ int launch(const pdegym_params_tumor* prm, const pdegym_bufs_tumor* buf, const p
   }
   const pdegym_mlp net = policy ? *policy : pdegym_mlp{};
   int rc = 0;
-  pol::dispatch(policy != nullptr, pl.wide, [&](auto wide_tag, auto policy_tag) {
-    constexpr bool W = decltype(wide_tag)::value, Pol = decltype(policy_tag)::value;
-    if (!Pol || pol::lds_limit_raised<&tumor_rollout_kernel<W, Pol>>("cannot raise the dynamic LDS limit of tumor_rollout_kernel", rc))
-      tumor_rollout_kernel<W, Pol><<<pl.grid, pl.block, pl.lds_bytes, (hipStream_t)stream>>>(*prm, *buf, *wrap, ro, net, (int)pl.extra_off, B);
+  pol::dispatch(policy, pl.wide, [&](auto wide_tag, auto policy_tag, auto gauss_tag) {
+    constexpr bool W = decltype(wide_tag)::value, Pol = decltype(policy_tag)::value, G = decltype(gauss_tag)::value;
+    if (!Pol || pol::lds_limit_raised<&tumor_rollout_kernel<W, Pol, G>>("cannot raise the dynamic LDS limit of tumor_rollout_kernel", rc))
+      tumor_rollout_kernel<W, Pol, G><<<pl.grid, pl.block, pl.lds_bytes, (hipStream_t)stream>>>(*prm, *buf, *wrap, ro, net, (int)pl.extra_off, B);
   });
   return rc ? rc : pdegym::check_launch(what);
 }

@@ -9,6 +9,10 @@ parameters: ``refresh()`` re-transposes the layers
 whose parameters changed (checked through the tensors' version counters; called automatically by ``__call__`` /
 ``forward_into`` outside graph capture and by ``DeviceRollout.run`` before it replays its hipGraph).  The copies keep their
 addresses, so a captured graph sees refreshed weights.
+
+``FusedMLP.squashed_gaussian`` / ``FusedMLP.from_sb3(policy, stochastic=True)``: the actor SAC samples while it learns -- a
+state-dependent standard deviation, the tanh squash AFTER the noise, the result rescaled to the action box -- as a second head of
+the same kernels (include/pdegym.h: PDEGYM_MLP_HEAD_SQUASHED_GAUSSIAN).
 """
 from __future__ import annotations
 
@@ -59,6 +63,7 @@ class FusedMLP:
         if clamp is not None and not float(clamp[0]) <= float(clamp[1]):
             raise ValueError("clamp must be (lo, hi) with lo <= hi")
         self.module, self.layers = module, layers
+        self.head, self.log_std_bounds, self._heads = N.MLP_HEAD_PLAIN, (0.0, 0.0), None
         # blocked transpose [ceil(in/4), out, 4] (include/pdegym.h); the buffers keep their addresses for captured graphs
         self._wt = [torch.zeros((w.shape[1] + 3) // 4, w.shape[0], 4, dtype=torch.float32, device=w.device) for w, _, _ in layers]
         self._seen = [None] * len(layers)
@@ -79,8 +84,54 @@ class FusedMLP:
             self.refresh()
 
     @classmethod
-    def from_sb3(cls, policy, clamp=None, backend=None):
-        """The deterministic actor of a Stable-Baselines3 policy as a ``FusedMLP`` (duck-typed, SB3 itself is not imported):
+    def squashed_gaussian(cls, latent, mu, log_std, log_std_bounds=(-20.0, 2.0), backend=None):
+        """The squashed-Gaussian actor of SAC: ``latent`` (an iterable of Linear / Tanh / ReLU modules, may be empty) followed by the two
+        ``torch.nn.Linear`` heads ``mu`` and ``log_std`` of equal shapes [A, width].  Per action, in float32 and in SB3's order
+        (include/pdegym.h)::
+
+            a = tanh(mu(s) + exp(clip(log_std(s), *log_std_bounds)) * eps),    command = lo + 0.5 (a + 1) (hi - lo)
+
+        ``eps`` is what ``forward_into`` / ``rollout_net`` are given as ``noise`` -- STANDARD-NORMAL draws, not pre-scaled noise;
+        ``noise=None`` is the deterministic actor ``tanh(mu(s))``, rescaled.  ``(lo, hi)`` is the ``clamp`` they are given, here the
+        action box: this head has no default clamp, ``clamp=None`` is a ``ValueError``.  ``out_dim == A``; the fused last layer
+        holds the rows ``[mu; log_std]`` (its bias a concatenated buffer of the wrapper's, rewritten in place by ``refresh()`` like
+        the weights, which watches all four parameter tensors).  ``forward_into`` takes A <= 8; inside the rollout kernels A is the
+        engine's (1, or 2 for two-command traffic).  A replay buffer that stores SB3's scaled action recovers it from the command
+        as ``2 (c - lo) / (hi - lo) - 1``.  Log-probabilities are not computed: SAC recomputes them under autograd at update time."""
+        import torch
+        for m, name in ((mu, "mu"), (log_std, "log_std")):
+            if not isinstance(m, torch.nn.Linear):
+                raise ValueError(f"{name} must be a torch.nn.Linear, got {type(m).__name__}")
+        if mu.weight.shape != log_std.weight.shape:
+            raise ValueError(f"mu and log_std must have equal shapes, got {tuple(mu.weight.shape)} and {tuple(log_std.weight.shape)}")
+        if any(p.dtype != torch.float32 for m in (mu, log_std) for p in m.parameters()):
+            raise ValueError("FusedMLP needs float32 parameters")
+        if (mu.bias is None) != (log_std.bias is None):
+            raise ValueError("mu and log_std must both have a bias or both have none")
+        lo_, hi_ = float(log_std_bounds[0]), float(log_std_bounds[1])
+        if not lo_ <= hi_:
+            raise ValueError("log_std_bounds must be (min, max) with min <= max")
+        A = int(mu.weight.shape[0])
+        fused = torch.nn.Linear(int(mu.weight.shape[1]), 2 * A, bias=mu.bias is not None, device=mu.weight.device)
+        self = cls(torch.nn.Sequential(*list(latent), fused), clamp=None, backend=backend)
+        self.module = None                               # (the fused layer is the wrapper's own: its values come from the heads)
+        self.head, self.log_std_bounds, self._heads = N.MLP_HEAD_SQUASHED_GAUSSIAN, (lo_, hi_), (mu, log_std)
+        self.latent = list(latent)
+        self._fused = fused.requires_grad_(False)
+        self._heads_seen = None
+        self.out_dim = A
+        self.refresh(force=True)
+        return self
+
+    @classmethod
+    def from_sb3(cls, policy, clamp=None, backend=None, stochastic=False):
+        """``stochastic=True``: the actor an SB3 ``SACPolicy`` SAMPLES from while it learns, as ``squashed_gaussian(actor.latent_pi,
+        actor.mu, actor.log_std)`` with SB3's ``LOG_STD_MIN`` / ``LOG_STD_MAX`` (-20, 2); ``use_sde`` (gSDE) actors are refused, and so
+        are policies without ``actor.log_std`` (PPO's Gaussian has a state-independent deviation: ``DeviceRollout(action_noise=True)``
+        with pre-scaled draws is exact for it).  ``clamp`` is not taken here: the box is what each call passes.
+        ``stochastic=False`` (the default):
+
+        The deterministic actor of a Stable-Baselines3 policy as a ``FusedMLP`` (duck-typed, SB3 itself is not imported):
         ``ActorCriticPolicy`` (PPO / A2C ``MlpPolicy``): ``mlp_extractor.policy_net`` followed by ``action_net`` -- the mean of
         the Gaussian, which SB3 clips to the action box (pass ``clamp``); ``SACPolicy``: ``actor.latent_pi`` + ``actor.mu`` with
         the tanh squashing of ``actor.forward(deterministic=True)``; ``TD3Policy``: ``actor.mu`` alone (a Sequential that already
@@ -88,6 +139,16 @@ class FusedMLP:
         with ``policy`` (no copy), so ``model.learn()`` steps are picked up by ``refresh()``.  Observations must already be
         flat vectors (``FlattenExtractor``), which is what ``MlpPolicy`` uses on these environments."""
         import torch
+        if stochastic:
+            actor = getattr(policy, "actor", None)
+            if actor is None or not (hasattr(actor, "mu") and hasattr(actor, "log_std")):
+                raise ValueError("stochastic=True expects an SB3 SACPolicy (actor.latent_pi, actor.mu, actor.log_std)")
+            if getattr(actor, "use_sde", False):
+                raise ValueError("stochastic=True: gSDE actors (use_sde=True) are not supported")
+            if clamp is not None:
+                raise ValueError("stochastic=True: the action box is the clamp each call passes, not a property of the wrapper")
+            lat = getattr(actor, "latent_pi", None)
+            return cls.squashed_gaussian(list(lat) if lat is not None else [], actor.mu, actor.log_std, (-20.0, 2.0), backend=backend)
         if hasattr(policy, "mlp_extractor") and hasattr(policy, "action_net"):
             mods = list(policy.mlp_extractor.policy_net) + [policy.action_net]
         elif hasattr(policy, "actor") and hasattr(policy.actor, "mu"):
@@ -105,6 +166,17 @@ class FusedMLP:
         steps bump a tensor's version counter).  Not callable while a hipGraph is being captured."""
         import torch
         with torch.no_grad():
+            if self._heads is not None:      # the fused last layer [mu; log_std]: rewritten in place when any of the four tensors changed
+                mu, ls = self._heads
+                seen = tuple(p._version for m in (mu, ls) for p in (m.weight, m.bias) if p is not None)
+                if force or seen != self._heads_seen:
+                    A = mu.weight.shape[0]
+                    self._fused.weight[:A].copy_(mu.weight.detach())
+                    self._fused.weight[A:].copy_(ls.weight.detach())
+                    if mu.bias is not None:
+                        self._fused.bias[:A].copy_(mu.bias.detach())
+                        self._fused.bias[A:].copy_(ls.bias.detach())
+                    self._heads_seen = seen
             for i, (w, _, _) in enumerate(self.layers):
                 if force or w._version != self._seen[i]:
                     out_dim, in_dim = w.shape
@@ -118,8 +190,14 @@ class FusedMLP:
         net = N.Mlp()
         net.x_f64, net.y_f64 = int(x_f64), int(y_f64)
         net.n_layers = len(self.layers)
+        if self.head == N.MLP_HEAD_SQUASHED_GAUSSIAN:
+            if clamp is None:
+                raise ValueError("a squashed-Gaussian head needs clamp=(lo, hi), the action box its output is rescaled to")
+            if not float(clamp[0]) < float(clamp[1]):
+                raise ValueError("a squashed-Gaussian head needs an action box (lo, hi) with lo < hi")
+            net.head, (net.log_std_min, net.log_std_max) = self.head, self.log_std_bounds
         net.clamp = 0 if clamp is None else 1
-        net.lo, net.hi = (0.0, 0.0) if clamp is None else clamp
+        net.lo, net.hi = (0.0, 0.0) if clamp is None else (float(clamp[0]), float(clamp[1]))
         for i, (w, b, act) in enumerate(self.layers):
             L = net.layer[i]
             L.w, L.b = self._wt[i].data_ptr(), (b.data_ptr() if b is not None else None)
@@ -136,7 +214,7 @@ class FusedMLP:
         the hidden rows within 160 KB of LDS: any row the kernels take).  ``extra_lds_bytes``: LDS of the engine's own per
         workgroup of 16 instances, which starts on the 16-byte boundary after the policy's (csrc/pdegym_policy.h: plan)."""
         dims = [(int(w.shape[1]), int(w.shape[0])) for w, _, _ in self.layers]
-        if dims[0][0] != in_dim or dims[-1][1] != out_dim or any(o > 256 for _, o in dims):
+        if dims[0][0] != in_dim or self.out_dim != out_dim or any(o > 256 for _, o in dims):
             return False
         return (self.rollout_lds_bytes(in_dim) + 15) // 16 * 16 + extra_lds_bytes <= self.ROLLOUT_LDS_BYTES
 
@@ -149,7 +227,8 @@ class FusedMLP:
         dims = [(int(w.shape[1]), int(w.shape[0])) for w, _, _ in self.layers]
         if any(o > 64 for _, o in dims):
             stride = lambda w: (w + 63) // 64 * 64 + 4                  # noqa: E731
-            floats = 16 * (stride((in_dim + 15) // 16 * 16) + 2 * stride(256)) + 32
+            kept = 64 if self.head == N.MLP_HEAD_SQUASHED_GAUSSIAN else 32       # wide_kept: [mu; log_std] of two commands per row
+            floats = 16 * (stride((in_dim + 15) // 16 * 16) + 2 * stride(256)) + kept
         else:
             floats = sum((((i + 3) // 4) | 1) * 4 * o + 64 for i, o in dims) + 16 * (((in_dim + 3) // 4) * 4 + 128)
         return 4 * floats
@@ -157,7 +236,8 @@ class FusedMLP:
     def rollout_net(self, obs, actions, clamp="default", noise=None) -> N.Mlp:
         """The descriptor for a rollout that reads ``obs`` and writes ``actions`` ([T, B] or [T, B, A]): weights refreshed (unless
         capturing), ``clamp`` (default: the policy's own), and ``noise`` -- float32, contiguous, the actions' shape -- added to
-        the network output of step t before the clamp."""
+        the network output of step t before the clamp.  Squashed-Gaussian head: ``noise`` holds the standard-normal draws ``eps`` and
+        the clamp is the action box (required)."""
         import torch
         self._refresh_unless_capturing(obs)
         net = self._net(self.clamp if clamp == "default" else clamp)
@@ -174,7 +254,9 @@ class FusedMLP:
         makes around its float32 policy.  ``noise`` (float32, same shape as the action): added to the network output before
         the clamp -- the caller's pre-scaled exploration noise of a Gaussian policy.  Returns ``out``.
         A NaN observation propagates as in PyTorch (the row's output is NaN) and the clamp keeps a NaN like ``torch.clamp`` /
-        ``np.clip``; +-Inf is clamped to the bound (include/pdegym.h, conventions)."""
+        ``np.clip``; +-Inf is clamped to the bound (include/pdegym.h, conventions).  Squashed-Gaussian head (``squashed_gaussian``):
+        ``noise`` is ``eps`` (standard-normal draws; None: the deterministic actor), ``clamp`` the action box (required), and
+        ``out_dim`` <= 8."""
         B = obs.shape[0]
         x = obs.reshape(B, -1)
         if x.shape[1] != self.in_dim:
@@ -199,4 +281,4 @@ class FusedMLP:
     def __call__(self, obs):
         import torch
         out = torch.empty(obs.shape[0], self.out_dim, dtype=obs.dtype, device=obs.device)
-        return self.forward_into(obs, out)
+        return self.forward_into(obs, out)      # (squashed-Gaussian head: a ValueError -- it has no default box; use forward_into)

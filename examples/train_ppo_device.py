@@ -10,6 +10,9 @@ algorithm in plain torch on the batched engine:
                 clamped and stored, then the env-step with fused auto-reset; layers of 65 .. 256 units -- ``hidden`` below --
                 are evaluated in the same kernel by the 16 waves of a workgroup together on the matrix cores; anything else
                 falls back to one ``pdegym_mlp_forward`` launch + one env-step launch per step inside a hipGraph);
+  * targets  -- ``DeviceRolloutBuffer``: the critic on all T + 1 observation slots in one batched call, then GAE(lambda)
+                advantages, returns and the statistics of the episodes that ended inside the buffer in ONE launch
+                (``pdegym_gae``: SB3's ``compute_returns_and_advantage`` bit for bit) instead of a Python loop over T;
   * update   -- ordinary torch autograd on the same ``torch.nn.Sequential`` the rollout evaluates (``FusedMLP`` picks the new
                 weights up at the next ``run()``).
 
@@ -28,7 +31,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import pde_control_gym  # noqa: E402
-from pde_control_gym import DeviceRollout, FusedMLP  # noqa: E402
+from pde_control_gym import DeviceRollout, DeviceRolloutBuffer, FusedMLP  # noqa: E402
 from pde_control_gym.src import TunedReward1D  # noqa: E402
 
 
@@ -78,6 +81,7 @@ def main(iterations=30, B=2048, T=64, quiet=False, hidden=64):
     opt = torch.optim.Adam(list(actor.parameters()) + list(critic.parameters()) + [log_std], lr=1e-3)
     rollout = DeviceRollout(venv, FusedMLP(actor), T, action_noise=True)
     gamma, lam, clip, epochs, nmb = 0.99, 0.95, 0.2, 6, 4
+    buffer = DeviceRolloutBuffer(rollout, gamma=gamma, gae_lambda=lam)
     history = []
     t_roll = t_upd = 0.0
     for it in range(iterations):
@@ -90,23 +94,15 @@ def main(iterations=30, B=2048, T=64, quiet=False, hidden=64):
         torch.cuda.synchronize()
         t_roll += time.perf_counter() - t0
         t0 = time.perf_counter()
-        obs, rew = rollout.obs, rollout.rewards
-        done = (rollout.terminated | rollout.truncated).float()
+        obs = rollout.obs
+        buffer.compute(critic=critic)                     # values of the T + 1 slots, then GAE: an episode end cuts the bootstrap
         with torch.no_grad():
-            val = critic(obs.reshape(-1, D)).reshape(T + 1, B)
-            adv = torch.zeros(T, B, device=dev)
-            last = torch.zeros(B, device=dev)
-            for t in reversed(range(T)):                  # GAE; an episode end cuts the bootstrap
-                nonterm = 1.0 - done[t]
-                delta = rew[t] + gamma * val[t + 1] * nonterm - val[t]
-                last = delta + gamma * lam * nonterm * last
-                adv[t] = last
-            ret = adv + val[:T]
             mean_old = actor(obs[:T].reshape(-1, D)).reshape(T, B)
             a_raw = mean_old + rollout.action_noise       # the sample before the clamp: what the log-probabilities refer to
             logp_old = -0.5 * ((a_raw - mean_old) / std_old) ** 2 - log_std.detach()
         flat = lambda x: x.reshape(T * B, *x.shape[2:])   # noqa: E731
-        o_f, a_f, lp_f, adv_f, ret_f = flat(obs[:T]), flat(a_raw), flat(logp_old), flat(adv), flat(ret)
+        batch = buffer.flat()
+        o_f, a_f, lp_f, adv_f, ret_f = batch.observations, flat(a_raw), flat(logp_old), batch.advantages, batch.returns
         adv_f = (adv_f - adv_f.mean()) / (adv_f.std() + 1e-8)
         for _ in range(epochs):
             perm = torch.randperm(T * B, device=dev)
@@ -123,7 +119,9 @@ def main(iterations=30, B=2048, T=64, quiet=False, hidden=64):
                 opt.step()
         torch.cuda.synchronize()
         t_upd += time.perf_counter() - t0
-        stats = {"iter": it, "episode_return": rew.sum(0).mean().item(), "mean_norm": obs[:T].norm(dim=2).mean().item(),
+        # mean return of the episodes that ENDED in this rollout (auto-reset ends them anywhere in the buffer; one that was cut off
+        # early restarts at once and runs on into the next rollout, carried by the buffer's accumulators)
+        stats = {"iter": it, "episode_return": buffer.finished_episodes()[1].item(), "mean_norm": obs[:T].norm(dim=2).mean().item(),
                  "truncated_frac": rollout.truncated.float().mean().item() * T, "std": log_std.exp().item()}
         history.append(stats)
         if not quiet and (it % 5 == 0 or it == iterations - 1):

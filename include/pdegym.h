@@ -23,6 +23,8 @@
  *   pdegym_traffic_backstep_rollout replaces runSingleEpisode's loop around it (same cell)
  *   pdegym_ns2d_adjoint_f64 replaces the backward march and the control read-off of the adjoint-optimisation baseline
  *                                                examples/NavierStokes/NS2Doptimization.py:83-107
+ *   pdegym_gae              replaces what SB3's PPO runs after every rollout of the reference's training scripts
+ *                           (examples/transportPDE/transport1Dppo.py:88-90): RolloutBuffer.compute_returns_and_advantage
  *
  * One call advances EVERY instance of a batch by one env-step (S PDE sub-steps for the 1D envs, one
  * Chorin projection step with K Jacobi sweeps for NS2D).  Instances are independent.
@@ -740,6 +742,50 @@ typedef struct pdegym_adjoint_ns2d {
 /* U_ref: [nt_ref, ny, nx, 2], the targets of :79-80 as the step kernels read them (pdegym_bufs_ns2d.U_ref). */
 int pdegym_ns2d_adjoint_f64(const pdegym_params_ns2d* prm, const void* U_ref, int32_t nt_ref, const pdegym_adjoint_ns2d* adj, int32_t B,
                             void* stream);
+
+/* ---- GAE(lambda) advantages, returns and episode statistics of a [T, B] rollout, one launch -----------------------------------
+ * What every PPO user of the reference runs after a rollout (transport1Dppo.py, reactionDiffusion1Dppo.py, NS2Dppo.py and the
+ * traffic and tumour notebooks: PPO("MlpPolicy", env)): Stable-Baselines3's RolloutBuffer.compute_returns_and_advantage
+ * (stable_baselines3/common/buffers.py) and the truncation bootstrap of OnPolicyAlgorithm.collect_rollouts
+ * (common/on_policy_algorithm.py: rewards[idx] += gamma * V(terminal_observation) where an episode was cut off by a time limit),
+ * restated for the buffers of pdegym_*_rollout.  One lane per environment, t from T-1 down to 0, float32 with ONE rounding per
+ * operation (nothing is fused, whatever the compiler flags), in SB3's order -- bit-identical to its NumPy loop:
+ *     g  = (float)gamma;   gl = (float)(gamma * gae_lambda)         the product in double, rounded once: NumPy's weak-scalar rule
+ *     done = terminated[t,b] | truncated[t,b];   nn = 1.0f - (float)done
+ *     r  = (float)rewards[t,b];   if (boot && truncated[t,b] && !terminated[t,b]) r = r + g * boot[t,b]
+ *     delta = (r + (g * values[t+1,b]) * nn) - values[t,b]
+ *     last  = delta + ((gl * nn) * last)                            last = 0 before t = T-1
+ *     advantages[t,b] = last;   returns[t,b] = last + values[t,b]
+ * done[t] is SB3's episode_starts[t + 1] (its `dones` for t = T-1); values[t+1] after a restart is the value of the new episode's
+ * first observation, multiplied by nn = 0, exactly as in SB3.  No clamps and no special cases: non-finite inputs propagate as IEEE
+ * arithmetic makes them (conventions above), 0 * NaN crosses an episode boundary as it does in NumPy, and boot is a SELECT -- a NaN
+ * in an entry the rule does not pick has no effect.  Columns are independent: a value in one changes no bit of another.
+ * Episode statistics (optional), forward in t, in double: acc += (double)r_as_loaded (the reward BEFORE the bootstrap term; the
+ * float64 reward itself with rewards_f64), len += 1; where done, episode_return[t,b] = acc and episode_length[t,b] = len and both
+ * go back to zero; elsewhere the outputs receive 0.0 and 0.  ep_return_acc / ep_length_acc carry the running episode from one
+ * call to the next (given together; NULL: every environment starts from zero); episode_return / episode_length are given together
+ * or not at all (NULL: the statistics are skipped, and accumulators are then refused).
+ * Every [., ld] array has `ld` ELEMENTS between consecutive rows t, ld >= B: a column shard of a wider batch is a pointer offset.
+ * Errors: -1 null descriptor; -2 T < 1, B < 1, ld < B, gamma or gae_lambda not finite; -3 a required pointer is NULL, the optional
+ * outputs are not given together, or an output (the accumulators included) overlaps an input or another output. */
+typedef struct pdegym_gae_args {
+  int32_t T;                 /* >= 1 steps                                                                                     */
+  int32_t rewards_f64;       /* 0: rewards float32; nonzero: float64, rounded ONCE to float32 as it is read (SB3 stores float32) */
+  const void* rewards;       /* [T, ld]                                                                                        */
+  const float* values;       /* [T + 1, ld]: V(observation slot t); slot T is SB3's last_values                                */
+  const uint8_t* terminated; /* [T, ld]                                                                                        */
+  const uint8_t* truncated;  /* [T, ld] or NULL                                                                                */
+  const float* boot;         /* optional [T, ld]: V(terminal observation); USED only where truncated && !terminated            */
+  int64_t ld;                /* elements between consecutive rows t of EVERY [., ld] array, >= B                               */
+  double gamma, gae_lambda;  /* the Python doubles                                                                             */
+  float* advantages;         /* [T, ld], written for b < B                                                                     */
+  float* returns;            /* [T, ld], written for b < B                                                                     */
+  double* ep_return_acc;     /* optional [B], in/out: sum of the rewards of the running episode                                */
+  int32_t* ep_length_acc;    /* optional [B], in/out: its length so far                                                        */
+  double* episode_return;    /* optional [T, ld]: where an episode ended at (t, b) its return, else 0.0                        */
+  int32_t* episode_length;   /* optional [T, ld]: its length, else 0                                                           */
+} pdegym_gae_args;
+int pdegym_gae(const pdegym_gae_args* g, int32_t B, void* stream);
 
 /* ---- test-only: kernel dispatch overrides -------------------------------------------------------------------------
  * Nothing on the product path calls this (the reference has no counterpart); the parity tests use it to run the SAME step

@@ -36,6 +36,7 @@ EXPORTS = [
     "pdegym_backstep_gain_parabolic", "pdegym_backstep_gain_transport", "pdegym_backstep_control",
     "pdegym_ns2d_adjoint_f64", "pdegym_transport_backstep_rollout", "pdegym_parabolic_backstep_rollout",
     "pdegym_traffic_backstep_control", "pdegym_traffic_backstep_rollout", "pdegym_tumor_therapy_step", "pdegym_tumor_rollout",
+    "pdegym_gae",
 ]
 # keys of pdegym_debug_set (test-only dispatch overrides, include/pdegym.h)
 DEBUG_NS_GENERIC, DEBUG_NS_NO_COL, DEBUG_NS_COL_MIN_BATCH, DEBUG_NS_NO_LDS_JACOBI = range(4)
@@ -184,6 +185,14 @@ class AdjointNS2D(C.Structure):
                 ("width", C.c_double), ("grad", C.c_void_p), ("actions", C.c_void_p), ("lam", C.c_void_p)]
 
 
+class Gae(C.Structure):
+    _fields_ = [("T", C.c_int32), ("rewards_f64", C.c_int32), ("rewards", C.c_void_p), ("values", C.c_void_p),
+                ("terminated", C.c_void_p), ("truncated", C.c_void_p), ("boot", C.c_void_p), ("ld", C.c_int64),
+                ("gamma", C.c_double), ("gae_lambda", C.c_double), ("advantages", C.c_void_p), ("returns", C.c_void_p),
+                ("ep_return_acc", C.c_void_p), ("ep_length_acc", C.c_void_p), ("episode_return", C.c_void_p),
+                ("episode_length", C.c_void_p)]
+
+
 class NativeError(RuntimeError):
     pass
 
@@ -267,6 +276,8 @@ def load():
     lib.pdegym_traffic_backstep_rollout.restype = C.c_int
     lib.pdegym_ns2d_adjoint_f64.argtypes = [C.POINTER(ParamsNS2D), C.c_void_p, C.c_int32, C.POINTER(AdjointNS2D), C.c_int32, C.c_void_p]
     lib.pdegym_ns2d_adjoint_f64.restype = C.c_int
+    lib.pdegym_gae.argtypes = [C.POINTER(Gae), C.c_int32, C.c_void_p]
+    lib.pdegym_gae.restype = C.c_int
     lib.pdegym_debug_set.argtypes = [C.c_int32, C.c_int32]
     lib.pdegym_debug_set.restype = C.c_int32
     if lib.pdegym_abi_version() != ABI_VERSION:

@@ -495,6 +495,49 @@ class HipBackend:
             c.clamp, c.lo, c.hi = 1, float(clamp[0]), float(clamp[1])
         N.check(self.lib.pdegym_backstep_control(C.byref(c), B, N.current_stream_ptr(obs.device)), "pdegym_backstep_control")
 
+    @_on_device_of("rewards")
+    def gae(self, rewards, values, terminated, truncated, advantages, returns, gamma: float, gae_lambda: float, boot=None,
+            ep_return_acc=None, ep_length_acc=None, episode_return=None, episode_length=None):
+        """GAE(lambda) advantages and returns of a rollout, and optionally its episode statistics, in one launch (pdegym_gae: SB3's
+        ``compute_returns_and_advantage``, bit for bit).  ``rewards`` [T, B] float32 or float64, ``values`` [T + 1, B] float32,
+        ``terminated`` / ``truncated`` (or None) / ``boot`` (or None) [T, B]; outputs ``advantages`` / ``returns`` [T, B] float32,
+        ``episode_return`` float64 / ``episode_length`` int32 [T, B] with the accumulators ``ep_return_acc`` float64 /
+        ``ep_length_acc`` int32 [B].  Every 2-D tensor has unit inner stride and the SAME row stride ``ld = stride(0)`` (column
+        shards of a wider batch are plain views); ``gamma`` / ``gae_lambda``: the Python doubles."""
+        import torch
+        if rewards.dim() != 2 or rewards.dtype not in (torch.float32, torch.float64):
+            raise N.NativeError("gae: rewards must be a float32 or float64 [T, B] tensor")
+        T, B = (int(s) for s in rewards.shape)
+        ld = int(rewards.stride(0)) if T > 1 else max(int(values.stride(0)), B)
+        wanted = {"rewards": (rewards, T, rewards.dtype), "values": (values, T + 1, torch.float32),
+                  "terminated": (terminated, T, torch.uint8), "truncated": (truncated, T, torch.uint8), "boot": (boot, T, torch.float32),
+                  "advantages": (advantages, T, torch.float32), "returns": (returns, T, torch.float32),
+                  "episode_return": (episode_return, T, torch.float64), "episode_length": (episode_length, T, torch.int32)}
+        for name, (x, rows, dtype) in wanted.items():
+            if x is None:
+                if name in ("truncated", "boot", "episode_return", "episode_length"):
+                    continue
+                raise N.NativeError(f"gae: {name} is required")
+            if not x.is_cuda or x.device != rewards.device or x.dtype != dtype or tuple(x.shape) != (rows, B):
+                raise N.NativeError(f"gae: {name} must be a {dtype} HIP tensor [{rows}, {B}] on the rewards' device, "
+                                    f"got {x.dtype} {tuple(x.shape)} on {x.device}")
+            if (B > 1 and x.stride(1) != 1) or (rows > 1 and x.stride(0) != ld):
+                raise N.NativeError(f"gae: {name} must have unit inner stride and the row stride {ld} of the other arrays, "
+                                    f"got strides {tuple(x.stride())}")
+        for name, x, dtype in (("ep_return_acc", ep_return_acc, torch.float64), ("ep_length_acc", ep_length_acc, torch.int32)):
+            if x is not None and (not x.is_cuda or x.device != rewards.device or x.dtype != dtype or tuple(x.shape) != (B,)
+                                  or (B > 1 and x.stride(0) != 1)):
+                raise N.NativeError(f"gae: {name} must be a dense {dtype} HIP tensor [{B}] on the rewards' device")
+        g = N.Gae()
+        g.T, g.rewards_f64, g.ld = T, int(rewards.dtype == torch.float64), ld
+        g.gamma, g.gae_lambda = float(gamma), float(gae_lambda)
+        for name in ("rewards", "values", "terminated", "truncated", "boot", "advantages", "returns", "episode_return", "episode_length"):
+            x = wanted[name][0]
+            setattr(g, name, None if x is None else x.data_ptr())
+        g.ep_return_acc = None if ep_return_acc is None else ep_return_acc.data_ptr()
+        g.ep_length_acc = None if ep_length_acc is None else ep_length_acc.data_ptr()
+        N.check(self.lib.pdegym_gae(C.byref(g), B, N.current_stream_ptr(rewards.device)), "pdegym_gae")
+
     @_on_device_of("obs")
     def backstep_rollout1d(self, kind: str, P: N.Params1D, T: dict, obs, actions, rewards, terminated, truncated, B: int, law: N.Backstep,
                            obs_noise=None, obs_seen=None):

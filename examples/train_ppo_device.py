@@ -14,13 +14,15 @@ algorithm in plain torch on the batched engine:
                 advantages, returns and the statistics of the episodes that ended inside the buffer in ONE launch
                 (``pdegym_gae``: SB3's ``compute_returns_and_advantage`` bit for bit) instead of a Python loop over T;
   * update   -- ordinary torch autograd on the same ``torch.nn.Sequential`` the rollout evaluates (``FusedMLP`` picks the new
-                weights up at the next ``run()``).
+                weights up at the next ``run()``); with ``fused_grad`` and layers of at most 64 units, actor and critic go through
+                ``FusedMLP.with_grad`` instead: one forward launch and a three-launch backward (``pdegym_mlp_backward``) per network
+                and minibatch that fill the same Parameters' ``.grad``, so the optimiser and the gradient clipping stay as they are.
 
 The plant is the reference's unstable reaction-diffusion benchmark u_t = u_xx + beta(x) u with boundary actuation
 (ReactionDiffusionPDE1D, Dirichlet control at x = 1).  Uncontrolled, ||u|| grows; the printed mean ||u|| over an episode falls
 as the policy learns to damp it.
 
-    python examples/train_ppo_device.py [iterations] [num_envs] [hidden units per layer: 64]
+    python examples/train_ppo_device.py [iterations] [num_envs] [hidden units per layer: 64] [fused_grad: 0]
 """
 import os
 import sys
@@ -62,7 +64,7 @@ def mlp(sizes, out_tanh=False):
     return torch.nn.Sequential(*mods)
 
 
-def main(iterations=30, B=2048, T=64, quiet=False, hidden=64):
+def main(iterations=30, B=2048, T=64, quiet=False, hidden=64, fused_grad=False):
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
     venv = make_env(B, horizon=T)        # one rollout = one episode of every environment
@@ -79,7 +81,14 @@ def main(iterations=30, B=2048, T=64, quiet=False, hidden=64):
         actor[-1].weight.mul_(0.01)
     log_std = torch.nn.Parameter(torch.full((1,), -0.7, device=dev))
     opt = torch.optim.Adam(list(actor.parameters()) + list(critic.parameters()) + [log_std], lr=1e-3)
-    rollout = DeviceRollout(venv, FusedMLP(actor), T, action_noise=True)
+    policy = FusedMLP(actor)
+    rollout = DeviceRollout(venv, policy, T, action_noise=True)
+    # the networks of the update: the modules themselves under torch autograd, or their fused forward + backward launches
+    actor_fn, critic_fn = actor, critic
+    if fused_grad and hidden <= 64:
+        actor_fn, critic_fn = policy.with_grad, FusedMLP(critic).with_grad
+    elif fused_grad and not quiet:
+        print(f"fused_grad: layers of {hidden} units are wider than the 64 the fused backward pass takes; the update uses torch autograd")
     gamma, lam, clip, epochs, nmb = 0.99, 0.95, 0.2, 6, 4
     buffer = DeviceRolloutBuffer(rollout, gamma=gamma, gae_lambda=lam)
     history = []
@@ -107,11 +116,11 @@ def main(iterations=30, B=2048, T=64, quiet=False, hidden=64):
         for _ in range(epochs):
             perm = torch.randperm(T * B, device=dev)
             for mb in perm.chunk(nmb):
-                mean = actor(o_f[mb]).squeeze(-1)
+                mean = actor_fn(o_f[mb]).squeeze(-1)
                 logp = -0.5 * ((a_f[mb] - mean) / log_std.exp()) ** 2 - log_std
                 ratio = (logp - lp_f[mb]).exp()
                 pg = -torch.min(ratio * adv_f[mb], ratio.clamp(1 - clip, 1 + clip) * adv_f[mb]).mean()
-                vloss = 0.5 * (critic(o_f[mb]).squeeze(-1) - ret_f[mb]).pow(2).mean()
+                vloss = 0.5 * (critic_fn(o_f[mb]).squeeze(-1) - ret_f[mb]).pow(2).mean()
                 loss = pg + 0.5 * vloss - 1e-3 * log_std.sum()
                 opt.zero_grad(set_to_none=True)
                 loss.backward()
@@ -135,4 +144,4 @@ def main(iterations=30, B=2048, T=64, quiet=False, hidden=64):
 
 if __name__ == "__main__":
     main(int(sys.argv[1]) if len(sys.argv) > 1 else 30, int(sys.argv[2]) if len(sys.argv) > 2 else 2048,
-         hidden=int(sys.argv[3]) if len(sys.argv) > 3 else 64)
+         hidden=int(sys.argv[3]) if len(sys.argv) > 3 else 64, fused_grad=bool(int(sys.argv[4])) if len(sys.argv) > 4 else False)

@@ -15,7 +15,7 @@ batched engine, on the plant of examples/train_ppo_device.py:
                 ``latent`` / ``mu`` / ``log_std`` modules the rollout evaluates (``FusedMLP`` picks the new weights up at the next
                 ``run()``).
 
-    python examples/train_sac_device.py [iterations] [num_envs] [hidden units per layer: 64]
+    python examples/train_sac_device.py [iterations] [num_envs] [hidden units per layer: 64] [fused_grad: 0]
 """
 import copy
 import math
@@ -41,17 +41,22 @@ def mlp(sizes):
     return torch.nn.Sequential(*mods)
 
 
-def sample(latent, mu, log_std, obs):
-    """Reparameterised action in [-1, 1] and its log-probability (the update's own forward pass, under autograd)."""
-    h = latent(obs)
-    mean, ls = mu(h), log_std(h).clamp(LOG_STD_MIN, LOG_STD_MAX)
+def sample(latent, mu, log_std, obs, raw=None):
+    """Reparameterised action in [-1, 1] and its log-probability (the update's own forward pass, under autograd).  ``raw``: the rows
+    [mu, log_std] of the fused last layer from ``FusedMLP.with_grad`` instead of the three modules."""
+    if raw is None:
+        h = latent(obs)
+        mean, ls = mu(h), log_std(h)
+    else:
+        mean, ls = raw[:, :raw.shape[1] // 2], raw[:, raw.shape[1] // 2:]
+    ls = ls.clamp(LOG_STD_MIN, LOG_STD_MAX)
     z = mean + ls.exp() * torch.randn_like(mean)
     a = torch.tanh(z)
     logp = (-0.5 * ((z - mean) / ls.exp()) ** 2 - ls - 0.5 * math.log(2 * math.pi)).sum(-1) - torch.log(1 - a * a + 1e-6).sum(-1)
     return a, logp
 
 
-def main(iterations=30, num_envs=1024, n_steps=32, hidden=64, one_launch=None, quiet=False, updates=8, batch=2048):
+def main(iterations=30, num_envs=1024, n_steps=32, hidden=64, one_launch=None, quiet=False, updates=8, batch=2048, fused_grad=False):
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
     B, T = num_envs, n_steps
@@ -75,8 +80,15 @@ def main(iterations=30, num_envs=1024, n_steps=32, hidden=64, one_launch=None, q
     opt_q = torch.optim.Adam(list(q1.parameters()) + list(q2.parameters()), lr=3e-4)
     opt_alpha = torch.optim.Adam([log_alpha], lr=3e-4)
     start = {k: [p.detach().clone() for p in ps] for k, ps in (("actor", actor_params), ("q1", list(q1.parameters())), ("q2", list(q2.parameters())))}
-    rollout = DeviceRollout(venv, FusedMLP.squashed_gaussian(latent, mu, log_std, (LOG_STD_MIN, LOG_STD_MAX)), T,
-                            action_low=lo, action_high=hi, action_noise=True, one_launch=one_launch)
+    policy = FusedMLP.squashed_gaussian(latent, mu, log_std, (LOG_STD_MIN, LOG_STD_MAX))
+    rollout = DeviceRollout(venv, policy, T, action_low=lo, action_high=hi, action_noise=True, one_launch=one_launch)
+    # the networks of the update: the modules under torch autograd, or (fused_grad, layers of at most 64 units) FusedMLP.with_grad --
+    # the critics' gradient with respect to the action column is the dx of pdegym_mlp_backward
+    q1_fn, q2_fn, raw_fn = q1, q2, None
+    if fused_grad and hidden <= 64:
+        q1_fn, q2_fn, raw_fn = FusedMLP(q1).with_grad, FusedMLP(q2).with_grad, policy.with_grad
+    elif fused_grad and not quiet:
+        print(f"fused_grad: layers of {hidden} units are wider than the 64 the fused backward pass takes; the update uses torch autograd")
     # the replay buffer: device tensors, a ring of `cap` transitions filled T * B at a time
     cap = max(16 * T * B, batch)
     buf = {k: torch.zeros(cap, n, device=dev) for k, n in (("obs", D), ("next", D), ("act", 1), ("rew", 1), ("term", 1))}
@@ -111,13 +123,13 @@ def main(iterations=30, num_envs=1024, n_steps=32, hidden=64, one_launch=None, q
                 q_next = torch.min(q1_t(torch.cat([o2, a2], 1)), q2_t(torch.cat([o2, a2], 1))) - alpha * logp2.unsqueeze(1)
                 target = r + gamma * (1.0 - d) * q_next
             oa = torch.cat([o, a], 1)
-            q_loss = (q1(oa) - target).pow(2).mean() + (q2(oa) - target).pow(2).mean()
+            q_loss = (q1_fn(oa) - target).pow(2).mean() + (q2_fn(oa) - target).pow(2).mean()
             opt_q.zero_grad(set_to_none=True)
             q_loss.backward()
             opt_q.step()
-            a_pi, logp = sample(latent, mu, log_std, o)
+            a_pi, logp = sample(latent, mu, log_std, o, None if raw_fn is None else raw_fn(o))
             oa_pi = torch.cat([o, a_pi], 1)
-            actor_loss = (alpha * logp.unsqueeze(1) - torch.min(q1(oa_pi), q2(oa_pi))).mean()
+            actor_loss = (alpha * logp.unsqueeze(1) - torch.min(q1_fn(oa_pi), q2_fn(oa_pi))).mean()
             opt_actor.zero_grad(set_to_none=True)
             actor_loss.backward()
             opt_actor.step()
@@ -148,4 +160,4 @@ def main(iterations=30, num_envs=1024, n_steps=32, hidden=64, one_launch=None, q
 
 if __name__ == "__main__":
     main(int(sys.argv[1]) if len(sys.argv) > 1 else 30, int(sys.argv[2]) if len(sys.argv) > 2 else 1024,
-         hidden=int(sys.argv[3]) if len(sys.argv) > 3 else 64)
+         hidden=int(sys.argv[3]) if len(sys.argv) > 3 else 64, fused_grad=bool(int(sys.argv[4])) if len(sys.argv) > 4 else False)

@@ -25,6 +25,8 @@
  *                                                examples/NavierStokes/NS2Doptimization.py:83-107
  *   pdegym_gae              replaces what SB3's PPO runs after every rollout of the reference's training scripts
  *                           (examples/transportPDE/transport1Dppo.py:88-90): RolloutBuffer.compute_returns_and_advantage
+ *   pdegym_mlp_backward     replaces the autograd backward pass of the MlpPolicy networks in the gradient step of the same scripts
+ *                           (model.learn: PPO.train / SAC.train), for layers of at most 64 units
  *
  * One call advances EVERY instance of a batch by one env-step (S PDE sub-steps for the 1D envs, one
  * Chorin projection step with K Jacobi sweeps for NS2D).  Instances are independent.
@@ -607,6 +609,56 @@ enum { PDEGYM_MLP_HEAD_PLAIN = 0, PDEGYM_MLP_HEAD_SQUASHED_GAUSSIAN = 1 };
 /* y[b, :] = net(x[b, :]) for b < B; x_stride / y_stride = ELEMENTS between consecutive rows (>= the row lengths). */
 int pdegym_mlp_forward(const pdegym_mlp* net, const void* x, int64_t x_stride, void* y, int64_t y_stride, int32_t B,
                        void* stream);
+
+/* ---- backward pass of the same network (the gradient step of the reference's PPO / SAC training scripts) ------------------------
+ * Given dy = dLoss/dy [B, out_dim], pdegym_mlp_backward writes dLoss/dW and dLoss/db of every layer, and optionally dLoss/dx, in three
+ * launches whatever the number of layers (csrc/pdegym_mlp_backward.hip).  Nothing is saved by the forward launch: the activations are
+ * recomputed from `net` (its blocked weights and biases) with the forward kernel's own reduction, hence with its bits.
+ *
+ * net      the forward descriptor, with head == PLAIN, clamp == 0 and noise == NULL (a clamp or a squashed-Gaussian head is the
+ *          caller's to differentiate); x_f64 is allowed -- rows are rounded to float32 as they are read -- and y_f64 is ignored.
+ * Limits   n_layers <= PDEGYM_MLP_MAX_LAYERS, every layer's out_dim <= 64, the first layer's in_dim <= 1024; anything else is -2.
+ *          (SB3's PPO default [64, 64] and every observation row of the five families fit; 256-unit layers do not.)
+ * Inputs   x [B, in_dim] (x_stride), dy [B, out_dim] float32 (dy_stride), w[l] = the ROW-MAJOR [out_dim, in_dim] float32 weights of
+ *          layer l -- torch.nn.Linear.weight's own storage: dH = dZ W reduces over it with `in` contiguous, and no second blocked
+ *          copy can go stale.  w[0] is needed only with dx.  Strides are ELEMENTS between rows (>= the row lengths).
+ * Outputs  dw[l] [out_dim, in_dim] float32 contiguous (torch layout), WRITTEN, not accumulated; db[l] [out_dim], NULL exactly where the
+ *          layer has no bias; dx [B, in_dim] float32 (dx_stride) or NULL -- only with float32 x.  Rows >= B are not touched.
+ * slabs    the B rows are cut into ceil(B / 16) tiles of 16 rows and the tiles into `slabs` runs of consecutive tiles (slab s: tiles
+ *          floor(s tiles / slabs) .. floor((s + 1) tiles / slabs) - 1); a slab's partial sums are formed rows ascending and the slabs'
+ *          partials are added in ascending order.  0: the library's choice, min(tiles, 256) -- a function of B alone.
+ *          1 <= slabs <= tiles otherwise.
+ * workspace  device memory of at least pdegym_mlp_backward_workspace (net, B, slabs) bytes, 4-byte aligned; every byte that is read
+ *          was written by the same call.
+ * Arithmetic  float32 throughout.  Activation derivatives as torch's backward ops, each operation rounded on its own:
+ *          tanh dz = dh * (1 - h * h); ReLU dz = (h <= 0) ? 0 : dh (a NaN activation passes the gradient, as threshold_backward).
+ *          The three products dW_l = dZ_l^T H_{l-1} (over rows), db_l = sum_rows dZ_l and dH_{l-1} = dZ_l W_l (over the layer's units) run
+ *          on v_mfma_f32_16x16x4_f32, an exact fmaf chain: the order of every sum is fixed by the code.
+ * Determinism  no floating-point atomics; every output bit is a function of the inputs, B and slabs alone -- not of the stream, of
+ *          earlier calls or of what the workspace held.  Rows >= B of the last tile are never read and contribute nothing (they are
+ *          selected to zero, not multiplied by it).
+ * Non-finite data propagates as IEEE makes it: a NaN in row i of x or dy reaches dx[i] and the weight gradients, and no other row of dx.
+ * Errors: -1 null descriptor / arguments; -2 a limit above, B < 1, a stride shorter than its row, slabs out of range, a workspace that
+ * is too small, dx with x_f64; -3 a required pointer is NULL, db that does not match the layer's bias, or an output (the workspace
+ * included) that overlaps an input or another output as byte ranges. */
+typedef struct pdegym_mlp_backward_args {
+  const void* x;
+  int64_t x_stride;
+  const float* dy;
+  int64_t dy_stride;
+  const float* w[PDEGYM_MLP_MAX_LAYERS];
+  float* dw[PDEGYM_MLP_MAX_LAYERS];
+  float* db[PDEGYM_MLP_MAX_LAYERS];
+  float* dx;
+  int64_t dx_stride;
+  int32_t slabs;
+  int32_t reserved_;
+  void* workspace;
+  int64_t workspace_bytes;
+} pdegym_mlp_backward_args;
+/* bytes of workspace for B rows and `slabs` (0: the library's choice), or a negative code */
+int64_t pdegym_mlp_backward_workspace(const pdegym_mlp* net, int32_t B, int32_t slabs);
+int pdegym_mlp_backward(const pdegym_mlp* net, const pdegym_mlp_backward_args* a, int32_t B, void* stream);
 
 /* ---- backstepping baseline (the controller every result table of the reference compares the learned policies against) ------
  * Gains: theta [R, m] float32 rows, sampled by the caller (the examples use linspace(dx, X, m), NOT the plant's grid) -> gain [R, m]

@@ -36,13 +36,14 @@ EXPORTS = [
     "pdegym_backstep_gain_parabolic", "pdegym_backstep_gain_transport", "pdegym_backstep_control",
     "pdegym_ns2d_adjoint_f64", "pdegym_transport_backstep_rollout", "pdegym_parabolic_backstep_rollout",
     "pdegym_traffic_backstep_control", "pdegym_traffic_backstep_rollout", "pdegym_tumor_therapy_step", "pdegym_tumor_rollout",
-    "pdegym_gae",
+    "pdegym_gae", "pdegym_mlp_backward", "pdegym_mlp_backward_workspace",
 ]
 # keys of pdegym_debug_set (test-only dispatch overrides, include/pdegym.h)
 DEBUG_NS_GENERIC, DEBUG_NS_NO_COL, DEBUG_NS_COL_MIN_BATCH, DEBUG_NS_NO_LDS_JACOBI = range(4)
 MLP_MAX_LAYERS, MLP_MAX_WIDTH, MLP_MAX_INPUT = 4, 256, 8192
 MLP_IDENTITY, MLP_TANH, MLP_RELU = 0, 1, 2
 MLP_HEAD_PLAIN, MLP_HEAD_SQUASHED_GAUSSIAN = 0, 1
+MLP_BACKWARD_MAX_WIDTH, MLP_BACKWARD_MAX_INPUT = 64, 1024      # pdegym_mlp_backward: widest layer, widest first-layer input
 BACKSTEP_TREE, BACKSTEP_ORDERED = 0, 1
 TRAFFIC_BACKSTEP_TREE, TRAFFIC_BACKSTEP_NUMPY = 0, 1
 TRAFFIC_BACKSTEP_NUMPY_MAX_M = 129      # the longest row whose np.trapz sum is un-recursed (128 terms)
@@ -168,6 +169,13 @@ class Mlp(C.Structure):
     _anonymous_ = ("layers_",)
 
 
+class MlpBackward(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("x_stride", C.c_int64), ("dy", C.c_void_p), ("dy_stride", C.c_int64),
+                ("w", C.c_void_p * MLP_MAX_LAYERS), ("dw", C.c_void_p * MLP_MAX_LAYERS), ("db", C.c_void_p * MLP_MAX_LAYERS),
+                ("dx", C.c_void_p), ("dx_stride", C.c_int64), ("slabs", C.c_int32), ("reserved_", C.c_int32),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
 class Backstep(C.Structure):
     _fields_ = [("gain0", C.c_void_p), ("gain_stride", C.c_int64), ("gain_pool", C.c_void_p), ("reset_count", C.c_void_p),
                 ("pool_rows", C.c_int32), ("m", C.c_int32), ("obs", C.c_void_p), ("obs_stride", C.c_int64), ("len", C.c_int32),
@@ -278,6 +286,10 @@ def load():
     lib.pdegym_ns2d_adjoint_f64.restype = C.c_int
     lib.pdegym_gae.argtypes = [C.POINTER(Gae), C.c_int32, C.c_void_p]
     lib.pdegym_gae.restype = C.c_int
+    lib.pdegym_mlp_backward_workspace.argtypes = [C.POINTER(Mlp), C.c_int32, C.c_int32]
+    lib.pdegym_mlp_backward_workspace.restype = C.c_int64
+    lib.pdegym_mlp_backward.argtypes = [C.POINTER(Mlp), C.POINTER(MlpBackward), C.c_int32, C.c_void_p]
+    lib.pdegym_mlp_backward.restype = C.c_int
     lib.pdegym_debug_set.argtypes = [C.c_int32, C.c_int32]
     lib.pdegym_debug_set.restype = C.c_int32
     if lib.pdegym_abi_version() != ABI_VERSION:

@@ -447,6 +447,56 @@ class HipBackend:
         N.check(self.lib.pdegym_mlp_forward(C.byref(net), x.data_ptr(), x.stride(0), y.data_ptr(), y.stride(0), B,
                                             N.current_stream_ptr(x.device)), "pdegym_mlp_forward")
 
+    @_on_device_of("x")
+    def mlp_backward(self, net: N.Mlp, x, dy, weights, dw, db, dx=None, slabs: int = 0):
+        """Gradients of the network ``net`` describes (plain head, no clamp, no noise) for ``dy`` = dLoss/dy, in three launches
+        (pdegym_mlp_backward): ``x`` [B, in_dim] float32 or float64 (``net.x_f64`` set by the caller), ``dy`` [B, out_dim] float32, both
+        with unit inner stride; ``weights[l]`` the contiguous row-major [out, in] float32 weights of layer l (``Linear.weight``);
+        ``dw[l]`` / ``db[l]`` (None where the layer has no bias) contiguous float32 outputs of the parameters' shapes, written, not
+        accumulated; ``dx`` [B, in_dim] float32 or None.  ``slabs``: include/pdegym.h (0: the library's choice).  The workspace is
+        the backend's own, cached per (device, size)."""
+        import torch
+        B, nl = int(x.shape[0]) if x.dim() == 2 else -1, int(net.n_layers)
+        want_x = torch.float64 if net.x_f64 else torch.float32
+        rows = (("x", x, want_x, int(net.layer[0].in_dim)), ("dy", dy, torch.float32, int(net.layer[nl - 1].out_dim)),
+                ("dx", dx, torch.float32, int(net.layer[0].in_dim)))
+        for name, t_, dtype, width in rows:
+            if t_ is None and name == "dx":
+                continue
+            if (not torch.is_tensor(t_) or not t_.is_cuda or t_.device != x.device or t_.dtype != dtype or t_.dim() != 2
+                    or tuple(t_.shape) != (B, width) or (width > 1 and t_.stride(1) != 1) or (B > 1 and t_.stride(0) < width)):
+                raise N.NativeError(f"mlp_backward: {name} must be a {dtype} HIP tensor [{B}, {width}] with unit inner stride on x's device")
+        if not (len(weights) == len(dw) == len(db) == nl):
+            raise N.NativeError(f"mlp_backward: weights, dw and db must have one entry per layer ({nl})")
+        a = N.MlpBackward()
+        for l in range(nl):
+            shape = (int(net.layer[l].out_dim), int(net.layer[l].in_dim))
+            for name, t_, shp in (("weights", weights[l], shape), ("dw", dw[l], shape), ("db", db[l], shape[:1])):
+                if t_ is None and name == "db":
+                    continue
+                if (not torch.is_tensor(t_) or not t_.is_cuda or t_.device != x.device or t_.dtype != torch.float32
+                        or tuple(t_.shape) != shp or not t_.is_contiguous()):
+                    raise N.NativeError(f"mlp_backward: {name}[{l}] must be a contiguous float32 HIP tensor {shp} on x's device")
+            a.w[l], a.dw[l], a.db[l] = weights[l].data_ptr(), dw[l].data_ptr(), (None if db[l] is None else db[l].data_ptr())
+        need = int(self.lib.pdegym_mlp_backward_workspace(C.byref(net), B, int(slabs)))
+        if need < 0:
+            N.check(need, "pdegym_mlp_backward_workspace")
+        ws = self._mlp_backward_workspace(x.device, need)
+        a.x, a.x_stride, a.dy, a.dy_stride = x.data_ptr(), (x.stride(0) if B > 1 else x.shape[1]), dy.data_ptr(), (dy.stride(0) if B > 1 else dy.shape[1])
+        if dx is not None:
+            a.dx, a.dx_stride = dx.data_ptr(), (dx.stride(0) if B > 1 else dx.shape[1])
+        a.slabs, a.workspace, a.workspace_bytes = int(slabs), ws.data_ptr(), ws.numel()
+        N.check(self.lib.pdegym_mlp_backward(C.byref(net), C.byref(a), B, N.current_stream_ptr(x.device)), "pdegym_mlp_backward")
+
+    def _mlp_backward_workspace(self, device, nbytes: int):
+        """The workspace of ``mlp_backward``: one uint8 tensor per (device, size), kept (every launch of one stream uses it in turn)."""
+        import torch
+        cache = self.__dict__.setdefault("_mlp_bw_ws", {})
+        key = (device.index, nbytes)
+        if key not in cache:
+            cache[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        return cache[key]
+
     # ---- backstepping baseline -------------------------------------------------------------------
     @_on_device_of("theta")
     def backstep_gain(self, kind: str, theta, gain, dx: float):

@@ -1,0 +1,446 @@
+// pdegym_mlp_backward.hip -- backward pass of the small MLP that pdegym_mlp_forward evaluates (see include/pdegym.h:
+// pdegym_mlp_backward): dW, db of every layer and optionally dx, float32, deterministic, no atomics.
+//
+// The caller is the update half of the reference's training scripts (PPO / SAC "MlpPolicy": two hidden layers of 64 units): per
+// network and minibatch torch autograd issues about ten small GEMMs and as many elementwise kernels; here a backward pass is three
+// launches, whatever the number of layers.
+//
+//   1. mlp_backward_tiles: a workgroup of four waves owns a SLAB of consecutive 16-row tiles.  Per tile it recomputes the
+//      activations of every layer into LDS with the forward kernel's own reduction (pdegym_mlp_tile.h: the same bits, nothing is
+//      saved by the forward launch), then walks the layers backwards: dZ_l = dH_l * act'(H_l) elementwise, dW_l += dZ_l^T H_{l-1} and
+//      db_l += sum_rows dZ_l into accumulators that live in registers across the tiles of the slab, dH_{l-1} = dZ_l W_l into LDS
+//      (or into dx for the first layer).  The first layer's dZ_0 goes to the workspace instead of into a dW_0 accumulator: at
+//      in_dim = 1024 that accumulator would be 256 registers per lane, so dW_0 is the second launch, which needs no LDS and spreads
+//      over in_dim as well as over the slabs.
+//   2. mlp_backward_dw0: a workgroup owns (64 input columns, one slab): dW_0 partial = dZ_0^T X, rows ascending.
+//   3. mlp_backward_reduce: dw, db = the slabs' partials added in ascending slab order, one thread per element.
+//
+// All three products run on v_mfma_f32_16x16x4_f32 (float32 in, float32 accumulate: an exact fmaf chain), so the order of every sum
+// is fixed by the code: rows ascending within a slab, slabs ascending, a layer's units in blocks of 16 (four MFMAs per block, unit 16 kb + 4 lg + c in the c-th).  Rows >= B of
+// the last tile are selected to zero (never multiplied by zero: a non-finite weight would turn that into NaN) and never read.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "pdegym.h"
+#include "pdegym_common.h"
+#include "pdegym_mlp_tile.h"
+
+namespace {
+
+using namespace pdegym_mlp_tile;     // v4f, lds_stride, kStage, activate, load_w, reduce_blocks
+
+constexpr int kRows = 16;                   // rows per tile (the M of the MFMA tile)
+constexpr int kWidth = 64;                  // widest layer output this file takes
+constexpr int kMaxIn = 1024;                // widest first-layer input
+constexpr int kLayers = PDEGYM_MLP_MAX_LAYERS;
+constexpr int kLdh = lds_stride(kWidth);    // LDS row stride of a [16, 64] block: 16 rows x one float, or x one float4, hit distinct banks
+constexpr int kXChunk = 512;                // observation entries per row staged at a time, as in the forward kernel
+constexpr int kMaxSlabs = 256;              // the library's choice: min(tiles, 256) -- B = 32768: 256 slabs of 128 rows
+
+struct Plan {
+  const void* x;
+  long long x_stride;
+  const float* dy;
+  long long dy_stride;
+  const float* w[kLayers];      // row-major [out, in]
+  float* dw[kLayers];
+  float* db[kLayers];
+  float* dx;
+  long long dx_stride;
+  float* dz0;                   // workspace: [16 * tiles, 64] the first layer's dZ, zero in rows >= B and columns >= out_dim
+  float* part;                  // workspace: [slabs, per_slab] partial dW_l, db_l of every layer, in the order of off_w / off_b
+  int off_w[kLayers], off_b[kLayers];
+  int in[kLayers], out[kLayers];
+  int per_slab, n_layers, B, tiles, slabs;
+};
+
+__device__ __forceinline__ v4f mma(float a, float b, v4f acc) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0); }
+
+__device__ __forceinline__ int slab_begin(const Plan& P, int slab) { return (int)((long long)slab * P.tiles / P.slabs); }
+
+// torch's backward ops (tanh_backward, threshold_backward), each operation rounded on its own
+__device__ __forceinline__ float act_backward(float dh, float h, int act) {
+  if (act == PDEGYM_MLP_TANH) return __fmul_rn(dh, __fsub_rn(1.0f, __fmul_rn(h, h)));
+  if (act == PDEGYM_MLP_RELU) return h <= 0.f ? 0.f : dh;      // a NaN activation passes the gradient
+  return dh;
+}
+
+template <typename TX>
+__global__ __launch_bounds__(256) void mlp_backward_tiles(pdegym_mlp N, Plan P, int ldx) {
+  extern __shared__ __attribute__((aligned(16))) float bw_smem[];
+  float* const hs = bw_smem;                                   // [kLayers][16][kLdh]: the activations of every layer
+  float* const gs = hs + kLayers * kRows * kLdh;               // [2][16][kLdh]: dH / dZ of the layer at hand, and of the one below
+  float* const xs = gs + 2 * kRows * kLdh;                     // [16][ldx]: a chunk of the observation rows
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int li = lane & 15, lg = lane >> 4;
+  const int er = tid >> 4, ec = tid & 15;      // elementwise passes: thread = (row er, columns ec, ec + 16, ec + 32, ec + 48)
+  const TX* __restrict__ x = static_cast<const TX*>(P.x);
+  const int B = P.B, nl = P.n_layers;
+  const int n = 16 * wave + li;                 // this lane's unit: neuron of the forward tiles, column of D in the backward ones
+
+  v4f accw[kLayers][4], accb[kLayers];           // dW_l (l >= 1) tiles [unit tile = wave][input tile], db_l; live across the slab
+#pragma unroll
+  for (int l = 0; l < kLayers; ++l) {
+    accb[l] = (v4f){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int t = 0; t < 4; ++t) accw[l][t] = (v4f){0.f, 0.f, 0.f, 0.f};
+  }
+
+  const int t_end = slab_begin(P, blockIdx.x + 1);
+  for (int tile = slab_begin(P, blockIdx.x); tile < t_end; ++tile) {
+    const int row0 = tile * kRows;
+    // ---- forward, as pdegym_mlp_forward computes it: the same operands in the same order --------------------------------------------
+#pragma unroll
+    for (int l = 0; l < kLayers; ++l) {
+      if (l >= nl) break;
+      const pdegym_mlp_layer L = N.layer[l];
+      const int K = L.in_dim, H = L.out_dim, ngroups = (K + 3) >> 2;
+      const v4f* __restrict__ wq = reinterpret_cast<const v4f*>(L.w);
+      const int col[1] = {n < H ? n : H - 1};
+      const bool any_tile = 16 * wave < H;
+      v4f acc[1] = {(v4f){0.f, 0.f, 0.f, 0.f}};
+      v4f wfirst[kStage][1];
+      if (l == 0) {
+        for (int c0 = 0; c0 < K; c0 += kXChunk) {
+          const int clen = (K - c0) < kXChunk ? (K - c0) : kXChunk;
+          const int cpad = (clen + 15) & ~15;
+          for (int rr = 0; rr < 4; ++rr) {
+            const int r = 4 * wave + rr;
+            const bool row_ok = row0 + r < B;
+            const TX* src = x + (long long)(row_ok ? row0 + r : 0) * P.x_stride + c0;
+            for (int c = lane; c < cpad; c += 64) xs[r * ldx + c] = (row_ok && c < clen) ? (float)src[c] : 0.f;
+          }
+          if (any_tile) load_w<1>(wfirst, wq, H, ngroups, c0 / 16, lg, col);
+          __syncthreads();
+          if (any_tile) reduce_blocks<1>(acc, wfirst, wq, H, ngroups, c0 / 16, cpad / 16, xs + li * ldx, lg, col);
+          __syncthreads();
+        }
+      } else if (any_tile) {
+        load_w<1>(wfirst, wq, H, ngroups, 0, lg, col);
+        reduce_blocks<1>(acc, wfirst, wq, H, ngroups, 0, (K + 15) >> 4, hs + ((l - 1) * kRows + li) * kLdh, lg, col);
+      }
+      const float bias = (L.b && n < H) ? L.b[n] : 0.f;
+      const float av[4] = {acc[0].x, acc[0].y, acc[0].z, acc[0].w};
+#pragma unroll
+      for (int v = 0; v < 4; ++v) {      // D[row 4 lg + v][unit n]; zero past the layer's width and past the batch
+        const int r = 4 * lg + v;
+        hs[(l * kRows + r) * kLdh + n] = (n < H && row0 + r < B) ? activate(av[v] + bias, L.act) : 0.f;
+      }
+      __syncthreads();
+    }
+
+    // ---- backward -------------------------------------------------------------------------------------------------------------------
+    float* g = gs;                       // dH of the layer at hand, then its dZ in place
+    float* gn = gs + kRows * kLdh;       // dH of the layer below
+    {
+      const int H = P.out[nl - 1];
+      const bool row_ok = row0 + er < B;
+      const float* src = P.dy + (long long)(row_ok ? row0 + er : 0) * P.dy_stride;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int c = ec + 16 * j;
+        g[er * kLdh + c] = (row_ok && c < H) ? src[c] : 0.f;
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int l = kLayers - 1; l >= 0; --l) {
+      if (l >= nl) continue;
+      const int K = P.in[l], H = P.out[l], act = N.layer[l].act;
+      // dZ_l = dH_l * act'(H_l), in place; selected to zero outside the batch and the layer
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int c = ec + 16 * j;
+        const bool ok = row0 + er < B && c < H;
+        const float dz = ok ? act_backward(g[er * kLdh + c], hs[(l * kRows + er) * kLdh + c], act) : 0.f;
+        g[er * kLdh + c] = dz;
+        if (l == 0) P.dz0[(long long)(row0 + er) * kWidth + c] = dz;
+      }
+      __syncthreads();
+      // db_l += sum_rows dZ_l, dW_l += dZ_l^T H_{l-1}: A[unit][row] = dZ, B[row][input] = H (or ones); rows in four groups of four
+      if (16 * wave < H) {
+        float a[4];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) a[s] = g[(4 * s + lg) * kLdh + n];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) accb[l] = mma(a[s], 1.0f, accb[l]);
+        if (l >= 1) {
+          const float* hin = hs + (l - 1) * kRows * kLdh;
+#pragma unroll
+          for (int t = 0; t < 4; ++t) {
+            if (16 * t < K) {      // wave-uniform
+#pragma unroll
+              for (int s = 0; s < 4; ++s) accw[l][t] = mma(a[s], hin[(4 * s + lg) * kLdh + 16 * t + li], accw[l][t]);
+            }
+          }
+        }
+      }
+      // dH_{l-1} = dZ_l W_l (into dx for the first layer): A[row][unit] = dZ, B[unit][input] = W row-major, units in blocks of 16
+      if (l >= 1 || P.dx) {
+        const float* __restrict__ W = P.w[l];
+        const int in_tiles = (K + 15) >> 4, unit_blocks = (H + 15) >> 4;
+        for (int t = wave; t < in_tiles; t += 4) {
+          const int i = 16 * t + li, ic = i < K ? i : K - 1;
+          v4f d = {0.f, 0.f, 0.f, 0.f};
+          for (int kb = 0; kb < unit_blocks; ++kb) {
+            const v4f a4 = *reinterpret_cast<const v4f*>(g + li * kLdh + 16 * kb + 4 * lg);
+            const int o = 16 * kb + 4 * lg;
+            float wv[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+              const float v = W[(long long)(o + c < H ? o + c : H - 1) * K + ic];
+              wv[c] = o + c < H ? v : 0.f;
+            }
+            d = mma(a4.x, wv[0], d);
+            d = mma(a4.y, wv[1], d);
+            d = mma(a4.z, wv[2], d);
+            d = mma(a4.w, wv[3], d);
+          }
+          const float dv[4] = {d.x, d.y, d.z, d.w};
+#pragma unroll
+          for (int v = 0; v < 4; ++v) {
+            const int r = 4 * lg + v;
+            if (l >= 1) gn[r * kLdh + i] = dv[v];                  // (i < 64: in_tiles <= 4)
+            else if (i < K && row0 + r < B) P.dx[(long long)(row0 + r) * P.dx_stride + i] = dv[v];
+          }
+        }
+      }
+      __syncthreads();
+      float* const swap = g;
+      g = gn, gn = swap;
+    }
+  }
+
+  // ---- the slab's partial sums --------------------------------------------------------------------------------------------------------
+  float* const part = P.part + (long long)blockIdx.x * P.per_slab;
+#pragma unroll
+  for (int l = 0; l < kLayers; ++l) {
+    if (l >= nl) break;
+    const int K = P.in[l], H = P.out[l];
+    if (16 * wave >= H) continue;
+    const float bv[4] = {accb[l].x, accb[l].y, accb[l].z, accb[l].w};
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {      // D[unit 16 wave + 4 lg + v][column li]: every column of the db tile holds the sum
+      const int o = 16 * wave + 4 * lg + v;
+      if (li == 0 && o < H) part[P.off_b[l] + o] = bv[v];
+    }
+    if (l >= 1) {
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const float wv[4] = {accw[l][t].x, accw[l][t].y, accw[l][t].z, accw[l][t].w};
+        const int i = 16 * t + li;
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          const int o = 16 * wave + 4 * lg + v;
+          if (o < H && i < K) part[P.off_w[l] + o * K + i] = wv[v];
+        }
+      }
+    }
+  }
+}
+
+// dW_0 partial of (64 input columns blockIdx.x, slab blockIdx.y) = dZ_0^T X over the slab's rows, ascending.  No LDS, no barrier.
+template <typename TX>
+__global__ __launch_bounds__(256) void mlp_backward_dw0(Plan P) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int li = lane & 15, lg = lane >> 4;
+  const int K = P.in[0], H = P.out[0], B = P.B;
+  if (16 * wave >= H) return;
+  const TX* __restrict__ x = static_cast<const TX*>(P.x);
+  const int i0 = 64 * blockIdx.x;
+  v4f acc[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) acc[t] = (v4f){0.f, 0.f, 0.f, 0.f};
+  const int t_end = slab_begin(P, blockIdx.y + 1);
+  for (int tile = slab_begin(P, blockIdx.y); tile < t_end; ++tile) {
+    const int row0 = tile * kRows;
+    float a[4], b[4][4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) a[s] = P.dz0[(long long)(row0 + 4 * s + lg) * kWidth + 16 * wave + li];
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        const int r = row0 + 4 * s + lg, i = i0 + 16 * t + li;
+        const bool ok = r < B && i < K;
+        const TX v = x[ok ? (long long)r * P.x_stride + i : 0];
+        b[t][s] = ok ? (float)v : 0.f;
+      }
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      if (i0 + 16 * t < K) {      // wave-uniform
+#pragma unroll
+        for (int s = 0; s < 4; ++s) acc[t] = mma(a[s], b[t][s], acc[t]);
+      }
+    }
+  }
+  float* const part = P.part + (long long)blockIdx.y * P.per_slab + P.off_w[0];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const float wv[4] = {acc[t].x, acc[t].y, acc[t].z, acc[t].w};
+    const int i = i0 + 16 * t + li;
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      const int o = 16 * wave + 4 * lg + v;
+      if (o < H && i < K) part[o * K + i] = wv[v];
+    }
+  }
+}
+
+// dw, db = the slabs' partials, added in ascending slab order; one thread per element, eight loads in flight
+__global__ __launch_bounds__(256) void mlp_backward_reduce(Plan P) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= P.per_slab) return;
+  float* dst = nullptr;
+#pragma unroll
+  for (int l = 0; l < kLayers; ++l) {
+    if (l >= P.n_layers) break;
+    if (e >= P.off_w[l] && e < P.off_b[l]) dst = P.dw[l] + (e - P.off_w[l]);
+    if (e >= P.off_b[l] && e < P.off_b[l] + P.out[l]) dst = P.db[l] ? P.db[l] + (e - P.off_b[l]) : nullptr;
+  }
+  if (!dst) return;
+  const float* src = P.part + e;
+  float sum = src[0];
+  int k = 1;
+  for (; k + 8 <= P.slabs; k += 8) {
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = src[(long long)(k + j) * P.per_slab];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) sum = __fadd_rn(sum, v[j]);
+  }
+  for (; k < P.slabs; ++k) sum = __fadd_rn(sum, src[(long long)k * P.per_slab]);
+  *dst = sum;
+}
+
+struct Range {
+  const char* lo;
+  const char* hi;      // one past the last byte
+  bool overlaps(const Range& o) const { return lo && o.lo && lo < o.hi && o.lo < hi; }
+};
+
+// bytes [p, p + ((rows - 1) * stride + width) * size): the part of a [rows, stride] array the call touches
+Range extent(const void* p, int64_t rows, int64_t stride, int64_t width, int64_t size) {
+  const char* c = (const char*)p;
+  return {c, c ? c + ((rows - 1) * stride + width) * size : c};
+}
+
+// the descriptor limits of the backward pass; 0, or the code of pdegym::fail
+int check_net(const pdegym_mlp* net) {
+  if (!net) return pdegym::fail(-1, "null descriptor");
+  if (net->n_layers < 1 || net->n_layers > kLayers) return pdegym::fail(-2, "n_layers must be 1..4");
+  if (net->head != PDEGYM_MLP_HEAD_PLAIN) return pdegym::fail(-2, "mlp_backward: the head must be PLAIN (a squashed-Gaussian head is applied by the caller)");
+  if (net->clamp) return pdegym::fail(-2, "mlp_backward: clamp must be 0");
+  if (net->noise) return pdegym::fail(-2, "mlp_backward: noise must be NULL");
+  for (int l = 0; l < net->n_layers; ++l) {
+    const pdegym_mlp_layer& L = net->layer[l];
+    if (!L.w) return pdegym::fail(-3, "null weight pointer");
+    if (L.in_dim < 1 || L.out_dim < 1) return pdegym::fail(-2, "layer dimensions must be >= 1");
+    if (L.out_dim > kWidth) return pdegym::fail(-2, "mlp_backward: a layer wider than 64 units");
+    if (l == 0 && L.in_dim > kMaxIn) return pdegym::fail(-2, "mlp_backward: in_dim above 1024");
+    if (l > 0 && L.in_dim != net->layer[l - 1].out_dim) return pdegym::fail(-2, "layer input size does not match the previous layer");
+    if (L.act < PDEGYM_MLP_IDENTITY || L.act > PDEGYM_MLP_RELU) return pdegym::fail(-2, "unknown activation");
+  }
+  return 0;
+}
+
+// the number of slabs in use (the library's choice for 0), or the code of pdegym::fail
+int resolve_slabs(int32_t B, int32_t slabs) {
+  if (B < 1) return pdegym::fail(-2, "B must be >= 1");
+  const int tiles = (int)(((int64_t)B + kRows - 1) / kRows);
+  if (slabs < 0) return pdegym::fail(-2, "slabs must be >= 0");
+  if (slabs > tiles) return pdegym::fail(-2, "more slabs than tiles of 16 rows");
+  return slabs ? slabs : (tiles < kMaxSlabs ? tiles : kMaxSlabs);
+}
+
+int per_slab_floats(const pdegym_mlp* net) {
+  int n = 0;
+  for (int l = 0; l < net->n_layers; ++l) n += net->layer[l].out_dim * (net->layer[l].in_dim + 1);
+  return n;
+}
+
+int64_t dz0_floats(int32_t B) { return (((int64_t)B + kRows - 1) / kRows) * kRows * kWidth; }
+
+}  // namespace
+
+extern "C" {
+
+int64_t pdegym_mlp_backward_workspace(const pdegym_mlp* net, int32_t B, int32_t slabs) {
+  if (int rc = check_net(net)) return rc;
+  const int s = resolve_slabs(B, slabs);
+  if (s < 0) return s;
+  return (dz0_floats(B) + (int64_t)s * per_slab_floats(net)) * (int64_t)sizeof(float);
+}
+
+int pdegym_mlp_backward(const pdegym_mlp* net, const pdegym_mlp_backward_args* a, int32_t B, void* stream) {
+  if (int rc = check_net(net)) return rc;
+  if (!a) return pdegym::fail(-1, "null arguments");
+  const int slabs = resolve_slabs(B, a->slabs);
+  if (slabs < 0) return slabs;
+  const int nl = net->n_layers, K0 = net->layer[0].in_dim, n_out = net->layer[nl - 1].out_dim;
+  if (!a->x || !a->dy) return pdegym::fail(-3, "null x/dy");
+  if (!a->workspace) return pdegym::fail(-3, "null workspace");
+  for (int l = 0; l < nl; ++l) {
+    if (!a->dw[l]) return pdegym::fail(-3, "null dw");
+    if (!a->w[l] && (l > 0 || a->dx)) return pdegym::fail(-3, "null row-major weights (w[0] is needed with dx, the others always)");
+    if (a->db[l] && !net->layer[l].b) return pdegym::fail(-3, "db given for a layer without bias");
+    if (!a->db[l] && net->layer[l].b) return pdegym::fail(-3, "null db for a layer with bias");
+  }
+  if (a->dx && net->x_f64) return pdegym::fail(-2, "dx needs float32 x");
+  if (a->x_stride < K0 || a->dy_stride < n_out || (a->dx && a->dx_stride < K0)) return pdegym::fail(-2, "row stride shorter than the row");
+  const int64_t need = (dz0_floats(B) + (int64_t)slabs * per_slab_floats(net)) * (int64_t)sizeof(float);
+  if (a->workspace_bytes < need) return pdegym::fail(-2, "workspace smaller than pdegym_mlp_backward_workspace answers");
+
+  Range in[2 + 3 * kLayers], out[2 + 2 * kLayers];
+  int n_in = 0, n_outr = 0;
+  in[n_in++] = extent(a->x, B, a->x_stride, K0, net->x_f64 ? 8 : 4);
+  in[n_in++] = extent(a->dy, B, a->dy_stride, n_out, 4);
+  for (int l = 0; l < nl; ++l) {
+    const pdegym_mlp_layer& L = net->layer[l];
+    const int64_t cells = (int64_t)L.out_dim * L.in_dim;
+    in[n_in++] = extent(a->w[l], 1, cells, cells, 4);
+    in[n_in++] = extent(L.w, 1, 0, (int64_t)((L.in_dim + 3) / 4) * L.out_dim * 4, 4);
+    in[n_in++] = extent(L.b, 1, L.out_dim, L.out_dim, 4);
+    out[n_outr++] = extent(a->dw[l], 1, cells, cells, 4);
+    out[n_outr++] = extent(a->db[l], 1, L.out_dim, L.out_dim, 4);
+  }
+  out[n_outr++] = extent(a->dx, B, a->dx_stride, K0, 4);
+  out[n_outr++] = extent(a->workspace, 1, need, need, 1);
+  for (int i = 0; i < n_outr; ++i) {
+    for (int j = 0; j < n_in; ++j)
+      if (out[i].overlaps(in[j])) return pdegym::fail(-3, "an output or the workspace overlaps an input");
+    for (int j = i + 1; j < n_outr; ++j)
+      if (out[i].overlaps(out[j])) return pdegym::fail(-3, "two outputs overlap (the workspace counts as one)");
+  }
+
+  Plan P = {};
+  P.x = a->x, P.x_stride = a->x_stride, P.dy = a->dy, P.dy_stride = a->dy_stride, P.dx = a->dx, P.dx_stride = a->dx_stride;
+  P.dz0 = static_cast<float*>(a->workspace);
+  P.part = P.dz0 + dz0_floats(B);
+  int at = 0;
+  for (int l = 0; l < nl; ++l) {
+    const pdegym_mlp_layer& L = net->layer[l];
+    P.w[l] = a->w[l], P.dw[l] = a->dw[l], P.db[l] = a->db[l], P.in[l] = L.in_dim, P.out[l] = L.out_dim;
+    P.off_w[l] = at, at += L.out_dim * L.in_dim;
+    P.off_b[l] = at, at += L.out_dim;
+  }
+  P.per_slab = at, P.n_layers = nl, P.B = B, P.tiles = (int)(((int64_t)B + kRows - 1) / kRows), P.slabs = slabs;
+  hipStream_t st = (hipStream_t)stream;
+  const int kin = ((K0 < kXChunk ? K0 : kXChunk) + 15) & ~15;
+  const int ldx = lds_stride(kin);
+  const size_t lds_bytes = (size_t)((kLayers + 2) * kRows * kLdh + kRows * ldx) * sizeof(float);      // <= 58 KB: no opt-in needed
+  const dim3 grid0((unsigned)((K0 + 63) / 64), (unsigned)slabs);
+  const dim3 block(256), grid_reduce((unsigned)((P.per_slab + 255) / 256));
+  if (net->x_f64) {
+    mlp_backward_tiles<double><<<dim3(slabs), block, lds_bytes, st>>>(*net, P, ldx);
+    mlp_backward_dw0<double><<<grid0, block, 0, st>>>(P);
+  } else {
+    mlp_backward_tiles<float><<<dim3(slabs), block, lds_bytes, st>>>(*net, P, ldx);
+    mlp_backward_dw0<float><<<grid0, block, 0, st>>>(P);
+  }
+  mlp_backward_reduce<<<grid_reduce, block, 0, st>>>(P);
+  return pdegym::check_launch("mlp_backward");
+}
+
+}  // extern "C"

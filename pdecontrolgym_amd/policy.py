@@ -13,6 +13,9 @@ addresses, so a captured graph sees refreshed weights.
 ``FusedMLP.squashed_gaussian`` / ``FusedMLP.from_sb3(policy, stochastic=True)``: the actor SAC samples while it learns -- a
 state-dependent standard deviation, the tanh squash AFTER the noise, the result rescaled to the action box -- as a second head of
 the same kernels (include/pdegym.h: PDEGYM_MLP_HEAD_SQUASHED_GAUSSIAN).
+
+``FusedMLP.with_grad(obs)``: the same forward launch under autograd -- its backward is ``pdegym_mlp_backward``
+(csrc/pdegym_mlp_backward.hip) and fills the ``.grad`` of the wrapped module's Parameters, for layers of at most 64 units.
 """
 from __future__ import annotations
 
@@ -31,7 +34,10 @@ class FusedMLP:
     """``policy = FusedMLP(torch_module)``; ``policy(obs)`` -> ``[B, out_dim]`` float32 actions on the same device.
 
     ``clamp=(lo, hi)`` fuses the action-box clamp into the launch.  ``forward_into(obs, out)`` writes into a caller tensor
-    (``pde_control_gym.DeviceRollout`` points it at slot t of its action buffer).  Inference only (no autograd graph).
+    (``pde_control_gym.DeviceRollout`` points it at slot t of its action buffer).  ``__call__`` and ``forward_into`` are inference
+    only (no autograd graph); ``with_grad(obs)`` is the differentiable evaluation -- the same forward launch with a ``grad_fn``
+    whose backward is ``pdegym_mlp_backward`` (three launches) and fills the ``.grad`` of the wrapped module's own Parameters, for
+    networks that ``fits_backward()``.
     """
 
     def __init__(self, module, clamp=None, backend=None):
@@ -186,11 +192,12 @@ class FusedMLP:
                     self._seen[i] = w._version
         return self
 
-    def _net(self, clamp, x_f64=False, y_f64=False) -> N.Mlp:
+    def _net(self, clamp, x_f64=False, y_f64=False, plain=False) -> N.Mlp:
+        """``plain``: the descriptor of the bare layers, whatever the wrapper's head (what ``with_grad`` evaluates and differentiates)."""
         net = N.Mlp()
         net.x_f64, net.y_f64 = int(x_f64), int(y_f64)
         net.n_layers = len(self.layers)
-        if self.head == N.MLP_HEAD_SQUASHED_GAUSSIAN:
+        if self.head == N.MLP_HEAD_SQUASHED_GAUSSIAN and not plain:
             if clamp is None:
                 raise ValueError("a squashed-Gaussian head needs clamp=(lo, hi), the action box its output is rescaled to")
             if not float(clamp[0]) < float(clamp[1]):
@@ -278,7 +285,100 @@ class FusedMLP:
         self.backend.mlp_forward(net, x, y, B)
         return out
 
+    # ---- the differentiable evaluation (pdegym_mlp_forward + pdegym_mlp_backward) -------------------------------------------------
+    def backward_limit(self):
+        """None when ``pdegym_mlp_backward`` takes this network, otherwise the limit it breaks, in words."""
+        for i, (w, _, _) in enumerate(self.layers):
+            if w.shape[0] > N.MLP_BACKWARD_MAX_WIDTH:
+                return f"layer {i} has {w.shape[0]} units, the backward pass takes at most {N.MLP_BACKWARD_MAX_WIDTH} per layer"
+        if self.in_dim > N.MLP_BACKWARD_MAX_INPUT:
+            return f"rows of {self.in_dim} inputs, the backward pass takes at most {N.MLP_BACKWARD_MAX_INPUT}"
+        return None
+
+    def fits_backward(self) -> bool:
+        """Whether ``with_grad`` can differentiate this network: every layer of at most 64 units, rows of at most 1024 inputs."""
+        return self.backward_limit() is None
+
+    def grad_parameters(self):
+        """The Parameters ``with_grad`` returns gradients for, in its order: weight, bias (if any) of every layer of the wrapped
+        module; with a squashed-Gaussian head the latent layers' followed by those of ``mu`` and of ``log_std``."""
+        own = self.layers[:-1] if self._heads is not None else self.layers
+        ps = [p for w, b, _ in own for p in (w, b) if p is not None]
+        if self._heads is not None:
+            ps += [p for m in self._heads for p in (m.weight, m.bias) if p is not None]
+        return ps
+
+    def with_grad(self, obs):
+        """``[B, n]`` float32 WITH a ``grad_fn``: the last layer's output (no clamp, no noise, no head: a squashed-Gaussian wrapper
+        returns the raw ``[B, 2A]`` rows -- mu columns, then log_std columns -- and SAC's torch code applies clip / exp / tanh under
+        autograd).  Forward: one ``pdegym_mlp_forward`` launch after ``refresh()``; backward: ``pdegym_mlp_backward``, which returns the
+        gradients of ``grad_parameters()`` -- so ``loss.backward()`` fills (accumulates into) the ``.grad`` of the module's own
+        Parameters and any torch optimiser works unchanged -- and of ``obs`` when it is float32 and requires grad.  The activations
+        are recomputed in the backward launch, nothing is kept but ``obs``.  ``ValueError`` when the network does not
+        ``fits_backward()``; ``RuntimeError`` inside a stream capture (``refresh()`` cannot run there: a captured update would
+        train on stale weight copies)."""
+        import torch
+        why = self.backward_limit()
+        if why is not None:
+            raise ValueError(f"FusedMLP.with_grad: {why}")
+        B = obs.shape[0]
+        x = obs.reshape(B, -1)
+        if x.shape[1] != self.in_dim:
+            raise ValueError(f"observation rows have {x.shape[1]} entries, the network takes {self.in_dim}")
+        if x.dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"FusedMLP.with_grad: obs must be float32 or float64, got {x.dtype}")
+        if x.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("FusedMLP.with_grad cannot run inside a stream capture: refresh() has to see the optimiser's last step")
+        self.refresh()
+        return _with_grad_function().apply(self, x, *self.grad_parameters())
+
     def __call__(self, obs):
         import torch
         out = torch.empty(obs.shape[0], self.out_dim, dtype=obs.dtype, device=obs.device)
         return self.forward_into(obs, out)      # (squashed-Gaussian head: a ValueError -- it has no default box; use forward_into)
+
+
+_function = None
+
+
+def _with_grad_function():
+    """The ``torch.autograd.Function`` behind ``FusedMLP.with_grad`` (built on first use: this module imports torch lazily)."""
+    global _function
+    if _function is not None:
+        return _function
+    import torch
+
+    class FusedMLPFunction(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, policy, x, *params):
+            xd = x.detach()
+            if xd.stride(1) != 1 or (xd.shape[0] > 1 and xd.stride(0) < xd.shape[1]):
+                xd = xd.contiguous()
+            n_out = int(policy.layers[-1][0].shape[0])
+            y = torch.empty(xd.shape[0], n_out, dtype=torch.float32, device=xd.device)
+            policy.backend.mlp_forward(policy._net(None, xd.dtype == torch.float64, plain=True), xd, y, xd.shape[0])
+            ctx.policy, ctx.want_dx = policy, bool(ctx.needs_input_grad[1]) and x.dtype == torch.float32
+            ctx.save_for_backward(xd, *params)      # (the parameters: autograd refuses a backward after they changed in place)
+            return y
+
+        @staticmethod
+        def backward(ctx, dy):
+            policy = ctx.policy
+            xd = ctx.saved_tensors[0]
+            dy = dy.to(torch.float32).contiguous()
+            weights = [w.detach() for w, _, _ in policy.layers]
+            dw = [torch.empty_like(w) for w in weights]
+            db = [None if b is None else torch.empty_like(b.detach()) for _, b, _ in policy.layers]
+            dx = torch.empty(xd.shape, dtype=torch.float32, device=xd.device) if ctx.want_dx else None
+            policy.backend.mlp_backward(policy._net(None, xd.dtype == torch.float64, plain=True), xd, dy, weights, dw, db, dx)
+            heads = policy._heads is not None
+            grads = [g for w_, b_ in zip(dw[:-1] if heads else dw, db[:-1] if heads else db) for g in (w_, b_) if g is not None]
+            if heads:      # rows 0 .. A-1 of the fused last layer are mu's, rows A .. 2A-1 log_std's
+                A = dw[-1].shape[0] // 2
+                for rows in (slice(0, A), slice(A, 2 * A)):
+                    grads += [dw[-1][rows]] + ([db[-1][rows]] if db[-1] is not None else [])
+            wanted = ctx.needs_input_grad[2:]
+            return (None, dx) + tuple(g if need else None for g, need in zip(grads, wanted))
+
+    _function = FusedMLPFunction
+    return _function

@@ -42,6 +42,14 @@
  *   - calls only ENQUEUE work on `stream` (a hipStream_t passed as void*); they never synchronise;
  *   - return value 0 = success, negative = error (message via pdegym_last_error()); nothing throws;
  *   - arrays are C-contiguous; the grid axis is the fastest axis;
+ *   - a pointer needs only the NATURAL ALIGNMENT OF ITS ELEMENT TYPE (1 byte for the uint8 flags, 4 for float / int32, 8 for double /
+ *     int64), unless its parameter says otherwise: a slot of a [T + 1, B, obs_dim] rollout buffer, a view into a larger tensor and an
+ *     array carved out of a pool are all valid, and the results do not depend on where a buffer starts.  The exceptions -- the
+ *     blocked MLP weights and obs / U_ref / lam of the adjoint march: 16 bytes; the workspace of pdegym_mlp_backward: 4 -- are
+ *     stated at the parameter, and a pointer that violates one is refused with -2 and a message naming the argument BEFORE anything
+ *     is launched (never rerouted to another kernel: the bits of a result must not depend on an address).  The refusals are new
+ *     with this wording (the struct layouts and PDEGYM_ABI_VERSION are unchanged): earlier libraries launched such a call and its
+ *     16-byte accesses were the undefined behaviour the requirement now names;
  *   - non-finite data is ordinary data, as it is to the reference: a NaN command, observation or state cell propagates exactly as
  *     NumPy / PyTorch propagate it there (a stencil spreads it to the cells that read it, norms and rewards become NaN, comparisons
  *     with it are false), and every clamp (the action clips of the environments, the fused clamp of pdegym_mlp_forward, of the
@@ -256,7 +264,9 @@ typedef struct pdegym_params_ns2d {
   double gamma;             /* NSReward(gamma)                                             ns_reward.py:15-28 */
 } pdegym_params_ns2d;
 
-/* T = float (f32 entry points) or double (f64 entry points). Fields are [B, ny, nx], row = y, col = x. */
+/* T = float (f32 entry points) or double (f64 entry points). Fields are [B, ny, nx], row = y, col = x.  Every member needs only its
+ * element's alignment, on every grid: the register-tiled kernels (64 x 64, 128 x 128, 256 x 256) move 8- and 16-byte pieces of a row
+ * through accesses that are typed with the element's alignment. */
 typedef struct pdegym_bufs_ns2d {
   void* u;                  /* [B, ny, nx] in/out; may be NULL (together with v) when state_in is given        */
   void* v;                  /* [B, ny, nx] in/out                                                             */
@@ -542,7 +552,9 @@ int pdegym_tumor_rollout(const pdegym_params_tumor* prm, const pdegym_bufs_tumor
  * transport1DtestAlgorithm.py (the RL controllers).  pdegym_mlp_forward evaluates such a network for B observation rows
  * in ONE launch (float32; weights in a blocked transpose of torch.nn.Linear.weight W[out_dim, in_dim]:
  * w[(k / 4) * out_dim * 4 + n * 4 + k % 4] = W[n][k], zero-padded to a multiple of four k, 16-byte aligned -- one 16-byte
- * load per lane brings four consecutive inputs of its neuron and a wave's load is contiguous), optionally clamping the
+ * load per lane brings four consecutive inputs of its neuron and a wave's load is contiguous; a layer whose w is not 16-byte aligned
+ * is refused with -2, by pdegym_mlp_forward, pdegym_mlp_backward and every rollout that takes the network as its policy; x, y, b
+ * and noise need only their element's alignment), optionally clamping the
  * output to the action box, so that policy + step + auto-reset of a rollout are two launches per env-step.
  * Summation order is k ascending with the bias added last (not a BLAS order): float32-rounding agreement with torch. */
 #define PDEGYM_MLP_MAX_LAYERS 4
@@ -551,7 +563,7 @@ int pdegym_tumor_rollout(const pdegym_params_tumor* prm, const pdegym_bufs_tumor
 enum { PDEGYM_MLP_IDENTITY = 0, PDEGYM_MLP_TANH = 1, PDEGYM_MLP_RELU = 2 };
 
 typedef struct {
-  const float* w;      /* [ceil(in_dim / 4), out_dim, 4] blocked transpose, see above  */
+  const float* w;      /* [ceil(in_dim / 4), out_dim, 4] blocked transpose, see above; 16-BYTE ALIGNED (else -2) */
   const float* b;      /* [out_dim] or NULL                                         */
   int32_t in_dim, out_dim;
   int32_t act;         /* PDEGYM_MLP_* applied to this layer's output               */
@@ -628,8 +640,9 @@ int pdegym_mlp_forward(const pdegym_mlp* net, const void* x, int64_t x_stride, v
  *          floor(s tiles / slabs) .. floor((s + 1) tiles / slabs) - 1); a slab's partial sums are formed rows ascending and the slabs'
  *          partials are added in ascending order.  0: the library's choice, min(tiles, 256) -- a function of B alone.
  *          1 <= slabs <= tiles otherwise.
- * workspace  device memory of at least pdegym_mlp_backward_workspace (net, B, slabs) bytes, 4-byte aligned; every byte that is read
- *          was written by the same call.
+ * workspace  device memory of at least pdegym_mlp_backward_workspace (net, B, slabs) bytes, 4-byte aligned (else -2); every byte that
+ *          is read was written by the same call.  net->layer[l].w: 16-byte aligned, as for pdegym_mlp_forward (else -2, from
+ *          pdegym_mlp_backward_workspace as well: the size query checks the same descriptor).
  * Arithmetic  float32 throughout.  Activation derivatives as torch's backward ops, each operation rounded on its own:
  *          tanh dz = dh * (1 - h * h); ReLU dz = (h <= 0) ? 0 : dh (a NaN activation passes the gradient, as threshold_backward).
  *          The three products dW_l = dZ_l^T H_{l-1} (over rows), db_l = sum_rows dZ_l and dH_{l-1} = dZ_l W_l (over the layer's units) run
@@ -639,7 +652,7 @@ int pdegym_mlp_forward(const pdegym_mlp* net, const void* x, int64_t x_stride, v
  *          selected to zero, not multiplied by it).
  * Non-finite data propagates as IEEE makes it: a NaN in row i of x or dy reaches dx[i] and the weight gradients, and no other row of dx.
  * Errors: -1 null descriptor / arguments; -2 a limit above, B < 1, a stride shorter than its row, slabs out of range, a workspace that
- * is too small, dx with x_f64; -3 a required pointer is NULL, db that does not match the layer's bias, or an output (the workspace
+ * is too small or not 4-byte aligned, blocked weights that are not 16-byte aligned, dx with x_f64; -3 a required pointer is NULL, db that does not match the layer's bias, or an output (the workspace
  * included) that overlaps an input or another output as byte ranges. */
 typedef struct pdegym_mlp_backward_args {
   const void* x;
@@ -784,14 +797,17 @@ int pdegym_traffic_backstep_rollout(const pdegym_params_traffic* prm, const pdeg
 typedef struct pdegym_adjoint_ns2d {
   int32_t T;                /* forward steps of the trajectory (the script's T = 199, :65); T - 1 backward steps                 */
   int32_t t0;               /* time index of obs slot 0 (0 after a reset)                                                        */
-  const double* obs;        /* [T + 1, B, ny, nx, 2] the forward rollout, pdegym_rollout_ns2d.obs (slot 0 is not read)   :74-76  */
+  const double* obs;        /* [T + 1, B, ny, nx, 2] the forward rollout, pdegym_rollout_ns2d.obs (slot 0 is not read)   :74-76;
+                               16-BYTE ALIGNED (else -2): the march reads (u, v) pairs                                              */
   const double* a_nom;      /* [T] nominal commands, the script's u_ref                                                  :81     */
   double ratio, width;
   double* grad;             /* [T, B] out                                                                                        */
   double* actions;          /* [T, B] out                                                                                :104-107 */
-  double* lam;              /* optional [T, B, ny, nx, 2] out: Lam1[::-1] (:103) and Lam2 in the same order; NULL = not stored   */
+  double* lam;              /* optional [T, B, ny, nx, 2] out: Lam1[::-1] (:103) and Lam2 in the same order; NULL = not stored;
+                               16-BYTE ALIGNED (else -2)                                                                            */
 } pdegym_adjoint_ns2d;
-/* U_ref: [nt_ref, ny, nx, 2], the targets of :79-80 as the step kernels read them (pdegym_bufs_ns2d.U_ref). */
+/* U_ref: [nt_ref, ny, nx, 2], the targets of :79-80 as the step kernels read them (pdegym_bufs_ns2d.U_ref); 16-BYTE ALIGNED (else -2).
+ * a_nom, grad and actions need 8 bytes. */
 int pdegym_ns2d_adjoint_f64(const pdegym_params_ns2d* prm, const void* U_ref, int32_t nt_ref, const pdegym_adjoint_ns2d* adj, int32_t B,
                             void* stream);
 

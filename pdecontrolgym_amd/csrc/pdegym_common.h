@@ -12,6 +12,10 @@ char* error_slot();
 int fail(int code, const char* msg);
 int check_launch(const char* what);
 
+// Pointers need only the natural alignment of their element type (include/pdegym.h, Conventions).  Where a parameter states more --
+// its kernel reads it through a naturally aligned 16-byte type -- the host function refuses another pointer before it launches.
+inline bool is_aligned(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
+
 // Per-device caches: the library keeps no state that is bound to "the first device that called" (a process may drive
 // several GPUs, one engine per device, each call made with that engine's device current).
 constexpr int kMaxDevices = 64;

@@ -214,6 +214,7 @@ extern "C" int pdegym_mlp_forward(const pdegym_mlp* net, const void* x, int64_t 
   for (int l = 0; l < net->n_layers; ++l) {
     const pdegym_mlp_layer& L = net->layer[l];
     if (!L.w) return pdegym::fail(-3, "null weight pointer");
+    if (!pdegym::is_aligned(L.w, 16)) return pdegym::fail(-2, "layer weights (w) must be 16-byte aligned");
     if (L.in_dim < 1 || L.out_dim < 1) return pdegym::fail(-2, "layer dimensions must be >= 1");
     if (L.out_dim > PDEGYM_MLP_MAX_WIDTH) return pdegym::fail(-2, "layer wider than PDEGYM_MLP_MAX_WIDTH");
     if (l == 0 && L.in_dim > PDEGYM_MLP_MAX_INPUT) return pdegym::fail(-2, "observation wider than PDEGYM_MLP_MAX_INPUT");

@@ -336,6 +336,7 @@ int check_net(const pdegym_mlp* net) {
   for (int l = 0; l < net->n_layers; ++l) {
     const pdegym_mlp_layer& L = net->layer[l];
     if (!L.w) return pdegym::fail(-3, "null weight pointer");
+    if (!pdegym::is_aligned(L.w, 16)) return pdegym::fail(-2, "layer weights (w) must be 16-byte aligned");
     if (L.in_dim < 1 || L.out_dim < 1) return pdegym::fail(-2, "layer dimensions must be >= 1");
     if (L.out_dim > kWidth) return pdegym::fail(-2, "mlp_backward: a layer wider than 64 units");
     if (l == 0 && L.in_dim > kMaxIn) return pdegym::fail(-2, "mlp_backward: in_dim above 1024");
@@ -381,6 +382,7 @@ int pdegym_mlp_backward(const pdegym_mlp* net, const pdegym_mlp_backward_args* a
   const int nl = net->n_layers, K0 = net->layer[0].in_dim, n_out = net->layer[nl - 1].out_dim;
   if (!a->x || !a->dy) return pdegym::fail(-3, "null x/dy");
   if (!a->workspace) return pdegym::fail(-3, "null workspace");
+  if (!pdegym::is_aligned(a->workspace, 4)) return pdegym::fail(-2, "workspace must be 4-byte aligned");
   for (int l = 0; l < nl; ++l) {
     if (!a->dw[l]) return pdegym::fail(-3, "null dw");
     if (!a->w[l] && (l > 0 || a->dx)) return pdegym::fail(-3, "null row-major weights (w[0] is needed with dx, the others always)");

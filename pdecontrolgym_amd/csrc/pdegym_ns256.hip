@@ -226,7 +226,7 @@ __global__ __launch_bounds__(kNT, 2) void ns256_fused_step(NSConst C, NSScal<flo
     const float* p = P.p + (size_t)b * kCells + (size_t)r0 * kN + c0;
 #pragma unroll
     for (int a = 0; a < kPR; ++a) {
-      const float4 x = *reinterpret_cast<const float4*>(p + a * kN);
+      const float4 x = *gvec<float4>(p + a * kN);
       ph[a][0] = x.x; ph[a][1] = x.y; ph[a][2] = x.z; ph[a][3] = x.w;
     }
 #pragma unroll
@@ -255,7 +255,7 @@ __global__ __launch_bounds__(kNT, 2) void ns256_fused_step(NSConst C, NSScal<flo
   {
     float* pd = (P.p_out ? P.p_out : P.p) + (size_t)b * kCells + (size_t)r0 * kN + c0;
 #pragma unroll
-    for (int a = 0; a < kPR; ++a) *reinterpret_cast<float4*>(pd + a * kN) = make_float4(ph[a][0], ph[a][1], ph[a][2], ph[a][3]);
+    for (int a = 0; a < kPR; ++a) *gvec<float4>(pd + a * kN) = make_float4(ph[a][0], ph[a][1], ph[a][2], ph[a][3]);
   }
 
   // ---- back: corrector (:143-145), apply_boundary(u, v) (:146), observation (:147-154), reward (ns_reward.py:28) ----
@@ -286,7 +286,7 @@ __global__ __launch_bounds__(kNT, 2) void ns256_fused_step(NSConst C, NSScal<flo
     float c1u[4], c1v[4], c2u[4], c2v[4];                            // C(r-1), C(r-2)
     auto prow = [&](int a, float (&v)[4]) __attribute__((always_inline)) {                          // p row r0 + a, -1 <= a
       const int ac = a < 0 ? 0 : (a < kPR - 1 ? a : kPR - 1);
-      const float4 x = *reinterpret_cast<const float4*>(pg + ac * kN);
+      const float4 x = *gvec<float4>(pg + ac * kN);
       v[0] = a < 0 ? pt[0] : (a < kPR ? x.x : pb[0]);
       v[1] = a < 0 ? pt[1] : (a < kPR ? x.y : pb[1]);
       v[2] = a < 0 ? pt[2] : (a < kPR ? x.z : pb[2]);
@@ -294,7 +294,7 @@ __global__ __launch_bounds__(kNT, 2) void ns256_fused_step(NSConst C, NSScal<flo
     };
     auto urow = [&](int row, float4 (&q)[2]) __attribute__((always_inline)) {
       const int rc = row < 0 ? 0 : (row > kN - 1 ? kN - 1 : row);
-      const float4* rrow = reinterpret_cast<const float4*>(uref + (rc * kN + c0b) * 2);
+      const auto rrow = gvec<float4>(uref + (rc * kN + c0b) * 2);
       q[0] = rrow[0];
       q[1] = rrow[1];
     };
@@ -318,7 +318,7 @@ __global__ __launch_bounds__(kNT, 2) void ns256_fused_step(NSConst C, NSScal<flo
       }
       bc_row(fu, nbu, rr, c0b, C.bc, 0, bsel, act, C.action_dim, a0);
       bc_row(fv, nbv, rr, c0b, C.bc, 1, bsel, act, C.action_dim, a0);
-      float4* orow = reinterpret_cast<float4*>(obs + (rr * kN + c0b) * 2);
+      const auto orow = gvec<float4>(obs + (rr * kN + c0b) * 2);
       orow[0] = make_float4(fu[0], fv[0], fu[1], fv[1]);
       orow[1] = make_float4(fu[2], fv[2], fu[3], fv[3]);
       const float d0 = fu[0] - ref[0].x, d1 = fv[0] - ref[0].y, d2 = fu[1] - ref[0].z, d3 = fv[1] - ref[0].w;
@@ -383,10 +383,10 @@ __global__ __launch_bounds__(kNT, 2) void ns256_fused_step(NSConst C, NSScal<flo
 __global__ __launch_bounds__(256) void ns256_split_obs(const float* obs, float* u, float* v, size_t ncell4) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;   // one thread per four cells
   if (i >= ncell4) return;
-  const float4* q = reinterpret_cast<const float4*>(obs) + 2 * i;
+  const auto q = gvec<float4>(obs) + 2 * i;
   const float4 a = q[0], d = q[1];
-  reinterpret_cast<float4*>(u)[i] = make_float4(a.x, a.z, d.x, d.z);
-  reinterpret_cast<float4*>(v)[i] = make_float4(a.y, a.w, d.y, d.w);
+  gvec<float4>(u)[i] = make_float4(a.x, a.z, d.x, d.z);
+  gvec<float4>(v)[i] = make_float4(a.y, a.w, d.y, d.w);
 }
 
 }  // namespace

@@ -204,8 +204,8 @@ __device__ __forceinline__ void front_rows(const NSConst& C, const NSScal<double
         q[k] = edge ? 0.0 : S.rho_over_dt * (dudx + dvdy);
       }
       double* dst = rhs + (size_t)i * kN + c0;
-      *reinterpret_cast<double2*>(dst) = make_double2(q[0], q[1]);
-      *reinterpret_cast<double2*>(dst + 2) = make_double2(q[2], q[3]);
+      *gvec<double2>(dst) = make_double2(q[0], q[1]);
+      *gvec<double2>(dst + 2) = make_double2(q[2], q[3]);
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -229,7 +229,7 @@ __device__ __forceinline__ double back_rows(const NSConst& C, const NSScal<doubl
   const double a0 = act[0];
   auto prow = [&](int row, double (&v)[4]) __attribute__((always_inline)) {
     const int rc = row < 0 ? 0 : (row > kN - 1 ? kN - 1 : row);
-    const double2 x = *reinterpret_cast<const double2*>(pf + (size_t)rc * kN), y = *reinterpret_cast<const double2*>(pf + (size_t)rc * kN + 2);
+    const double2 x = *gvec<double2>(pf + (size_t)rc * kN), y = *gvec<double2>(pf + (size_t)rc * kN + 2);
     v[0] = x.x; v[1] = x.y; v[2] = y.x; v[3] = y.y;
   };
   double s0u[4], s0v[4], s1u[4], s1v[4], s2u[4], s2v[4];
@@ -255,8 +255,8 @@ __device__ __forceinline__ double back_rows(const NSConst& C, const NSScal<doubl
     bc_row<double>(fu, nbu, rr, c0, C.bc, 0, bsel, act, C.action_dim, a0);
     bc_row<double>(fv, nbv, rr, c0, C.bc, 1, bsel, act, C.action_dim, a0);
     const size_t o = ((size_t)rr * kN + c0) * 2;
-    const double2* rrow = reinterpret_cast<const double2*>(uref + o);
-    double2* orow = reinterpret_cast<double2*>(obs + o);
+    const auto rrow = gvec<double2>(uref + o);
+    const auto orow = gvec<double2>(obs + o);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const double2 ref = rrow[k];
@@ -349,8 +349,8 @@ __global__ __launch_bounds__(kNT, 2) void ns256_pass_f64(NSConst C, NSScal<doubl
     double ph[kPR + 1][4], rq[kRR][4];
 #pragma unroll
     for (int a = 0; a < kPR; ++a) {
-      const double2 x = *reinterpret_cast<const double2*>(ps + a * kN), y = *reinterpret_cast<const double2*>(ps + a * kN + 2);
-      const double2 r = *reinterpret_cast<const double2*>(rs + a * kN), s = *reinterpret_cast<const double2*>(rs + a * kN + 2);
+      const double2 x = *gvec<double2>(ps + a * kN), y = *gvec<double2>(ps + a * kN + 2);
+      const double2 r = *gvec<double2>(rs + a * kN), s = *gvec<double2>(rs + a * kN + 2);
       ph[a][0] = x.x; ph[a][1] = x.y; ph[a][2] = y.x; ph[a][3] = y.y;
       const double q0 = S.dxdy * r.x, q1 = S.dxdy * r.y, q2 = S.dxdy * s.x, q3 = S.dxdy * s.y;       // dx dy rhs (:108)
       if (a < kRR) {
@@ -391,8 +391,8 @@ __global__ __launch_bounds__(kNT, 2) void ns256_pass_f64(NSConst C, NSScal<doubl
       const int g = g0 + a;
       if (g >= st_lo && g < st_hi) {        // wave-uniform
         const double (&row)[4] = ph[a];
-        *reinterpret_cast<double2*>(pd + a * kN) = make_double2(row[0], row[1]);
-        *reinterpret_cast<double2*>(pd + a * kN + 2) = make_double2(row[2], row[3]);
+        *gvec<double2>(pd + a * kN) = make_double2(row[0], row[1]);
+        *gvec<double2>(pd + a * kN + 2) = make_double2(row[2], row[3]);
       }
     }
   }
@@ -444,10 +444,10 @@ __global__ void ns256_finish_f64(NSConst C, NSScal<double> S, NSPtrs<double> P, 
 __global__ __launch_bounds__(256) void ns256_split_obs_f64(const double* obs, double* u, double* v, size_t ncell2) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;   // one thread per two cells
   if (i >= ncell2) return;
-  const double2* q = reinterpret_cast<const double2*>(obs) + 2 * i;
+  const auto q = gvec<double2>(obs) + 2 * i;
   const double2 a = q[0], d = q[1];
-  reinterpret_cast<double2*>(u)[i] = make_double2(a.x, d.x);
-  reinterpret_cast<double2*>(v)[i] = make_double2(a.y, d.y);
+  gvec<double2>(u)[i] = make_double2(a.x, d.x);
+  gvec<double2>(v)[i] = make_double2(a.y, d.y);
 }
 
 }  // namespace

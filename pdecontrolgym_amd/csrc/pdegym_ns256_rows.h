@@ -17,22 +17,22 @@ __device__ __forceinline__ void load_state_row(const T* su, const T* sv, int row
   const int r = row < 0 ? 0 : (row > kN - 1 ? kN - 1 : row);
   if constexpr (sizeof(T) == 4) {          // 16-byte loads either way
     if constexpr (INTERLEAVED) {
-      const float4* q = reinterpret_cast<const float4*>(su + (r * kN + c0) * 2);
+      const auto q = gvec<float4>(su + (r * kN + c0) * 2);
       const float4 a = q[0], d = q[1];
       fu[0] = a.x; fv[0] = a.y; fu[1] = a.z; fv[1] = a.w; fu[2] = d.x; fv[2] = d.y; fu[3] = d.z; fv[3] = d.w;
     } else {
-      const float4 a = *reinterpret_cast<const float4*>(su + r * kN + c0);
-      const float4 d = *reinterpret_cast<const float4*>(sv + r * kN + c0);
+      const float4 a = *gvec<float4>(su + r * kN + c0);
+      const float4 d = *gvec<float4>(sv + r * kN + c0);
       fu[0] = a.x; fu[1] = a.y; fu[2] = a.z; fu[3] = a.w; fv[0] = d.x; fv[1] = d.y; fv[2] = d.z; fv[3] = d.w;
     }
   } else {
     if constexpr (INTERLEAVED) {
-      const double2* q = reinterpret_cast<const double2*>(su + (r * kN + c0) * 2);
+      const auto q = gvec<double2>(su + (r * kN + c0) * 2);
       const double2 a = q[0], b = q[1], c = q[2], d = q[3];
       fu[0] = a.x; fv[0] = a.y; fu[1] = b.x; fv[1] = b.y; fu[2] = c.x; fv[2] = c.y; fu[3] = d.x; fv[3] = d.y;
     } else {
-      const double2* qu = reinterpret_cast<const double2*>(su + r * kN + c0);
-      const double2* qv = reinterpret_cast<const double2*>(sv + r * kN + c0);
+      const auto qu = gvec<double2>(su + r * kN + c0);
+      const auto qv = gvec<double2>(sv + r * kN + c0);
       const double2 a = qu[0], b = qu[1], c = qv[0], d = qv[1];
       fu[0] = a.x; fu[1] = a.y; fu[2] = b.x; fu[3] = b.y; fv[0] = c.x; fv[1] = c.y; fv[2] = d.x; fv[3] = d.y;
     }

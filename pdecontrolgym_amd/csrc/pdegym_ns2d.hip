@@ -407,14 +407,14 @@ template <int PR, int PC>
 __device__ __forceinline__ void load_patch(float (&f)[PR][PC], const float* g, int n, int r0, int c0) {
   using V = typename VecOf<PC>::type;
 #pragma unroll
-  for (int a = 0; a < PR; ++a) unpack_row<PC>(*reinterpret_cast<const V*>(g + ((r0 + a) * n + c0)), f[a]);
+  for (int a = 0; a < PR; ++a) unpack_row<PC>(*gvec<V>(g + ((r0 + a) * n + c0)), f[a]);
 }
 
 template <int PR, int PC>
 __device__ __forceinline__ void store_patch(const float (&f)[PR][PC], float* g, int n, int r0, int c0) {
   using V = typename VecOf<PC>::type;
 #pragma unroll
-  for (int a = 0; a < PR; ++a) *reinterpret_cast<V*>(g + ((r0 + a) * n + c0)) = pack_row<PC>(f[a]);
+  for (int a = 0; a < PR; ++a) *gvec<V>(g + ((r0 + a) * n + c0)) = pack_row<PC>(f[a]);
 }
 
 // apply_boundary on HR consecutive rows of a thread's patch, held in f: the four ordered passes (lower, upper, left, right) only
@@ -618,7 +618,7 @@ __global__ __launch_bounds__(512, 4) void ns_tile_step(NSConst C, NSScal<float> 
     if constexpr (INTERLEAVED) {  // (u, v) interleaved: the previous call's observation IS the state
 #pragma unroll
       for (int a = 0; a < PR; ++a) {
-        const float4* row = reinterpret_cast<const float4*>(sin + ((r0 + a) * n + c0) * 2);
+        const auto row = gvec<float4>(sin + ((r0 + a) * n + c0) * 2);
 #pragma unroll
         for (int q = 0; q < PC / 2; ++q) {
           const float4 w = row[q];
@@ -822,12 +822,12 @@ __global__ __launch_bounds__(512, 4) void ns_tile_step(NSConst C, NSScal<float> 
 #pragma unroll
       for (int la = 0; la < HR; ++la) {
         if constexpr (!INTERLEAVED) {
-          *reinterpret_cast<V*>(u + ((r0c + a0 + la) * n + c0c)) = pack_row<PC>(uf[la]);
-          *reinterpret_cast<V*>(v + ((r0c + a0 + la) * n + c0c)) = pack_row<PC>(vf[la]);
+          *gvec<V>(u + ((r0c + a0 + la) * n + c0c)) = pack_row<PC>(uf[la]);
+          *gvec<V>(v + ((r0c + a0 + la) * n + c0c)) = pack_row<PC>(vf[la]);
         }
         const int o = ((r0c + a0 + la) * n + c0c) * 2;
-        const float4* rrow = reinterpret_cast<const float4*>(uref + o);
-        float4* orow = reinterpret_cast<float4*>(obs + o);
+        const auto rrow = gvec<float4>(uref + o);
+        const auto orow = gvec<float4>(obs + o);
 #pragma unroll
         for (int q = 0; q < PC / 2; ++q) {
           const float4 w = rrow[q];
@@ -938,12 +938,12 @@ __global__ __launch_bounds__(F64Tile::NT, 2) void ns_tile_step_f64(NSConst C, NS
   {
     auto load_row = [&](int grow, double (&ru)[2], double (&rv)[2]) {
       if constexpr (INTERLEAVED) {
-        const double2* row = reinterpret_cast<const double2*>(sin + ((size_t)grow * n + c0) * 2);
+        const auto row = gvec<double2>(sin + ((size_t)grow * n + c0) * 2);
         const double2 w0 = row[0], w1 = row[1];
         ru[0] = w0.x; rv[0] = w0.y; ru[1] = w1.x; rv[1] = w1.y;
       } else {
-        const double2 wu = *reinterpret_cast<const double2*>(u + grow * n + c0);
-        const double2 wv = *reinterpret_cast<const double2*>(v + grow * n + c0);
+        const double2 wu = *gvec<double2>(u + grow * n + c0);
+        const double2 wv = *gvec<double2>(v + grow * n + c0);
         ru[0] = wu.x; ru[1] = wu.y; rv[0] = wv.x; rv[1] = wv.y;
       }
     };
@@ -1051,7 +1051,7 @@ __global__ __launch_bounds__(F64Tile::NT, 2) void ns_tile_step_f64(NSConst C, NS
     double ph[PR + 1][2];
 #pragma unroll
     for (int a = 0; a < PR; ++a) {
-      const double2 w = *reinterpret_cast<const double2*>(p + (r0 + a) * n + c0);
+      const double2 w = *gvec<double2>(p + (r0 + a) * n + c0);
       ph[a][0] = w.x; ph[a][1] = w.y;
     }
     ph[PR][0] = ph[PR][1] = 0.0;
@@ -1070,7 +1070,7 @@ __global__ __launch_bounds__(F64Tile::NT, 2) void ns_tile_step_f64(NSConst C, NS
     }
   }
 #pragma unroll
-  for (int a = 0; a < PR; ++a) *reinterpret_cast<double2*>(pout + (r0 + a) * n + c0) = make_double2(pf[a][0], pf[a][1]);
+  for (int a = 0; a < PR; ++a) *gvec<double2>(pout + (r0 + a) * n + c0) = make_double2(pf[a][0], pf[a][1]);
 
   // ---- corrector (:143-146), observation, reward ----
   double acc = 0.0;
@@ -1116,13 +1116,13 @@ __global__ __launch_bounds__(F64Tile::NT, 2) void ns_tile_step_f64(NSConst C, NS
       for (int la = 0; la < HR; ++la) {
         const int a = a0 + la;
         if constexpr (!INTERLEAVED) {
-          *reinterpret_cast<double2*>(u + (r0 + a) * n + c0) = make_double2(uf[la][0], uf[la][1]);
-          *reinterpret_cast<double2*>(v + (r0 + a) * n + c0) = make_double2(vf[la][0], vf[la][1]);
+          *gvec<double2>(u + (r0 + a) * n + c0) = make_double2(uf[la][0], uf[la][1]);
+          *gvec<double2>(v + (r0 + a) * n + c0) = make_double2(vf[la][0], vf[la][1]);
         }
         const size_t o = ((size_t)(r0 + a) * n + c0) * 2;
-        const double2 w0 = *reinterpret_cast<const double2*>(uref + o), w1 = *reinterpret_cast<const double2*>(uref + o + 2);
-        *reinterpret_cast<double2*>(obs + o) = make_double2(uf[la][0], vf[la][0]);
-        *reinterpret_cast<double2*>(obs + o + 2) = make_double2(uf[la][1], vf[la][1]);
+        const double2 w0 = *gvec<double2>(uref + o), w1 = *gvec<double2>(uref + o + 2);
+        *gvec<double2>(obs + o) = make_double2(uf[la][0], vf[la][0]);
+        *gvec<double2>(obs + o + 2) = make_double2(uf[la][1], vf[la][1]);
         // per thread: its cells in index order, du^2 then dv^2; then block_sum across lanes (not gen_back's column order: rtol 1e-12)
         const double d0 = uf[la][0] - w0.x, d1 = vf[la][0] - w0.y, d2 = uf[la][1] - w1.x, d3 = vf[la][1] - w1.y;
         acc += d0 * d0;

@@ -248,6 +248,10 @@ int pdegym_ns2d_adjoint_f64(const pdegym_params_ns2d* prm, const void* U_ref, in
   if (adj->T < 1) return pdegym::fail(-2, "T must be >= 1");
   if (adj->t0 < 0) return pdegym::fail(-2, "t0 must be >= 0");
   if (nt_ref < 1) return pdegym::fail(-2, "nt_ref must be >= 1");
+  // the march moves (u, v) / (lambda1, lambda2) pairs as one naturally aligned 16-byte access
+  if (!pdegym::is_aligned(U_ref, 16)) return pdegym::fail(-2, "U_ref must be 16-byte aligned");
+  if (!pdegym::is_aligned(adj->obs, 16)) return pdegym::fail(-2, "obs must be 16-byte aligned");
+  if (!pdegym::is_aligned(adj->lam, 16)) return pdegym::fail(-2, "lam must be 16-byte aligned");
   const int ny = C.ny;
   if (C.nx > 64 || !(ny == 8 || ny == 11 || ny == 16 || ny == 21 || ny == 26 || ny == 31 || ny == 32))
     return pdegym::fail(-2, "the adjoint march needs a column-kernel grid: 8, 11, 16, 21, 26, 31 or 32 rows, 3 .. 64 columns");

@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
 
 #include "pdegym.h"
@@ -119,6 +120,41 @@ template <>
 struct VecOf<2, float> { using type = float2; };
 template <>
 struct VecOf<2, double> { using type = double2; };
+
+// A caller's field pointer is only element-aligned (include/pdegym.h, Conventions).  The 8- / 16-byte pieces of a row move through
+// these two, which tell the compiler the element's alignment and no more: gfx950 global accesses need none beyond the dword (as for
+// pdegym_f4u in pdegym_1d_body.h), and the instructions are the ones the naturally aligned float4 / double2 casts gave.
+template <typename V, typename T>
+__device__ __forceinline__ V ldg(const T* p) {
+  V v;
+  __builtin_memcpy(&v, __builtin_assume_aligned(p, alignof(T)), sizeof(V));
+  return v;
+}
+template <typename V, typename T>
+__device__ __forceinline__ void stg(T* p, const V& v) {
+  __builtin_memcpy(__builtin_assume_aligned(p, alignof(T)), &v, sizeof(V));
+}
+// gvec<V>(p): p seen as an array of V (float4, float2, double2) in global memory, with the syntax of a V* -- q[i], *q, q + i -- and
+// the alignment of the element
+template <typename V, typename T>
+struct GVecRef {
+  T* p;
+  __device__ __forceinline__ operator V() const { return ldg<V>(p); }
+  __device__ __forceinline__ const GVecRef& operator=(const V& v) const {
+    stg(p, v);
+    return *this;
+  }
+};
+template <typename V, typename T>
+struct GVecPtr {
+  static constexpr int kPer = sizeof(V) / sizeof(T);
+  T* p;
+  __device__ __forceinline__ GVecRef<V, T> operator[](ptrdiff_t i) const { return {p + i * kPer}; }
+  __device__ __forceinline__ GVecRef<V, T> operator*() const { return {p}; }
+  __device__ __forceinline__ GVecPtr operator+(ptrdiff_t i) const { return {p + i * kPer}; }
+};
+template <typename V, typename T>
+__device__ __forceinline__ GVecPtr<V, T> gvec(T* p) { return {p}; }
 
 template <int PC, typename T>
 __device__ __forceinline__ typename VecOf<PC, T>::type pack_row(const T (&r)[PC]) {

@@ -70,6 +70,7 @@ inline const char* check(const pdegym_mlp& N, int n_in, int n_out, bool allow_wi
   for (int l = 0; l < N.n_layers; ++l) {
     const pdegym_mlp_layer& L = N.layer[l];
     if (!L.w) return "policy: null weight pointer";
+    if (!pdegym::is_aligned(L.w, 16)) return "policy: layer weights (w) must be 16-byte aligned";
     if (L.in_dim != (l ? N.layer[l - 1].out_dim : n_in)) return "policy: layer input size must match the observation row / the previous layer";
     if (L.out_dim < 1 || L.out_dim > (allow_wide ? kWideMax : kMaxWidth))
       return allow_wide ? "policy inside the rollout kernel: layers of 1..256 units" : "policy inside the rollout kernel: layers of 1..64 units";

@@ -23,7 +23,42 @@ static void expect_error(const char* what, int rc) {
   }
 }
 
+/* an alignment the header states at the parameter: code -2 (never the failed launch, -100) and the argument's name in the message */
+static void expect_misaligned(const char* what, int rc, const char* argument) {
+  const char* msg = pdegym_last_error();
+  if (rc != -2 || msg == NULL || strstr(msg, argument) != msg || strstr(msg, "16-byte aligned") == NULL) {
+    ++n_calls;
+    ++n_bad;
+    printf("UNEXPECTED %s -> %d \"%s\" (expected -2 naming %s)\n", what, rc, msg ? msg : "(null)", argument);
+    return;
+  }
+  expect_error(what, rc);
+}
+
+/* validation passed: the launch (-100), or raising a kernel's LDS limit in front of it (-4), failed for want of a device */
+static void expect_passed_validation(const char* what, int rc) {
+  if (rc != -100 && rc != -4) {
+    ++n_calls;
+    ++n_bad;
+    printf("UNEXPECTED %s -> %d \"%s\" (a well-formed call fails only at the launch)\n", what, rc, pdegym_last_error());
+    return;
+  }
+  expect_error(what, rc);
+}
+
+/* validation passed: only the launch failed, for want of a device */
+static void expect_launch(const char* what, int rc) {
+  if (rc != -100) {
+    ++n_calls;
+    ++n_bad;
+    printf("UNEXPECTED %s -> %d \"%s\" (a well-formed call fails only at the launch)\n", what, rc, pdegym_last_error());
+    return;
+  }
+  expect_error(what, rc);
+}
+
 #define FAKE(k) ((void*)(uintptr_t)(0x7f0000000000ull + 4096ull * (k)))
+#define OFF(p, bytes) ((void*)((char*)(uintptr_t)(p) + (bytes)))
 
 static pdegym_params1d good1d(void) {
   pdegym_params1d P;
@@ -214,6 +249,77 @@ int main(void) {
   expect_error("ns2d_step_f64 100x100 well-formed, no device", pdegym_ns2d_step_f64(&N2, &nb, 8, NULL));
   net.clamp = 0; net.layer[0].out_dim = 64;
   expect_error("mlp_forward well-formed, no device", pdegym_mlp_forward(&net, FAKE(50), 257, FAKE(51), 1, 4096, NULL));
+
+  /* ---- pointer alignment (Conventions: the element's own, unless the parameter says more) ---- */
+  /* blocked MLP weights: 16 bytes, every layer, refused before the launch */
+  for (int l = 0; l < 2; ++l)
+    for (int off = 4; off < 16; off += 4) {
+      pdegym_mlp m = net;
+      m.layer[l].w = OFF(net.layer[l].w, off);
+      expect_misaligned("mlp_forward blocked weights displaced", pdegym_mlp_forward(&m, FAKE(50), 257, FAKE(51), 1, 4096, NULL), "layer weights (w)");
+    }
+  { pdegym_mlp m = net;       /* everything else of the descriptor and the call: float-aligned is enough */
+    m.layer[0].b = OFF(net.layer[0].b, 4); m.layer[1].b = OFF(net.layer[1].b, 12); m.noise = OFF(FAKE(56), 4); m.noise_stride = 1;
+    expect_launch("mlp_forward x, y, b, noise displaced", pdegym_mlp_forward(&m, OFF(FAKE(50), 4), 257, OFF(FAKE(51), 8), 1, 4096, NULL)); }
+  /* the in-kernel policy of a rollout reads the same blocked weights */
+  { pdegym_rollout1d rp = ro;
+    pdegym_mlp m = net;
+    c = b; c.u = NULL;
+    m.layer[1].w = OFF(net.layer[1].w, 8);
+    rp.policy = &m;
+    const int rc = pdegym_parabolic_rollout(&P, &c, &rp, 64, NULL);
+    expect_error("parabolic_rollout policy weights displaced", rc);
+    if (rc != -2 || strstr(pdegym_last_error(), "layer weights (w) must be 16-byte aligned") == NULL) { ++n_bad; printf("UNEXPECTED code or message for displaced policy weights (1D rollout)\n"); } }
+  { pdegym_params_traffic tp;       /* the traffic rollout takes the same check: 2M = 102 inputs, one command */
+    pdegym_bufs_traffic t2;
+    pdegym_rollout_traffic r2;
+    pdegym_mlp m = net;
+    memset(&tp, 0, sizeof tp); memset(&t2, 0, sizeof t2); memset(&r2, 0, sizeof r2);
+    tp.M = 51; tp.control_freq = 2; tp.sim = PDEGYM_TRAFFIC_OUTLET; tp.dt = 0.25; tp.dx = 10; tp.T = 240; tp.vm = 40; tp.rm = 0.16; tp.tau = 60;
+    t2.r = FAKE(90); t2.y = FAKE(91); t2.time = FAKE(92); t2.rs = FAKE(93); t2.qs_clip = FAKE(94); t2.obs = FAKE(95); t2.reward = FAKE(96);
+    t2.done = FAKE(97); t2.truncated = FAKE(98); t2.action = FAKE(99); t2.action_stride = 1;
+    r2.T = 4; r2.obs = FAKE(100); r2.actions = FAKE(101); r2.rewards = FAKE(102); r2.done = FAKE(103); r2.truncated = FAKE(104);
+    m.layer[0].in_dim = 102;
+    r2.policy = &m;
+    expect_passed_validation("traffic_rollout with a policy, no device", pdegym_traffic_rollout(&tp, &t2, &r2, 8, NULL));
+    m.layer[0].w = OFF(net.layer[0].w, 12);
+    const int rc = pdegym_traffic_rollout(&tp, &t2, &r2, 8, NULL);
+    expect_error("traffic_rollout policy weights displaced", rc);
+    if (rc != -2 || strstr(pdegym_last_error(), "layer weights (w) must be 16-byte aligned") == NULL) { ++n_bad; printf("UNEXPECTED code or message for displaced policy weights (traffic rollout)\n"); } }
+  /* Navier-Stokes: every field needs only its element's alignment, on the register-tiled grids too (their row pieces are typed
+   * with it): a call with one field displaced passes the validation and fails only for want of a device */
+  {
+    const int f32_grids[] = {64, 128, 256}, f64_grids[] = {128, 256};
+    nb.state_in = NULL; nb.u = FAKE(69); nb.v = FAKE(72); nb.p_out = FAKE(73);
+    for (int prec = 0; prec < 2; ++prec)
+      for (int gi = 0; gi < (prec ? 2 : 3); ++gi)
+        for (int w = 0; w < 8; ++w) {
+          pdegym_bufs_ns2d d = nb;
+          const int off = prec ? 8 : 4 * (1 + w % 3);
+          if (w == 7) { d.state_in = FAKE(70); d.u = d.v = NULL; }
+          void** field[] = {&d.u, &d.v, &d.p, &d.p_out, &d.scratch, (void**)&d.U_ref, &d.obs, (void**)&d.state_in};
+          if (*field[w] == NULL) continue;
+          *field[w] = OFF(*field[w], off);
+          N2.nx = N2.ny = prec ? f64_grids[gi] : f32_grids[gi];
+          expect_passed_validation("ns2d_step tiled grid, one field displaced",
+                                   prec ? pdegym_ns2d_step_f64(&N2, &d, 2, NULL) : pdegym_ns2d_step_f32(&N2, &d, 2, NULL));
+        }
+    /* the [B] arrays of the same grids, and every field of the column / workgroup grids: element alignment */
+    { pdegym_bufs_ns2d d = nb;
+      d.action = OFF(nb.action, 4); d.reward = OFF(nb.reward, 4); d.time_index = OFF(nb.time_index, 4); d.terminated = OFF(nb.terminated, 1);
+      d.action_ref = OFF(nb.action_ref, 4);
+      N2.nx = N2.ny = 64;
+      expect_launch("ns2d_step_f32 64x64, [B] arrays displaced", pdegym_ns2d_step_f32(&N2, &d, 2, NULL));
+      d = nb;
+      d.u = OFF(nb.u, 8); d.v = OFF(nb.v, 8); d.p = OFF(nb.p, 8); d.p_out = OFF(nb.p_out, 8); d.scratch = OFF(nb.scratch, 8);
+      d.U_ref = OFF(nb.U_ref, 8); d.obs = OFF(nb.obs, 8);
+      N2.nx = N2.ny = 21;
+      expect_launch("ns2d_step_f64 21x21, every field displaced", pdegym_ns2d_step_f64(&N2, &d, 3072, NULL));
+      N2.nx = 24; N2.ny = 20;
+      expect_launch("ns2d_step_f64 20x24, every field displaced", pdegym_ns2d_step_f64(&N2, &d, 8, NULL));
+      N2.nx = N2.ny = 64;                      /* float64 has no 64 x 64 tile: the workgroup kernel, element alignment */
+      expect_launch("ns2d_step_f64 64x64, every field displaced", pdegym_ns2d_step_f64(&N2, &d, 8, NULL)); }
+  }
 
   printf("%s %d calls, %d unexpected\n", n_bad ? "VALIDATION-FAILED" : "VALIDATION-OK", n_calls, n_bad);
   return n_bad ? 1 : 0;

@@ -30,6 +30,29 @@ static void expect_ok(const char* what, int rc) {
   }
 }
 
+/* an alignment the header states at the parameter: code -2 (never the failed launch, -100) and the argument's name in the message */
+static void expect_misaligned(const char* what, int rc, const char* argument) {
+  const char* msg = pdegym_last_error();
+  if (rc != -2 || msg == NULL || strstr(msg, argument) == NULL || strstr(msg, "aligned") == NULL) {
+    ++n_calls;
+    ++n_bad;
+    printf("UNEXPECTED %s -> %d \"%s\" (expected -2 naming %s)\n", what, rc, msg ? msg : "(null)", argument);
+    return;
+  }
+  expect_error(what, rc);
+}
+
+/* a well-formed call fails only at the launch, for want of a device */
+static void expect_launch(const char* what, int rc) {
+  if (rc != -100) {
+    ++n_calls;
+    ++n_bad;
+    printf("UNEXPECTED %s -> %d \"%s\" (a well-formed call fails only at the launch)\n", what, rc, pdegym_last_error());
+    return;
+  }
+  expect_error(what, rc);
+}
+
 #define FAKE(k) ((void*)(uintptr_t)(0x7f0000000000ull + 4096ull * (k)))
 
 static pdegym_params_ns2d good_prm(int ny, int nx) {
@@ -86,6 +109,15 @@ int main(void) {
         expect_error("adjoint other boundary table", pdegym_ns2d_adjoint_f64(&p, uref, 7, &a, 4, NULL));
       }
   p = good_prm(21, 21); p.bc[0][0] = 3; expect_error("adjoint bad bc code", pdegym_ns2d_adjoint_f64(&p, uref, 7, &a, 4, NULL));
+
+  /* U_ref, obs and lam are moved as (u, v) pairs of 16 bytes: a pointer that is only double-aligned is refused with -2 and its
+   * name, before any launch (a call that reaches the launch answers -100 here); the [T] / [T, B] arrays need 8 bytes only */
+  p = good_prm(21, 21);
+  a = good_adj(); expect_misaligned("adjoint U_ref + 8", pdegym_ns2d_adjoint_f64(&p, (const char*)uref + 8, 7, &a, 4, NULL), "U_ref");
+  a = good_adj(); a.obs += 1; expect_misaligned("adjoint obs + 8", pdegym_ns2d_adjoint_f64(&p, uref, 7, &a, 4, NULL), "obs");
+  a = good_adj(); a.lam = (double*)FAKE(5) + 1; expect_misaligned("adjoint lam + 8", pdegym_ns2d_adjoint_f64(&p, uref, 7, &a, 4, NULL), "lam");
+  a = good_adj(); a.a_nom += 1; a.grad += 1; a.actions += 1;
+  expect_launch("adjoint a_nom, grad, actions + 8", pdegym_ns2d_adjoint_f64(&p, uref, 7, &a, 4, NULL));
 
   p = good_prm(21, 21); a = good_adj();
   expect_ok("adjoint B=0", pdegym_ns2d_adjoint_f64(&p, uref, 7, &a, 0, NULL));

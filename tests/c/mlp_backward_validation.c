@@ -43,6 +43,18 @@ static void expect_launch(const char* what, int rc) {
   expect_error(what, rc);
 }
 
+/* an alignment the header states at the parameter: code -2 (never the failed launch) and the argument's name in the message */
+static void expect_misaligned(const char* what, int64_t rc, const char* argument) {
+  const char* msg = pdegym_last_error();
+  if (rc != -2 || msg == NULL || strstr(msg, argument) == NULL || strstr(msg, "aligned") == NULL) {
+    ++n_calls;
+    ++n_bad;
+    printf("UNEXPECTED %s -> %lld \"%s\" (expected -2 naming %s)\n", what, (long long)rc, msg ? msg : "(null)", argument);
+    return;
+  }
+  expect_error(what, rc);
+}
+
 /* 64 MiB apart: no two arrays of the cases below overlap unless a case makes them */
 #define FAKE(k) ((void*)(uintptr_t)(0x7f0000000000ull + 0x4000000ull * (k)))
 #define B_ 49
@@ -151,6 +163,22 @@ int main(void) {
   a = args_good(&n); a.workspace = (char*)a.dx + 4 * ((size_t)(B_ - 1) * K_ + K_ - 1); expect_refused("workspace on dx's last float", pdegym_mlp_backward(&n, &a, B_, NULL));
   n = net_good(); n.x_f64 = 1; a = args_good(&n); a.dx = NULL; a.dw[0] = (float*)a.x + ((size_t)(B_ - 1) * XS_ + K_);      /* past the float32 extent */
   expect_refused("dw[0] inside float64 x", pdegym_mlp_backward(&n, &a, B_, NULL));
+
+  /* the two alignment requirements the header states: refused with -2 and the argument's name, before any launch (a call that reaches
+   * the launch answers -100 here).  Every other pointer needs only its element's alignment: the launches below include such ones. */
+  for (int l = 0; l < 3; ++l)
+    for (int off = 4; off < 16; off += 4) {
+      n = net_good(); n.layer[l].w = (const float*)((const char*)n.layer[l].w + off); a = args_good(&n);
+      expect_misaligned("blocked weights off a 16-byte boundary", pdegym_mlp_backward(&n, &a, B_, NULL), "(w)");
+      expect_misaligned("workspace query, blocked weights displaced", pdegym_mlp_backward_workspace(&n, B_, 2), "(w)");
+    }
+  n = net_good();
+  for (int off = 1; off < 4; ++off) {
+    a = args_good(&n); a.workspace = (char*)a.workspace + off;
+    expect_misaligned("workspace off a 4-byte boundary", pdegym_mlp_backward(&n, &a, B_, NULL), "workspace");
+  }
+  a = args_good(&n); a.workspace = (char*)a.workspace + 4; a.x = (const char*)a.x + 4; a.dy += 1; a.dx += 3; a.w[1] += 1; a.dw[0] += 1; a.dw[2] += 3; a.db[1] += 1;
+  expect_launch("launch (every element-aligned pointer displaced)", pdegym_mlp_backward(&n, &a, B_, NULL));
 
   /* well-formed calls: the host side runs up to the launch; without a device that launch fails with a message */
   n = net_good();

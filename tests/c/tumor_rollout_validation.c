@@ -136,6 +136,18 @@ int main(void) {
   c = good(201); with_policy(&c, 64); c.net.layer[0].in_dim = 200; expect_refused("policy: 200 inputs on rows of 201", ROLL(c));
   c = good(201); with_policy(&c, 64); c.net.layer[2].out_dim = 2; expect_refused("policy: two outputs", ROLL(c));
   c = good(201); with_policy(&c, 64); c.net.layer[1].w = NULL; expect_refused("policy: NULL weights", ROLL(c));
+  /* the blocked weights are 16-byte aligned by the header, in the narrow (64) and the cooperative (256) evaluation alike: -2 and the
+   * argument's name before the launch; the float64 arrays of the call need 8 bytes only */
+  for (int hidden = 64; hidden <= 256; hidden += 192)
+    for (int off = 4; off < 16; off += 4) {
+      c = good(201); with_policy(&c, hidden); c.net.layer[2].w = (const float*)((const char*)c.net.layer[2].w + off);
+      const int rc = ROLL(c);
+      expect_refused("policy: blocked weights off a 16-byte boundary", rc);
+      if (rc != -2 || strstr(pdegym_last_error(), "layer weights (w) must be 16-byte aligned") == NULL) { ++n_bad; printf("UNEXPECTED code or message for displaced policy weights\n"); }
+    }
+  c = good(201); with_policy(&c, 64); c.b.u += 1; c.r.obs += 1; c.r.actions += 1; c.r.rewards += 1; c.w.final_obs += 1;
+  c.r.terminated += 1; c.r.truncated += 3; c.net.noise += 1; c.net.layer[0].b += 1;
+  expect_launch("rollout with a 64-64 policy, every element-aligned pointer displaced", ROLL(c));
   c = good(201); with_policy(&c, 257); expect_refused("policy: 257 units", ROLL(c));
   c = good(201); with_policy(&c, 64); c.net.n_layers = 5; expect_refused("policy: 5 layers", ROLL(c));
   c = good(201); with_policy(&c, 64); c.net.lo = 2.f; expect_refused("policy: lo>hi", ROLL(c));

@@ -6,6 +6,13 @@ before write or a store past the end of a buffer can go unseen.  This module giv
 - ``guarded(shape, dtype, device)`` allocates ``[guard | payload | guard]`` in ONE allocation.  Each guard is at least 4 KiB of a
   fixed byte pattern and the payload starts 256-byte aligned (the alignment a fresh torch tensor has, so the kernels take the same
   vector-store paths).  ``check_guards()`` names the buffer and the first changed byte, counted from the payload's start or end.
+- ``shift`` (a multiple of the element size, default 0) DISPLACES the payload: it starts ``shift`` bytes past a 256-byte boundary,
+  the pointer a C caller gets who carves arrays out of one pool, or slot t of a rollout buffer whose rows are an odd number of
+  elements.  ``Arena(device, policy=...)`` derives every buffer's shift: ``"one"`` = one element of the buffer's own dtype,
+  ``"mixed"`` = a residue that is a function of the buffer's NAME (float32 / int32 1..3 elements, float64 / int64 one element, uint8
+  1..15 elements), so that the inputs and outputs of one launch are aligned differently from each other -- a kernel that peels to
+  align its loads and reuses the peel for its stores shows up.  ``keep_aligned`` names the buffers whose documented contract demands
+  an alignment (include/pdegym.h says so at the parameter): they stay at shift 0 (tests/test_gpu_pointer_alignment.py).
 - ``poison_(t)`` fills a float or flag tensor with a recognisable pattern: the NaN 0x7FC0DEAD (float32), the NaN 0x7FF8DEADDEADBEEF
   (float64), 0xA5 (uint8).  The kernels produce canonical NaNs, so "still holds the poison bits" is an exact test.  Integer buffers
   that a kernel indexes with are never filled with arbitrary bits (a faulty reset would turn that into a wild access): poison them with
@@ -15,6 +22,8 @@ before write or a store past the end of a buffer can go unseen.  This module giv
 Plain helper module (not a conftest): imported by the tests that need it.
 """
 from __future__ import annotations
+
+import zlib
 
 import torch
 
@@ -101,28 +110,32 @@ def assert_bits_equal(a: torch.Tensor, b: torch.Tensor, where=None, name: str = 
 class Guarded:
     """One ``[guard | payload | guard]`` allocation; ``t`` is the contiguous payload."""
 
-    def __init__(self, name: str, shape, dtype, device, pinned: bool = False):
+    def __init__(self, name: str, shape, dtype, device, pinned: bool = False, shift: int = 0):
         shape = tuple(int(s) for s in shape)
         item = torch.empty((), dtype=dtype).element_size()
         numel = 1
         for s in shape:
             numel *= s
-        self.name, self.nbytes = name, numel * item
-        # the tail guard starts right at the payload's end (a one-element overrun lands in it) and runs to the next 256-byte boundary
-        # past another GUARD_BYTES
-        tail = GUARD_BYTES + (-self.nbytes) % ALIGN
-        total = GUARD_BYTES + self.nbytes + tail
+        shift = int(shift)
+        if not 0 <= shift < ALIGN or shift % item:
+            raise ValueError(f"shift {shift} of '{name}' is not a multiple of the element size {item} below {ALIGN}")
+        self.name, self.nbytes, self.shift = name, numel * item, shift
+        # the head guard is GUARD_BYTES + shift: the payload starts `shift` bytes past a 256-byte boundary.  The tail guard starts
+        # right at the payload's end (a one-element overrun lands in it) and runs to the next 256-byte boundary past another GUARD_BYTES
+        head = GUARD_BYTES + shift
+        tail = GUARD_BYTES + (-(shift + self.nbytes)) % ALIGN
+        total = head + self.nbytes + tail
         if pinned:
             base = torch.empty(total + ALIGN, dtype=torch.uint8, pin_memory=True)
         else:
             base = torch.empty(total + ALIGN, dtype=torch.uint8, device=device)
-        shift = (-base.data_ptr()) % ALIGN              # (the HIP allocator's blocks are aligned already; host memory may not be)
-        self.raw = base[shift:shift + total]
+        skip = (-base.data_ptr()) % ALIGN               # (the HIP allocator's blocks are aligned already; host memory may not be)
+        self.raw = base[skip:skip + total]
         self.raw.fill_(GUARD_BYTE)
-        self.t = self.raw[GUARD_BYTES:GUARD_BYTES + self.nbytes].view(dtype).view(shape)
+        self.t = self.raw[head:head + self.nbytes].view(dtype).view(shape)
         self.t.zero_()
-        self._head = self.raw[:GUARD_BYTES]
-        self._tail = self.raw[GUARD_BYTES + self.nbytes:]
+        self._head = self.raw[:head]
+        self._tail = self.raw[head + self.nbytes:]
 
     def check_guards(self):
         """Raise AssertionError naming the first changed guard byte: its distance before the payload, or after its end."""
@@ -131,7 +144,7 @@ class Guarded:
             if bool(bad.any()):
                 idx = torch.nonzero(bad)
                 if before:
-                    off = GUARD_BYTES - int(idx[-1].item())        # the changed byte closest to the payload
+                    off = part.numel() - int(idx[-1].item())       # the changed byte closest to the payload
                     raise AssertionError(f"guard of '{self.name}' changed {off} byte(s) BEFORE the payload "
                                          f"({int(bad.sum())} byte(s) in all)")
                 off = int(idx[0].item())
@@ -139,20 +152,45 @@ class Guarded:
                                      f"({self.nbytes} bytes; {int(bad.sum())} byte(s) in all)")
 
 
-def guarded(shape, dtype, device, pinned: bool = False, name: str = "buffer"):
+def guarded(shape, dtype, device, pinned: bool = False, name: str = "buffer", shift: int = 0):
     """Allocate a guarded buffer: returns (payload tensor, check_guards).  The payload starts zero-filled."""
-    g = Guarded(name, shape, dtype, device, pinned)
+    g = Guarded(name, shape, dtype, device, pinned, shift)
     return g.t, g.check_guards
+
+
+POLICIES = (None, "one", "mixed")
+
+
+def policy_shift(policy, name: str, dtype) -> int:
+    """Bytes past a 256-byte boundary at which the payload of buffer ``name`` starts under ``policy`` (see the module docstring)."""
+    if policy is None:
+        return 0
+    item = torch.empty((), dtype=dtype).element_size()
+    if policy == "one":
+        return item
+    if policy == "mixed":
+        h = zlib.crc32(name.encode())                   # deterministic: the same name gets the same residue in every process
+        if item == 1:
+            return 1 + h % 15
+        if item == 4:
+            return 4 * (1 + h % 3)
+        return item                                     # 8-byte elements: the one residue mod 16 that is not aligned
+    raise ValueError(f"unknown displacement policy {policy!r}: one of {POLICIES}")
 
 
 class Arena:
     """Named guarded buffers of one test case: ``a.new(name, shape, dtype)`` returns the payload; ``a.check()`` checks every guard."""
 
-    def __init__(self, device, pinned: bool = False):
+    def __init__(self, device, pinned: bool = False, policy: str | None = None, keep_aligned=()):
+        policy_shift(policy, "", torch.uint8)           # (refuses an unknown policy here, not at the first buffer)
         self.device, self.pinned, self.bufs = device, pinned, {}
+        self.policy, self.keep_aligned = policy, frozenset(keep_aligned)
+
+    def shift_of(self, name: str, dtype) -> int:
+        return 0 if name in self.keep_aligned else policy_shift(self.policy, name, dtype)
 
     def new(self, name: str, shape, dtype, pinned: bool | None = None):
-        g = Guarded(name, shape, dtype, self.device, self.pinned if pinned is None else pinned)
+        g = Guarded(name, shape, dtype, self.device, self.pinned if pinned is None else pinned, self.shift_of(name, dtype))
         self.bufs[name] = g
         return g.t
 

@@ -139,10 +139,11 @@ def test_time_offset_and_target_clamp_follow_the_restatement(fixture):
     _same(actions[..., 0], wa, "actions")
 
 
-def _poisoned_call(g, c, with_lam):
+def _poisoned_call(g, c, with_lam, policy=None):
+    """``policy`` displaces a_nom, grad and actions (tests/poison.py); obs, U_ref and lam keep the 16 bytes the header demands."""
     B, T, ny, nx = _batch(c), c["T"], c["n"], c.get("nx", c["n"])
     core = _engine(c, B, g["U_ref"])
-    arena = poison.Arena("cuda")
+    arena = poison.Arena("cuda", policy=policy, keep_aligned=("obs", "U_ref", "lam"))
     src_obs = _rollout_of(g, B)
     obs = arena.like("obs", src_obs)
     uref = arena.like("U_ref", core.t["U_ref"])
@@ -160,9 +161,9 @@ def _poisoned_call(g, c, with_lam):
 
 
 @pytest.mark.parametrize("name", ["n21_K2_T6", "n8_K3_T1", "restatement_only/r8x64_K3_T3"])
-def test_outputs_are_fully_written_and_inputs_left_alone(fixture, name):
+def test_outputs_are_fully_written_and_inputs_left_alone(fixture, name, policy=None):
     g, c = fixture[name], R.case_of(name)
-    grad, actions, lam = _poisoned_call(g, c, with_lam=True)
+    grad, actions, lam = _poisoned_call(g, c, with_lam=True, policy=policy)
     poison.assert_written(grad, name="grad")
     poison.assert_written(actions, name="actions")
     poison.assert_written(lam, name="lam")
@@ -171,10 +172,10 @@ def test_outputs_are_fully_written_and_inputs_left_alone(fixture, name):
     assert not bool(lam[-1].any()) and not bool(grad[-1].any())          # time index T-1: the zero field
 
 
-def test_lam_is_optional(fixture):
+def test_lam_is_optional(fixture, policy=None):
     name = "n21_K2_T6"
     g, c = fixture[name], R.CASES[name]
-    grad, actions, lam = _poisoned_call(g, c, with_lam=False)
+    grad, actions, lam = _poisoned_call(g, c, with_lam=False, policy=policy)
     assert lam is None
     poison.assert_written(grad, name="grad")
     poison.assert_written(actions, name="actions")

@@ -205,9 +205,10 @@ def test_noise_and_clamp_inside_the_launch(kind, n, order, use_graph):
 
 # ---- (d) the output contract on poisoned buffers ------------------------------------------------------------------------------------
 @pytest.mark.parametrize("kind,n,order", [("transport", 100, "ordered"), ("parabolic", 101, "tree"), ("parabolic", 513, "ordered")])
-def test_rollout_writes_exactly_its_outputs(kind, n, order):
+def test_rollout_writes_exactly_its_outputs(kind, n, order, policy=None):
     """Every element the header says is written is written -- obs slots 1 .. T, actions, rewards, flags, obs_seen -- whatever the
-    buffers held before (NaN poison, wrong flags); gains, pools, noise and reset pools keep their bits; every guard band is intact."""
+    buffers held before (NaN poison, wrong flags); gains, pools, noise and reset pools keep their bits; every guard band is intact.
+    ``policy`` displaces every guarded buffer of the poisoned run off its 256-byte boundary (tests/poison.py)."""
     build = _pool_build(kind, order) if n <= 101 else _shape_build(kind, n, None, order)
     T = POOL_T if n <= 101 else SHAPE_T
     rng = np.random.default_rng(5)
@@ -215,7 +216,7 @@ def test_rollout_writes_exactly_its_outputs(kind, n, order):
     def run(poisoned):
         venv, ctrl = build()
         core, B = venv.core, venv.num_envs
-        arena = poison.Arena("cuda")
+        arena = poison.Arena("cuda", policy=policy if poisoned else None)
         ctrl.gain, ctrl.pool_gain = arena.like("gain", ctrl.gain), arena.like("pool_gain", ctrl.pool_gain)
         for k in ("reset_init", "reset_beta", "beta", "time_index", "bsum", "ring", "reset_count", "norm_now", "norm_back"):
             core.t[k] = arena.like(k, core.t[k])

@@ -82,10 +82,11 @@ def test_gain_kernels_equal_the_restatement_bitwise(kind, m):
 
 @pytest.mark.parametrize("m,R", [(2, 1), (65, 3), (129, 70), (513, 5)])
 @pytest.mark.parametrize("kind", ["transport", "parabolic"])
-def test_gain_kernels_write_exactly_their_rows(kind, m, R):
-    """Poisoned output with guard bands: every element of [R, m] is written, nothing outside it; theta is left alone."""
+def test_gain_kernels_write_exactly_their_rows(kind, m, R, policy=None):
+    """Poisoned output with guard bands: every element of [R, m] is written, nothing outside it; theta is left alone.
+    ``policy`` displaces every guarded buffer off its 256-byte boundary (tests/poison.py; tests/test_gpu_pointer_alignment.py)."""
     dx = 5e-3
-    arena = poison.Arena("cuda")
+    arena = poison.Arena("cuda", policy=policy)
     th = arena.like("theta", _dev(_theta(kind, m, dx)[:R], torch.float32))
     out = poison.poison_(arena.new("gain", (R + 2, m), torch.float64))
     _backend().backstep_gain(kind, th, out[1:R + 1], dx)
@@ -171,9 +172,9 @@ def test_float_output_is_the_double_rounded_once_plus_noise_then_clamp(ordered):
     np.testing.assert_array_equal(_control(o, g, m, 1e-2, ordered, torch.float32, noise=_dev(nz)), a64.astype(f32) + nz)
 
 
-def test_control_writes_exactly_its_outputs_and_follows_the_pool_rule():
+def test_control_writes_exactly_its_outputs_and_follows_the_pool_rule(policy=None):
     """Poisoned outputs with guard bands, B = 6 instances inside buffers of 8; gain rows by the documented pool rule for restart
-    counters 0 .. 5 with P = 7 pool rows."""
+    counters 0 .. 5 with P = 7 pool rows.  ``policy`` displaces every guarded buffer off its 256-byte boundary (tests/poison.py; tests/test_gpu_pointer_alignment.py)."""
     rng = np.random.default_rng(11)
     B, P, m = 6, 7, 65
     gain0, pool = rng.normal(0, 3, (B, m)), rng.normal(0, 3, (P, m))
@@ -183,7 +184,7 @@ def test_control_writes_exactly_its_outputs_and_follows_the_pool_rule():
     picked = np.stack([gain0[b] if rows[b] is None else pool[rows[b]] for b in range(B)])
     want = _law_rows(picked, obs, m, 1e-2)
     assert not np.array_equal(want, _law_rows(np.stack([gain0[0]] + [pool[b] for b in range(1, B)]), obs, m, 1e-2))
-    arena = poison.Arena("cuda")
+    arena = poison.Arena("cuda", policy=policy)
     o, g, gp, rc = (arena.like(k, _dev(v)) for k, v in (("obs", obs), ("gain0", gain0), ("pool", pool), ("count", counts)))
     for dtype, ref in ((torch.float64, want), (torch.float32, want.astype(f32))):
         out = poison.poison_(arena.new(f"out{dtype}", (B + 2,), dtype))

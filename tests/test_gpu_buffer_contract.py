@@ -69,6 +69,15 @@ def _f32(a):
     return torch.tensor(np.asarray(a, dtype=np.float32))
 
 
+def _arena(policy=None, keep_aligned=()):
+    """The arena of a case.  ``policy`` (None, "one", "mixed": tests/poison.py) displaces every buffer off its 256-byte boundary --
+    tests/test_gpu_pointer_alignment.py runs the cases of this module that way; ``keep_aligned`` names the buffers whose parameter in
+    include/pdegym.h demands an alignment."""
+    return PZ.Arena("cuda", policy=policy, keep_aligned=keep_aligned)
+
+
+
+
 def guard_engine(env, arena, skip=()):
     """Swap every tensor of ``env.t`` (and the observation pair ``env._obs``) for a guarded copy; aliases stay aliases."""
     seen = {}
@@ -136,7 +145,7 @@ def _init_beta(B, n, seed, f64_beta=False):
 OUT1D = ("obs", "reward", "norm_now", "norm_back", "terminated", "truncated")
 
 
-def _run_1d_pair(kind, n, B, mode, S=3, steps=3, nt=None, seed=0, action_kind=None, f64_beta=False, flux=None):
+def _run_1d_pair(kind, n, B, mode, S=3, steps=3, nt=None, seed=0, action_kind=None, f64_beta=False, flux=None, policy=None):
     """Clean engine + guarded, poisoned engine over the same sequence; returns (clean, poisoned, arena, oracle results)."""
     from oracle import pde_oracle as po
     from pdecontrolgym_amd import _native as N
@@ -147,11 +156,12 @@ def _run_1d_pair(kind, n, B, mode, S=3, steps=3, nt=None, seed=0, action_kind=No
     spec, orw = _reward(mode, nt)
     extra = {"flux": flux} if flux else {}
     clean, pois = _mk1d(kind, kw, spec, B, hist, **extra), _mk1d(kind, kw, spec, B, hist, **extra)
-    arena = PZ.Arena("cuda")
+    arena = _arena(policy)
     guard_engine(pois, arena)
     init, beta = _init_beta(B, n, seed, f64_beta)
     clean.reset(init, beta)
     pois.reset(init, beta)
+    pois.t["beta"] = arena.like("beta", pois.t["beta"])      # (reset installs its own beta tensor: guard the one the steps read)
     for k in OUT1D:                                # pure outputs: poisoned before every call
         if pois.t[k] is not None:
             PZ.poison_(pois.t[k])
@@ -176,7 +186,7 @@ def _run_1d_pair(kind, n, B, mode, S=3, steps=3, nt=None, seed=0, action_kind=No
             for k in OUT1D:
                 PZ.poison_(pois.t[k] if k != "obs" else pois._obs[pois._flip ^ 1])
         oc, rc, tec, trc = clean.step(at, action_kind=ak)
-        op, rp, tep, trp = pois.step(at, action_kind=ak)
+        op, rp, tep, trp = pois.step(arena.like(f"action{s}", at.cuda()), action_kind=ak)      # (a [B] device tensor is read in place)
         o_ref, r_ref, te_ref, tr_ref = orc.step(a, {N.ACTION_F32: "f32", N.ACTION_F64: "f64", N.ACTION_WEAK: "weak"}[ak])
         torch.cuda.synchronize()
         arena.check()
@@ -247,7 +257,7 @@ def test_1d_wide_kernels(n):
 
 @pytest.mark.parametrize("kind,n,hist", [("transport", 166, False), ("parabolic", 487, True), ("transport", 2049, False),
                                          ("parabolic", 38, False)])
-def test_1d_shared_beta_row_is_not_over_read(kind, n, hist):
+def test_1d_shared_beta_row_is_not_over_read(kind, n, hist, policy=None):
     """beta_stride = 0 (one beta row for every instance) with NaN right after the row: results equal the clean run and stay finite."""
     B, S, nt = 5, 3, 12
     kw = _kw1d(kind, n, S, nt)
@@ -257,7 +267,7 @@ def test_1d_shared_beta_row_is_not_over_read(kind, n, hist):
     for e in (clean, pois):
         e.reset(init, beta[0])                        # a [n] beta: the shared row
     assert clean.t["beta"].dim() == 1
-    arena = PZ.Arena("cuda")
+    arena = _arena(policy)
     guard_engine(pois, arena)
     shared = arena.new("beta_shared_nan_tail", (2, n), torch.float32)
     shared[0].copy_(_f32(beta[0]))
@@ -288,7 +298,7 @@ def test_1d_reward_none_leaves_reward_alone():
     _run_1d_pair("parabolic", 257, 1, "none_reward")
 
 
-def test_1d_state_in_leaves_u_alone():
+def test_1d_state_in_leaves_u_alone(policy=None):
     """state_in mode (the engine default for full-state sensing): the rows come from the previous observation; u is not touched."""
     import ctypes as C
     from pdecontrolgym_amd import _native as N
@@ -301,7 +311,7 @@ def test_1d_state_in_leaves_u_alone():
     init, beta = _init_beta(B, n, 3)
     for e in (clean, pois):
         e.reset(init, beta)
-    arena = PZ.Arena("cuda")
+    arena = _arena(policy)
     guard_engine(pois, arena)
     u_alone = arena.new("u_alone", (B, n), torch.float32)
     PZ.poison_(u_alone)
@@ -328,7 +338,7 @@ def test_1d_state_in_leaves_u_alone():
             PZ.assert_written(pois.t[k], None, f"state_in: {k}", like=clean.t[k])
 
 
-def test_1d_auto_reset_final_obs_and_pools():
+def test_1d_auto_reset_final_obs_and_pools(policy=None):
     """Fused auto-reset with pool rows != B and reset_beta: final_obs rows only for the instances that finished (NaN elsewhere),
     pools read only within their rows (NaN right after the last pool row), results equal to the clean run."""
     B, n, S, nt = 5, 130, 4, 10
@@ -338,7 +348,7 @@ def test_1d_auto_reset_final_obs_and_pools():
     init, beta = _init_beta(B, n, 5)
     P = 7
     pool, bpool = _init_beta(P, n, 6)
-    arena = PZ.Arena("cuda")
+    arena = _arena(policy)
     for e in (clean, pois):
         e.reset(init, beta)
     clean.enable_auto_reset(_f32(pool), beta_pool=_f32(bpool))
@@ -360,7 +370,7 @@ def test_1d_auto_reset_final_obs_and_pools():
         PZ.poison_(pois.t["final_obs"])
         clean.t["final_obs"].zero_()
         oc, rc, tec, trc = clean.step(a)
-        op, rp, tep, trp = pois.step(a)
+        op, rp, tep, trp = pois.step(arena.like(f"action{s}", a.cuda()))
         arena.check()
         fin = (tec | trc).bool().cpu()
         fin_seen += int(fin.sum())
@@ -373,21 +383,24 @@ def test_1d_auto_reset_final_obs_and_pools():
     assert fin_seen >= 2 * B
 
 
-def test_1d_masked_reset_leaves_others_alone():
+def test_1d_masked_reset_leaves_others_alone(policy=None):
     """pdegym_reset1d_masked: unmasked instances keep the poison in every output the reset writes (history included)."""
     B, n, nt = 5, 101, 9
     kw = _kw1d("parabolic", n, 2, nt)
     spec, _ = _reward("none", nt)
     env = _mk1d("parabolic", kw, spec, B, True)
-    arena = PZ.Arena("cuda")
+    arena = _arena(policy)
     guard_engine(env, arena)
     init, beta = _init_beta(B, n, 8)
     env.set_beta(beta)
-    mask = torch.tensor([1, 0, 1, 0, 0], dtype=torch.uint8, device="cuda")
+    mask = arena.like("mask", torch.tensor([1, 0, 1, 0, 0], dtype=torch.uint8, device="cuda"))
+    init_t = arena.like("init", _f32(init).cuda())
+    if policy is not None:
+        assert mask.data_ptr() % 16 != 0 and init_t.data_ptr() % 16 != 0
     for k in ("u", "bsum", "ring", "obs", "history"):
         PZ.poison_(env.t[k])
     PZ.fill_int_(env.t["time_index"], nt // 2)
-    env.backend.reset1d(env.params, env.t, _f32(init).cuda(), mask, B)
+    env.backend.reset1d(env.params, env.t, init_t, mask, B)
     arena.check()
     on, off = mask.bool(), ~mask.bool()
     for k in ("u", "bsum", "obs", "history"):
@@ -404,7 +417,7 @@ def test_1d_masked_reset_leaves_others_alone():
 
 
 @pytest.mark.parametrize("kind", ["transport", "parabolic"])
-def test_1d_reset_initialises_poisoned_state(kind):
+def test_1d_reset_initialises_poisoned_state(kind, policy=None):
     """reset(mask=None) over NaN state (ring, bsum, u, obs) and in-range wrong integers, then a whole episode past the look-back:
     every output equals the clean run (ring slots 1..127 and look-back rows are read here) and the oracle."""
     from oracle import pde_oracle as po
@@ -413,7 +426,7 @@ def test_1d_reset_initialises_poisoned_state(kind):
     kw = _kw1d(kind, n, S, nt)
     spec, orw = _reward("none", nt)
     clean, pois = _mk1d(kind, kw, spec, B, False), _mk1d(kind, kw, spec, B, False)
-    arena = PZ.Arena("cuda")
+    arena = _arena(policy)
     guard_engine(pois, arena)
     for k in ("u", "bsum", "ring", "obs", "norm_now", "norm_back", "reward", "terminated", "truncated"):
         PZ.poison_(pois.t[k])
@@ -439,15 +452,18 @@ def test_1d_reset_initialises_poisoned_state(kind):
         np.testing.assert_allclose(rc.cpu().numpy(), r_ref, rtol=1e-6, atol=2e-6 * max(1.0, nrm))
 
 
-def test_1d_rollout_contract():
+ROLLOUT_1D_CASES = [("parabolic", 257, "Dirchilet", "full"), ("transport", 229, "Dirchilet", "full"), ("parabolic", 101, "Neumann", "full"),
+                    ("transport", 150, "Dirchilet", "collocated")]
+
+
+def test_1d_rollout_contract(policy=None, cases=ROLLOUT_1D_CASES, lengths=(1, 7), widths=(32, 128)):
     """pdegym_*_rollout: FULL, plain and general (Neumann, scalar sensing) forms, with and without an in-kernel policy, T in {1, 7}:
-    every written slot equals T step calls; obs[0] is left alone; obs_seen receives obs + obs_noise."""
+    every written slot equals T step calls; obs[0] is left alone; obs_seen receives obs + obs_noise.  ``lengths``: the T of each
+    rollout; ``widths``: the policy's hidden units at the first T (one fma chain per neuron up to 64) and at every other one."""
     from pdecontrolgym_amd.batch1d import PDEBatch1D
     from pdecontrolgym_amd.policy import FusedMLP
-    cases = [("parabolic", 257, "Dirchilet", "full"), ("transport", 229, "Dirchilet", "full"), ("parabolic", 101, "Neumann", "full"),
-             ("transport", 150, "Dirchilet", "collocated")]
     for (kind, n, ctl, sens) in cases:
-        for Tn in (1, 7):
+        for Tn in lengths:
             for use_policy in (False, True):
                 B, S, nt = 5, 3, 30
                 kw = _kw1d(kind, n, S, nt, ctl, sens)
@@ -457,7 +473,7 @@ def test_1d_rollout_contract():
                 init, beta = _init_beta(B, n, 11)
                 for e in (ref, env):
                     e.reset(init, beta)
-                arena = PZ.Arena("cuda")
+                arena = _arena(policy)
                 guard_engine(env, arena)
                 od = env.obs_dim
                 obs = arena.new("ro_obs", (Tn + 1, B, od), torch.float32)
@@ -472,7 +488,7 @@ def test_1d_rollout_contract():
                 pol, kwp = None, {}
                 if use_policy:
                     torch.manual_seed(0)
-                    width = 32 if Tn == 1 else 128          # one fma chain per neuron / the cooperative MFMA form
+                    width = widths[0] if Tn == lengths[0] else widths[1]          # one fma chain per neuron / the cooperative MFMA form
                     mod = torch.nn.Sequential(torch.nn.Linear(od, width), torch.nn.Tanh(), torch.nn.Linear(width, 1)).cuda()
                     pol = FusedMLP(mod, clamp=(-1.0, 1.0))
                     PZ.poison_(acts)
@@ -590,11 +606,11 @@ def test_ns_host_io_prepared_call_follows_replaced_tensors():
     both("load_state_dict", 2.2)
 
 
-def test_rownorm2_ragged():
+def test_rownorm2_ragged(policy=None):
     from pdecontrolgym_amd.backend import default_backend
     be = default_backend()
     for B, n in ((1, 1), (5, 63), (7, 65), (3, 2049)):
-        arena = PZ.Arena("cuda")
+        arena = _arena(policy)
         rows = arena.new("rows", (B, n), torch.float32)
         rows.copy_(torch.randn(B, n))
         out = arena.new("out", (B,), torch.float32)
@@ -606,12 +622,12 @@ def test_rownorm2_ragged():
         np.testing.assert_allclose(out.cpu().numpy(), ref, rtol=4 * 2.0 ** -24 * (n + 2))   # float32 sum of n squares
 
 
-def test_selftest_quotient_counter_only():
+def test_selftest_quotient_counter_only(policy=None):
     """pdegym_selftest_quotient writes the one counter it is given and nothing past it."""
     import ctypes as C
     from pdecontrolgym_amd import _native as N
     lib = N.load()
-    arena = PZ.Arena("cuda")
+    arena = _arena(policy)
     a = arena.new("a", (1000,), torch.float32)
     a.copy_(torch.randn(1000))
     cnt = arena.new("count", (1,), torch.int32)
@@ -627,7 +643,7 @@ NS_OUT = ("reward", "terminated")
 
 
 def _ns_pair(n, B, K, dtype, ny=None, steps=2, seed=0, interleaved=True, dispatch=None, p_out=False, oracle=False,
-             poison_state=False):
+             poison_state=False, policy=None):
     """Clean and guarded+poisoned NSBatch2D over the same steps; scratch, the partner observation and p_out start as NaN."""
     from pdecontrolgym_amd import _native as N
     from pdecontrolgym_amd.batch2d import NSBatch2D
@@ -643,7 +659,7 @@ def _ns_pair(n, B, K, dtype, ny=None, steps=2, seed=0, interleaved=True, dispatc
         for e in (clean, pois):
             e.t["p_out"] = torch.zeros_like(e.t["p"])
             e._p_pingpong = True
-    arena = PZ.Arena("cuda")
+    arena = _arena(policy)
     guard_engine(pois, arena)
     # U_ref / action_ref with NaN right after their stated extent (nt_ref rows)
     U = arena.new("U_ref_nan_tail", (pois.t["U_ref"].shape[0] + 1,) + tuple(pois.t["U_ref"].shape[1:]), dtype)
@@ -664,8 +680,8 @@ def _ns_pair(n, B, K, dtype, ny=None, steps=2, seed=0, interleaved=True, dispatc
         PZ.fill_int_(pois.t["time_index"], pois.nt // 2)
     ctx = N.ns_dispatch(**(dispatch or {}))
     with ctx:
-        for e in (clean, pois):
-            e.reset(u0, v0, p0)
+        clean.reset(u0, v0, p0)
+        pois.reset(*(arena.like(k, torch.as_tensor(x, dtype=dtype, device="cuda")) for k, x in (("u0", u0), ("v0", v0), ("p0", p0))))
         orc = None
         if oracle:
             orc = po.NavierStokesOracle(**kw)
@@ -680,7 +696,7 @@ def _ns_pair(n, B, K, dtype, ny=None, steps=2, seed=0, interleaved=True, dispatc
             if pois.t["p_out"] is not None:
                 PZ.poison_(pois.t["p_out"])
             oc, rc, tc = clean.step(a)
-            op, rp, tp = pois.step(a)
+            op, rp, tp = pois.step(arena.like(f"action{s}", torch.as_tensor(np.asarray(a), dtype=dtype, device="cuda").reshape(B, -1)))
             arena.check()
             where = f"NS {dtype} {ny or n}x{n} B={B} K={K} {dispatch} step {s}"
             PZ.assert_written(op, None, f"{where}: obs", like=oc)
@@ -757,7 +773,7 @@ def test_ns256_contract(dtype, interleaved):
 
 
 @pytest.mark.parametrize("dtype", ["float32", "float64"])
-def test_ns_solve_pressure_contract(dtype):
+def test_ns_solve_pressure_contract(dtype, policy=None):
     """pdegym_ns2d_solve_pressure_*: aliasing and non-aliasing p_out; scratch starts as NaN; only p_out is written."""
     from pdecontrolgym_amd.batch2d import NSBatch2D
     from tests.test_gpu_ns2d import _random_case, BC_MIX
@@ -766,7 +782,7 @@ def test_ns_solve_pressure_contract(dtype):
         kw, u0, v0, p0, _ = _random_case(n, 3, 13, 5, BC_MIX)
         env = NSBatch2D(num_envs=3, device="cuda", dtype=dt, **kw)
         be = env.backend
-        arena = PZ.Arena("cuda")
+        arena = _arena(policy)
         u = arena.like("u", torch.tensor(u0, dtype=dt))
         v = arena.like("v", torch.tensor(v0, dtype=dt))
         p_in = arena.like("p_in", torch.tensor(p0, dtype=dt))
@@ -784,19 +800,22 @@ def test_ns_solve_pressure_contract(dtype):
         PZ.assert_bits_equal(p_in, ref, None, f"solve_pressure {dtype} n={n}: p_out aliasing p_in")
 
 
-def test_ns_masked_reset_leaves_others_alone():
+def test_ns_masked_reset_leaves_others_alone(policy=None):
     from pdecontrolgym_amd.batch2d import NSBatch2D
     from tests.test_gpu_ns2d import _random_case, BC_MIX
     for dt in (torch.float32, torch.float64):
         kw, u0, v0, p0, _ = _random_case(21, 5, 5, 6, BC_MIX)
         env = NSBatch2D(num_envs=5, device="cuda", dtype=dt, interleaved_state=False, **kw)
-        arena = PZ.Arena("cuda")
+        arena = _arena(policy)
         guard_engine(env, arena)
         for k in ("u", "v", "p", "obs"):
             PZ.poison_(env.t[k])
         PZ.fill_int_(env.t["time_index"], 3)
-        mask = torch.tensor([0, 1, 1, 0, 1], dtype=torch.uint8, device="cuda")
-        env.reset(u0, v0, p0, mask=mask)
+        mask = arena.like("mask", torch.tensor([0, 1, 1, 0, 1], dtype=torch.uint8, device="cuda"))
+        fields = [arena.like(k, torch.as_tensor(x, dtype=dt, device="cuda")) for k, x in (("u0", u0), ("v0", v0), ("p0", p0))]
+        if policy is not None:
+            assert all(x.data_ptr() % 16 != 0 for x in fields + [mask])
+        env.reset(*fields, mask=mask)
         arena.check()
         on = mask.bool()
         for k in ("u", "v", "p", "obs"):
@@ -806,7 +825,7 @@ def test_ns_masked_reset_leaves_others_alone():
         assert env.t["time_index"].cpu().tolist() == [3, 0, 0, 3, 0]
 
 
-def test_ns_auto_reset_final_obs():
+def test_ns_auto_reset_final_obs(policy=None):
     """Fused NS auto-reset: final_obs only for finishing instances (NaN elsewhere), pools with NaN after the last pool row."""
     from pdecontrolgym_amd.batch2d import NSBatch2D
     from tests.test_gpu_ns2d import _random_case, BC_MIX
@@ -816,7 +835,7 @@ def test_ns_auto_reset_final_obs():
         kw = dict(kw, T=3 * kw["dt"], U_ref=kw["U_ref"][:3], action_ref=kw["action_ref"][:3])
         clean = NSBatch2D(num_envs=B, device="cuda", dtype=dt, **kw)
         pois = NSBatch2D(num_envs=B, device="cuda", dtype=dt, **kw)
-        arena = PZ.Arena("cuda")
+        arena = _arena(policy)
         pools = []
         for nm, x in (("u0", u0), ("v0", v0), ("p0", p0)):
             g = arena.new("pool_" + nm, (P + 1, n, n), dt)
@@ -850,7 +869,7 @@ def test_ns_auto_reset_final_obs():
         assert with_te >= B
 
 
-def test_ns_rollout_contract():
+def test_ns_rollout_contract(policy=None):
     """pdegym_ns2d_rollout_*: slots 1..T written and equal to step calls, slot 0 untouched, no stray writes."""
     from pdecontrolgym_amd.batch2d import NSBatch2D
     from tests.test_gpu_ns2d import _random_case, BC_MIX
@@ -865,7 +884,7 @@ def test_ns_rollout_contract():
             env = NSBatch2D(num_envs=B, device="cuda", dtype=dt, **kw)
             for e in (ref, env):
                 e.reset(u0, v0, p0)
-            arena = PZ.Arena("cuda")
+            arena = _arena(policy)
             guard_engine(env, arena)
             PZ.poison_(env.t["scratch"])
             obs = arena.new("ro_obs", (Tn + 1, B, ny, 21, 2), dt)
@@ -895,11 +914,11 @@ def _traffic(M_dx, B, sim="outlet", T=0.5):
 
 @pytest.mark.parametrize("wide", [False, True])
 @pytest.mark.parametrize("B", [1, 5])
-def test_traffic_contract(B, wide):
+def test_traffic_contract(B, wide, policy=None):
     """Register (M = 51) and wide (M = 201) step kernels, reset, masked reset: outputs complete, others untouched, guards intact."""
     for sim in ("outlet", "both"):
         clean, pois = _traffic(10 if not wide else 40, B, sim), _traffic(10 if not wide else 40, B, sim)
-        arena = PZ.Arena("cuda")
+        arena = _arena(policy)
         guard_engine(pois, arena)
         rs = np.random.default_rng(1).uniform(0.1, 0.14, B)
         for k in ("r", "y", "obs", "time"):
@@ -907,7 +926,7 @@ def test_traffic_contract(B, wide):
         for o in pois._obs:
             PZ.poison_(o)
         clean.reset(rs)
-        pois.reset(rs)
+        pois.reset(arena.like("rs", torch.as_tensor(rs, device="cuda")))      # (reset adopts the tensor it is given)
         arena.check()
         for k in ("r", "y", "time"):
             PZ.assert_written(pois.t[k], None, f"traffic reset: {k}", like=clean.t[k])
@@ -920,7 +939,7 @@ def test_traffic_contract(B, wide):
                 PZ.poison_(pois.t[k])
             PZ.poison_(pois._obs[pois._flip ^ 1])
             oc = clean.step(a if A == 2 else a[:, 0])
-            op = pois.step(a if A == 2 else a[:, 0])
+            op = pois.step(arena.like(f"action{s}", torch.as_tensor(np.ascontiguousarray(a if A == 2 else a[:, 0]), device="cuda")))
             arena.check()
             for x, y, nm in zip(op, oc, ("obs", "reward", "done", "truncated")):
                 PZ.assert_written(x, None, f"traffic {sim} M={clean.M} B={B} step {s}: {nm}", like=y)
@@ -929,7 +948,9 @@ def test_traffic_contract(B, wide):
         if B > 1:
             for k in ("r", "y", "obs", "time"):
                 PZ.poison_(pois.t[k])
-            mask = torch.tensor([1] + [0] * (B - 1), dtype=torch.uint8, device="cuda")
+            mask = arena.like("mask", torch.tensor([1] + [0] * (B - 1), dtype=torch.uint8, device="cuda"))
+            if policy is not None:
+                assert mask.data_ptr() % 16 != 0 and pois.t["rs"].data_ptr() % 16 != 0
             pois.reset(rs, mask=mask)
             arena.check()
             for k in ("r", "y", "obs", "time"):
@@ -939,7 +960,7 @@ def test_traffic_contract(B, wide):
                 PZ.assert_untouched(t, ~sel, f"traffic masked reset: {k} of other instances")
 
 
-def test_traffic_rollout_contract():
+def test_traffic_rollout_contract(policy=None):
     """All three rollout instantiations (no policy; policy of <= 64 units; policy of 65..256 units)."""
     from pdecontrolgym_amd.policy import FusedMLP
     for width in (None, 32, 128):
@@ -948,7 +969,7 @@ def test_traffic_rollout_contract():
         rs = np.random.default_rng(3).uniform(0.1, 0.14, B)
         for e in (ref, env):
             e.reset(rs)
-        arena = PZ.Arena("cuda")
+        arena = _arena(policy)
         guard_engine(env, arena)
         M = env.M
         obs = arena.new("ro_obs", (Tn + 1, B, 2 * M), torch.float64)
@@ -987,7 +1008,7 @@ def _tumor(nx_big, B):
 
 
 @pytest.mark.parametrize("nx_big", [False, True])
-def test_tumor_contract(nx_big):
+def test_tumor_contract(nx_big, policy=None):
     """Both row-staging paths (nx <= 256, larger).  Reset over poisoned state (init_stride 0), step with an active mask, advance
     modes 0..3 and a whole episode (RUN_TO_END), a day past nt - 1, a masked reset.  Before every call the trajectory rows and t1_log
     entries past each instance's time index are poisoned; after it, the days each participating instance simulated (t_in+1 ..
@@ -997,7 +1018,7 @@ def test_tumor_contract(nx_big):
     from tests.test_tumor import tumor_ic
     B = 5
     (clean, X), (pois, _) = _tumor(nx_big, B), _tumor(nx_big, B)
-    arena = PZ.Arena("cuda")
+    arena = _arena(policy)
     guard_engine(pois, arena)
     ic = tumor_ic(X, clean.nx)
     for k in ("u", "remaining", "history", "t1_log"):
@@ -1006,7 +1027,8 @@ def test_tumor_contract(nx_big):
     PZ.fill_int_(pois.t["time_index"], 3)
     PZ.fill_int_(pois.t["days"], 1)
     clean.reset(ic)                                    # init [nx]: init_stride = 0
-    pois.reset(ic)
+    ic_t = arena.like("init", torch.as_tensor(ic, dtype=torch.float64, device="cuda"))
+    pois.reset(ic_t)
     arena.check()
     for k in ("u", "remaining", "time_index", "stage", "days", "history"):
         PZ.assert_bits_equal(pois.t[k], clean.t[k], None, f"tumour reset: {k}")
@@ -1050,7 +1072,7 @@ def test_tumor_contract(nx_big):
         t_in, snap = before_call()
         c = rng.uniform(0, 1, B)
         clean.step(c, active=active)
-        pois.step(c, active=active)
+        pois.step(arena.like(f"control{s}", torch.as_tensor(c, device="cuda")), active=arena.like("active", torch.as_tensor(active, device="cuda")))
         check(f"tumour step {s}", active.astype(bool), t_in, snap)
     for mode, days in ((N.TUMOR_RUN_GROWTH, 5), (N.TUMOR_RUN_POST, 5), (N.TUMOR_RUN_TO_END, 5), (N.TUMOR_RUN_ONE_DAY, 5),
                        (N.TUMOR_RUN_TO_END, nt)):
@@ -1063,7 +1085,7 @@ def test_tumor_contract(nx_big):
             clean.t["control"].zero_()
             pois.t["control"].zero_()
         clean.advance(mode, days, active=active)
-        pois.advance(mode, days, active=active)
+        pois.advance(mode, days, active=arena.like("active", torch.as_tensor(active, device="cuda")))
         check(f"tumour advance mode {mode} ({days} days)", part, t_in, snap)
     t_end, lethal = clean.t["time_index"].cpu().numpy(), clean.t["truncated"].cpu().numpy().astype(bool)
     assert ((t_end == nt - 1) | lethal)[part].all(), "RUN_TO_END with nt days runs every participating episode to its end"
@@ -1096,9 +1118,11 @@ def test_tumor_contract(nx_big):
     # masked reset: the others keep everything
     for k in ("u", "remaining"):
         PZ.poison_(pois.t[k])
-    mask = torch.tensor([0, 0, 1, 0, 1], dtype=torch.uint8, device="cuda")
+    mask = arena.like("mask", torch.tensor([0, 0, 1, 0, 1], dtype=torch.uint8, device="cuda"))
+    if policy is not None:
+        assert mask.data_ptr() % 16 != 0 and ic_t.data_ptr() % 16 != 0
     before = {k: pois.t[k].clone() for k in ("time_index", "stage", "days")}
-    pois.reset(ic, mask=mask)
+    pois.reset(ic_t, mask=mask)
     arena.check()
     on = mask.bool()
     PZ.assert_written(pois.t["u"], on, "tumour masked reset: u")
@@ -1114,7 +1138,7 @@ MLP_CASES = [(w, B, in_dim, xf, yf) for (w, B, in_dim) in ((64, 1, 5), (128, 15,
 
 
 @pytest.mark.parametrize("width,B,in_dim,x_f64,y_f64", MLP_CASES)
-def test_mlp_forward_contract_vs_float64(width, B, in_dim, x_f64, y_f64):
+def test_mlp_forward_contract_vs_float64(width, B, in_dim, x_f64, y_f64, policy=None):
     """pdegym_mlp_forward at the 64/128/256 launchers, every x/y dtype pair, ragged B and in_dim (one above the 512-entry staging
     chunk), x/y/noise strides wider than the rows with NaN in the gaps; the y gap keeps its poison.  Against a float64 evaluation of
     the same float32 network: |y - y64| <= 4 * 2^-24 * (in_dim + 2 * width + 2) * (|W| |h| + |b|) summed magnitudes + 1e-6, the
@@ -1126,7 +1150,7 @@ def test_mlp_forward_contract_vs_float64(width, B, in_dim, x_f64, y_f64):
                               torch.nn.Linear(width, out_dim)).cuda()
     pol = FusedMLP(mod, clamp=None)
     xdt, ydt = (torch.float64 if x_f64 else torch.float32), (torch.float64 if y_f64 else torch.float32)
-    arena = PZ.Arena("cuda")
+    arena = _arena(policy)
     xs, ys, ns = in_dim + 3, out_dim + 5, out_dim + 2
     xbuf = arena.new("x", (B, xs), xdt)
     PZ.poison_(xbuf)

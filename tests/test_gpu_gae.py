@@ -62,14 +62,15 @@ def test_the_fixture_holds_every_planted_shape():
     assert (((tr == 1) & (te == 0))[:, 5:]).any() and (~done[:, 5:]).any()          # ... also among the random columns
 
 
-def _launch(rew, val, te, tr, boot, gamma, lam, ld=None, stats=True, acc=None, cols=None):
+def _launch(rew, val, te, tr, boot, gamma, lam, ld=None, stats=True, acc=None, cols=None, policy=None):
     """One pdegym_gae launch on guarded device copies of the NumPy arrays, row stride ``ld`` (default B); ``tr`` / ``boot`` may be
     None; ``acc``: (ep_return_acc, ep_length_acc) NumPy arrays to start from, None = accumulators not given; ``cols``: a slice of
     columns -- the launch then covers that shard only, as views of the full-width buffers.  Returns the outputs as NumPy arrays
-    (full width) after the contract checks of the module docstring."""
+    (full width) after the contract checks of the module docstring.  ``policy``: the displacement of every guarded buffer off its
+    256-byte boundary (tests/poison.py; tests/test_gpu_pointer_alignment.py)."""
     T, B = rew.shape
     ld = B if ld is None else ld
-    A = poison.Arena("cuda")
+    A = poison.Arena("cuda", policy=policy)
     sel = slice(0, B) if cols is None else cols
     nb = len(range(*sel.indices(B)))
 

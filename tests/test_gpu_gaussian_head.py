@@ -35,12 +35,13 @@ def _close(case, got, want, what):
 
 # ---- (a) pdegym_mlp_forward ---------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("case", gx.FORWARD_CASES, ids=[c.name for c in gx.FORWARD_CASES])
-def test_forward_kernel_against_the_float64_expectation(case):
-    """Every buffer in a guarded allocation; with ``gaps`` the rows sit in wider, poisoned rows.  Only the A columns of y are written."""
+def test_forward_kernel_against_the_float64_expectation(case, policy=None):
+    """Every buffer in a guarded allocation; with ``gaps`` the rows sit in wider, poisoned rows.  Only the A columns of y are written.
+    ``policy`` displaces every guarded buffer off its 256-byte boundary (tests/poison.py; tests/test_gpu_pointer_alignment.py)."""
     b = gx.build(case)
     B, K, A = case.B, case.sizes[0], case.A
     gx_, gy, gn = (5, 3, 2) if case.gaps else (0, 0, 0)
-    arena = poison.Arena("cuda")
+    arena = poison.Arena("cuda", policy=policy)
     xbig = poison.poison_(arena.new("x", (B, K + gx_), F64 if case.x_f64 else F32))
     ybig = poison.poison_(arena.new("y", (B, A + gy), F64 if case.y_f64 else F32))
     xbig[:, :K] = torch.from_numpy(b.x_dev)

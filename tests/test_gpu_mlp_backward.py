@@ -37,9 +37,10 @@ M = 8.0
 FLOOR = 2.0 ** -20
 
 
-def _launch(net, x_np, dy_np, x_f64=False, gaps=False, want_dx=True, slabs=0, ws_fill=None):
+def _launch(net, x_np, dy_np, x_f64=False, gaps=False, want_dx=True, slabs=0, ws_fill=None, policy=None):
     """One pdegym_mlp_backward call under the buffer contract.  ``net``: a Linear / Tanh / ReLU stack on the device.  Returns
-    {"dw": [...], "db": [...], "dx"} as NumPy arrays."""
+    {"dw": [...], "db": [...], "dx"} as NumPy arrays.  ``policy``: the displacement of x, dy, dx, the row-major w[], dw and db off their 256-byte
+    boundaries; the blocked weights and biases of the descriptor and the workspace are the library's own tensors (tests/poison.py; tests/test_gpu_pointer_alignment.py)."""
     import ctypes as C
 
     from pdecontrolgym_amd.policy import FusedMLP
@@ -48,13 +49,13 @@ def _launch(net, x_np, dy_np, x_f64=False, gaps=False, want_dx=True, slabs=0, ws
     B, K = x_np.shape
     out = dy_np.shape[1]
     gx, gy, gd = (5, 3, 2) if gaps else (0, 0, 0)
-    arena = poison.Arena("cuda")
+    arena = poison.Arena("cuda", policy=policy)
     xbig = poison.poison_(arena.new("x", (B, K + gx), F64 if x_f64 else F32))
     dybig = poison.poison_(arena.new("dy", (B, out + gy), F32))
     xbig[:, :K] = torch.from_numpy(x_np)
     dybig[:, :out] = torch.from_numpy(np.asarray(dy_np, np.float32))
     dxbig = poison.poison_(arena.new("dx", (B, K + gd), F32)) if want_dx else None
-    weights = [w.detach() for w, _, _ in pol.layers]
+    weights = [arena.like(f"w{l}", w.detach()) for l, (w, _, _) in enumerate(pol.layers)]      # the row-major w[] of the call
     dw = [poison.poison_(arena.new(f"dw{l}", w.shape, F32)) for l, w in enumerate(weights)]
     db = [None if b is None else poison.poison_(arena.new(f"db{l}", b.shape, F32)) for l, (_, b, _) in enumerate(pol.layers)]
     desc = pol._net(None, x_f64, plain=True)
@@ -94,13 +95,13 @@ def _assert_equal(case_name, got, want, what):
 
 # ---- (a) exactly summable cases ----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("case", R.CASES, ids=[c.name for c in R.CASES])
-def test_backward_kernels_are_exact(case):
+def test_backward_kernels_are_exact(case, policy=None):
     """dw, db, dx equal the float64 expectation exactly, for the case's slab count and for every other one the batch allows: the order
     of summation cannot matter on these inputs, so all of them are bit-equal too."""
     b = R.build(case)
     net = b.net.cuda()
     for slabs in [case.slabs] + [s for s in R.valid_slabs(case.B) if s != case.slabs]:
-        got = _launch(net, b.x_dev, b.dy, case.x_f64, case.gaps, case.dx, slabs)
+        got = _launch(net, b.x_dev, b.dy, case.x_f64, case.gaps, case.dx, slabs, policy=policy)
         assert (got["dx"] is not None) == case.dx
         _assert_equal(case.name, got, b.want, f"(slabs = {slabs})")
 

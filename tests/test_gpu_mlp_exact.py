@@ -33,14 +33,15 @@ def _compare(case, got, want, what="output"):
 
 # ---- (a) pdegym_mlp_forward on exactly summable networks ------------------------------------------------------------------------------------
 @pytest.mark.parametrize("case", mx.FORWARD_CASES, ids=[c.name for c in mx.FORWARD_CASES])
-def test_forward_kernel_is_exact(case):
+def test_forward_kernel_is_exact(case, policy=None):
     """Every buffer in a guarded allocation; with ``gaps`` the rows sit in wider, poisoned rows (x_stride > K, y_stride > out_dim,
-    noise_stride > out_dim): a read of a gap turns the output into NaN, a store into one is found."""
+    noise_stride > out_dim): a read of a gap turns the output into NaN, a store into one is found.
+    ``policy`` displaces every guarded buffer off its 256-byte boundary (tests/poison.py; tests/test_gpu_pointer_alignment.py)."""
     from pdecontrolgym_amd.policy import FusedMLP
     b = mx.build(case)
     B, K, out = case.B, case.sizes[0], case.sizes[-1]
     gx, gy, gn = (5, 3, 2) if case.gaps else (0, 0, 0)
-    arena = poison.Arena("cuda")
+    arena = poison.Arena("cuda", policy=policy)
     xbig = poison.poison_(arena.new("x", (B, K + gx), F64 if case.x_f64 else F32))
     ybig = poison.poison_(arena.new("y", (B, out + gy), F64 if case.y_f64 else F32))
     xbig[:, :K] = torch.from_numpy(b.x_dev)

@@ -228,14 +228,15 @@ def test_one_launch_equals_two_launches_with_restarts_inside_the_launch(use_grap
 # ---- output contracts ---------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("M", [51, 129, 200])
 @pytest.mark.parametrize("sim", ["outlet", "both", "inlet"])
-def test_control_writes_exactly_its_outputs(M, sim):
-    """Poisoned output fully written, guard bands of every buffer intact, inputs untouched (register and strided kernels)."""
+def test_control_writes_exactly_its_outputs(M, sim, policy=None):
+    """Poisoned output fully written, guard bands of every buffer intact, inputs untouched (register and strided kernels).
+    ``policy`` displaces every guarded buffer off its 256-byte boundary (tests/poison.py; tests/test_gpu_pointer_alignment.py)."""
     from pde_control_gym import TrafficBacksteppingController
     B = 5
     rs, obs, want, _ = _control_case(M, B, sim)
     core = _core(sim, M, B, rs)
     ctrl = TrafficBacksteppingController(core, order="numpy" if M <= 129 else "tree")
-    arena = poison.Arena("cuda")
+    arena = poison.Arena("cuda", policy=policy)
     shape = (B, 2) if sim == "both" else (B,)
     o = arena.like("obs", torch.as_tensor(obs, device="cuda"))
     nz = arena.like("noise", torch.as_tensor(np.random.default_rng(4).normal(0, 0.01, shape).astype(np.float32), device="cuda"))
@@ -254,9 +255,10 @@ def test_control_writes_exactly_its_outputs(M, sim):
 
 @pytest.mark.parametrize("sim", ["outlet", "both", "inlet"])
 @pytest.mark.parametrize("order", ["numpy", "tree"])
-def test_rollout_writes_exactly_its_outputs(order, sim):
+def test_rollout_writes_exactly_its_outputs(order, sim, policy=None):
     """Observation slots 1 .. T, actions, rewards and flags poisoned and fully written; slot 0, the weights and the noise untouched;
-    every guard band intact; the engine state as after the clean run (restarts inside the launch included)."""
+    every guard band intact; the engine state as after the clean run (restarts inside the launch included).
+    ``policy`` displaces every guarded buffer off its 256-byte boundary (tests/poison.py; tests/test_gpu_pointer_alignment.py)."""
     from pde_control_gym import TrafficBacksteppingController
     B, T = 5, 40
     A = 2 if sim == "both" else 1
@@ -286,7 +288,7 @@ def test_rollout_writes_exactly_its_outputs(order, sim):
         return dict(obs=obs, actions=actions, rewards=rewards, done=done, truncated=trunc), state
 
     cout, cstate = run(None)
-    arena = poison.Arena("cuda")
+    arena = poison.Arena("cuda", policy=policy)
     pout, pstate = run(arena)
     arena.check()
     for k, v in pout.items():

@@ -72,6 +72,44 @@ def _equal(got, want, what):
             assert got.dtype == want.dtype and torch.equal(poison.bits(got), poison.bits(want)), what
 
 
+def guard_venv(venv, arena):
+    """Every tensor the wrapper-step kernels address in a guarded copy of ``arena``: the engine's dictionary (state, [B] outputs,
+    xscale, t_benchmark) and the wrapper's state (init rows, counters, final_obs, obs).  Returns the wrapper state."""
+    from tests.test_gpu_buffer_contract import guard_engine
+    guard_engine(venv.core, arena)
+    W = venv._wrapper_state()
+    for k, v in list(W.items()):
+        if torch.is_tensor(v):
+            W[k] = arena.like("wrap_" + k, v)
+    venv._consecutive, venv.treatment_calls, venv.soft_constraint_violations = W["consecutive"], W["treatment_calls"], W["soft_constraint_violations"]
+    venv._final_obs, venv._fused_obs = W["final_obs"], W["obs"]
+    return W
+
+
+@pytest.mark.parametrize("nx,T,weekends", [(201, 600, True), (70, 300, False)])
+def test_therapy_step_on_guarded_buffers(nx, T, weekends, displace=None):
+    """pdegym_tumor_therapy_step with every pointer of the call in a guarded allocation -- the engine's state and [B] outputs, the
+    command (bufs.control), the wrapper's counters, init, final_obs and obs: the steps equal step_tensor's launch sequence on fresh
+    tensors bit for bit, and every guard is intact.  ``displace``: a policy of tests/poison.py that moves every one of them off
+    its 256-byte boundary (tests/test_gpu_pointer_alignment.py)."""
+    acts, want, want_state = _reference(nx, T, weekends)
+    venv = _venv(nx, T, weekends, fused=True)
+    arena = poison.Arena("cuda", policy=displace)
+    W = guard_venv(venv, arena)
+    commands = [arena.like(f"control{s}", a) for s, a in enumerate(acts)]
+    if displace is not None:
+        for t in [venv.core.t[k] for k in ENGINE_KEYS + ("reward", "terminated", "truncated", "xscale")] + commands[:1] + \
+                 [v for v in W.values() if torch.is_tensor(v)]:
+            assert t.data_ptr() % 16 != 0 and t.data_ptr() % t.element_size() == 0
+    got, got_state = _steps(venv, commands)
+    arena.check()
+    for g, w, name in zip(got, want, ("obs", "reward", "terminated", "truncated", "terminal_obs")):
+        _equal(g, w, name)
+    _equal(got_state, want_state, "end state")
+    for c, a in zip(commands, acts):
+        assert torch.equal(c, a), "a command was changed"
+
+
 # ---- fused_step and the rollout with commands given ahead == step_tensor ---------------------------------------------------------------
 @pytest.mark.parametrize("nx,T,weekends", CONFIGS)
 def test_therapy_step_equals_step_tensor(nx, T, weekends):
@@ -216,10 +254,11 @@ def test_fused_step_reproduces_the_reference_wrapper(golden_tumor, case, n):
 
 # ---- output contract -----------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("with_policy", [False, True])
-def test_output_contract_on_poisoned_guarded_buffers(with_policy):
+def test_output_contract_on_poisoned_guarded_buffers(with_policy, displace=None):
     """Every buffer of the launch in a guarded allocation; outputs poisoned.  Slots 1..T and rows 0..T-1 are written for every patient;
     slot 0, actions given ahead, init and xscale are left as they were; final_obs is written exactly where an episode ended; and
-    the poisoned run returns the bits of a clean one."""
+    the poisoned run returns the bits of a clean one.  ``displace``: a policy of tests/poison.py that moves every guarded buffer off its
+    256-byte boundary (tests/test_gpu_pointer_alignment.py)."""
     from pde_control_gym import FusedMLP
     T, nx = 24, 201
     acts = torch.from_numpy(np.stack(_actions())).cuda()
@@ -229,6 +268,9 @@ def test_output_contract_on_poisoned_guarded_buffers(with_policy):
     def run(arena):
         venv = _venv(nx, 600, True)
         c = venv.core
+        if arena:                                       # the engine state the kernel reads and writes, and its [B] outputs
+            from tests.test_gpu_buffer_contract import guard_engine
+            guard_engine(c, arena)
         new = (lambda name, shape, dtype: arena.new(name, shape, dtype)) if arena else (lambda name, shape, dtype: torch.zeros(shape, dtype=dtype, device="cuda"))
         obs, actions = new("obs", (T + 1, B, nx), torch.float64), new("actions", (T, B), torch.float64)
         rewards, term, trunc = new("rewards", (T, B), torch.float64), new("terminated", (T, B), torch.uint8), new("truncated", (T, B), torch.uint8)
@@ -257,7 +299,7 @@ def test_output_contract_on_poisoned_guarded_buffers(with_policy):
                     xscale=xs, u=c.t["u"], W=W, core=c, first=c.t["u"])
 
     clean = run(None)
-    arena = poison.Arena("cuda")
+    arena = poison.Arena("cuda", policy=displace)
     got = run(arena)
     arena.check()
     for k in ("rewards", "terminated", "truncated"):

@@ -40,6 +40,71 @@ def test_one_element_overrun_lands_in_the_guard():
         g.check_guards()
 
 
+DTYPES = (torch.uint8, torch.int32, torch.float32, torch.float64, torch.int64)
+
+
+@pytest.mark.parametrize("policy", ["one", "mixed"])
+def test_displaced_payload_alignment_and_guard_size(policy):
+    """Arena(policy=...): data_ptr() % 256 == shift for every dtype, shift a multiple of the element size and (for 'mixed') no
+    multiple of 16; both guards keep their 4 KiB; the tail guard starts at the payload's last byte + 1."""
+    a = P.Arena("cpu", policy=policy, keep_aligned=("held",))
+    seen = {}
+    for dtype in DTYPES:
+        item = torch.empty((), dtype=dtype).element_size()
+        for name in ("obs", "reward", "u", "terminated", "w0", "scratch"):
+            t = a.new(f"{name}_{item}", (3, 5), dtype)
+            g = a.bufs[f"{name}_{item}"]
+            shift = a.shift_of(f"{name}_{item}", dtype)
+            assert g.shift == shift and t.data_ptr() % 256 == shift
+            assert shift % item == 0 and shift % 16 != 0 and 0 < shift < 256
+            if policy == "one":
+                assert shift == item
+            else:
+                assert shift // item in ({1: range(1, 16), 4: range(1, 4), 8: range(1, 2)}[item])
+                assert shift == P.policy_shift("mixed", f"{name}_{item}", dtype)       # a function of the name alone
+            seen.setdefault(item, set()).add(shift)
+            assert t.shape == (3, 5) and t.dtype == dtype and t.is_contiguous() and bool((t == 0).all())
+            assert t.data_ptr() - g.raw.data_ptr() == 4096 + shift
+            assert g._tail.data_ptr() == t.data_ptr() + g.nbytes
+            assert g._tail.numel() >= 4096 and (g._tail.data_ptr() + g._tail.numel()) % 256 == 0
+    if policy == "mixed":                       # the residues do differ between the buffers of one launch
+        assert len(seen[1]) >= 3 and len(seen[4]) >= 2
+    held = a.new("held", (7,), torch.float32)
+    assert held.data_ptr() % 256 == 0 and a.bufs["held"].shift == 0
+    a.check()
+    with pytest.raises(ValueError):
+        P.Arena("cpu", policy="two")
+    with pytest.raises(ValueError):
+        P.Guarded("x", (3,), torch.float32, "cpu", shift=6)
+
+
+def test_default_shift_is_zero():
+    a = P.Arena("cpu")
+    assert a.new("x", (5,), torch.float32).data_ptr() % 256 == 0 and a.bufs["x"].shift == 0
+    t, _ = P.guarded((5,), torch.float64, "cpu")
+    assert t.data_ptr() % 256 == 0
+
+
+@pytest.mark.parametrize("dtype", [torch.uint8, torch.float32, torch.float64])
+@pytest.mark.parametrize("policy", ["one", "mixed"])
+def test_displaced_one_element_overrun_and_underrun(policy, dtype):
+    """Displaced payload: element [numel] is byte +0 AFTER the payload, element [-1] lands in the head guard right before it."""
+    item = torch.empty((), dtype=dtype).element_size()
+    a = P.Arena("cpu", policy=policy)
+    t = a.new("reward", (5,), dtype)
+    g = a.bufs["reward"]
+    start = 4096 + g.shift
+    g.raw[start:start + 6 * item].view(dtype)[5] = 0
+    with pytest.raises(AssertionError, match=r"'reward' changed at byte \+0 AFTER"):
+        a.check()
+    g.raw[start + 5 * item:start + 6 * item] = P.GUARD_BYTE
+    a.check()
+    g.raw[start - item:start + 5 * item].view(dtype)[0] = 0
+    with pytest.raises(AssertionError, match=rf"'reward' changed 1 byte\(s\) BEFORE the payload \({item} byte"):
+        a.check()
+    del t
+
+
 def test_poison_patterns():
     f = P.poison_(torch.zeros(3, dtype=torch.float32))
     d = P.poison_(torch.zeros(3, dtype=torch.float64))
@@ -130,3 +195,26 @@ def test_every_launched_kernel_is_in_the_contract_suite():
         return getattr(importlib.import_module("tests." + mod) if mod else C, name, None)
     for k, tests in C.KERNEL_CASES.items():
         assert tests and all(callable(named(t)) for t in tests), (k, tests)
+
+
+def test_every_launched_kernel_is_in_the_alignment_suite():
+    """Every kernel launched in pdecontrolgym_amd/csrc/*.hip -- by hipLaunchKernelGGL or by the chevron syntax, with or without
+    template arguments -- is listed in test_gpu_pointer_alignment.ALIGNMENT_CASES, and every test named there exists: a kernel added
+    later cannot skip the displaced-pointer suite."""
+    import glob
+    import os
+    import re
+    from tests import test_gpu_pointer_alignment as A
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    launched = set()
+    for f in glob.glob(os.path.join(root, "pdecontrolgym_amd", "csrc", "*.hip")):
+        src = open(f).read()
+        launched |= set(re.findall(r"hipLaunchKernelGGL\(\s*\(?\s*([A-Za-z_]\w*)", src))
+        launched |= set(re.findall(r"([A-Za-z_]\w*)\s*(?:<[^<>;]*>)?\s*<<<", src))
+    assert len(launched) >= 45
+    missing = sorted(launched - set(A.ALIGNMENT_CASES))
+    assert not missing, f"kernels without a case in test_gpu_pointer_alignment.ALIGNMENT_CASES: {missing}"
+    stale = sorted(set(A.ALIGNMENT_CASES) - launched)
+    assert not stale, f"ALIGNMENT_CASES names kernels nothing launches: {stale}"
+    for k, tests in A.ALIGNMENT_CASES.items():
+        assert tests and all(callable(getattr(A, t, None)) for t in tests), (k, tests)

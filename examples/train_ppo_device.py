@@ -16,13 +16,18 @@ algorithm in plain torch on the batched engine:
   * update   -- ordinary torch autograd on the same ``torch.nn.Sequential`` the rollout evaluates (``FusedMLP`` picks the new
                 weights up at the next ``run()``); with ``fused_grad`` and layers of at most 64 units, actor and critic go through
                 ``FusedMLP.with_grad`` instead: one forward launch and a three-launch backward (``pdegym_mlp_backward``) per network
-                and minibatch that fill the same Parameters' ``.grad``, so the optimiser and the gradient clipping stay as they are.
+                and minibatch that fill the same Parameters' ``.grad``, so the optimiser and the gradient clipping stay as they are;
+                with ``fused_loss`` everything between the networks' outputs and their backward passes is ``PPOLoss`` (at most three
+                launches, ``pdegym_ppo_loss``: the gathers by the minibatch's indices, log-probability, clipped surrogate, value and
+                entropy terms and their gradients) and ``result.backward()``.  The loss is the same one (``vf_coef = 0.25`` is this
+                file's ``0.5 * (0.5 * mse)``, ``ent_coef = 1e-3`` its ``-1e-3 * log_std.sum()``), with ONE difference: under the
+                switch the advantages are normalised per minibatch, as SB3's ``PPO.train`` does, not once over the whole buffer.
 
 The plant is the reference's unstable reaction-diffusion benchmark u_t = u_xx + beta(x) u with boundary actuation
 (ReactionDiffusionPDE1D, Dirichlet control at x = 1).  Uncontrolled, ||u|| grows; the printed mean ||u|| over an episode falls
 as the policy learns to damp it.
 
-    python examples/train_ppo_device.py [iterations] [num_envs] [hidden units per layer: 64] [fused_grad: 0]
+    python examples/train_ppo_device.py [iterations] [num_envs] [hidden units per layer: 64] [fused_grad: 0] [fused_loss: 0]
 """
 import os
 import sys
@@ -33,7 +38,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import pde_control_gym  # noqa: E402
-from pde_control_gym import DeviceRollout, DeviceRolloutBuffer, FusedMLP  # noqa: E402
+from pde_control_gym import DeviceRollout, DeviceRolloutBuffer, FusedMLP, PPOLoss  # noqa: E402
 from pde_control_gym.src import TunedReward1D  # noqa: E402
 
 
@@ -64,7 +69,7 @@ def mlp(sizes, out_tanh=False):
     return torch.nn.Sequential(*mods)
 
 
-def main(iterations=30, B=2048, T=64, quiet=False, hidden=64, fused_grad=False):
+def main(iterations=30, B=2048, T=64, quiet=False, hidden=64, fused_grad=False, fused_loss=False):
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
     venv = make_env(B, horizon=T)        # one rollout = one episode of every environment
@@ -91,6 +96,7 @@ def main(iterations=30, B=2048, T=64, quiet=False, hidden=64, fused_grad=False):
         print(f"fused_grad: layers of {hidden} units are wider than the 64 the fused backward pass takes; the update uses torch autograd")
     gamma, lam, clip, epochs, nmb = 0.99, 0.95, 0.2, 6, 4
     buffer = DeviceRolloutBuffer(rollout, gamma=gamma, gae_lambda=lam)
+    head = PPOLoss(clip_range=clip, ent_coef=1e-3, vf_coef=0.25, normalize_advantage=True) if fused_loss else None
     history = []
     t_roll = t_upd = 0.0
     for it in range(iterations):
@@ -108,14 +114,26 @@ def main(iterations=30, B=2048, T=64, quiet=False, hidden=64, fused_grad=False):
         with torch.no_grad():
             mean_old = actor(obs[:T].reshape(-1, D)).reshape(T, B)
             a_raw = mean_old + rollout.action_noise       # the sample before the clamp: what the log-probabilities refer to
-            logp_old = -0.5 * ((a_raw - mean_old) / std_old) ** 2 - log_std.detach()
+            if fused_loss:                                # through the head's own device function: the first epoch sees ratio == 1
+                logp_old = head.log_prob(mean_old.reshape(-1, 1), log_std, a_raw.reshape(-1, 1)).reshape(T, B)
+            else:
+                logp_old = -0.5 * ((a_raw - mean_old) / std_old) ** 2 - log_std.detach()
         flat = lambda x: x.reshape(T * B, *x.shape[2:])   # noqa: E731
         batch = buffer.flat()
         o_f, a_f, lp_f, adv_f, ret_f = batch.observations, flat(a_raw), flat(logp_old), batch.advantages, batch.returns
-        adv_f = (adv_f - adv_f.mean()) / (adv_f.std() + 1e-8)
+        if not fused_loss:
+            adv_f = (adv_f - adv_f.mean()) / (adv_f.std() + 1e-8)
         for _ in range(epochs):
             perm = torch.randperm(T * B, device=dev)
             for mb in perm.chunk(nmb):
+                if fused_loss:
+                    obs_mb = o_f[mb]
+                    result = head(actor_fn(obs_mb), log_std, critic_fn(obs_mb), a_f, lp_f, adv_f, ret_f, index=mb)
+                    opt.zero_grad(set_to_none=True)
+                    result.backward()
+                    torch.nn.utils.clip_grad_norm_(list(actor.parameters()) + list(critic.parameters()), 0.5)
+                    opt.step()
+                    continue
                 mean = actor_fn(o_f[mb]).squeeze(-1)
                 logp = -0.5 * ((a_f[mb] - mean) / log_std.exp()) ** 2 - log_std
                 ratio = (logp - lp_f[mb]).exp()
@@ -144,4 +162,5 @@ def main(iterations=30, B=2048, T=64, quiet=False, hidden=64, fused_grad=False):
 
 if __name__ == "__main__":
     main(int(sys.argv[1]) if len(sys.argv) > 1 else 30, int(sys.argv[2]) if len(sys.argv) > 2 else 2048,
-         hidden=int(sys.argv[3]) if len(sys.argv) > 3 else 64, fused_grad=bool(int(sys.argv[4])) if len(sys.argv) > 4 else False)
+         hidden=int(sys.argv[3]) if len(sys.argv) > 3 else 64, fused_grad=bool(int(sys.argv[4])) if len(sys.argv) > 4 else False,
+         fused_loss=bool(int(sys.argv[5])) if len(sys.argv) > 5 else False)

@@ -27,6 +27,11 @@
  *                           (examples/transportPDE/transport1Dppo.py:88-90): RolloutBuffer.compute_returns_and_advantage
  *   pdegym_mlp_backward     replaces the autograd backward pass of the MlpPolicy networks in the gradient step of the same scripts
  *                           (model.learn: PPO.train / SAC.train), for layers of at most 64 units
+ *   pdegym_ppo_loss         replaces the loss of PPO.train in the same scripts (stable_baselines3/ppo/ppo.py: clipped surrogate,
+ *                           F.mse_loss value term, entropy term, approx_kl, clip_fraction, per-minibatch advantage normalisation)
+ *                           for MlpPolicy's DiagGaussianDistribution, the minibatch gathers and the autograd pass back to the
+ *                           networks' outputs
+ *   pdegym_diag_gaussian_log_prob  replaces DiagGaussianDistribution.log_prob (common/distributions.py)
  *
  * One call advances EVERY instance of a batch by one env-step (S PDE sub-steps for the 1D envs, one
  * Chorin projection step with K Jacobi sweeps for NS2D).  Instances are independent.
@@ -46,7 +51,8 @@
  *     int64), unless its parameter says otherwise: a slot of a [T + 1, B, obs_dim] rollout buffer, a view into a larger tensor and an
  *     array carved out of a pool are all valid, and the results do not depend on where a buffer starts.  The exceptions -- the
  *     blocked MLP weights and obs / U_ref / lam of the adjoint march: 16 bytes; the workspace of pdegym_mlp_backward: 4 -- are
- *     stated at the parameter, and a pointer that violates one is refused with -2 and a message naming the argument BEFORE anything
+ *     stated at the parameter (every pointer of pdegym_ppo_loss and pdegym_diag_gaussian_log_prob takes element accesses only;
+ *     the workspace of pdegym_ppo_loss holds doubles and needs 4 bytes), and a pointer that violates one is refused with -2 and a message naming the argument BEFORE anything
  *     is launched (never rerouted to another kernel: the bits of a result must not depend on an address).  The refusals are new
  *     with this wording (the struct layouts and PDEGYM_ABI_VERSION are unchanged): earlier libraries launched such a call and its
  *     16-byte accesses were the undefined behaviour the requirement now names;
@@ -854,6 +860,71 @@ typedef struct pdegym_gae_args {
   int32_t* episode_length;   /* optional [T, ld]: its length, else 0                                                           */
 } pdegym_gae_args;
 int pdegym_gae(const pdegym_gae_args* g, int32_t B, void* stream);
+
+/* ---- PPO loss head: surrogate, value and entropy terms of a minibatch with their gradients, at most three launches --------------
+ * SB3's PPO.train (stable_baselines3/ppo/ppo.py) for the DiagGaussianDistribution of MlpPolicy on a Box action space
+ * (common/distributions.py), from the outputs of the two networks to the gradients with respect to those outputs.  Row i < N of the
+ * minibatch reads mean[i, 0..A) and values[i] (dense, minibatch order) and row k = index ? index[i] : i of the rollout buffer:
+ * actions[k, 0..A), old_log_prob[k], advantages[k], returns[k] -- the gather of a_f[mb] and friends happens in the kernel.
+ * Per row, float32 with ONE rounding per operation, in this order (c = clip_range; * + - / are single roundings, exp is expf):
+ *     inv_j = exp(-log_std[j])                                                                        (once per lane)
+ *     a     = advantages[k];  with normalize_advantage and N > 1:  a = (a - (float)mean_N) / ((float)std_N + 1e-8f)
+ *     z_j   = (actions[k,j] - mean[i,j]) * inv_j
+ *     t_j   = ((-0.5f * (z_j * z_j)) - log_std[j]) - 0.5 log(2 pi);   logp = t_0, then logp = logp + t_j for j = 1 .. A-1
+ *     lr    = logp - old_log_prob[k];   ratio = exp(lr)
+ *     s1    = a * ratio;   s2 = a * clamp(ratio, (float)(1 - c), (float)(1 + c))        the clamp keeps a NaN, like torch.clamp
+ *     surr  = min(s1, s2), NaN if either is (torch.min)
+ *     g     = 0 where (ratio > (float)(1 + c) && a > 0) || (ratio < (float)(1 - c) && a < 0), else -(s1 * (float)(1.0 / N))
+ *     d_mean[i,j] = (g * z_j) * inv_j;      the term of d_log_std[j]: g * ((z_j * z_j) - 1)
+ *     dv    = values[i] - returns[k];   the term of value_loss: dv * dv;   d_values[i] = dv * (float)(2 vf_coef / N)
+ *     the term of approx_kl: (ratio - 1) - lr;   of clip_fraction: |ratio - 1| > (float)c
+ * g is what torch's min / clamp backward gives (the clamp passes the gradient on its closed interval, ties add up to the full
+ * gradient); the advantage normalisation is a constant with respect to the gradients, as in SB3.  mean_N and std_N (unbiased) of
+ * the N gathered advantages are formed in float64 about the first gathered advantage (equal advantages: std_N == 0 exactly).
+ * Every sum over rows is a float64 sum of the float32 terms in an order that is a function of N alone (csrc/pdegym_ppo_loss.hip),
+ * rounded once at the end: bit-reproducible from run to run.
+ *     policy_loss  = -sum surr / N;   value_loss = sum dv^2 / N (0 without values);   entropy_loss = -sum_j (0.5 + 0.5 log 2 pi + log_std[j])
+ *     loss         = policy_loss + ent_coef * entropy_loss + vf_coef * value_loss            (in double, rounded once)
+ *     d_log_std[j] = sum_i g_i (z_ij^2 - 1) - ent_coef
+ *     stats[8]     = loss, policy_loss, value_loss, entropy_loss, approx_kl, clip_fraction, adv_mean, adv_std  (the last two 0 and 1
+ *                    without normalisation)
+ * Non-finite data is ordinary data: a NaN advantage without normalisation reaches the sums and its own row of d_mean only, with
+ * normalisation every row; a NaN return reaches d_values[i], value_loss and loss only.  index entries must lie in [0, M).
+ * Every pointer takes element accesses only (natural alignment of float / int64); the workspace holds doubles and needs 4 bytes.
+ * Errors: -1 null descriptor; -2 N < 1, A outside 1 .. 8, a stride < A, M < 1 with an index, clip_range negative or not finite,
+ * ent_coef / vf_coef not finite, workspace too small or not 4-byte aligned; -3 a required pointer is NULL, values / d_values not
+ * given together (values needs returns), or an output (the workspace included) overlaps an input or another output. */
+typedef struct pdegym_ppo_loss_args {
+  int32_t A;                   /* action dimensions, 1 .. 8                                                                    */
+  int32_t normalize_advantage; /* nonzero: normalise the N gathered advantages (skipped for N == 1, as SB3 does)               */
+  const float* mean;           /* [N, ld_mean]: the actor's output                                                             */
+  int64_t ld_mean;             /* elements between rows, >= A                                                                  */
+  const float* values;         /* optional [N]: the critic's output; NULL = no value term                                      */
+  const float* log_std;        /* [A], shared by all rows                                                                      */
+  const int64_t* index;        /* optional [N], entries in [0, M): the minibatch's rows of the buffer; NULL = row i            */
+  int64_t M;                   /* rows of the buffer arrays (used with index; without it they have N rows)                     */
+  const float* actions;        /* [M, ld_actions]                                                                              */
+  int64_t ld_actions;          /* >= A                                                                                         */
+  const float* old_log_prob;   /* [M]                                                                                          */
+  const float* advantages;     /* [M]                                                                                          */
+  const float* returns;        /* [M]; required with values                                                                    */
+  double clip_range, ent_coef, vf_coef; /* the Python doubles; clip_range >= 0                                                 */
+  float* d_mean;               /* [N, ld_d_mean] out, columns < A written                                                      */
+  int64_t ld_d_mean;           /* >= A                                                                                         */
+  float* d_values;             /* [N] out; given if and only if values is                                                      */
+  float* d_log_std;            /* [A] out                                                                                      */
+  float* stats;                /* [8] out                                                                                      */
+  void* workspace;             /* pdegym_ppo_loss_workspace(N, A) bytes, 4-BYTE ALIGNED (else -2); every word read was written
+                                  by the same call                                                                             */
+  int64_t workspace_bytes;
+} pdegym_ppo_loss_args;
+int64_t pdegym_ppo_loss_workspace(int32_t N, int32_t A);      /* bytes; negative: error code (N < 1, A outside 1 .. 8)          */
+int pdegym_ppo_loss(const pdegym_ppo_loss_args* g, int32_t N, void* stream);
+/* out[i] = logp of row i as above (mean [N, ld], actions [N or more, ld_a] gathered by the optional index [N], log_std [A]): what
+ * fills old_log_prob after a rollout -- with unchanged weights pdegym_ppo_loss then sees lr == 0 and ratio == 1 exactly.
+ * Errors: -2 N < 1, A outside 1 .. 8, ld or ld_a < A; -3 a NULL pointer (index excepted), out overlapping an input. */
+int pdegym_diag_gaussian_log_prob(const float* mean, int64_t ld, const float* log_std, const float* actions, int64_t ld_a,
+                                  const int64_t* index, float* out, int32_t N, int32_t A, void* stream);
 
 /* ---- test-only: kernel dispatch overrides -------------------------------------------------------------------------
  * Nothing on the product path calls this (the reference has no counterpart); the parity tests use it to run the SAME step

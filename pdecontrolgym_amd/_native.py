@@ -37,6 +37,7 @@ EXPORTS = [
     "pdegym_ns2d_adjoint_f64", "pdegym_transport_backstep_rollout", "pdegym_parabolic_backstep_rollout",
     "pdegym_traffic_backstep_control", "pdegym_traffic_backstep_rollout", "pdegym_tumor_therapy_step", "pdegym_tumor_rollout",
     "pdegym_gae", "pdegym_mlp_backward", "pdegym_mlp_backward_workspace",
+    "pdegym_ppo_loss", "pdegym_ppo_loss_workspace", "pdegym_diag_gaussian_log_prob",
 ]
 # keys of pdegym_debug_set (test-only dispatch overrides, include/pdegym.h)
 DEBUG_NS_GENERIC, DEBUG_NS_NO_COL, DEBUG_NS_COL_MIN_BATCH, DEBUG_NS_NO_LDS_JACOBI = range(4)
@@ -46,6 +47,8 @@ MLP_HEAD_PLAIN, MLP_HEAD_SQUASHED_GAUSSIAN = 0, 1
 MLP_BACKWARD_MAX_WIDTH, MLP_BACKWARD_MAX_INPUT = 64, 1024      # pdegym_mlp_backward: widest layer, widest first-layer input
 BACKSTEP_TREE, BACKSTEP_ORDERED = 0, 1
 TRAFFIC_BACKSTEP_TREE, TRAFFIC_BACKSTEP_NUMPY = 0, 1
+PPO_LOSS_MAX_A = 8                      # action dimensions of pdegym_ppo_loss / pdegym_diag_gaussian_log_prob
+PPO_LOSS_STATS = ("loss", "policy_loss", "value_loss", "entropy_loss", "approx_kl", "clip_fraction", "adv_mean", "adv_std")
 TRAFFIC_BACKSTEP_NUMPY_MAX_M = 129      # the longest row whose np.trapz sum is un-recursed (128 terms)
 
 
@@ -201,6 +204,15 @@ class Gae(C.Structure):
                 ("episode_length", C.c_void_p)]
 
 
+class PpoLoss(C.Structure):
+    _fields_ = [("A", C.c_int32), ("normalize_advantage", C.c_int32), ("mean", C.c_void_p), ("ld_mean", C.c_int64),
+                ("values", C.c_void_p), ("log_std", C.c_void_p), ("index", C.c_void_p), ("M", C.c_int64), ("actions", C.c_void_p),
+                ("ld_actions", C.c_int64), ("old_log_prob", C.c_void_p), ("advantages", C.c_void_p), ("returns", C.c_void_p),
+                ("clip_range", C.c_double), ("ent_coef", C.c_double), ("vf_coef", C.c_double), ("d_mean", C.c_void_p),
+                ("ld_d_mean", C.c_int64), ("d_values", C.c_void_p), ("d_log_std", C.c_void_p), ("stats", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
 class NativeError(RuntimeError):
     pass
 
@@ -290,6 +302,13 @@ def load():
     lib.pdegym_mlp_backward_workspace.restype = C.c_int64
     lib.pdegym_mlp_backward.argtypes = [C.POINTER(Mlp), C.POINTER(MlpBackward), C.c_int32, C.c_void_p]
     lib.pdegym_mlp_backward.restype = C.c_int
+    lib.pdegym_ppo_loss_workspace.argtypes = [C.c_int32, C.c_int32]
+    lib.pdegym_ppo_loss_workspace.restype = C.c_int64
+    lib.pdegym_ppo_loss.argtypes = [C.POINTER(PpoLoss), C.c_int32, C.c_void_p]
+    lib.pdegym_ppo_loss.restype = C.c_int
+    lib.pdegym_diag_gaussian_log_prob.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                                  C.c_int32, C.c_int32, C.c_void_p]
+    lib.pdegym_diag_gaussian_log_prob.restype = C.c_int
     lib.pdegym_debug_set.argtypes = [C.c_int32, C.c_int32]
     lib.pdegym_debug_set.restype = C.c_int32
     if lib.pdegym_abi_version() != ABI_VERSION:

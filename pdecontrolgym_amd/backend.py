@@ -588,6 +588,82 @@ class HipBackend:
         g.ep_length_acc = None if ep_length_acc is None else ep_length_acc.data_ptr()
         N.check(self.lib.pdegym_gae(C.byref(g), B, N.current_stream_ptr(rewards.device)), "pdegym_gae")
 
+    @staticmethod
+    def _ppo_rows(what, name, x, rows, width, dtype, device):
+        """``x`` as a [rows, width] (width None: [rows]) tensor of ``dtype`` on ``device`` with unit inner stride: its row stride."""
+        import torch
+        shape = (rows,) if width is None else (rows, width)
+        if (not torch.is_tensor(x) or not x.is_cuda or x.device != device or x.dtype != dtype or tuple(x.shape) != shape
+                or (rows > 1 and x.stride(0) < (width or 1)) or (width is not None and width > 1 and x.stride(1) != 1)
+                or (width is None and rows > 1 and x.stride(0) != 1)):
+            raise N.NativeError(f"{what}: {name} must be a {dtype} HIP tensor {list(shape)} with unit inner stride on the mean's device, "
+                                f"got {getattr(x, 'dtype', type(x).__name__)} {tuple(getattr(x, 'shape', ()))}")
+        return (x.stride(0) if rows > 1 else width) if width is not None else 1
+
+    @_on_device_of("mean")
+    def ppo_loss(self, mean, log_std, values, actions, old_log_prob, advantages, returns, d_mean, d_values, d_log_std, stats,
+                 clip_range: float, ent_coef: float, vf_coef: float, normalize_advantage: bool, index=None, workspace=None):
+        """The PPO loss of a minibatch and its gradients in at most three launches (pdegym_ppo_loss: SB3's ``PPO.train`` loss for a
+        ``DiagGaussianDistribution``).  ``mean`` [N, A] and ``values`` [N] (or None: no value term) in minibatch order, ``log_std``
+        [A]; ``actions`` [M, A], ``old_log_prob`` / ``advantages`` / ``returns`` [M] are gathered by ``index`` (int64 [N], entries in
+        [0, M)) or, without it, M = N.  Outputs ``d_mean`` [N, A], ``d_values`` [N] (with ``values``), ``d_log_std`` [A], ``stats``
+        [8] (``N.PPO_LOSS_STATS``).  Everything float32 with unit inner stride (2-D tensors may have a row stride), on one device.
+        ``workspace``: None (the backend's own, cached per device and size, allocated at the first call of a shape) or a uint8
+        tensor of at least pdegym_ppo_loss_workspace(N, A) bytes."""
+        import torch
+        if not torch.is_tensor(mean) or mean.dim() != 2:
+            raise N.NativeError("ppo_loss: mean must be a float32 [N, A] tensor")
+        n, A = (int(s) for s in mean.shape)
+        dev, f32, what = mean.device, torch.float32, "ppo_loss"
+        M = n if index is None else (int(actions.shape[0]) if torch.is_tensor(actions) and actions.dim() == 2 else -1)
+        g = N.PpoLoss()
+        g.A, g.normalize_advantage, g.M = A, int(bool(normalize_advantage)), M
+        g.ld_mean = self._ppo_rows(what, "mean", mean, n, A, f32, dev)
+        g.ld_actions = self._ppo_rows(what, "actions", actions, M, A, f32, dev)
+        g.ld_d_mean = self._ppo_rows(what, "d_mean", d_mean, n, A, f32, dev)
+        dense = [("log_std", log_std, A, f32), ("old_log_prob", old_log_prob, M, f32), ("advantages", advantages, M, f32),
+                 ("d_log_std", d_log_std, A, f32), ("stats", stats, len(N.PPO_LOSS_STATS), f32)]
+        if index is not None:
+            dense.append(("index", index, n, torch.int64))
+        if (values is None) != (d_values is None):
+            raise N.NativeError("ppo_loss: values and d_values are given together")
+        if values is not None:
+            dense += [("values", values, n, f32), ("d_values", d_values, n, f32), ("returns", returns, M, f32)]
+        for name, x, rows, dtype in dense:
+            self._ppo_rows(what, name, x, rows, None, dtype, dev)
+            setattr(g, name, x.data_ptr())
+        g.mean, g.actions, g.d_mean = mean.data_ptr(), actions.data_ptr(), d_mean.data_ptr()
+        if workspace is None:
+            need = int(self.lib.pdegym_ppo_loss_workspace(n, A))
+            if need < 0:
+                N.check(need, "pdegym_ppo_loss_workspace")
+            workspace = self._mlp_backward_workspace(dev, need)
+        elif not torch.is_tensor(workspace) or workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous():
+            raise N.NativeError("ppo_loss: workspace must be a contiguous uint8 tensor on the mean's device")
+        g.clip_range, g.ent_coef, g.vf_coef = float(clip_range), float(ent_coef), float(vf_coef)
+        g.workspace, g.workspace_bytes = workspace.data_ptr(), workspace.numel()
+        N.check(self.lib.pdegym_ppo_loss(C.byref(g), n, N.current_stream_ptr(dev)), "pdegym_ppo_loss")
+
+    @_on_device_of("mean")
+    def diag_gaussian_log_prob(self, mean, log_std, actions, out, index=None):
+        """out[i] = log N(actions[index[i] or i]; mean[i], exp(log_std)) summed over the A dimensions, through the device function
+        ``ppo_loss`` uses (pdegym_diag_gaussian_log_prob): ``mean`` [N, A], ``actions`` [M, A], ``out`` [N], ``index`` int64 [N]."""
+        import torch
+        if not torch.is_tensor(mean) or mean.dim() != 2:
+            raise N.NativeError("diag_gaussian_log_prob: mean must be a float32 [N, A] tensor")
+        n, A = (int(s) for s in mean.shape)
+        dev, f32, what = mean.device, torch.float32, "diag_gaussian_log_prob"
+        M = n if index is None else (int(actions.shape[0]) if torch.is_tensor(actions) and actions.dim() == 2 else -1)
+        ld = self._ppo_rows(what, "mean", mean, n, A, f32, dev)
+        ld_a = self._ppo_rows(what, "actions", actions, M, A, f32, dev)
+        self._ppo_rows(what, "log_std", log_std, A, None, f32, dev)
+        self._ppo_rows(what, "out", out, n, None, f32, dev)
+        if index is not None:
+            self._ppo_rows(what, "index", index, n, None, torch.int64, dev)
+        N.check(self.lib.pdegym_diag_gaussian_log_prob(mean.data_ptr(), ld, log_std.data_ptr(), actions.data_ptr(), ld_a,
+                                                       None if index is None else index.data_ptr(), out.data_ptr(), n, A,
+                                                       N.current_stream_ptr(dev)), "pdegym_diag_gaussian_log_prob")
+
     @_on_device_of("obs")
     def backstep_rollout1d(self, kind: str, P: N.Params1D, T: dict, obs, actions, rewards, terminated, truncated, B: int, law: N.Backstep,
                            obs_noise=None, obs_seen=None):

@@ -15,7 +15,18 @@ batched engine, on the plant of examples/train_ppo_device.py:
                 ``latent`` / ``mu`` / ``log_std`` modules the rollout evaluates (``FusedMLP`` picks the new weights up at the next
                 ``run()``).
 
-    python examples/train_sac_device.py [iterations] [num_envs] [hidden units per layer: 64] [fused_grad: 0]
+    python examples/train_sac_device.py [iterations] [num_envs] [hidden units per layer: 64] [fused_grad: 0] [fused_loss: 0]
+
+``fused_loss`` sends the three sample / loss blocks of the update through ``pde_control_gym.SACLoss`` (pdegym_squashed_gaussian_sample
+and its backward, pdegym_sac_critic_loss, pdegym_sac_actor_loss): ``head.sample`` writes ``[obs | action]`` and the log-probability in
+one launch, ``head.critic`` gathers rewards and terminations by the minibatch's indices inside its kernel, ``result.backward()`` is
+one autograd call per step.  What differs from the default path: (1) the critic loss is SB3's ``0.5 * (mse(q1, y) + mse(q2, y))``,
+so the critics' gradients (and the ``Q loss`` printed) are HALF those of the default path's ``mse + mse``; (2) the noise is drawn
+with ``torch.randn`` ahead of ``head.sample`` (two [batch, 1] draws per update from one call) instead of ``randn_like`` inside
+``sample``, so the random stream is consumed differently and the two paths do not reproduce each other's numbers; (3) the gradient
+of the log-probability uses ``eps`` directly where autograd differentiates ``((z - mu) / sigma)^2`` through ``z``: equal in exact
+arithmetic; (4) actor and entropy-coefficient gradients come from ONE backward call, the two optimisers step after it (the default
+path steps the actor before it forms the entropy-coefficient loss, from the same detached ``logp``: the same numbers).
 """
 import copy
 import math
@@ -26,7 +37,7 @@ import time
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from pde_control_gym import DeviceRollout, FusedMLP  # noqa: E402
+from pde_control_gym import DeviceRollout, FusedMLP, SACLoss  # noqa: E402
 from train_ppo_device import make_env  # noqa: E402
 
 LOG_STD_MIN, LOG_STD_MAX = -20.0, 2.0
@@ -56,7 +67,8 @@ def sample(latent, mu, log_std, obs, raw=None):
     return a, logp
 
 
-def main(iterations=30, num_envs=1024, n_steps=32, hidden=64, one_launch=None, quiet=False, updates=8, batch=2048, fused_grad=False):
+def main(iterations=30, num_envs=1024, n_steps=32, hidden=64, one_launch=None, quiet=False, updates=8, batch=2048, fused_grad=False,
+         fused_loss=False):
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
     B, T = num_envs, n_steps
@@ -94,6 +106,14 @@ def main(iterations=30, num_envs=1024, n_steps=32, hidden=64, one_launch=None, q
     buf = {k: torch.zeros(cap, n, device=dev) for k, n in (("obs", D), ("next", D), ("act", 1), ("rew", 1), ("term", 1))}
     head, filled = 0, 0
     gamma, tau, target_entropy = 0.99, 0.005, -1.0
+    loss_head = SACLoss(gamma, target_entropy, (LOG_STD_MIN, LOG_STD_MAX)) if fused_loss else None
+
+    def raw_of(x):
+        """The rows [mu, log_std] of the actor: the fused last layer of ``with_grad``, or the modules' outputs side by side."""
+        if raw_fn is not None:
+            return raw_fn(x)
+        h = latent(x)
+        return torch.cat([mu(h), log_std(h)], 1)
     history = {"q_loss": [], "actor_loss": [], "alpha": [], "mean_reward": [], "mean_norm": []}
     t_roll = t_upd = 0.0
     for it in range(iterations):
@@ -116,6 +136,31 @@ def main(iterations=30, num_envs=1024, n_steps=32, hidden=64, one_launch=None, q
         head, filled = (head + T * B) % cap, min(filled + T * B, cap)
         for _ in range(updates):
             mb = torch.randint(0, filled, (min(batch, filled),), device=dev)
+            if loss_head is not None:
+                o, o2, a = (buf[k][mb] for k in ("obs", "next", "act"))          # (rewards and terminations: gathered in the kernel)
+                eps2, eps = torch.randn(2, mb.shape[0], 1, device=dev)
+                with torch.no_grad():
+                    block2, logp2 = loss_head.sample(raw_of(o2), eps2, obs=o2)        # [o2 | a2], log pi(a2 | o2)
+                    q1_next, q2_next = q1_t(block2), q2_t(block2)
+                oa = torch.cat([o, a], 1)
+                result = loss_head.critic(q1_fn(oa), q2_fn(oa), q1_next, q2_next, logp2, buf["rew"], buf["term"], log_alpha, index=mb)
+                opt_q.zero_grad(set_to_none=True)
+                result.backward()
+                opt_q.step()
+                q_loss = result.critic_loss
+                block, logp = loss_head.sample(raw_of(o), eps, obs=o)                 # [o | a_pi]: the critics' input, no cat
+                result = loss_head.actor(q1_fn(block), q2_fn(block), logp, log_alpha)
+                opt_actor.zero_grad(set_to_none=True)
+                opt_alpha.zero_grad(set_to_none=True)
+                result.backward()
+                opt_actor.step()
+                opt_alpha.step()
+                actor_loss = result.actor_loss
+                with torch.no_grad():
+                    for net, tgt in ((q1, q1_t), (q2, q2_t)):
+                        for p, pt in zip(net.parameters(), tgt.parameters()):
+                            pt.lerp_(p, tau)
+                continue
             o, o2, a, r, d = (buf[k][mb] for k in ("obs", "next", "act", "rew", "term"))
             alpha = log_alpha.exp().detach()
             with torch.no_grad():
@@ -160,4 +205,5 @@ def main(iterations=30, num_envs=1024, n_steps=32, hidden=64, one_launch=None, q
 
 if __name__ == "__main__":
     main(int(sys.argv[1]) if len(sys.argv) > 1 else 30, int(sys.argv[2]) if len(sys.argv) > 2 else 1024,
-         hidden=int(sys.argv[3]) if len(sys.argv) > 3 else 64, fused_grad=bool(int(sys.argv[4])) if len(sys.argv) > 4 else False)
+         hidden=int(sys.argv[3]) if len(sys.argv) > 3 else 64, fused_grad=bool(int(sys.argv[4])) if len(sys.argv) > 4 else False,
+         fused_loss=bool(int(sys.argv[5])) if len(sys.argv) > 5 else False)

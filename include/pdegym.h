@@ -32,6 +32,11 @@
  *                           for MlpPolicy's DiagGaussianDistribution, the minibatch gathers and the autograd pass back to the
  *                           networks' outputs
  *   pdegym_diag_gaussian_log_prob  replaces DiagGaussianDistribution.log_prob (common/distributions.py)
+ *   pdegym_squashed_gaussian_sample (+ _backward), pdegym_sac_critic_loss, pdegym_sac_actor_loss
+ *                           replace the losses of SAC.train (stable_baselines3/sac/sac.py) in the reference's SAC scripts
+ *                           (examples/transportPDE/transport1Dsac.py): SquashedDiagGaussianDistribution sample and log_prob, the
+ *                           soft Bellman target, critic, actor and entropy-coefficient losses and the autograd pass back to the
+ *                           networks' outputs
  *
  * One call advances EVERY instance of a batch by one env-step (S PDE sub-steps for the 1D envs, one
  * Chorin projection step with K Jacobi sweeps for NS2D).  Instances are independent.
@@ -925,6 +930,136 @@ int pdegym_ppo_loss(const pdegym_ppo_loss_args* g, int32_t N, void* stream);
  * Errors: -2 N < 1, A outside 1 .. 8, ld or ld_a < A; -3 a NULL pointer (index excepted), out overlapping an input. */
 int pdegym_diag_gaussian_log_prob(const float* mean, int64_t ld, const float* log_std, const float* actions, int64_t ld_a,
                                   const int64_t* index, float* out, int32_t N, int32_t A, void* stream);
+
+/* ---- SAC loss heads: squashed-Gaussian sample with its backward, critic loss, actor + entropy-coefficient loss ---------------------
+ * SB3's SAC.train (stable_baselines3/sac/sac.py) for the SquashedDiagGaussianDistribution of MlpPolicy (common/distributions.py,
+ * epsilon = 1e-6) and one or two Q critics, from the networks' outputs to the gradients with respect to those outputs.  Everything
+ * float32 with ONE rounding per operation in the order written below (* + - / are single roundings; exp, tanh and log are the
+ * device library's expf, tanhf, logf -- the only places where a result may differ from torch float32); every sum over rows is a
+ * float64 sum of the float32 terms in an order that is a function of N alone (csrc/pdegym_sac_loss.hip), rounded once.  No atomics:
+ * stream order is the only synchronisation, and every word of a workspace that is read was written by the same call.  Every pointer
+ * takes element accesses only (natural alignment of float / int64); a workspace holds doubles and needs 4 bytes.
+ *
+ * 1. pdegym_squashed_gaussian_sample (one launch, one row per lane).  raw[i] holds the 2A columns [mu_0 .. mu_{A-1}; log_std_0 ..]
+ *    of the actor's last layer (FusedMLP.squashed_gaussian(...).with_grad), eps[i] the A standard-normal draws.  Per column j:
+ *        ls    = clamp(log_std_j, log_std_min, log_std_max)                    the clamp keeps a NaN, like torch.clamp
+ *        sigma = exp(ls);   z = mu_j + (sigma * eps_j);   a_j = tanh(z);   w = 1 - (a_j * a_j);   u = w + 1e-6f
+ *        t_j   = (((-0.5f * (eps_j * eps_j)) - ls) - 0.5 log(2 pi)) - log(u)
+ *        logp  = t_0, then logp = logp + t_j for j = 1 .. A-1
+ *    which is SquashedDiagGaussianDistribution.log_prob on its own gaussian_actions: (z - mu) / sigma IS eps by construction, so
+ *    eps is used directly.  actions[i, D + j] = a_j in [-1, 1], log_prob[i] = logp.  With obs (and D >= 1) the launch also copies
+ *    obs[i, 0..D) into actions[i, 0..D): `actions` is then the critics' input block [obs | a], torch.cat([obs, a], 1) disappears.
+ *    Columns >= D + A of a row are never written.
+ *
+ * 2. pdegym_squashed_gaussian_sample_backward (one launch).  Recomputes a_j, w, u, sigma from raw and eps -- the forward launch saves
+ *    nothing -- and, with da_j = d_actions[i, j] (a NULL d_actions reads as +0) and dl = d_log_prob[i * d_log_prob_stride] (NULL: +0):
+ *        k        = ((2 * a_j) * w) / u;      se = sigma * eps_j;      daw = da_j * w
+ *        d_raw[i, j]     = daw + (dl * k)                                                                         (d / d mu_j)
+ *        d_raw[i, A + j] = (daw * se) + (dl * ((k * se) - 1))  where log_std_min <= log_std_j <= log_std_max, else +0   (d / d log_std_j)
+ *    The gate is the closed interval torch's clamp backward passes; it SELECTS 0 and never multiplies by it (a NaN log_std is outside).
+ *    The Gaussian part of logp contributes exactly -1 to d / d log_std and 0 to d / d mu: autograd over ((z - mu) / sigma)^2 with
+ *    z = mu + sigma eps leaves further terms that are 0 in exact arithmetic and rounding residue in floating point; they are dropped.
+ *    d_log_prob is an ARRAY with an element stride: d_log_prob_stride = 1 is a dense [N] array, 0 is ONE device scalar for all rows
+ *    (what pdegym_sac_actor_loss writes).  d_actions may point into a wider block: the action columns of a critic's dx [N, D + A]
+ *    are passed in place as d_actions = dx + D, ld_d_actions = D + A.
+ *    Saturated rows (|z| large: a_j = +-1) have w = 0, u = 1e-6f, a finite log_prob and k == 0 exactly.
+ *
+ * 3. pdegym_sac_critic_loss (two launches: rows, finish; the second is skipped without stats).  Row i < N reads q1[i], q2[i],
+ *    q1_target[i], q2_target[i], next_log_prob[i] (dense) and rewards[k], dones[k] (0.0 / 1.0) at k = index ? index[i] : i.
+ *    log_alpha is a DEVICE pointer to one float (no host synchronisation): alpha = exp(*log_alpha).
+ *        m   = min(q1_target[i], q2_target[i]), NaN if either is (torch.min); one critic: q1_target[i]
+ *        y   = r + (((1 - d) * (float)gamma) * (m - (alpha * next_log_prob[i])))
+ *        e_c = q_c[i] - y;     d_q_c[i] = e_c * (float)(1.0 / N);     target[i] = y
+ *        critic_loss = 0.5 * (sum e_1 * e_1 + sum e_2 * e_2) / N               (SB3: 0.5 * sum_c F.mse_loss(q_c, y))
+ *        stats[4]    = critic_loss, mean q1, mean q2 (0 with one critic), mean y
+ *    q2 / q2_target / d_q2 all NULL: one critic.  A NaN in a row reaches that row's outputs and the sums only.
+ *
+ * 4. pdegym_sac_actor_loss (two launches).  alpha = exp(*log_alpha);
+ *        m_i         = min over the critics as torch.min(torch.cat((q1_pi, q2_pi), 1), dim=1) computes it: the FIRST minimal
+ *                      column, a NaN counting as minimal; its gradient -(float)(1.0 / N) goes to that column (a tie: q1_pi), the
+ *                      other column gets 0
+ *        actor_loss    = sum((alpha * log_prob[i]) - m_i) / N
+ *        ent_mean      = sum(log_prob[i] + (float)target_entropy) / N
+ *        ent_coef_loss = -(*log_alpha) * ent_mean;      d_log_alpha[0] = -ent_mean
+ *        d_log_prob[0] = alpha * (float)(1.0 / N)       ONE scalar: d actor_loss / d log_prob[i] for every i (the sample backward
+ *                                                       takes it with d_log_prob_stride = 0)
+ *        stats[4]      = actor_loss, ent_coef_loss, alpha, mean log_prob
+ *
+ * Errors: -1 null descriptor; -2 N < 1, A outside 1 .. 8, a stride shorter than its row (ld_raw, ld_d_raw < 2A; ld_eps,
+ * ld_d_actions < A; ld_obs < D; ld_actions < D + A), D and obs not given together, d_log_prob_stride not 0 or 1,
+ * log_std_min >= log_std_max, M < 1 with an index, gamma or target_entropy not finite, a workspace too small or not 4-byte aligned;
+ * -3 a required pointer is NULL (d_actions and d_log_prob both NULL; q2 and its companions given in part), or an output (the workspace
+ * included) overlaps an input or another output. */
+typedef struct pdegym_squashed_gaussian_sample_args {
+  int32_t A;                   /* action dimensions, 1 .. 8                                                                    */
+  int32_t D;                   /* observation columns copied in front of the actions; 0 without obs                            */
+  const float* raw;            /* [N, ld_raw]: columns [mu; log_std], 2A of them                                               */
+  int64_t ld_raw;              /* >= 2A                                                                                        */
+  const float* eps;            /* [N, ld_eps]                                                                                  */
+  int64_t ld_eps;              /* >= A                                                                                         */
+  float log_std_min, log_std_max;
+  const float* obs;            /* optional [N, ld_obs]                                                                         */
+  int64_t ld_obs;              /* >= D                                                                                         */
+  float* actions;              /* [N, ld_actions] out: columns [0, D) the observation, [D, D + A) the actions                  */
+  int64_t ld_actions;          /* >= D + A                                                                                     */
+  float* log_prob;             /* [N] out                                                                                      */
+} pdegym_squashed_gaussian_sample_args;
+int pdegym_squashed_gaussian_sample(const pdegym_squashed_gaussian_sample_args* s, int32_t N, void* stream);
+
+typedef struct pdegym_squashed_gaussian_sample_backward_args {
+  int32_t A;
+  int32_t reserved_;
+  const float* raw;            /* [N, ld_raw], as in the forward call                                                          */
+  int64_t ld_raw;
+  const float* eps;            /* [N, ld_eps]                                                                                  */
+  int64_t ld_eps;
+  float log_std_min, log_std_max;
+  const float* d_actions;      /* optional [N, ld_d_actions]                                                                   */
+  int64_t ld_d_actions;        /* >= A                                                                                         */
+  const float* d_log_prob;     /* optional; not both NULL                                                                      */
+  int64_t d_log_prob_stride;   /* 1: a dense [N] array; 0: one device scalar                                                   */
+  float* d_raw;                /* [N, ld_d_raw] out, columns < 2A written                                                      */
+  int64_t ld_d_raw;            /* >= 2A                                                                                        */
+} pdegym_squashed_gaussian_sample_backward_args;
+int pdegym_squashed_gaussian_sample_backward(const pdegym_squashed_gaussian_sample_backward_args* s, int32_t N, void* stream);
+
+typedef struct pdegym_sac_critic_loss_args {
+  const float* q1;             /* [N]                                                                                          */
+  const float* q2;             /* optional [N]; with q2_target and d_q2                                                        */
+  const float* q1_target;      /* [N]                                                                                          */
+  const float* q2_target;      /* optional [N]                                                                                 */
+  const float* next_log_prob;  /* [N]                                                                                          */
+  const int64_t* index;        /* optional [N], entries in [0, M); NULL = row i                                                */
+  int64_t M;                   /* rows of rewards / dones (used with index; without it they have N rows)                       */
+  const float* rewards;        /* [M]                                                                                          */
+  const float* dones;          /* [M], 0.0 or 1.0                                                                              */
+  const float* log_alpha;      /* DEVICE pointer to one float                                                                  */
+  double gamma;                /* the Python double                                                                            */
+  float* d_q1;                 /* [N] out                                                                                      */
+  float* d_q2;                 /* [N] out; given if and only if q2 is                                                          */
+  float* target;               /* optional [N] out                                                                             */
+  float* stats;                /* optional [4] out                                                                             */
+  void* workspace;             /* pdegym_sac_loss_workspace(N) bytes, 4-BYTE ALIGNED (else -2)                                 */
+  int64_t workspace_bytes;
+} pdegym_sac_critic_loss_args;
+int pdegym_sac_critic_loss(const pdegym_sac_critic_loss_args* g, int32_t N, void* stream);
+
+typedef struct pdegym_sac_actor_loss_args {
+  const float* q1_pi;          /* [N]                                                                                          */
+  const float* q2_pi;          /* optional [N]; with d_q2_pi                                                                   */
+  const float* log_prob;       /* [N]                                                                                          */
+  const float* log_alpha;      /* DEVICE pointer to one float                                                                  */
+  double target_entropy;       /* the Python double                                                                            */
+  float* d_q1_pi;              /* [N] out                                                                                      */
+  float* d_q2_pi;              /* [N] out; given if and only if q2_pi is                                                       */
+  float* d_log_prob;           /* [1] out                                                                                      */
+  float* d_log_alpha;          /* [1] out                                                                                      */
+  float* stats;                /* optional [4] out                                                                             */
+  void* workspace;             /* pdegym_sac_loss_workspace(N) bytes, 4-BYTE ALIGNED (else -2)                                 */
+  int64_t workspace_bytes;
+} pdegym_sac_actor_loss_args;
+int pdegym_sac_actor_loss(const pdegym_sac_actor_loss_args* g, int32_t N, void* stream);
+int64_t pdegym_sac_loss_workspace(int32_t N);      /* bytes, for either loss; negative: error code (N < 1)                      */
 
 /* ---- test-only: kernel dispatch overrides -------------------------------------------------------------------------
  * Nothing on the product path calls this (the reference has no counterpart); the parity tests use it to run the SAME step

@@ -38,6 +38,8 @@ EXPORTS = [
     "pdegym_traffic_backstep_control", "pdegym_traffic_backstep_rollout", "pdegym_tumor_therapy_step", "pdegym_tumor_rollout",
     "pdegym_gae", "pdegym_mlp_backward", "pdegym_mlp_backward_workspace",
     "pdegym_ppo_loss", "pdegym_ppo_loss_workspace", "pdegym_diag_gaussian_log_prob",
+    "pdegym_squashed_gaussian_sample", "pdegym_squashed_gaussian_sample_backward", "pdegym_sac_critic_loss", "pdegym_sac_actor_loss",
+    "pdegym_sac_loss_workspace",
 ]
 # keys of pdegym_debug_set (test-only dispatch overrides, include/pdegym.h)
 DEBUG_NS_GENERIC, DEBUG_NS_NO_COL, DEBUG_NS_COL_MIN_BATCH, DEBUG_NS_NO_LDS_JACOBI = range(4)
@@ -49,6 +51,9 @@ BACKSTEP_TREE, BACKSTEP_ORDERED = 0, 1
 TRAFFIC_BACKSTEP_TREE, TRAFFIC_BACKSTEP_NUMPY = 0, 1
 PPO_LOSS_MAX_A = 8                      # action dimensions of pdegym_ppo_loss / pdegym_diag_gaussian_log_prob
 PPO_LOSS_STATS = ("loss", "policy_loss", "value_loss", "entropy_loss", "approx_kl", "clip_fraction", "adv_mean", "adv_std")
+SAC_LOSS_MAX_A = 8                      # action dimensions of pdegym_squashed_gaussian_sample (+ _backward)
+SAC_CRITIC_STATS = ("critic_loss", "q1_mean", "q2_mean", "target_mean")
+SAC_ACTOR_STATS = ("actor_loss", "ent_coef_loss", "alpha", "log_prob_mean")
 TRAFFIC_BACKSTEP_NUMPY_MAX_M = 129      # the longest row whose np.trapz sum is un-recursed (128 terms)
 
 
@@ -213,6 +218,32 @@ class PpoLoss(C.Structure):
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
 
 
+class SquashedGaussianSample(C.Structure):
+    _fields_ = [("A", C.c_int32), ("D", C.c_int32), ("raw", C.c_void_p), ("ld_raw", C.c_int64), ("eps", C.c_void_p),
+                ("ld_eps", C.c_int64), ("log_std_min", C.c_float), ("log_std_max", C.c_float), ("obs", C.c_void_p),
+                ("ld_obs", C.c_int64), ("actions", C.c_void_p), ("ld_actions", C.c_int64), ("log_prob", C.c_void_p)]
+
+
+class SquashedGaussianSampleBackward(C.Structure):
+    _fields_ = [("A", C.c_int32), ("reserved_", C.c_int32), ("raw", C.c_void_p), ("ld_raw", C.c_int64), ("eps", C.c_void_p),
+                ("ld_eps", C.c_int64), ("log_std_min", C.c_float), ("log_std_max", C.c_float), ("d_actions", C.c_void_p),
+                ("ld_d_actions", C.c_int64), ("d_log_prob", C.c_void_p), ("d_log_prob_stride", C.c_int64), ("d_raw", C.c_void_p),
+                ("ld_d_raw", C.c_int64)]
+
+
+class SacCriticLoss(C.Structure):
+    _fields_ = [("q1", C.c_void_p), ("q2", C.c_void_p), ("q1_target", C.c_void_p), ("q2_target", C.c_void_p),
+                ("next_log_prob", C.c_void_p), ("index", C.c_void_p), ("M", C.c_int64), ("rewards", C.c_void_p), ("dones", C.c_void_p),
+                ("log_alpha", C.c_void_p), ("gamma", C.c_double), ("d_q1", C.c_void_p), ("d_q2", C.c_void_p), ("target", C.c_void_p),
+                ("stats", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
+class SacActorLoss(C.Structure):
+    _fields_ = [("q1_pi", C.c_void_p), ("q2_pi", C.c_void_p), ("log_prob", C.c_void_p), ("log_alpha", C.c_void_p),
+                ("target_entropy", C.c_double), ("d_q1_pi", C.c_void_p), ("d_q2_pi", C.c_void_p), ("d_log_prob", C.c_void_p),
+                ("d_log_alpha", C.c_void_p), ("stats", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
 class NativeError(RuntimeError):
     pass
 
@@ -309,6 +340,14 @@ def load():
     lib.pdegym_diag_gaussian_log_prob.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                                   C.c_int32, C.c_int32, C.c_void_p]
     lib.pdegym_diag_gaussian_log_prob.restype = C.c_int
+    for name, struct in (("pdegym_squashed_gaussian_sample", SquashedGaussianSample),
+                         ("pdegym_squashed_gaussian_sample_backward", SquashedGaussianSampleBackward),
+                         ("pdegym_sac_critic_loss", SacCriticLoss), ("pdegym_sac_actor_loss", SacActorLoss)):
+        f = getattr(lib, name)
+        f.argtypes = [C.POINTER(struct), C.c_int32, C.c_void_p]
+        f.restype = C.c_int
+    lib.pdegym_sac_loss_workspace.argtypes = [C.c_int32]
+    lib.pdegym_sac_loss_workspace.restype = C.c_int64
     lib.pdegym_debug_set.argtypes = [C.c_int32, C.c_int32]
     lib.pdegym_debug_set.restype = C.c_int32
     if lib.pdegym_abi_version() != ABI_VERSION:

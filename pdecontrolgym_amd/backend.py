@@ -664,6 +664,145 @@ class HipBackend:
                                                        None if index is None else index.data_ptr(), out.data_ptr(), n, A,
                                                        N.current_stream_ptr(dev)), "pdegym_diag_gaussian_log_prob")
 
+    def _sac_workspace(self, what, workspace, n, dev):
+        import torch
+        if workspace is None:
+            need = int(self.lib.pdegym_sac_loss_workspace(n))
+            if need < 0:
+                N.check(need, "pdegym_sac_loss_workspace")
+            return self._mlp_backward_workspace(dev, need)
+        if not torch.is_tensor(workspace) or workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous():
+            raise N.NativeError(f"{what}: workspace must be a contiguous uint8 tensor on the device of the other tensors")
+        return workspace
+
+    @staticmethod
+    def _sac_shape(what, name, x):
+        import torch
+        if not torch.is_tensor(x) or x.dim() != 2:
+            raise N.NativeError(f"{what}: {name} must be a float32 2-D tensor")
+        return (int(s) for s in x.shape)
+
+    @_on_device_of("raw")
+    def squashed_gaussian_sample(self, raw, eps, actions, log_prob, log_std_min: float, log_std_max: float, obs=None):
+        """a = tanh(mu + exp(clip(log_std)) * eps) and SB3's squashed-Gaussian log-probability of it in one launch
+        (pdegym_squashed_gaussian_sample).  ``raw`` [N, 2A] = [mu; log_std], ``eps`` [N, A]; outputs ``actions`` [N, A] -- or, with
+        ``obs`` [N, D], the block [N, D + A] whose first D columns receive the observation -- and ``log_prob`` [N].  Everything float32
+        with unit inner stride (2-D tensors may have a row stride), on one device."""
+        import torch
+        what = "squashed_gaussian_sample"
+        n, A2 = self._sac_shape(what, "raw", raw)
+        A, dev, f32 = A2 // 2, raw.device, torch.float32
+        if A2 != 2 * A or A < 1:
+            raise N.NativeError(f"{what}: raw must have 2A columns [mu; log_std], got {A2}")
+        D = 0
+        if obs is not None:
+            _, D = self._sac_shape(what, "obs", obs)
+        s = N.SquashedGaussianSample()
+        s.A, s.D, s.log_std_min, s.log_std_max = A, D, float(log_std_min), float(log_std_max)
+        s.ld_raw = self._ppo_rows(what, "raw", raw, n, 2 * A, f32, dev)
+        s.ld_eps = self._ppo_rows(what, "eps", eps, n, A, f32, dev)
+        s.ld_actions = self._ppo_rows(what, "actions", actions, n, D + A, f32, dev)
+        self._ppo_rows(what, "log_prob", log_prob, n, None, f32, dev)
+        if obs is not None:
+            s.ld_obs = self._ppo_rows(what, "obs", obs, n, D, f32, dev)
+            s.obs = obs.data_ptr()
+        s.raw, s.eps, s.actions, s.log_prob = raw.data_ptr(), eps.data_ptr(), actions.data_ptr(), log_prob.data_ptr()
+        N.check(self.lib.pdegym_squashed_gaussian_sample(C.byref(s), n, N.current_stream_ptr(dev)), "pdegym_squashed_gaussian_sample")
+
+    @_on_device_of("raw")
+    def squashed_gaussian_sample_backward(self, raw, eps, d_actions, d_log_prob, d_raw, log_std_min: float, log_std_max: float):
+        """``d_raw`` [N, 2A] from ``d_actions`` [N, A] (any row stride: the action columns of a critic's dx in place) and / or
+        ``d_log_prob`` -- a dense [N] tensor, or a 1-element tensor / a [N] tensor of stride 0: one device scalar for all rows --
+        in one launch (pdegym_squashed_gaussian_sample_backward); either may be None, not both."""
+        import torch
+        what = "squashed_gaussian_sample_backward"
+        n, A2 = self._sac_shape(what, "raw", raw)
+        A, dev, f32 = A2 // 2, raw.device, torch.float32
+        if A2 != 2 * A or A < 1:
+            raise N.NativeError(f"{what}: raw must have 2A columns [mu; log_std], got {A2}")
+        s = N.SquashedGaussianSampleBackward()
+        s.A, s.log_std_min, s.log_std_max = A, float(log_std_min), float(log_std_max)
+        s.ld_raw = self._ppo_rows(what, "raw", raw, n, 2 * A, f32, dev)
+        s.ld_eps = self._ppo_rows(what, "eps", eps, n, A, f32, dev)
+        s.ld_d_raw = self._ppo_rows(what, "d_raw", d_raw, n, 2 * A, f32, dev)
+        if d_actions is not None:
+            s.ld_d_actions = self._ppo_rows(what, "d_actions", d_actions, n, A, f32, dev)
+            s.d_actions = d_actions.data_ptr()
+        if d_log_prob is not None:
+            if torch.is_tensor(d_log_prob) and d_log_prob.dim() == 1 and d_log_prob.dtype == f32 and d_log_prob.device == dev and (
+                    d_log_prob.shape[0] == 1 or (d_log_prob.shape[0] == n and d_log_prob.stride(0) == 0)):
+                s.d_log_prob_stride = 0
+            else:
+                self._ppo_rows(what, "d_log_prob", d_log_prob, n, None, f32, dev)
+                s.d_log_prob_stride = 1
+            s.d_log_prob = d_log_prob.data_ptr()
+        s.raw, s.eps, s.d_raw = raw.data_ptr(), eps.data_ptr(), d_raw.data_ptr()
+        N.check(self.lib.pdegym_squashed_gaussian_sample_backward(C.byref(s), n, N.current_stream_ptr(dev)),
+                "pdegym_squashed_gaussian_sample_backward")
+
+    @_on_device_of("q1")
+    def sac_critic_loss(self, q1, q2, q1_target, q2_target, next_log_prob, rewards, dones, log_alpha, gamma: float, d_q1, d_q2,
+                        target=None, stats=None, index=None, workspace=None):
+        """SAC's critic loss and its gradients in two launches (pdegym_sac_critic_loss).  ``q1`` / ``q2`` / ``q1_target`` /
+        ``q2_target`` / ``next_log_prob`` [N] dense (``q2``, ``q2_target``, ``d_q2`` None: one critic); ``rewards`` / ``dones`` [M]
+        float32 gathered by ``index`` (int64 [N]) or M = N; ``log_alpha`` a 1-element DEVICE tensor.  Outputs ``d_q1`` / ``d_q2`` [N],
+        optional ``target`` [N] and ``stats`` [4] (``N.SAC_CRITIC_STATS``)."""
+        import torch
+        what = "sac_critic_loss"
+        if not torch.is_tensor(q1) or q1.dim() != 1:
+            raise N.NativeError(f"{what}: q1 must be a float32 [N] tensor")
+        n, dev, f32 = int(q1.shape[0]), q1.device, torch.float32
+        M = n if index is None else (int(rewards.shape[0]) if torch.is_tensor(rewards) and rewards.dim() == 1 else -1)
+        g = N.SacCriticLoss()
+        g.M, g.gamma = M, float(gamma)
+        if len({q2 is None, q2_target is None, d_q2 is None}) != 1:
+            raise N.NativeError(f"{what}: q2, q2_target and d_q2 are given together")
+        named = [("q1", q1, n, f32), ("q1_target", q1_target, n, f32), ("next_log_prob", next_log_prob, n, f32), ("rewards", rewards, M, f32),
+                 ("dones", dones, M, f32), ("log_alpha", log_alpha, 1, f32), ("d_q1", d_q1, n, f32)]
+        if q2 is not None:
+            named += [("q2", q2, n, f32), ("q2_target", q2_target, n, f32), ("d_q2", d_q2, n, f32)]
+        if index is not None:
+            named.append(("index", index, n, torch.int64))
+        if target is not None:
+            named.append(("target", target, n, f32))
+        if stats is not None:
+            named.append(("stats", stats, len(N.SAC_CRITIC_STATS), f32))
+        for name, x, rows, dtype in named:
+            self._ppo_rows(what, name, x, rows, None, dtype, dev)
+            setattr(g, name, x.data_ptr())
+        workspace = self._sac_workspace(what, workspace, n, dev)
+        g.workspace, g.workspace_bytes = workspace.data_ptr(), workspace.numel()
+        N.check(self.lib.pdegym_sac_critic_loss(C.byref(g), n, N.current_stream_ptr(dev)), "pdegym_sac_critic_loss")
+
+    @_on_device_of("q1_pi")
+    def sac_actor_loss(self, q1_pi, q2_pi, log_prob, log_alpha, target_entropy: float, d_q1_pi, d_q2_pi, d_log_prob, d_log_alpha,
+                       stats=None, workspace=None):
+        """SAC's actor and entropy-coefficient losses and their gradients in two launches (pdegym_sac_actor_loss).  ``q1_pi`` /
+        ``q2_pi`` (None with ``d_q2_pi``: one critic) / ``log_prob`` [N], ``log_alpha`` a 1-element DEVICE tensor.  Outputs
+        ``d_q1_pi`` / ``d_q2_pi`` [N], ``d_log_prob`` [1] (ONE scalar for all rows), ``d_log_alpha`` [1], optional ``stats`` [4]
+        (``N.SAC_ACTOR_STATS``)."""
+        import torch
+        what = "sac_actor_loss"
+        if not torch.is_tensor(q1_pi) or q1_pi.dim() != 1:
+            raise N.NativeError(f"{what}: q1_pi must be a float32 [N] tensor")
+        n, dev, f32 = int(q1_pi.shape[0]), q1_pi.device, torch.float32
+        if (q2_pi is None) != (d_q2_pi is None):
+            raise N.NativeError(f"{what}: q2_pi and d_q2_pi are given together")
+        g = N.SacActorLoss()
+        g.target_entropy = float(target_entropy)
+        named = [("q1_pi", q1_pi, n), ("log_prob", log_prob, n), ("log_alpha", log_alpha, 1), ("d_q1_pi", d_q1_pi, n),
+                 ("d_log_prob", d_log_prob, 1), ("d_log_alpha", d_log_alpha, 1)]
+        if q2_pi is not None:
+            named += [("q2_pi", q2_pi, n), ("d_q2_pi", d_q2_pi, n)]
+        if stats is not None:
+            named.append(("stats", stats, len(N.SAC_ACTOR_STATS)))
+        for name, x, rows in named:
+            self._ppo_rows(what, name, x, rows, None, f32, dev)
+            setattr(g, name, x.data_ptr())
+        workspace = self._sac_workspace(what, workspace, n, dev)
+        g.workspace, g.workspace_bytes = workspace.data_ptr(), workspace.numel()
+        N.check(self.lib.pdegym_sac_actor_loss(C.byref(g), n, N.current_stream_ptr(dev)), "pdegym_sac_actor_loss")
+
     @_on_device_of("obs")
     def backstep_rollout1d(self, kind: str, P: N.Params1D, T: dict, obs, actions, rewards, terminated, truncated, B: int, law: N.Backstep,
                            obs_noise=None, obs_seen=None):

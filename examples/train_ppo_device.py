@@ -14,8 +14,9 @@ algorithm in plain torch on the batched engine:
                 advantages, returns and the statistics of the episodes that ended inside the buffer in ONE launch
                 (``pdegym_gae``: SB3's ``compute_returns_and_advantage`` bit for bit) instead of a Python loop over T;
   * update   -- ordinary torch autograd on the same ``torch.nn.Sequential`` the rollout evaluates (``FusedMLP`` picks the new
-                weights up at the next ``run()``); with ``fused_grad`` and layers of at most 64 units, actor and critic go through
-                ``FusedMLP.with_grad`` instead: one forward launch and a three-launch backward (``pdegym_mlp_backward``) per network
+                weights up at the next ``run()``); with ``fused_grad`` and layers of at most 256 units, actor and critic go through
+                ``FusedMLP.with_grad`` instead: one forward launch and a three-launch backward (``pdegym_mlp_backward``, or
+                ``pdegym_mlp_backward_wide`` for layers of more than 64 units) per network
                 and minibatch that fill the same Parameters' ``.grad``, so the optimiser and the gradient clipping stay as they are;
                 with ``fused_loss`` everything between the networks' outputs and their backward passes is ``PPOLoss`` (at most three
                 launches, ``pdegym_ppo_loss``: the gathers by the minibatch's indices, log-probability, clipped surrogate, value and
@@ -90,10 +91,10 @@ def main(iterations=30, B=2048, T=64, quiet=False, hidden=64, fused_grad=False, 
     rollout = DeviceRollout(venv, policy, T, action_noise=True)
     # the networks of the update: the modules themselves under torch autograd, or their fused forward + backward launches
     actor_fn, critic_fn = actor, critic
-    if fused_grad and hidden <= 64:
+    if fused_grad and hidden <= 256:
         actor_fn, critic_fn = policy.with_grad, FusedMLP(critic).with_grad
     elif fused_grad and not quiet:
-        print(f"fused_grad: layers of {hidden} units are wider than the 64 the fused backward pass takes; the update uses torch autograd")
+        print(f"fused_grad: layers of {hidden} units are wider than the 256 the fused backward passes take; the update uses torch autograd")
     gamma, lam, clip, epochs, nmb = 0.99, 0.95, 0.2, 6, 4
     buffer = DeviceRolloutBuffer(rollout, gamma=gamma, gae_lambda=lam)
     head = PPOLoss(clip_range=clip, ent_coef=1e-3, vf_coef=0.25, normalize_advantage=True) if fused_loss else None

@@ -94,13 +94,14 @@ def main(iterations=30, num_envs=1024, n_steps=32, hidden=64, one_launch=None, q
     start = {k: [p.detach().clone() for p in ps] for k, ps in (("actor", actor_params), ("q1", list(q1.parameters())), ("q2", list(q2.parameters())))}
     policy = FusedMLP.squashed_gaussian(latent, mu, log_std, (LOG_STD_MIN, LOG_STD_MAX))
     rollout = DeviceRollout(venv, policy, T, action_low=lo, action_high=hi, action_noise=True, one_launch=one_launch)
-    # the networks of the update: the modules under torch autograd, or (fused_grad, layers of at most 64 units) FusedMLP.with_grad --
-    # the critics' gradient with respect to the action column is the dx of pdegym_mlp_backward
+    # the networks of the update: the modules under torch autograd, or (fused_grad, layers of at most 256 units -- SB3's own 256-256
+    # among them) FusedMLP.with_grad -- the critics' gradient with respect to the action column is the dx of pdegym_mlp_backward
+    # (layers of at most 64 units) or of pdegym_mlp_backward_wide
     q1_fn, q2_fn, raw_fn = q1, q2, None
-    if fused_grad and hidden <= 64:
+    if fused_grad and hidden <= 256:
         q1_fn, q2_fn, raw_fn = FusedMLP(q1).with_grad, FusedMLP(q2).with_grad, policy.with_grad
     elif fused_grad and not quiet:
-        print(f"fused_grad: layers of {hidden} units are wider than the 64 the fused backward pass takes; the update uses torch autograd")
+        print(f"fused_grad: layers of {hidden} units are wider than the 256 the fused backward passes take; the update uses torch autograd")
     # the replay buffer: device tensors, a ring of `cap` transitions filled T * B at a time
     cap = max(16 * T * B, batch)
     buf = {k: torch.zeros(cap, n, device=dev) for k, n in (("obs", D), ("next", D), ("act", 1), ("rew", 1), ("term", 1))}

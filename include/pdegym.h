@@ -684,6 +684,32 @@ typedef struct pdegym_mlp_backward_args {
 int64_t pdegym_mlp_backward_workspace(const pdegym_mlp* net, int32_t B, int32_t slabs);
 int pdegym_mlp_backward(const pdegym_mlp* net, const pdegym_mlp_backward_args* a, int32_t B, void* stream);
 
+/* ---- the same backward pass for layers of up to 256 units (Stable-Baselines3's SAC networks: actor and critics of 256-256 ReLU) ---
+ * pdegym_mlp_backward_wide takes the descriptor and the argument structure of pdegym_mlp_backward and gives the same gradients under
+ * the same contract (csrc/pdegym_mlp_backward_wide.hip, three launches whatever the number of layers); only what differs is said here.
+ *
+ * Limits   n_layers <= PDEGYM_MLP_MAX_LAYERS, every layer's out_dim <= PDEGYM_MLP_MAX_WIDTH (256), the first layer's in_dim <= 1024;
+ *          anything else is -2.  A superset of pdegym_mlp_backward's domain: narrow networks are taken too.
+ * Launches 1. tiles: a workgroup of 16 waves per tile of 16 rows recomputes every layer's activations (the forward kernel's reduction
+ *          and bits), forms dZ_l in place, stores dZ_l and H_{l-1} (l >= 1; H_{-1} is x itself) in the workspace and forms
+ *          dH_{l-1} = dZ_l W_l, dx for the first layer.  2. accumulation: per (layer, 64 units, 64 inputs, slab) the partial
+ *          dZ_l^T H_{l-1} of the slab's rows, and db_l from the same dZ_l.  3. the slabs' partials added in ascending order.
+ * Order of every sum: the one stated above.  dW_l, db_l: rows ascending within a slab (four MFMAs per tile of 16 rows), slabs
+ *          ascending.  dH_{l-1}: the layer's units in blocks of 16, ascending, in ONE accumulator chain (a 256-unit layer: 16 blocks).
+ *          Hence on a network both entry points take, with the same explicit `slabs`, both return IDENTICAL BITS in dw, db and dx.
+ * slabs    as above; 0: this entry's own choice, min(ceil(tiles / 8), 64) with tiles = ceil(B / 16) -- a function of B alone.  A
+ *          slab costs one write and one read of every partial (83 000 floats for a 66-256-256-1 critic, against 4 500 for the
+ *          66-64-64-1 one), so slabs hold at least 8 tiles (128 rows: the accumulation then reads 128 x (in + out) floats per
+ *          64 x 64 partial it writes) and there are at most 64 of them (B = 32768: 21 MB of partials for that critic).
+ * workspace  at least pdegym_mlp_backward_wide_workspace (net, B, slabs) bytes, 4-byte aligned (else -2):
+ *          16 tiles x sum_l (pad64(out_l) + [l >= 1] pad64(in_l)) floats of dZ_l / H_{l-1}, then slabs x sum_l out_l (in_l + 1)
+ *          floats of partials (pad64: rounded up to a multiple of 64).  Every byte that is read was written by the same call.
+ * Determinism, non-finite data, rows >= B, alignment (blocked weights 16 bytes, everything else its element's) and every error
+ * code: as for pdegym_mlp_backward; -4 when the tile kernel's 130 KB of LDS cannot be granted (a compute unit of CDNA4 holds 160 KB).  No
+ * floating-point atomics, tickets or fences: stream order is the only synchronisation between the three launches. */
+int64_t pdegym_mlp_backward_wide_workspace(const pdegym_mlp* net, int32_t B, int32_t slabs);
+int pdegym_mlp_backward_wide(const pdegym_mlp* net, const pdegym_mlp_backward_args* a, int32_t B, void* stream);
+
 /* ---- backstepping baseline (the controller every result table of the reference compares the learned policies against) ------
  * Gains: theta [R, m] float32 rows, sampled by the caller (the examples use linspace(dx, X, m), NOT the plant's grid) -> gain [R, m]
  * float64, one wave per row, 2 <= m <= PDEGYM_MAX_N1D; dx is the Python double.  Both are BIT-IDENTICAL to the reference under

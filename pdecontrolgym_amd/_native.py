@@ -39,7 +39,7 @@ EXPORTS = [
     "pdegym_gae", "pdegym_mlp_backward", "pdegym_mlp_backward_workspace",
     "pdegym_ppo_loss", "pdegym_ppo_loss_workspace", "pdegym_diag_gaussian_log_prob",
     "pdegym_squashed_gaussian_sample", "pdegym_squashed_gaussian_sample_backward", "pdegym_sac_critic_loss", "pdegym_sac_actor_loss",
-    "pdegym_sac_loss_workspace",
+    "pdegym_sac_loss_workspace", "pdegym_mlp_backward_wide", "pdegym_mlp_backward_wide_workspace",
 ]
 # keys of pdegym_debug_set (test-only dispatch overrides, include/pdegym.h)
 DEBUG_NS_GENERIC, DEBUG_NS_NO_COL, DEBUG_NS_COL_MIN_BATCH, DEBUG_NS_NO_LDS_JACOBI = range(4)
@@ -47,6 +47,7 @@ MLP_MAX_LAYERS, MLP_MAX_WIDTH, MLP_MAX_INPUT = 4, 256, 8192
 MLP_IDENTITY, MLP_TANH, MLP_RELU = 0, 1, 2
 MLP_HEAD_PLAIN, MLP_HEAD_SQUASHED_GAUSSIAN = 0, 1
 MLP_BACKWARD_MAX_WIDTH, MLP_BACKWARD_MAX_INPUT = 64, 1024      # pdegym_mlp_backward: widest layer, widest first-layer input
+MLP_BACKWARD_WIDE_MAX_WIDTH, MLP_BACKWARD_WIDE_MAX_INPUT = 256, 1024      # pdegym_mlp_backward_wide: the same two limits
 BACKSTEP_TREE, BACKSTEP_ORDERED = 0, 1
 TRAFFIC_BACKSTEP_TREE, TRAFFIC_BACKSTEP_NUMPY = 0, 1
 PPO_LOSS_MAX_A = 8                      # action dimensions of pdegym_ppo_loss / pdegym_diag_gaussian_log_prob
@@ -333,6 +334,10 @@ def load():
     lib.pdegym_mlp_backward_workspace.restype = C.c_int64
     lib.pdegym_mlp_backward.argtypes = [C.POINTER(Mlp), C.POINTER(MlpBackward), C.c_int32, C.c_void_p]
     lib.pdegym_mlp_backward.restype = C.c_int
+    lib.pdegym_mlp_backward_wide_workspace.argtypes = [C.POINTER(Mlp), C.c_int32, C.c_int32]
+    lib.pdegym_mlp_backward_wide_workspace.restype = C.c_int64
+    lib.pdegym_mlp_backward_wide.argtypes = [C.POINTER(Mlp), C.POINTER(MlpBackward), C.c_int32, C.c_void_p]
+    lib.pdegym_mlp_backward_wide.restype = C.c_int
     lib.pdegym_ppo_loss_workspace.argtypes = [C.c_int32, C.c_int32]
     lib.pdegym_ppo_loss_workspace.restype = C.c_int64
     lib.pdegym_ppo_loss.argtypes = [C.POINTER(PpoLoss), C.c_int32, C.c_void_p]

@@ -455,7 +455,20 @@ class HipBackend:
         ``dw[l]`` / ``db[l]`` (None where the layer has no bias) contiguous float32 outputs of the parameters' shapes, written, not
         accumulated; ``dx`` [B, in_dim] float32 or None.  ``slabs``: include/pdegym.h (0: the library's choice).  The workspace is
         the backend's own, cached per (device, size)."""
+        self._mlp_backward_call("mlp_backward", self._mlp_backward_workspace, net, x, dy, weights, dw, db, dx, slabs)
+
+    @_on_device_of("x")
+    def mlp_backward_wide(self, net: N.Mlp, x, dy, weights, dw, db, dx=None, slabs: int = 0):
+        """``mlp_backward`` for layers of up to 256 units (pdegym_mlp_backward_wide: the tile launch, one accumulation launch over
+        every layer's dZ^T H, the slab reduction): the same arguments, checked the same way, and on a network both take with the
+        same explicit ``slabs`` the same bits.  ``slabs`` = 0 is this entry's own choice (include/pdegym.h).  Its workspace is a
+        cache of its own, per (device, size)."""
+        self._mlp_backward_call("mlp_backward_wide", self._mlp_backward_wide_workspace, net, x, dy, weights, dw, db, dx, slabs)
+
+    def _mlp_backward_call(self, entry: str, workspace, net, x, dy, weights, dw, db, dx, slabs):
+        """The argument checks and the call of ``pdegym_<entry>`` (``entry``: mlp_backward / mlp_backward_wide; one argument structure)."""
         import torch
+        query, call = getattr(self.lib, f"pdegym_{entry}_workspace"), getattr(self.lib, f"pdegym_{entry}")
         B, nl = int(x.shape[0]) if x.dim() == 2 else -1, int(net.n_layers)
         want_x = torch.float64 if net.x_f64 else torch.float32
         rows = (("x", x, want_x, int(net.layer[0].in_dim)), ("dy", dy, torch.float32, int(net.layer[nl - 1].out_dim)),
@@ -465,9 +478,9 @@ class HipBackend:
                 continue
             if (not torch.is_tensor(t_) or not t_.is_cuda or t_.device != x.device or t_.dtype != dtype or t_.dim() != 2
                     or tuple(t_.shape) != (B, width) or (width > 1 and t_.stride(1) != 1) or (B > 1 and t_.stride(0) < width)):
-                raise N.NativeError(f"mlp_backward: {name} must be a {dtype} HIP tensor [{B}, {width}] with unit inner stride on x's device")
+                raise N.NativeError(f"{entry}: {name} must be a {dtype} HIP tensor [{B}, {width}] with unit inner stride on x's device")
         if not (len(weights) == len(dw) == len(db) == nl):
-            raise N.NativeError(f"mlp_backward: weights, dw and db must have one entry per layer ({nl})")
+            raise N.NativeError(f"{entry}: weights, dw and db must have one entry per layer ({nl})")
         a = N.MlpBackward()
         for l in range(nl):
             shape = (int(net.layer[l].out_dim), int(net.layer[l].in_dim))
@@ -476,22 +489,31 @@ class HipBackend:
                     continue
                 if (not torch.is_tensor(t_) or not t_.is_cuda or t_.device != x.device or t_.dtype != torch.float32
                         or tuple(t_.shape) != shp or not t_.is_contiguous()):
-                    raise N.NativeError(f"mlp_backward: {name}[{l}] must be a contiguous float32 HIP tensor {shp} on x's device")
+                    raise N.NativeError(f"{entry}: {name}[{l}] must be a contiguous float32 HIP tensor {shp} on x's device")
             a.w[l], a.dw[l], a.db[l] = weights[l].data_ptr(), dw[l].data_ptr(), (None if db[l] is None else db[l].data_ptr())
-        need = int(self.lib.pdegym_mlp_backward_workspace(C.byref(net), B, int(slabs)))
+        need = int(query(C.byref(net), B, int(slabs)))
         if need < 0:
-            N.check(need, "pdegym_mlp_backward_workspace")
-        ws = self._mlp_backward_workspace(x.device, need)
+            N.check(need, f"pdegym_{entry}_workspace")
+        ws = workspace(x.device, need)
         a.x, a.x_stride, a.dy, a.dy_stride = x.data_ptr(), (x.stride(0) if B > 1 else x.shape[1]), dy.data_ptr(), (dy.stride(0) if B > 1 else dy.shape[1])
         if dx is not None:
             a.dx, a.dx_stride = dx.data_ptr(), (dx.stride(0) if B > 1 else dx.shape[1])
         a.slabs, a.workspace, a.workspace_bytes = int(slabs), ws.data_ptr(), ws.numel()
-        N.check(self.lib.pdegym_mlp_backward(C.byref(net), C.byref(a), B, N.current_stream_ptr(x.device)), "pdegym_mlp_backward")
+        N.check(call(C.byref(net), C.byref(a), B, N.current_stream_ptr(x.device)), f"pdegym_{entry}")
 
     def _mlp_backward_workspace(self, device, nbytes: int):
         """The workspace of ``mlp_backward``: one uint8 tensor per (device, size), kept (every launch of one stream uses it in turn)."""
         import torch
         cache = self.__dict__.setdefault("_mlp_bw_ws", {})
+        key = (device.index, nbytes)
+        if key not in cache:
+            cache[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        return cache[key]
+
+    def _mlp_backward_wide_workspace(self, device, nbytes: int):
+        """The workspace of ``mlp_backward_wide``, kept apart from ``mlp_backward``'s: one uint8 tensor per (device, size)."""
+        import torch
+        cache = self.__dict__.setdefault("_mlp_bw_wide_ws", {})
         key = (device.index, nbytes)
         if key not in cache:
             cache[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)

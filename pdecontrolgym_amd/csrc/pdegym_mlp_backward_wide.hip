@@ -1,0 +1,486 @@
+// pdegym_mlp_backward_wide.hip -- backward pass of the MLP that pdegym_mlp_forward evaluates, for layers of up to 256 units (see
+// include/pdegym.h: pdegym_mlp_backward_wide): dW, db of every layer and optionally dx, float32, deterministic, no atomics.
+//
+// The caller is the update half of the reference's SAC scripts ("MlpPolicy" of Stable-Baselines3: an actor and two critics of
+// 256-256 ReLU units).  pdegym_mlp_backward.hip keeps the dW_l accumulators of its hidden layers in registers across a slab, which
+// ends at 64 units: a [256, 256] dW is 256 KB, more than the register file of a SIMD.  Here EVERY layer's dZ_l and H_{l-1} go through
+// the workspace and one accumulation launch forms every dZ_l^T H_{l-1}:
+//
+//   1. mlp_backward_wide_tiles: a workgroup of 16 waves (the forward kernel's, one 16-unit tile of a 256-unit layer per wave) owns ONE
+//      16-row tile.  It recomputes the activations of every layer into LDS with the forward kernel's own reduction
+//      (pdegym_mlp_tile.h: the same bits), then walks the layers backwards: dZ_l = dH_l * act'(H_l) elementwise, in place; dZ_l and
+//      H_{l-1} (l >= 1; the first layer's input is x itself) to the workspace; dH_{l-1} = dZ_l W_l on the matrix cores into LDS, or
+//      into dx for the first layer.  It keeps nothing from one tile to the next, so its grid has no bearing on any sum.
+//   2. mlp_backward_wide_accumulate: a workgroup of four waves owns (layer, 64-unit block, 64-input block, slab): the partial
+//      dZ_l^T H_{l-1} of the slab's rows, ascending; the workgroups of input block 0 form db_l from the same dZ_l.  No LDS, no barrier.
+//   3. mlp_backward_wide_reduce: dw, db = the slabs' partials added in ascending slab order, one thread per element.
+//
+// All products run on v_mfma_f32_16x16x4_f32 (float32 in, float32 accumulate: an exact fmaf chain), in the order the header states
+// for pdegym_mlp_backward: rows ascending within a slab (four MFMAs per 16-row tile), slabs ascending, a layer's units in blocks of
+// 16 in ONE accumulator chain (four MFMAs per block, unit 16 kb + 4 lg + c in the c-th).  On a network both entry points take, with
+// the same explicit slab count, the two return identical bits.  Rows >= B of the last tile are selected to zero (never multiplied by
+// zero) and never read.
+//
+// The launches are made with hipLaunchKernel, the runtime's C entry point; tests/test_mlp_backward_wide.py
+// reads the kernels launched here from the launch(...) calls below.  Range / extent / the slab arithmetic restate those of
+// pdegym_mlp_backward.hip: that file stays byte for byte what it is, so they are not moved into a header.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "pdegym.h"
+#include "pdegym_common.h"
+#include "pdegym_mlp_tile.h"
+
+namespace {
+
+using namespace pdegym_mlp_tile;     // v4f, lds_stride, kStage, activate, load_w, reduce_blocks
+
+constexpr int kRows = 16;                   // rows per tile (the M of the MFMA tile)
+constexpr int kWaves = 16;                  // waves of the tile kernel: one 16-unit tile of the widest layer each
+constexpr int kWidth = PDEGYM_MLP_MAX_WIDTH;      // 256: widest layer output this file takes
+constexpr int kMaxIn = 1024;                // widest first-layer input
+constexpr int kLayers = PDEGYM_MLP_MAX_LAYERS;
+constexpr int kLdh = lds_stride(kWidth);    // 260: LDS row stride of a [16, 256] block
+constexpr int kXChunk = 512;                // observation entries per row staged at a time, as in the forward kernel
+constexpr int kBlock = 64;                  // units / inputs per workgroup of the accumulation kernel; the workspace rows are padded to it
+constexpr int kSlabTiles = 8;               // the library's choice: slabs of at least 8 tiles (128 rows) ...
+constexpr int kMaxSlabs = 64;               // ... and at most 64 of them
+constexpr int kMaxLdsBytes = ((kLayers + 2) * kRows * kLdh + kRows * lds_stride(kXChunk)) * (int)sizeof(float);      // 132 864
+static_assert(kWidth == 16 * kWaves, "one 16-unit tile per wave");
+static_assert(kMaxLdsBytes <= 160 * 1024, "the LDS of a CDNA4 compute unit");
+
+struct Plan {
+  const void* x;
+  long long x_stride;
+  const float* dy;
+  long long dy_stride;
+  const float* w[kLayers];      // row-major [out, in]
+  float* dw[kLayers];
+  float* db[kLayers];
+  float* dx;
+  long long dx_stride;
+  float* dz[kLayers];           // workspace: [16 * tiles, hp[l]] dZ_l, zero in rows >= B and columns >= out_dim
+  float* hin[kLayers];          // workspace: [16 * tiles, kp[l]] H_{l-1} for l >= 1, zero likewise (hin[0] is not used: x)
+  float* part;                  // workspace: [slabs, per_slab] partial dW_l, db_l of every layer, in the order of off_w / off_b
+  int off_w[kLayers], off_b[kLayers];
+  int in[kLayers], out[kLayers];
+  int hp[kLayers], kp[kLayers];      // out / in rounded up to a multiple of 64
+  int item0[kLayers + 1];            // first (unit block, input block) work item of layer l in the accumulation grid
+  int per_slab, n_layers, B, tiles, slabs;
+};
+
+__device__ __forceinline__ v4f mma(float a, float b, v4f acc) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0); }
+
+__device__ __forceinline__ int slab_begin(const Plan& P, int slab) { return (int)((long long)slab * P.tiles / P.slabs); }
+
+// torch's backward ops (tanh_backward, threshold_backward), each operation rounded on its own
+__device__ __forceinline__ float act_backward(float dh, float h, int act) {
+  if (act == PDEGYM_MLP_TANH) return __fmul_rn(dh, __fsub_rn(1.0f, __fmul_rn(h, h)));
+  if (act == PDEGYM_MLP_RELU) return h <= 0.f ? 0.f : dh;      // a NaN activation passes the gradient
+  return dh;
+}
+
+template <typename TX>
+__global__ __launch_bounds__(64 * kWaves) void mlp_backward_wide_tiles(pdegym_mlp N, Plan P, int ldx) {
+  extern __shared__ __attribute__((aligned(16))) float bww_smem[];
+  float* const hs = bww_smem;                                  // [kLayers][16][kLdh]: the activations of every layer
+  float* const gs = hs + kLayers * kRows * kLdh;               // [2][16][kLdh]: dH / dZ of the layer at hand, and of the one below
+  float* const xs = gs + 2 * kRows * kLdh;                     // [16][ldx]: a chunk of the observation rows
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int li = lane & 15, lg = lane >> 4;
+  const int er = tid >> 6, ec = tid & 63;      // elementwise passes: thread = (row er, columns ec, ec + 64, ec + 128, ec + 192)
+  const TX* __restrict__ x = static_cast<const TX*>(P.x);
+  const int B = P.B, nl = P.n_layers;
+  const int n = 16 * wave + li;                 // this lane's unit: neuron of the forward tiles
+  const int row0 = blockIdx.x * kRows;
+
+  // ---- forward, as pdegym_mlp_forward computes it: the same operands in the same order ------------------------------------------------
+#pragma unroll
+  for (int l = 0; l < kLayers; ++l) {
+    if (l >= nl) break;
+    const pdegym_mlp_layer L = N.layer[l];
+    const int K = L.in_dim, H = L.out_dim, ngroups = (K + 3) >> 2;
+    const v4f* __restrict__ wq = reinterpret_cast<const v4f*>(L.w);
+    const int col[1] = {n < H ? n : H - 1};
+    const bool any_tile = 16 * wave < H;
+    v4f acc[1] = {(v4f){0.f, 0.f, 0.f, 0.f}};
+    v4f wfirst[kStage][1];
+    if (l == 0) {
+      for (int c0 = 0; c0 < K; c0 += kXChunk) {
+        const int clen = (K - c0) < kXChunk ? (K - c0) : kXChunk;
+        const int cpad = (clen + 15) & ~15;
+        {
+          const int r = wave;      // one row per wave
+          const bool row_ok = row0 + r < B;
+          const TX* src = x + (long long)(row_ok ? row0 + r : 0) * P.x_stride + c0;
+          for (int c = lane; c < cpad; c += 64) xs[r * ldx + c] = (row_ok && c < clen) ? (float)src[c] : 0.f;
+        }
+        if (any_tile) load_w<1>(wfirst, wq, H, ngroups, c0 / 16, lg, col);
+        __syncthreads();
+        if (any_tile) reduce_blocks<1>(acc, wfirst, wq, H, ngroups, c0 / 16, cpad / 16, xs + li * ldx, lg, col);
+        __syncthreads();
+      }
+    } else if (any_tile) {
+      load_w<1>(wfirst, wq, H, ngroups, 0, lg, col);
+      reduce_blocks<1>(acc, wfirst, wq, H, ngroups, 0, (K + 15) >> 4, hs + ((l - 1) * kRows + li) * kLdh, lg, col);
+    }
+    const float bias = (L.b && n < H) ? L.b[n] : 0.f;
+    const float av[4] = {acc[0].x, acc[0].y, acc[0].z, acc[0].w};
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {      // D[row 4 lg + v][unit n]; zero past the layer's width and past the batch: all 256 columns are written
+      const int r = 4 * lg + v;
+      hs[(l * kRows + r) * kLdh + n] = (n < H && row0 + r < B) ? activate(av[v] + bias, L.act) : 0.f;
+    }
+    __syncthreads();
+  }
+
+  // ---- backward -----------------------------------------------------------------------------------------------------------------------
+  float* g = gs;                       // dH of the layer at hand, then its dZ in place
+  float* gn = gs + kRows * kLdh;       // dH of the layer below
+  {
+    int H = P.out[0];
+#pragma unroll
+    for (int k = 1; k < kLayers; ++k)
+      if (k < nl) H = P.out[k];
+    const bool row_ok = row0 + er < B;
+    const float* src = P.dy + (long long)(row_ok ? row0 + er : 0) * P.dy_stride;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int c = ec + 64 * j;
+      g[er * kLdh + c] = (row_ok && c < H) ? src[c] : 0.f;
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int l = kLayers - 1; l >= 0; --l) {
+    if (l >= nl) continue;
+    const int K = P.in[l], H = P.out[l], act = N.layer[l].act;
+    // dZ_l = dH_l * act'(H_l), in place; selected to zero outside the batch and the layer.  dZ_l and H_{l-1} go to the workspace, every
+    // row of the tile and every column up to the next multiple of 64: the accumulation kernel reads them without a bound.
+    {
+      float* const dzrow = P.dz[l] + (long long)(row0 + er) * P.hp[l];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int c = ec + 64 * j;
+        const bool ok = row0 + er < B && c < H;
+        const float dz = ok ? act_backward(g[er * kLdh + c], hs[(l * kRows + er) * kLdh + c], act) : 0.f;
+        g[er * kLdh + c] = dz;
+        if (c < P.hp[l]) dzrow[c] = dz;
+      }
+      if (l >= 1) {
+        float* const hrow = P.hin[l] + (long long)(row0 + er) * P.kp[l];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int c = ec + 64 * j;
+          if (c < P.kp[l]) hrow[c] = hs[((l - 1) * kRows + er) * kLdh + c];
+        }
+      }
+    }
+    __syncthreads();
+    // dH_{l-1} = dZ_l W_l (into dx for the first layer): A[row][unit] = dZ, B[unit][input] = W row-major, units in blocks of 16 in
+    // one accumulator chain
+    if (l >= 1 || P.dx) {
+      const float* __restrict__ W = P.w[l];
+      const int in_tiles = (K + 15) >> 4, unit_blocks = (H + 15) >> 4;
+      for (int t = wave; t < in_tiles; t += kWaves) {
+        const int i = 16 * t + li, ic = i < K ? i : K - 1;
+        v4f d = {0.f, 0.f, 0.f, 0.f};
+        for (int kb = 0; kb < unit_blocks; ++kb) {
+          const v4f a4 = *reinterpret_cast<const v4f*>(g + li * kLdh + 16 * kb + 4 * lg);
+          const int o = 16 * kb + 4 * lg;
+          float wv[4];
+#pragma unroll
+          for (int c = 0; c < 4; ++c) {
+            const float v = W[(long long)(o + c < H ? o + c : H - 1) * K + ic];
+            wv[c] = o + c < H ? v : 0.f;
+          }
+          d = mma(a4.x, wv[0], d);
+          d = mma(a4.y, wv[1], d);
+          d = mma(a4.z, wv[2], d);
+          d = mma(a4.w, wv[3], d);
+        }
+        const float dv[4] = {d.x, d.y, d.z, d.w};
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          const int r = 4 * lg + v;
+          if (l >= 1) gn[r * kLdh + i] = dv[v];                  // (i < 256: in_tiles <= 16)
+          else if (i < K && row0 + r < B) P.dx[(long long)(row0 + r) * P.dx_stride + i] = dv[v];
+        }
+      }
+    }
+    __syncthreads();
+    float* const swap = g;
+    g = gn, gn = swap;
+  }
+}
+
+// The partial dW_l of (work item blockIdx.x = layer, 64 units, 64 inputs; slab blockIdx.y) = dZ_l^T H_{l-1} over the slab's rows,
+// ascending, and with input block 0 the partial db_l = dZ_l^T 1.  No LDS, no barrier.
+template <typename TX>
+__global__ __launch_bounds__(256) void mlp_backward_wide_accumulate(Plan P) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int li = lane & 15, lg = lane >> 4;
+  // the layer of this work item and its figures, selected with constant indices (the plan lives in the kernel's arguments)
+  int l = 0, K = P.in[0], H = P.out[0], hp = P.hp[0], kp = P.kp[0], first = 0, off_w = P.off_w[0], off_b = P.off_b[0];
+  const float* __restrict__ dzl = P.dz[0];
+  const float* __restrict__ hl = nullptr;
+#pragma unroll
+  for (int k = 1; k < kLayers; ++k)
+    if (k < P.n_layers && (int)blockIdx.x >= P.item0[k]) {
+      l = k, K = P.in[k], H = P.out[k], hp = P.hp[k], kp = P.kp[k], first = P.item0[k], off_w = P.off_w[k], off_b = P.off_b[k];
+      dzl = P.dz[k], hl = P.hin[k];
+    }
+  const int B = P.B;
+  const int in_blocks = kp / kBlock, item = (int)blockIdx.x - first;
+  const int u0 = kBlock * (item / in_blocks) + 16 * wave, i0 = kBlock * (item % in_blocks);
+  if (u0 >= H) return;      // wave-uniform
+  const bool bias_too = i0 == 0;
+  const TX* __restrict__ x = static_cast<const TX*>(P.x);
+  v4f acc[4], accb = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int t = 0; t < 4; ++t) acc[t] = (v4f){0.f, 0.f, 0.f, 0.f};
+  const int t_end = slab_begin(P, blockIdx.y + 1);
+  for (int tile = slab_begin(P, blockIdx.y); tile < t_end; ++tile) {
+    const int row0 = tile * kRows;
+    float a[4], b[4][4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) a[s] = dzl[(long long)(row0 + 4 * s + lg) * hp + u0 + li];
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        const int r = row0 + 4 * s + lg, i = i0 + 16 * t + li;
+        if (l == 0) {
+          const bool ok = r < B && i < K;
+          const TX v = x[ok ? (long long)r * P.x_stride + i : 0];
+          b[t][s] = ok ? (float)v : 0.f;
+        } else {
+          b[t][s] = hl[(long long)r * kp + i];      // (padded to 64 columns and 16 rows, zero there)
+        }
+      }
+    if (bias_too) {
+#pragma unroll
+      for (int s = 0; s < 4; ++s) accb = mma(a[s], 1.0f, accb);
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      if (i0 + 16 * t < K) {      // wave-uniform
+#pragma unroll
+        for (int s = 0; s < 4; ++s) acc[t] = mma(a[s], b[t][s], acc[t]);
+      }
+    }
+  }
+  float* const part = P.part + (long long)blockIdx.y * P.per_slab;
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const float wv[4] = {acc[t].x, acc[t].y, acc[t].z, acc[t].w};
+    const int i = i0 + 16 * t + li;
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      const int o = u0 + 4 * lg + v;
+      if (o < H && i < K) part[off_w + o * K + i] = wv[v];
+    }
+  }
+  if (bias_too) {
+    const float bv[4] = {accb.x, accb.y, accb.z, accb.w};
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {      // D[unit u0 + 4 lg + v][column li]: every column of the db tile holds the sum
+      const int o = u0 + 4 * lg + v;
+      if (li == 0 && o < H) part[off_b + o] = bv[v];
+    }
+  }
+}
+
+// dw, db = the slabs' partials, added in ascending slab order; one thread per element, eight loads in flight
+__global__ __launch_bounds__(256) void mlp_backward_wide_reduce(Plan P) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= P.per_slab) return;
+  float* dst = nullptr;
+#pragma unroll
+  for (int l = 0; l < kLayers; ++l) {
+    if (l >= P.n_layers) break;
+    if (e >= P.off_w[l] && e < P.off_b[l]) dst = P.dw[l] + (e - P.off_w[l]);
+    if (e >= P.off_b[l] && e < P.off_b[l] + P.out[l]) dst = P.db[l] ? P.db[l] + (e - P.off_b[l]) : nullptr;
+  }
+  if (!dst) return;
+  const float* src = P.part + e;
+  float sum = src[0];
+  int k = 1;
+  for (; k + 8 <= P.slabs; k += 8) {
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = src[(long long)(k + j) * P.per_slab];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) sum = __fadd_rn(sum, v[j]);
+  }
+  for (; k < P.slabs; ++k) sum = __fadd_rn(sum, src[(long long)k * P.per_slab]);
+  *dst = sum;
+}
+
+// hipLaunchKernel takes the arguments as an array of pointers to them (their types are the kernel's: nothing is deduced from p)
+template <typename T>
+struct as_declared {
+  using type = T;
+};
+template <typename... A>
+void launch(void (*kernel)(A...), dim3 grid, dim3 block, size_t lds_bytes, hipStream_t stream, typename as_declared<A>::type... p) {
+  void* args[] = {(void*)&p...};
+  (void)hipLaunchKernel((const void*)kernel, grid, block, args, lds_bytes, stream);      // (check_launch reads the error)
+}
+
+struct Range {
+  const char* lo;
+  const char* hi;      // one past the last byte
+  bool overlaps(const Range& o) const { return lo && o.lo && lo < o.hi && o.lo < hi; }
+};
+
+// bytes [p, p + ((rows - 1) * stride + width) * size): the part of a [rows, stride] array the call touches
+Range extent(const void* p, int64_t rows, int64_t stride, int64_t width, int64_t size) {
+  const char* c = (const char*)p;
+  return {c, c ? c + ((rows - 1) * stride + width) * size : c};
+}
+
+// the descriptor limits of the wide backward pass; 0, or the code of pdegym::fail
+int check_net(const pdegym_mlp* net) {
+  if (!net) return pdegym::fail(-1, "null descriptor");
+  if (net->n_layers < 1 || net->n_layers > kLayers) return pdegym::fail(-2, "n_layers must be 1..4");
+  if (net->head != PDEGYM_MLP_HEAD_PLAIN) return pdegym::fail(-2, "mlp_backward_wide: the head must be PLAIN (a squashed-Gaussian head is applied by the caller)");
+  if (net->clamp) return pdegym::fail(-2, "mlp_backward_wide: clamp must be 0");
+  if (net->noise) return pdegym::fail(-2, "mlp_backward_wide: noise must be NULL");
+  for (int l = 0; l < net->n_layers; ++l) {
+    const pdegym_mlp_layer& L = net->layer[l];
+    if (!L.w) return pdegym::fail(-3, "null weight pointer");
+    if (!pdegym::is_aligned(L.w, 16)) return pdegym::fail(-2, "layer weights (w) must be 16-byte aligned");
+    if (L.in_dim < 1 || L.out_dim < 1) return pdegym::fail(-2, "layer dimensions must be >= 1");
+    if (L.out_dim > kWidth) return pdegym::fail(-2, "mlp_backward_wide: a layer wider than 256 units");
+    if (l == 0 && L.in_dim > kMaxIn) return pdegym::fail(-2, "mlp_backward_wide: in_dim above 1024");
+    if (l > 0 && L.in_dim != net->layer[l - 1].out_dim) return pdegym::fail(-2, "layer input size does not match the previous layer");
+    if (L.act < PDEGYM_MLP_IDENTITY || L.act > PDEGYM_MLP_RELU) return pdegym::fail(-2, "unknown activation");
+  }
+  return 0;
+}
+
+int64_t tiles_of(int32_t B) { return ((int64_t)B + kRows - 1) / kRows; }
+
+// the number of slabs in use (the library's choice for 0), or the code of pdegym::fail
+int resolve_slabs(int32_t B, int32_t slabs) {
+  if (B < 1) return pdegym::fail(-2, "B must be >= 1");
+  const int tiles = (int)tiles_of(B);
+  if (slabs < 0) return pdegym::fail(-2, "slabs must be >= 0");
+  if (slabs > tiles) return pdegym::fail(-2, "more slabs than tiles of 16 rows");
+  if (slabs) return slabs;
+  const int own = (tiles + kSlabTiles - 1) / kSlabTiles;
+  return own < kMaxSlabs ? own : kMaxSlabs;
+}
+
+int pad64(int n) { return (n + kBlock - 1) / kBlock * kBlock; }
+
+int per_slab_floats(const pdegym_mlp* net) {
+  int n = 0;
+  for (int l = 0; l < net->n_layers; ++l) n += net->layer[l].out_dim * (net->layer[l].in_dim + 1);
+  return n;
+}
+
+// floats per row of the dZ_l (every layer) and H_{l-1} (l >= 1) blocks of the workspace
+int row_floats(const pdegym_mlp* net) {
+  int n = 0;
+  for (int l = 0; l < net->n_layers; ++l) n += pad64(net->layer[l].out_dim) + (l >= 1 ? pad64(net->layer[l].in_dim) : 0);
+  return n;
+}
+
+int64_t workspace_bytes(const pdegym_mlp* net, int32_t B, int slabs) {
+  return (tiles_of(B) * kRows * row_floats(net) + (int64_t)slabs * per_slab_floats(net)) * (int64_t)sizeof(float);
+}
+
+template <typename TX>
+int launch_all(const pdegym_mlp* net, const Plan& P, hipStream_t st) {
+  static signed char attr[pdegym::kMaxDevices] = {};
+  if (!pdegym::raise_dynamic_lds_limit(reinterpret_cast<const void*>(&mlp_backward_wide_tiles<TX>), kMaxLdsBytes, attr))
+    return pdegym::fail(-4, "cannot raise the dynamic LDS limit of mlp_backward_wide_tiles");
+  const int K0 = P.in[0];
+  const int kin = ((K0 < kXChunk ? K0 : kXChunk) + 15) & ~15;
+  const int ldx = lds_stride(kin);
+  const size_t lds_bytes = (size_t)((kLayers + 2) * kRows * kLdh + kRows * ldx) * sizeof(float);      // 101 .. 130 KB: above the 64 KB a kernel gets without asking
+  launch(mlp_backward_wide_tiles<TX>, dim3((unsigned)P.tiles), dim3(64 * kWaves), lds_bytes, st, *net, P, ldx);
+  launch(mlp_backward_wide_accumulate<TX>, dim3((unsigned)P.item0[P.n_layers], (unsigned)P.slabs), dim3(256), 0, st, P);
+  launch(mlp_backward_wide_reduce, dim3((unsigned)((P.per_slab + 255) / 256)), dim3(256), 0, st, P);
+  return pdegym::check_launch("mlp_backward_wide");
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t pdegym_mlp_backward_wide_workspace(const pdegym_mlp* net, int32_t B, int32_t slabs) {
+  if (int rc = check_net(net)) return rc;
+  const int s = resolve_slabs(B, slabs);
+  if (s < 0) return s;
+  return workspace_bytes(net, B, s);
+}
+
+int pdegym_mlp_backward_wide(const pdegym_mlp* net, const pdegym_mlp_backward_args* a, int32_t B, void* stream) {
+  if (int rc = check_net(net)) return rc;
+  if (!a) return pdegym::fail(-1, "null arguments");
+  const int slabs = resolve_slabs(B, a->slabs);
+  if (slabs < 0) return slabs;
+  const int nl = net->n_layers, K0 = net->layer[0].in_dim, n_out = net->layer[nl - 1].out_dim;
+  if (!a->x || !a->dy) return pdegym::fail(-3, "null x/dy");
+  if (!a->workspace) return pdegym::fail(-3, "null workspace");
+  if (!pdegym::is_aligned(a->workspace, 4)) return pdegym::fail(-2, "workspace must be 4-byte aligned");
+  for (int l = 0; l < nl; ++l) {
+    if (!a->dw[l]) return pdegym::fail(-3, "null dw");
+    if (!a->w[l] && (l > 0 || a->dx)) return pdegym::fail(-3, "null row-major weights (w[0] is needed with dx, the others always)");
+    if (a->db[l] && !net->layer[l].b) return pdegym::fail(-3, "db given for a layer without bias");
+    if (!a->db[l] && net->layer[l].b) return pdegym::fail(-3, "null db for a layer with bias");
+  }
+  if (a->dx && net->x_f64) return pdegym::fail(-2, "dx needs float32 x");
+  if (a->x_stride < K0 || a->dy_stride < n_out || (a->dx && a->dx_stride < K0)) return pdegym::fail(-2, "row stride shorter than the row");
+  const int64_t need = workspace_bytes(net, B, slabs);
+  if (a->workspace_bytes < need) return pdegym::fail(-2, "workspace smaller than pdegym_mlp_backward_wide_workspace answers");
+
+  Range in[2 + 3 * kLayers], out[2 + 2 * kLayers];
+  int n_in = 0, n_outr = 0;
+  in[n_in++] = extent(a->x, B, a->x_stride, K0, net->x_f64 ? 8 : 4);
+  in[n_in++] = extent(a->dy, B, a->dy_stride, n_out, 4);
+  for (int l = 0; l < nl; ++l) {
+    const pdegym_mlp_layer& L = net->layer[l];
+    const int64_t cells = (int64_t)L.out_dim * L.in_dim;
+    in[n_in++] = extent(a->w[l], 1, cells, cells, 4);
+    in[n_in++] = extent(L.w, 1, 0, (int64_t)((L.in_dim + 3) / 4) * L.out_dim * 4, 4);
+    in[n_in++] = extent(L.b, 1, L.out_dim, L.out_dim, 4);
+    out[n_outr++] = extent(a->dw[l], 1, cells, cells, 4);
+    out[n_outr++] = extent(a->db[l], 1, L.out_dim, L.out_dim, 4);
+  }
+  out[n_outr++] = extent(a->dx, B, a->dx_stride, K0, 4);
+  out[n_outr++] = extent(a->workspace, 1, need, need, 1);
+  for (int i = 0; i < n_outr; ++i) {
+    for (int j = 0; j < n_in; ++j)
+      if (out[i].overlaps(in[j])) return pdegym::fail(-3, "an output or the workspace overlaps an input");
+    for (int j = i + 1; j < n_outr; ++j)
+      if (out[i].overlaps(out[j])) return pdegym::fail(-3, "two outputs overlap (the workspace counts as one)");
+  }
+
+  Plan P = {};
+  P.x = a->x, P.x_stride = a->x_stride, P.dy = a->dy, P.dy_stride = a->dy_stride, P.dx = a->dx, P.dx_stride = a->dx_stride;
+  const int64_t rows = tiles_of(B) * kRows;
+  float* ws = static_cast<float*>(a->workspace);
+  int at = 0, items = 0;
+  for (int l = 0; l < nl; ++l) {
+    const pdegym_mlp_layer& L = net->layer[l];
+    P.w[l] = a->w[l], P.dw[l] = a->dw[l], P.db[l] = a->db[l], P.in[l] = L.in_dim, P.out[l] = L.out_dim;
+    P.hp[l] = pad64(L.out_dim), P.kp[l] = pad64(L.in_dim);
+    P.dz[l] = ws, ws += rows * P.hp[l];
+    if (l >= 1) P.hin[l] = ws, ws += rows * P.kp[l];
+    P.off_w[l] = at, at += L.out_dim * L.in_dim;
+    P.off_b[l] = at, at += L.out_dim;
+    P.item0[l] = items, items += (P.hp[l] / kBlock) * (P.kp[l] / kBlock);
+  }
+  for (int l = nl; l <= kLayers; ++l) P.item0[l] = items;
+  P.part = ws;
+  P.per_slab = at, P.n_layers = nl, P.B = B, P.tiles = (int)tiles_of(B), P.slabs = slabs;
+  hipStream_t st = (hipStream_t)stream;
+  return net->x_f64 ? launch_all<double>(net, P, st) : launch_all<float>(net, P, st);
+}
+
+}  // extern "C"

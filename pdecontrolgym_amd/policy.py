@@ -15,7 +15,9 @@ state-dependent standard deviation, the tanh squash AFTER the noise, the result 
 the same kernels (include/pdegym.h: PDEGYM_MLP_HEAD_SQUASHED_GAUSSIAN).
 
 ``FusedMLP.with_grad(obs)``: the same forward launch under autograd -- its backward is ``pdegym_mlp_backward``
-(csrc/pdegym_mlp_backward.hip) and fills the ``.grad`` of the wrapped module's Parameters, for layers of at most 64 units.
+(csrc/pdegym_mlp_backward.hip) for layers of at most 64 units and ``pdegym_mlp_backward_wide``
+(csrc/pdegym_mlp_backward_wide.hip) for layers of up to 256 -- SB3's SAC networks --, and fills the ``.grad`` of the wrapped module's
+Parameters.
 """
 from __future__ import annotations
 
@@ -37,7 +39,8 @@ class FusedMLP:
     (``pde_control_gym.DeviceRollout`` points it at slot t of its action buffer).  ``__call__`` and ``forward_into`` are inference
     only (no autograd graph); ``with_grad(obs)`` is the differentiable evaluation -- the same forward launch with a ``grad_fn``
     whose backward is ``pdegym_mlp_backward`` (three launches) and fills the ``.grad`` of the wrapped module's own Parameters, for
-    networks that ``fits_backward()``.
+    networks that ``fits_backward()`` (layers of at most 64 units); wider ones that ``fits_backward_wide()`` (up to 256 units) go
+    through ``pdegym_mlp_backward_wide``, three launches as well.
     """
 
     def __init__(self, module, clamp=None, backend=None):
@@ -285,7 +288,7 @@ class FusedMLP:
         self.backend.mlp_forward(net, x, y, B)
         return out
 
-    # ---- the differentiable evaluation (pdegym_mlp_forward + pdegym_mlp_backward) -------------------------------------------------
+    # ---- the differentiable evaluation (pdegym_mlp_forward + pdegym_mlp_backward / _wide) ---------------------------------------------
     def backward_limit(self):
         """None when ``pdegym_mlp_backward`` takes this network, otherwise the limit it breaks, in words."""
         for i, (w, _, _) in enumerate(self.layers):
@@ -299,6 +302,28 @@ class FusedMLP:
         """Whether ``with_grad`` can differentiate this network: every layer of at most 64 units, rows of at most 1024 inputs."""
         return self.backward_limit() is None
 
+    def wide_backward_limit(self):
+        """None when ``pdegym_mlp_backward_wide`` takes this network, otherwise the limit it breaks, in words."""
+        for i, (w, _, _) in enumerate(self.layers):
+            if w.shape[0] > N.MLP_BACKWARD_WIDE_MAX_WIDTH:
+                return f"layer {i} has {w.shape[0]} units, the wide backward pass takes at most {N.MLP_BACKWARD_WIDE_MAX_WIDTH} per layer"
+        if self.in_dim > N.MLP_BACKWARD_WIDE_MAX_INPUT:
+            return f"rows of {self.in_dim} inputs, the wide backward pass takes at most {N.MLP_BACKWARD_WIDE_MAX_INPUT}"
+        return None
+
+    def fits_backward_wide(self) -> bool:
+        """Whether ``pdegym_mlp_backward_wide`` can differentiate this network: every layer of at most 256 units, rows of at most 1024
+        inputs (a superset of ``fits_backward()``; ``with_grad`` uses it for the networks that do not fit the narrow pass)."""
+        return self.wide_backward_limit() is None
+
+    def _backward_entry(self):
+        """The backend method behind ``with_grad``'s backward: ``mlp_backward`` for a network that ``fits_backward()``, otherwise
+        ``mlp_backward_wide`` where the backend offers it and the network ``fits_backward_wide()``, otherwise None."""
+        if self.fits_backward():
+            return self.backend.mlp_backward
+        wide = getattr(self.backend, "mlp_backward_wide", None)
+        return wide if wide is not None and self.fits_backward_wide() else None
+
     def grad_parameters(self):
         """The Parameters ``with_grad`` returns gradients for, in its order: weight, bias (if any) of every layer of the wrapped
         module; with a squashed-Gaussian head the latent layers' followed by those of ``mu`` and of ``log_std``."""
@@ -311,16 +336,16 @@ class FusedMLP:
     def with_grad(self, obs):
         """``[B, n]`` float32 WITH a ``grad_fn``: the last layer's output (no clamp, no noise, no head: a squashed-Gaussian wrapper
         returns the raw ``[B, 2A]`` rows -- mu columns, then log_std columns -- and SAC's torch code applies clip / exp / tanh under
-        autograd).  Forward: one ``pdegym_mlp_forward`` launch after ``refresh()``; backward: ``pdegym_mlp_backward``, which returns the
+        autograd).  Forward: one ``pdegym_mlp_forward`` launch after ``refresh()``; backward: ``pdegym_mlp_backward`` for a network
+        that ``fits_backward()``, ``pdegym_mlp_backward_wide`` for a wider one that ``fits_backward_wide()``; either returns the
         gradients of ``grad_parameters()`` -- so ``loss.backward()`` fills (accumulates into) the ``.grad`` of the module's own
         Parameters and any torch optimiser works unchanged -- and of ``obs`` when it is float32 and requires grad.  The activations
-        are recomputed in the backward launch, nothing is kept but ``obs``.  ``ValueError`` when the network does not
-        ``fits_backward()``; ``RuntimeError`` inside a stream capture (``refresh()`` cannot run there: a captured update would
+        are recomputed in the backward launch, nothing is kept but ``obs``.  ``ValueError`` when the network fits neither pass (or
+        does not ``fits_backward()`` on a backend without the wide pass), naming the limit of ``backward_limit()``; ``RuntimeError`` inside a stream capture (``refresh()`` cannot run there: a captured update would
         train on stale weight copies)."""
         import torch
-        why = self.backward_limit()
-        if why is not None:
-            raise ValueError(f"FusedMLP.with_grad: {why}")
+        if self._backward_entry() is None:
+            raise ValueError(f"FusedMLP.with_grad: {self.backward_limit()}")
         B = obs.shape[0]
         x = obs.reshape(B, -1)
         if x.shape[1] != self.in_dim:
@@ -370,7 +395,7 @@ def _with_grad_function():
             dw = [torch.empty_like(w) for w in weights]
             db = [None if b is None else torch.empty_like(b.detach()) for _, b, _ in policy.layers]
             dx = torch.empty(xd.shape, dtype=torch.float32, device=xd.device) if ctx.want_dx else None
-            policy.backend.mlp_backward(policy._net(None, xd.dtype == torch.float64, plain=True), xd, dy, weights, dw, db, dx)
+            policy._backward_entry()(policy._net(None, xd.dtype == torch.float64, plain=True), xd, dy, weights, dw, db, dx)
             heads = policy._heads is not None
             grads = [g for w_, b_ in zip(dw[:-1] if heads else dw, db[:-1] if heads else db) for g in (w_, b_) if g is not None]
             if heads:      # rows 0 .. A-1 of the fused last layer are mu's, rows A .. 2A-1 log_std's

@@ -23,12 +23,25 @@ algorithm in plain torch on the batched engine:
                 entropy terms and their gradients) and ``result.backward()``.  The loss is the same one (``vf_coef = 0.25`` is this
                 file's ``0.5 * (0.5 * mse)``, ``ent_coef = 1e-3`` its ``-1e-3 * log_std.sum()``), with ONE difference: under the
                 switch the advantages are normalised per minibatch, as SB3's ``PPO.train`` does, not once over the whole buffer.
+                With ``fused_opt`` the tail of a minibatch step -- ``clip_grad_norm_`` and ``Adam`` over 13 tensors, then the
+                ``refresh()`` of the blocked weight copies at the next forward -- is ONE ``FusedAdam.step()`` (``pdegym_fused_adam``,
+                two launches) that writes the copies of the attached ``FusedMLP`` wrappers itself.  What differs from the default
+                path: (1) the global norm is taken over ALL of the optimiser's tensors, ``log_std`` included (the default path clips
+                actor and critic and leaves ``log_std`` out), so the clip coefficient differs whenever ``log_std``'s gradient is not
+                negligible; (2) the gradients themselves are not scaled in place, only the update sees the scaled values; (3) the
+                float32 arithmetic is Adam's single-tensor order with the norm summed in float64 (include/pdegym.h), where torch's
+                default is the multi-tensor path: equal to rounding.
+                ``graph_update`` (needs the three switches above) captures one minibatch step -- gather, both ``with_grad``
+                forwards, ``PPOLoss``, ``backward()`` and ``FusedAdam.step()`` -- into ONE ``torch.cuda.graph`` after the first step
+                has run eagerly, and replays it for every later minibatch of the run: the minibatch's indices, the actions and the
+                old log-probabilities are copied into static tensors outside the graph (``randperm`` stays outside as well), the
+                attached wrappers need no ``refresh()`` and the optimiser no host work.  The numbers are those of ``fused_opt``.
 
 The plant is the reference's unstable reaction-diffusion benchmark u_t = u_xx + beta(x) u with boundary actuation
 (ReactionDiffusionPDE1D, Dirichlet control at x = 1).  Uncontrolled, ||u|| grows; the printed mean ||u|| over an episode falls
 as the policy learns to damp it.
 
-    python examples/train_ppo_device.py [iterations] [num_envs] [hidden units per layer: 64] [fused_grad: 0] [fused_loss: 0]
+    python examples/train_ppo_device.py [iterations] [num_envs] [hidden units per layer: 64] [fused_grad: 0] [fused_loss: 0] [fused_opt: 0] [graph_update: 0]
 """
 import os
 import sys
@@ -39,7 +52,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import pde_control_gym  # noqa: E402
-from pde_control_gym import DeviceRollout, DeviceRolloutBuffer, FusedMLP, PPOLoss  # noqa: E402
+from pde_control_gym import DeviceRollout, DeviceRolloutBuffer, FusedAdam, FusedMLP, PPOLoss  # noqa: E402
 from pde_control_gym.src import TunedReward1D  # noqa: E402
 
 
@@ -70,7 +83,10 @@ def mlp(sizes, out_tanh=False):
     return torch.nn.Sequential(*mods)
 
 
-def main(iterations=30, B=2048, T=64, quiet=False, hidden=64, fused_grad=False, fused_loss=False):
+nmb_of_update = 4      # minibatches per epoch
+
+
+def main(iterations=30, B=2048, T=64, quiet=False, hidden=64, fused_grad=False, fused_loss=False, fused_opt=False, graph_update=False):
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
     venv = make_env(B, horizon=T)        # one rollout = one episode of every environment
@@ -91,11 +107,25 @@ def main(iterations=30, B=2048, T=64, quiet=False, hidden=64, fused_grad=False, 
     rollout = DeviceRollout(venv, policy, T, action_noise=True)
     # the networks of the update: the modules themselves under torch autograd, or their fused forward + backward launches
     actor_fn, critic_fn = actor, critic
+    fused_nets = [policy]
     if fused_grad and hidden <= 256:
-        actor_fn, critic_fn = policy.with_grad, FusedMLP(critic).with_grad
+        fused_nets.append(FusedMLP(critic))
+        actor_fn, critic_fn = policy.with_grad, fused_nets[1].with_grad
     elif fused_grad and not quiet:
         print(f"fused_grad: layers of {hidden} units are wider than the 256 the fused backward passes take; the update uses torch autograd")
-    gamma, lam, clip, epochs, nmb = 0.99, 0.95, 0.2, 6, 4
+    clipped = list(actor.parameters()) + list(critic.parameters())
+    if fused_opt:      # one launch pair per minibatch: clip over all 13 tensors, Adam, the blocked copies of the attached wrappers
+        opt = FusedAdam(clipped + [log_std], lr=1e-3, max_grad_norm=0.5)
+        for net in fused_nets:
+            opt.attach(net)
+    graph = step_fn = None
+    if graph_update:
+        if not (fused_grad and fused_loss and fused_opt and hidden <= 256) or (T * B) % nmb_of_update:
+            raise ValueError("graph_update needs fused_grad, fused_loss and fused_opt, layers of at most 256 units and T * B divisible by 4")
+        static = {"mb": torch.zeros(T * B // nmb_of_update, dtype=torch.int64, device=dev), "a": torch.empty(T * B, device=dev),
+                  "lp": torch.empty(T * B, device=dev)}
+    start = {"actor": [p.detach().clone() for p in actor.parameters()], "critic": [p.detach().clone() for p in critic.parameters()]}
+    gamma, lam, clip, epochs, nmb = 0.99, 0.95, 0.2, 6, nmb_of_update
     buffer = DeviceRolloutBuffer(rollout, gamma=gamma, gae_lambda=lam)
     head = PPOLoss(clip_range=clip, ent_coef=1e-3, vf_coef=0.25, normalize_advantage=True) if fused_loss else None
     history = []
@@ -124,15 +154,41 @@ def main(iterations=30, B=2048, T=64, quiet=False, hidden=64, fused_grad=False, 
         o_f, a_f, lp_f, adv_f, ret_f = batch.observations, flat(a_raw), flat(logp_old), batch.advantages, batch.returns
         if not fused_loss:
             adv_f = (adv_f - adv_f.mean()) / (adv_f.std() + 1e-8)
+        if graph_update:
+            static["a"].copy_(a_f)
+            static["lp"].copy_(lp_f)
+            if step_fn is None:
+                def step_fn(o_f=o_f, adv_f=adv_f, ret_f=ret_f):      # (views of the rollout's and the buffer's own tensors: fixed addresses)
+                    obs_mb = o_f[static["mb"]]
+                    result = head(actor_fn(obs_mb), log_std, critic_fn(obs_mb), static["a"], static["lp"], adv_f, ret_f, index=static["mb"])
+                    result.backward()
+                    opt.step()
         for _ in range(epochs):
             perm = torch.randperm(T * B, device=dev)
             for mb in perm.chunk(nmb):
+                if graph_update:
+                    static["mb"].copy_(mb)
+                    if graph is not None:      # (the captured backward WRITES the gradients it allocated: nothing to zero)
+                        graph.replay()
+                        continue
+                    opt.zero_grad(set_to_none=True)
+                    if "warm" not in static:      # the very first step runs eagerly: it allocates what the graph reuses
+                        step_fn()
+                        static["warm"] = True
+                    else:
+                        torch.cuda.synchronize()
+                        graph = torch.cuda.CUDAGraph()
+                        with torch.cuda.graph(graph):
+                            step_fn()
+                        graph.replay()
+                    continue
                 if fused_loss:
                     obs_mb = o_f[mb]
                     result = head(actor_fn(obs_mb), log_std, critic_fn(obs_mb), a_f, lp_f, adv_f, ret_f, index=mb)
                     opt.zero_grad(set_to_none=True)
                     result.backward()
-                    torch.nn.utils.clip_grad_norm_(list(actor.parameters()) + list(critic.parameters()), 0.5)
+                    if not fused_opt:
+                        torch.nn.utils.clip_grad_norm_(clipped, 0.5)
                     opt.step()
                     continue
                 mean = actor_fn(o_f[mb]).squeeze(-1)
@@ -143,7 +199,8 @@ def main(iterations=30, B=2048, T=64, quiet=False, hidden=64, fused_grad=False, 
                 loss = pg + 0.5 * vloss - 1e-3 * log_std.sum()
                 opt.zero_grad(set_to_none=True)
                 loss.backward()
-                torch.nn.utils.clip_grad_norm_(list(actor.parameters()) + list(critic.parameters()), 0.5)
+                if not fused_opt:
+                    torch.nn.utils.clip_grad_norm_(clipped, 0.5)
                 opt.step()
         torch.cuda.synchronize()
         t_upd += time.perf_counter() - t0
@@ -152,6 +209,9 @@ def main(iterations=30, B=2048, T=64, quiet=False, hidden=64, fused_grad=False, 
         stats = {"iter": it, "episode_return": buffer.finished_episodes()[1].item(), "mean_norm": obs[:T].norm(dim=2).mean().item(),
                  "truncated_frac": rollout.truncated.float().mean().item() * T, "std": log_std.exp().item()}
         history.append(stats)
+        if fused_opt and it == iterations - 1:      # whether the fused step reached every tensor of either network
+            stats["moved"] = {k: all(not torch.equal(p.detach(), s) for p, s in zip(net.parameters(), start[k]))
+                              for k, net in (("actor", actor), ("critic", critic))}
         if not quiet and (it % 5 == 0 or it == iterations - 1):
             print(f"iter {it:3d}  episode return {stats['episode_return']:+8.3f}  mean ||u|| over the episode {stats['mean_norm']:7.3f}  "
                   f"episodes cut off per env {stats['truncated_frac']:.3f}  policy std {stats['std']:.3f}")
@@ -164,4 +224,6 @@ def main(iterations=30, B=2048, T=64, quiet=False, hidden=64, fused_grad=False, 
 if __name__ == "__main__":
     main(int(sys.argv[1]) if len(sys.argv) > 1 else 30, int(sys.argv[2]) if len(sys.argv) > 2 else 2048,
          hidden=int(sys.argv[3]) if len(sys.argv) > 3 else 64, fused_grad=bool(int(sys.argv[4])) if len(sys.argv) > 4 else False,
-         fused_loss=bool(int(sys.argv[5])) if len(sys.argv) > 5 else False)
+         fused_loss=bool(int(sys.argv[5])) if len(sys.argv) > 5 else False,
+         fused_opt=bool(int(sys.argv[6])) if len(sys.argv) > 6 else False,
+         graph_update=bool(int(sys.argv[7])) if len(sys.argv) > 7 else False)

@@ -15,7 +15,7 @@ batched engine, on the plant of examples/train_ppo_device.py:
                 ``latent`` / ``mu`` / ``log_std`` modules the rollout evaluates (``FusedMLP`` picks the new weights up at the next
                 ``run()``).
 
-    python examples/train_sac_device.py [iterations] [num_envs] [hidden units per layer: 64] [fused_grad: 0] [fused_loss: 0]
+    python examples/train_sac_device.py [iterations] [num_envs] [hidden units per layer: 64] [fused_grad: 0] [fused_loss: 0] [fused_opt: 0]
 
 ``fused_loss`` sends the three sample / loss blocks of the update through ``pde_control_gym.SACLoss`` (pdegym_squashed_gaussian_sample
 and its backward, pdegym_sac_critic_loss, pdegym_sac_actor_loss): ``head.sample`` writes ``[obs | action]`` and the log-probability in
@@ -27,6 +27,15 @@ with ``torch.randn`` ahead of ``head.sample`` (two [batch, 1] draws per update f
 of the log-probability uses ``eps`` directly where autograd differentiates ``((z - mu) / sigma)^2`` through ``z``: equal in exact
 arithmetic; (4) actor and entropy-coefficient gradients come from ONE backward call, the two optimisers step after it (the default
 path steps the actor before it forms the entropy-coefficient loss, from the same detached ``logp``: the same numbers).
+
+``fused_opt`` replaces the three torch ``Adam`` optimisers and the ``lerp_`` loop over the target critics by three
+``pde_control_gym.FusedAdam`` (pdegym_fused_adam, two launches per step): the actor's is attached to the rollout's squashed-Gaussian
+wrapper, the critics' to their ``with_grad`` wrappers (with ``fused_grad``) and, through ``attach_target(..., tau)``, to the target
+critics, which ``step(polyak=True)`` moves in the same launch -- the weight copies are written by the step, ``refresh()`` finds
+nothing to do.  What differs from the default path: (1) the targets move right after the critics' step instead of at the end of the
+update (nothing reads them in between: the same numbers); (2) the average is SB3's ``polyak_update`` order
+``(1 - tau) * target + tau * param`` in place of ``lerp_``'s ``target + tau * (param - target)``: equal to rounding; (3) the float32
+arithmetic is Adam's single-tensor order (include/pdegym.h) where torch's default is the multi-tensor path: equal to rounding.
 """
 import copy
 import math
@@ -37,7 +46,7 @@ import time
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from pde_control_gym import DeviceRollout, FusedMLP, SACLoss  # noqa: E402
+from pde_control_gym import DeviceRollout, FusedAdam, FusedMLP, SACLoss  # noqa: E402
 from train_ppo_device import make_env  # noqa: E402
 
 LOG_STD_MIN, LOG_STD_MAX = -20.0, 2.0
@@ -68,7 +77,7 @@ def sample(latent, mu, log_std, obs, raw=None):
 
 
 def main(iterations=30, num_envs=1024, n_steps=32, hidden=64, one_launch=None, quiet=False, updates=8, batch=2048, fused_grad=False,
-         fused_loss=False):
+         fused_loss=False, fused_opt=False):
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
     B, T = num_envs, n_steps
@@ -98,8 +107,10 @@ def main(iterations=30, num_envs=1024, n_steps=32, hidden=64, one_launch=None, q
     # among them) FusedMLP.with_grad -- the critics' gradient with respect to the action column is the dx of pdegym_mlp_backward
     # (layers of at most 64 units) or of pdegym_mlp_backward_wide
     q1_fn, q2_fn, raw_fn = q1, q2, None
+    critic_nets = []
     if fused_grad and hidden <= 256:
-        q1_fn, q2_fn, raw_fn = FusedMLP(q1).with_grad, FusedMLP(q2).with_grad, policy.with_grad
+        critic_nets = [FusedMLP(q1), FusedMLP(q2)]
+        q1_fn, q2_fn, raw_fn = critic_nets[0].with_grad, critic_nets[1].with_grad, policy.with_grad
     elif fused_grad and not quiet:
         print(f"fused_grad: layers of {hidden} units are wider than the 256 the fused backward passes take; the update uses torch autograd")
     # the replay buffer: device tensors, a ring of `cap` transitions filled T * B at a time
@@ -108,6 +119,15 @@ def main(iterations=30, num_envs=1024, n_steps=32, hidden=64, one_launch=None, q
     head, filled = 0, 0
     gamma, tau, target_entropy = 0.99, 0.005, -1.0
     loss_head = SACLoss(gamma, target_entropy, (LOG_STD_MIN, LOG_STD_MAX)) if fused_loss else None
+    q_step = opt_q.step
+    if fused_opt:      # the steps write the wrappers' weight copies; the critics' step moves the targets as well
+        opt_actor = FusedAdam(actor_params, lr=3e-4).attach(policy)
+        opt_q = FusedAdam(list(q1.parameters()) + list(q2.parameters()), lr=3e-4)
+        for net in critic_nets:
+            opt_q.attach(net)
+        opt_q.attach_target(list(q1.parameters()) + list(q2.parameters()), list(q1_t.parameters()) + list(q2_t.parameters()), tau)
+        opt_alpha = FusedAdam([log_alpha], lr=3e-4)
+        q_step = lambda: opt_q.step(polyak=True)      # noqa: E731
 
     def raw_of(x):
         """The rows [mu, log_std] of the actor: the fused last layer of ``with_grad``, or the modules' outputs side by side."""
@@ -147,7 +167,7 @@ def main(iterations=30, num_envs=1024, n_steps=32, hidden=64, one_launch=None, q
                 result = loss_head.critic(q1_fn(oa), q2_fn(oa), q1_next, q2_next, logp2, buf["rew"], buf["term"], log_alpha, index=mb)
                 opt_q.zero_grad(set_to_none=True)
                 result.backward()
-                opt_q.step()
+                q_step()
                 q_loss = result.critic_loss
                 block, logp = loss_head.sample(raw_of(o), eps, obs=o)                 # [o | a_pi]: the critics' input, no cat
                 result = loss_head.actor(q1_fn(block), q2_fn(block), logp, log_alpha)
@@ -157,6 +177,8 @@ def main(iterations=30, num_envs=1024, n_steps=32, hidden=64, one_launch=None, q
                 opt_actor.step()
                 opt_alpha.step()
                 actor_loss = result.actor_loss
+                if fused_opt:
+                    continue
                 with torch.no_grad():
                     for net, tgt in ((q1, q1_t), (q2, q2_t)):
                         for p, pt in zip(net.parameters(), tgt.parameters()):
@@ -172,7 +194,7 @@ def main(iterations=30, num_envs=1024, n_steps=32, hidden=64, one_launch=None, q
             q_loss = (q1_fn(oa) - target).pow(2).mean() + (q2_fn(oa) - target).pow(2).mean()
             opt_q.zero_grad(set_to_none=True)
             q_loss.backward()
-            opt_q.step()
+            q_step()
             a_pi, logp = sample(latent, mu, log_std, o, None if raw_fn is None else raw_fn(o))
             oa_pi = torch.cat([o, a_pi], 1)
             actor_loss = (alpha * logp.unsqueeze(1) - torch.min(q1_fn(oa_pi), q2_fn(oa_pi))).mean()
@@ -183,6 +205,8 @@ def main(iterations=30, num_envs=1024, n_steps=32, hidden=64, one_launch=None, q
             opt_alpha.zero_grad(set_to_none=True)
             alpha_loss.backward()
             opt_alpha.step()
+            if fused_opt:
+                continue
             with torch.no_grad():
                 for net, tgt in ((q1, q1_t), (q2, q2_t)):
                     for p, pt in zip(net.parameters(), tgt.parameters()):
@@ -207,4 +231,5 @@ def main(iterations=30, num_envs=1024, n_steps=32, hidden=64, one_launch=None, q
 if __name__ == "__main__":
     main(int(sys.argv[1]) if len(sys.argv) > 1 else 30, int(sys.argv[2]) if len(sys.argv) > 2 else 1024,
          hidden=int(sys.argv[3]) if len(sys.argv) > 3 else 64, fused_grad=bool(int(sys.argv[4])) if len(sys.argv) > 4 else False,
-         fused_loss=bool(int(sys.argv[5])) if len(sys.argv) > 5 else False)
+         fused_loss=bool(int(sys.argv[5])) if len(sys.argv) > 5 else False,
+         fused_opt=bool(int(sys.argv[6])) if len(sys.argv) > 6 else False)

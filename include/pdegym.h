@@ -37,6 +37,9 @@
  *                           (examples/transportPDE/transport1Dsac.py): SquashedDiagGaussianDistribution sample and log_prob, the
  *                           soft Bellman target, critic, actor and entropy-coefficient losses and the autograd pass back to the
  *                           networks' outputs
+ *   pdegym_fused_adam       replaces the tail of every gradient step of those scripts (torch.nn.utils.clip_grad_norm_, torch.optim.Adam
+ *                           and, for SAC, stable_baselines3/common/utils.py: polyak_update) and writes the blocked weight copies of
+ *                           pdegym_mlp_forward while it is there
  *
  * One call advances EVERY instance of a batch by one env-step (S PDE sub-steps for the 1D envs, one
  * Chorin projection step with K Jacobi sweeps for NS2D).  Instances are independent.
@@ -1086,6 +1089,81 @@ typedef struct pdegym_sac_actor_loss_args {
 } pdegym_sac_actor_loss_args;
 int pdegym_sac_actor_loss(const pdegym_sac_actor_loss_args* g, int32_t N, void* stream);
 int64_t pdegym_sac_loss_workspace(int32_t N);      /* bytes, for either loss; negative: error code (N < 1)                      */
+
+/* ---- fused optimiser step: global-norm clip, Adam, weight mirrors and Polyak targets in two launches ------------------------------
+ * One call updates K <= PDEGYM_FUSED_ADAM_MAX_TENSORS float32 tensors as torch.nn.utils.clip_grad_norm_ followed by torch.optim.Adam
+ * (no weight decay, no amsgrad, one step count for all tensors) update them, writes each new parameter to its MIRRORS -- the
+ * blocked transpose pdegym_mlp_forward reads, so FusedMLP.refresh() has nothing left to do -- and, with `polyak`, moves a target
+ * copy towards it (SB3's polyak_update).  The table is passed by value in the kernel arguments (gradient addresses change from one
+ * eager step to the next; a stream capture bakes them in).
+ *
+ * Two launches on `stream`, stream order the only synchronisation (no atomics, no workgroup waits for another):
+ *   head    per-workgroup sums of g * g in float64 into the workspace (only when a norm is wanted: max_grad_norm > 0, or total_norm
+ *           given; otherwise the launch is one workgroup); thread 0 of workgroup 0 advances the state block:
+ *               state[0] += 1;   state[1] *= beta1;   state[2] *= beta2          (step count, beta1^t, beta2^t: doubles, no pow)
+ *   update  every workgroup adds the partial sums itself and updates its elements.
+ * Decomposition (a function of the list n_0 .. n_{K-1} alone): tensor k takes c_k = min(ceil(n_k / 1024), 256) workgroups of 256
+ * threads, in table order; workgroup j of tensor k, thread t takes the elements e = 1024 (j + c_k r) + 256 q + t, q = 0 .. 3,
+ * r = 0, 1, .. while e < n_k.  Order of the sum of squares: a thread adds its (double) g * g (one float32 product, widened) in the
+ * order r ascending, q ascending within r; a workgroup adds its threads with the wave reduction of csrc/pdegym_common.h per wave and
+ * the four waves in ascending order; the G = sum c_k partials are added the same way, thread t taking the partials t, t + 256, ..
+ * in ascending order, then the workgroup sum.
+ *
+ * Arithmetic: float32, every operation rounded on its own, in this order (the double-precision scalars are formed once per launch):
+ *     total  = (float) sqrt(sum_double(g^2))                                       one rounding
+ *     coef   = min(max_grad_norm / (total + 1e-6f), 1.0f)                          a NaN stays NaN, as torch.clamp keeps it
+ *     g'     = g * coef                                                            multiplied even when coef == 1 (clip_grad_norm_);
+ *                                                                                  without clipping g' = g
+ *     m      = m + (float)(1 - beta1) * (g' - m)
+ *     v      = (float)beta2 * v + (float)(1 - beta2) * (g' * g')
+ *     p      = p - (float)(lr / (1 - beta1^t)) * (m / (sqrt(v) / (float)sqrt(1 - beta2^t) + (float)eps))
+ *     pt     = (float)(1 - tau) * pt + (float)tau * p                              only with polyak, p the NEW value
+ * lr is the host double `lr`, or (double)*lr_device when lr_device is given.  UNLIKE clip_grad_norm_, g itself is NOT modified.
+ * Clipping is off for max_grad_norm <= 0 or NaN.  total_norm (optional, one float) receives `total` whenever a norm is computed.
+ *
+ * Mirrors of tensor k (each optional): `copy` receives p[e] at copy[e]; `wt`, for a tensor of shape (out, in), n = out * in,
+ * receives element (o, i) at wt[(i / 4) * wt_out_total * 4 + (wt_row0 + o) * 4 + i % 4] -- rows wt_row0 .. wt_row0 + out of a
+ * blocked array [ceil(in / 4), wt_out_total, 4]; its padding entries (i >= in) are never written.  The target pt has the same two
+ * mirrors (pt_copy, pt_wt with pt_wt_out_total, pt_wt_row0), written only with polyak; without polyak pt and its mirrors are untouched.
+ *
+ * Errors: -1 null descriptor; -2 K outside 1 .. 32, n < 1, a non-finite hyper-parameter, beta outside [0, 1), eps <= 0, tau outside
+ * [0, 1] with a target, out * in != n or row0 + out > out_total of a mirror, a workspace that is too small, a misaligned pointer
+ * (4 bytes; state: 8); -3 a NULL required pointer (p, g, m, v, state, workspace), a target mirror without a target, an output that
+ * overlaps another tensor of the call as a byte range (two blocked mirrors may share one array on disjoint rows). */
+#define PDEGYM_FUSED_ADAM_MAX_TENSORS 32
+typedef struct pdegym_fused_adam_tensor {
+  float* p;                    /* [n] parameter, updated in place                                                              */
+  const float* g;              /* [n] gradient, read only                                                                      */
+  float* m;                    /* [n] first moment                                                                             */
+  float* v;                    /* [n] second moment                                                                            */
+  int64_t n;
+  float* copy;                 /* NULL or [n]: plain mirror                                                                    */
+  float* wt;                   /* NULL or blocked mirror                                                                       */
+  int32_t out, in;             /* the tensor's shape, used with wt / pt_wt                                                     */
+  int32_t wt_out_total, wt_row0;
+  float* pt;                   /* NULL or [n]: Polyak target                                                                   */
+  float* pt_copy;              /* NULL or [n]: plain mirror of the target                                                      */
+  float* pt_wt;                /* NULL or blocked mirror of the target                                                         */
+  int32_t pt_wt_out_total, pt_wt_row0;
+} pdegym_fused_adam_tensor;
+
+typedef struct pdegym_fused_adam_args {
+  int32_t K;                   /* tensors in use, 1 .. 32                                                                      */
+  int32_t polyak;              /* != 0: update the targets in this call                                                        */
+  double lr;                   /* used when lr_device is NULL                                                                  */
+  const float* lr_device;      /* NULL or one float on the device                                                              */
+  double beta1, beta2, eps;
+  double max_grad_norm;        /* <= 0 or NaN: no clipping                                                                     */
+  double tau;                  /* in [0, 1] when any tensor has a target                                                       */
+  double* state;               /* [3] step count, beta1^t, beta2^t; start at {0, 1, 1}; 8-BYTE ALIGNED                         */
+  float* total_norm;           /* NULL or one float                                                                            */
+  void* workspace;             /* pdegym_fused_adam_workspace(...) bytes, 4-BYTE ALIGNED (else -2)                             */
+  int64_t workspace_bytes;
+  pdegym_fused_adam_tensor tensor[PDEGYM_FUSED_ADAM_MAX_TENSORS];
+} pdegym_fused_adam_args;
+int pdegym_fused_adam(const pdegym_fused_adam_args* a, void* stream);
+/* bytes for the tensor sizes n[0 .. K); negative: error code (K outside 1 .. 32, an n < 1) */
+int64_t pdegym_fused_adam_workspace(const int64_t* n, int32_t K);
 
 /* ---- test-only: kernel dispatch overrides -------------------------------------------------------------------------
  * Nothing on the product path calls this (the reference has no counterpart); the parity tests use it to run the SAME step

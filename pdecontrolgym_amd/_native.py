@@ -40,6 +40,7 @@ EXPORTS = [
     "pdegym_ppo_loss", "pdegym_ppo_loss_workspace", "pdegym_diag_gaussian_log_prob",
     "pdegym_squashed_gaussian_sample", "pdegym_squashed_gaussian_sample_backward", "pdegym_sac_critic_loss", "pdegym_sac_actor_loss",
     "pdegym_sac_loss_workspace", "pdegym_mlp_backward_wide", "pdegym_mlp_backward_wide_workspace",
+    "pdegym_fused_adam", "pdegym_fused_adam_workspace",
 ]
 # keys of pdegym_debug_set (test-only dispatch overrides, include/pdegym.h)
 DEBUG_NS_GENERIC, DEBUG_NS_NO_COL, DEBUG_NS_COL_MIN_BATCH, DEBUG_NS_NO_LDS_JACOBI = range(4)
@@ -55,6 +56,7 @@ PPO_LOSS_STATS = ("loss", "policy_loss", "value_loss", "entropy_loss", "approx_k
 SAC_LOSS_MAX_A = 8                      # action dimensions of pdegym_squashed_gaussian_sample (+ _backward)
 SAC_CRITIC_STATS = ("critic_loss", "q1_mean", "q2_mean", "target_mean")
 SAC_ACTOR_STATS = ("actor_loss", "ent_coef_loss", "alpha", "log_prob_mean")
+FUSED_ADAM_MAX_TENSORS = 32             # tensors of one pdegym_fused_adam call
 TRAFFIC_BACKSTEP_NUMPY_MAX_M = 129      # the longest row whose np.trapz sum is un-recursed (128 terms)
 
 
@@ -245,6 +247,20 @@ class SacActorLoss(C.Structure):
                 ("d_log_alpha", C.c_void_p), ("stats", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
 
 
+class FusedAdamTensor(C.Structure):
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_int64), ("copy", C.c_void_p),
+                ("wt", C.c_void_p), ("out", C.c_int32), ("in_", C.c_int32), ("wt_out_total", C.c_int32), ("wt_row0", C.c_int32),
+                ("pt", C.c_void_p), ("pt_copy", C.c_void_p), ("pt_wt", C.c_void_p), ("pt_wt_out_total", C.c_int32),
+                ("pt_wt_row0", C.c_int32)]
+
+
+class FusedAdam(C.Structure):
+    _fields_ = [("K", C.c_int32), ("polyak", C.c_int32), ("lr", C.c_double), ("lr_device", C.c_void_p), ("beta1", C.c_double),
+                ("beta2", C.c_double), ("eps", C.c_double), ("max_grad_norm", C.c_double), ("tau", C.c_double), ("state", C.c_void_p),
+                ("total_norm", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+                ("tensor", FusedAdamTensor * FUSED_ADAM_MAX_TENSORS)]
+
+
 class NativeError(RuntimeError):
     pass
 
@@ -353,6 +369,10 @@ def load():
         f.restype = C.c_int
     lib.pdegym_sac_loss_workspace.argtypes = [C.c_int32]
     lib.pdegym_sac_loss_workspace.restype = C.c_int64
+    lib.pdegym_fused_adam.argtypes = [C.POINTER(FusedAdam), C.c_void_p]
+    lib.pdegym_fused_adam.restype = C.c_int
+    lib.pdegym_fused_adam_workspace.argtypes = [C.POINTER(C.c_int64), C.c_int32]
+    lib.pdegym_fused_adam_workspace.restype = C.c_int64
     lib.pdegym_debug_set.argtypes = [C.c_int32, C.c_int32]
     lib.pdegym_debug_set.restype = C.c_int32
     if lib.pdegym_abi_version() != ABI_VERSION:

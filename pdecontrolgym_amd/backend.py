@@ -825,6 +825,77 @@ class HipBackend:
         g.workspace, g.workspace_bytes = workspace.data_ptr(), workspace.numel()
         N.check(self.lib.pdegym_sac_actor_loss(C.byref(g), n, N.current_stream_ptr(dev)), "pdegym_sac_actor_loss")
 
+    @_on_device_of("sizes")      # (no tensors: nothing to switch; the size query launches nothing)
+    def fused_adam_workspace(self, sizes) -> int:
+        """Bytes of workspace ``fused_adam`` needs for tensors of ``sizes`` elements (pdegym_fused_adam_workspace)."""
+        arr = (C.c_int64 * len(sizes))(*[int(s) for s in sizes])
+        need = int(self.lib.pdegym_fused_adam_workspace(arr, len(sizes)))
+        if need < 0:
+            N.check(need, "pdegym_fused_adam_workspace")
+        return need
+
+    @_on_device_of("state")
+    def fused_adam(self, entries, state, workspace, lr, beta1: float, beta2: float, eps: float, max_grad_norm=None, tau=None,
+                   polyak: bool = False, total_norm=None, cache=None):
+        """Clip, Adam step, weight mirrors and Polyak targets of up to 32 float32 tensors in two launches (pdegym_fused_adam).
+        ``entries``: one dict per tensor with ``p``, ``g``, ``m``, ``v`` and optionally ``copy``, ``wt`` = (blocked tensor, out_total,
+        row0), ``pt``, ``pt_copy``, ``pt_wt`` (include/pdegym.h).  ``state``: float64 [3] on the device (step, beta1^t, beta2^t);
+        ``workspace``: uint8, ``fused_adam_workspace`` bytes; ``lr``: a float or a 0-d float32 device tensor; ``total_norm``: None or a
+        1-element float32 device tensor.  ``cache``: a dict the caller keeps per entry list -- the descriptor is built once and only
+        the gradient addresses (and ``polyak``) are rewritten on later calls with the same list."""
+        import torch
+        a = None if cache is None else cache.get("fused_adam")
+        if a is None:
+            if not 1 <= len(entries) <= N.FUSED_ADAM_MAX_TENSORS:
+                raise N.NativeError(f"fused_adam: 1..{N.FUSED_ADAM_MAX_TENSORS} tensors per call, got {len(entries)}")
+            f32, dev = torch.float32, entries[0]["p"].device
+            if dev.type != "cuda":
+                raise N.NativeError("fused_adam: tensors must be on a HIP device; there is no CPU path")
+
+            def ptr(what, x, numel, dtype=f32):
+                if not torch.is_tensor(x) or x.dtype != dtype or x.device != dev or not x.is_contiguous() or x.numel() < numel:
+                    raise N.NativeError(f"fused_adam: {what} must be a contiguous {dtype} tensor of {numel} elements on {dev}")
+                return x.data_ptr()
+
+            a = N.FusedAdam()
+            a.K = len(entries)
+            for t, e in zip(a.tensor, entries):
+                p = e["p"]
+                n = p.numel()
+                t.n = n
+                t.out, t.in_ = (int(p.shape[0]), int(p.shape[1])) if p.dim() == 2 else (1, n)
+                for name in ("p", "m", "v", "copy", "pt", "pt_copy"):
+                    if e.get(name) is not None:
+                        setattr(t, name, ptr(name, e[name], n))
+                for name in ("wt", "pt_wt"):
+                    if e.get(name) is not None:
+                        blocked, out_total, row0 = e[name]
+                        setattr(t, name, ptr(name, blocked, (t.in_ + 3) // 4 * int(out_total) * 4))
+                        setattr(t, name + "_out_total", int(out_total))
+                        setattr(t, name + "_row0", int(row0))
+            a.state = ptr("state", state, 3, torch.float64)
+            a.workspace, a.workspace_bytes = ptr("workspace", workspace, 1, torch.uint8), workspace.numel()
+            if total_norm is not None:
+                a.total_norm = ptr("total_norm", total_norm, 1)
+            if torch.is_tensor(lr):
+                a.lr_device = ptr("lr", lr, 1)
+            a.beta1, a.beta2, a.eps = float(beta1), float(beta2), float(eps)
+            a.max_grad_norm = 0.0 if max_grad_norm is None else float(max_grad_norm)
+            a.tau = 0.0 if tau is None else float(tau)
+            if cache is not None:
+                cache["fused_adam"] = a
+                cache["device"] = dev
+        dev = entries[0]["p"].device
+        if not torch.is_tensor(lr):
+            a.lr = float(lr)
+        a.polyak = int(bool(polyak))
+        for t, e in zip(a.tensor, entries):
+            g = e["g"]
+            if g.dtype != torch.float32 or g.device != dev or not g.is_contiguous() or g.numel() != t.n:
+                raise N.NativeError("fused_adam: a gradient must be a contiguous float32 tensor of its parameter's size and device")
+            t.g = g.data_ptr()
+        N.check(self.lib.pdegym_fused_adam(C.byref(a), N.current_stream_ptr(dev)), "pdegym_fused_adam")
+
     @_on_device_of("obs")
     def backstep_rollout1d(self, kind: str, P: N.Params1D, T: dict, obs, actions, rewards, terminated, truncated, B: int, law: N.Backstep,
                            obs_noise=None, obs_seen=None):

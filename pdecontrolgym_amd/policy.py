@@ -76,6 +76,7 @@ class FusedMLP:
         # blocked transpose [ceil(in/4), out, 4] (include/pdegym.h); the buffers keep their addresses for captured graphs
         self._wt = [torch.zeros((w.shape[1] + 3) // 4, w.shape[0], 4, dtype=torch.float32, device=w.device) for w, _, _ in layers]
         self._seen = [None] * len(layers)
+        self._optimizer = None      # the pde_control_gym.FusedAdam that maintains the copies, once attached
         self.refresh(force=True)
         self.in_dim, self.out_dim = int(layers[0][0].shape[1]), int(layers[-1][0].shape[0])
         self.clamp = None if clamp is None else (float(clamp[0]), float(clamp[1]))
@@ -342,7 +343,8 @@ class FusedMLP:
         Parameters and any torch optimiser works unchanged -- and of ``obs`` when it is float32 and requires grad.  The activations
         are recomputed in the backward launch, nothing is kept but ``obs``.  ``ValueError`` when the network fits neither pass (or
         does not ``fits_backward()`` on a backend without the wide pass), naming the limit of ``backward_limit()``; ``RuntimeError`` inside a stream capture (``refresh()`` cannot run there: a captured update would
-        train on stale weight copies)."""
+        train on stale weight copies) -- unless the wrapper is attached to a ``pde_control_gym.FusedAdam``, whose step writes the
+        copies itself: ``refresh()`` is then skipped inside the capture and forward, loss, backward and step make one graph."""
         import torch
         if self._backward_entry() is None:
             raise ValueError(f"FusedMLP.with_grad: {self.backward_limit()}")
@@ -353,8 +355,10 @@ class FusedMLP:
         if x.dtype not in (torch.float32, torch.float64):
             raise ValueError(f"FusedMLP.with_grad: obs must be float32 or float64, got {x.dtype}")
         if x.is_cuda and torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("FusedMLP.with_grad cannot run inside a stream capture: refresh() has to see the optimiser's last step")
-        self.refresh()
+            if self._optimizer is None:      # (attached: the optimiser's own launch writes the copies, there is nothing to refresh)
+                raise RuntimeError("FusedMLP.with_grad cannot run inside a stream capture: refresh() has to see the optimiser's last step")
+        else:
+            self.refresh()
         return _with_grad_function().apply(self, x, *self.grad_parameters())
 
     def __call__(self, obs):

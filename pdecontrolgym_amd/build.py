@@ -142,6 +142,30 @@ def build_probe(force: bool = False) -> str:
     return PROBE_LIB
 
 
+LDS_RESIDUE_SRC = os.path.join(ROOT, "tests", "hip", "lds_residue.hip")
+LDS_RESIDUE_LIB = os.path.join(LIBDIR, "libpdegym_lds_residue.so")
+
+
+def build_lds_residue(force: bool = False) -> str:
+    """The test-only kernels of tests/test_gpu_lds_residue.py (tests/hip/lds_residue.hip: fill every CU's LDS with a bit pattern, read
+    LDS back unwritten) as their own small library, rebuilt when the source is newer: not part of the product ABI, and kept out of
+    csrc/ so that the product's kernel fingerprints do not depend on it."""
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(LDS_RESIDUE_SRC):
+        raise RuntimeError(f"{LDS_RESIDUE_SRC} is missing: the LDS-residue kernels are test tooling of the source tree")
+    if not force and os.path.exists(LDS_RESIDUE_LIB) and os.path.getmtime(LDS_RESIDUE_LIB) >= os.path.getmtime(LDS_RESIDUE_SRC):
+        return LDS_RESIDUE_LIB
+    if not os.path.exists(hipcc):
+        raise RuntimeError("hipcc not found: cannot build libpdegym_lds_residue.so")
+    os.makedirs(LIBDIR, exist_ok=True)
+    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-o", LDS_RESIDUE_LIB, LDS_RESIDUE_SRC],
+                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+    if r.returncode != 0:
+        raise RuntimeError("hipcc failed on lds_residue.hip:\n" + r.stdout.decode())
+    return LDS_RESIDUE_LIB
+
+
 if __name__ == "__main__":
     print(build(force=True, verbose=True))
     print(build_probe(force=True))
+    print(build_lds_residue(force=True))

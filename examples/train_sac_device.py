@@ -16,6 +16,7 @@ batched engine, on the plant of examples/train_ppo_device.py:
                 ``run()``).
 
     python examples/train_sac_device.py [iterations] [num_envs] [hidden units per layer: 64] [fused_grad: 0] [fused_loss: 0] [fused_opt: 0]
+                                        [fused_critic: 0]
 
 ``fused_loss`` sends the three sample / loss blocks of the update through ``pde_control_gym.SACLoss`` (pdegym_squashed_gaussian_sample
 and its backward, pdegym_sac_critic_loss, pdegym_sac_actor_loss): ``head.sample`` writes ``[obs | action]`` and the log-probability in
@@ -36,6 +37,15 @@ nothing to do.  What differs from the default path: (1) the targets move right a
 update (nothing reads them in between: the same numbers); (2) the average is SB3's ``polyak_update`` order
 ``(1 - tau) * target + tau * param`` in place of ``lerp_``'s ``target + tau * (param - target)``: equal to rounding; (3) the float32
 arithmetic is Adam's single-tensor order (include/pdegym.h) where torch's default is the multi-tensor path: equal to rounding.
+
+``fused_critic`` (needs the three switches above) calls the critics the way SB3 does, ``critic(obs, actions)``: the critic step is
+``q_fn(o, a)`` on the stored observation and action -- no ``torch.cat`` --, and the actor step samples plain actions (``head.sample``
+without ``obs=``) and runs ``q_fn(o, a_pi, params=False)``: each critic's backward is ONE launch that returns the ``[N, 1]`` gradient
+of the action alone -- no ``[N, D + 1]`` dx, no dW / db that the next ``zero_grad`` would throw away.  Every number equals the
+three-switch path's, bit for bit (``FusedMLP.with_grad``: the two-part rows give the bits of the concatenated ones), and the noise is
+drawn by the same two calls in the same order, so the printed history is the same for the same seed.  The critics' ``.grad`` after
+the actor step is no longer produced; nothing read it.  The target critics stay the torch modules on ``head.sample``'s block: their
+float32 sums are torch's GEMM order, which the kernels' order matches only to rounding -- moving them would change the history.
 """
 import copy
 import math
@@ -77,7 +87,9 @@ def sample(latent, mu, log_std, obs, raw=None):
 
 
 def main(iterations=30, num_envs=1024, n_steps=32, hidden=64, one_launch=None, quiet=False, updates=8, batch=2048, fused_grad=False,
-         fused_loss=False, fused_opt=False):
+         fused_loss=False, fused_opt=False, fused_critic=False):
+    if fused_critic and not (fused_grad and fused_loss and fused_opt and hidden <= 256):
+        raise ValueError("fused_critic needs fused_grad, fused_loss and fused_opt, and layers of at most 256 units")
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
     B, T = num_envs, n_steps
@@ -163,14 +175,22 @@ def main(iterations=30, num_envs=1024, n_steps=32, hidden=64, one_launch=None, q
                 with torch.no_grad():
                     block2, logp2 = loss_head.sample(raw_of(o2), eps2, obs=o2)        # [o2 | a2], log pi(a2 | o2)
                     q1_next, q2_next = q1_t(block2), q2_t(block2)
-                oa = torch.cat([o, a], 1)
-                result = loss_head.critic(q1_fn(oa), q2_fn(oa), q1_next, q2_next, logp2, buf["rew"], buf["term"], log_alpha, index=mb)
+                if fused_critic:                                                      # critic(obs, actions): the row in two parts
+                    q1_now, q2_now = q1_fn(o, a), q2_fn(o, a)
+                else:
+                    oa = torch.cat([o, a], 1)
+                    q1_now, q2_now = q1_fn(oa), q2_fn(oa)
+                result = loss_head.critic(q1_now, q2_now, q1_next, q2_next, logp2, buf["rew"], buf["term"], log_alpha, index=mb)
                 opt_q.zero_grad(set_to_none=True)
                 result.backward()
                 q_step()
                 q_loss = result.critic_loss
-                block, logp = loss_head.sample(raw_of(o), eps, obs=o)                 # [o | a_pi]: the critics' input, no cat
-                result = loss_head.actor(q1_fn(block), q2_fn(block), logp, log_alpha)
+                if fused_critic:      # plain actions; one backward launch per critic, for the action's gradient alone
+                    a_pi, logp = loss_head.sample(raw_of(o), eps)
+                    result = loss_head.actor(q1_fn(o, a_pi, params=False), q2_fn(o, a_pi, params=False), logp, log_alpha)
+                else:
+                    block, logp = loss_head.sample(raw_of(o), eps, obs=o)             # [o | a_pi]: the critics' input, no cat
+                    result = loss_head.actor(q1_fn(block), q2_fn(block), logp, log_alpha)
                 opt_actor.zero_grad(set_to_none=True)
                 opt_alpha.zero_grad(set_to_none=True)
                 result.backward()
@@ -232,4 +252,5 @@ if __name__ == "__main__":
     main(int(sys.argv[1]) if len(sys.argv) > 1 else 30, int(sys.argv[2]) if len(sys.argv) > 2 else 1024,
          hidden=int(sys.argv[3]) if len(sys.argv) > 3 else 64, fused_grad=bool(int(sys.argv[4])) if len(sys.argv) > 4 else False,
          fused_loss=bool(int(sys.argv[5])) if len(sys.argv) > 5 else False,
-         fused_opt=bool(int(sys.argv[6])) if len(sys.argv) > 6 else False)
+         fused_opt=bool(int(sys.argv[6])) if len(sys.argv) > 6 else False,
+         fused_critic=bool(int(sys.argv[7])) if len(sys.argv) > 7 else False)

@@ -713,6 +713,64 @@ int pdegym_mlp_backward(const pdegym_mlp* net, const pdegym_mlp_backward_args* a
 int64_t pdegym_mlp_backward_wide_workspace(const pdegym_mlp* net, int32_t B, int32_t slabs);
 int pdegym_mlp_backward_wide(const pdegym_mlp* net, const pdegym_mlp_backward_args* a, int32_t B, void* stream);
 
+/* ---- the critic(obs, action) call: rows in two parts, gradient to the action part alone, parameter gradients on request ----------
+ * SB3's critics are called as critic(obs, actions) (stable_baselines3/common/policies.py: ContinuousCritic.forward concatenates the
+ * two and evaluates its q-networks).  The three entry points below take the two arrays as they are: no [obs | action] block is
+ * written, and the actor step of a SAC update -- which wants dQ/d(action) and nothing else -- pays for neither the first D columns
+ * of dx nor the parameter gradients.  They launch the kernels of the entry points they shadow (new instantiations: no new kernel).
+ *
+ * Row      row b of the first layer's input is [ x[b, 0 .. D) | x2[b, 0 .. n2) ] with D = net->layer[0].in_dim - n2 >= 1 and
+ *          1 <= n2 <= 8 (the action limit of the heads; the two backward entry points also take n2 == 0, the plain row, with x2 and
+ *          dx2 NULL).  x: float32, or float64 with net->x_f64, rounded as it is read; x2: always float32.  Strides in ELEMENTS:
+ *          x_stride >= D, x2_stride >= n2.  x, x2, dx, dx2 need their element's alignment, the blocked weights 16 bytes.
+ * Limits   those of the shadowed entry point: in_dim = D + n2 <= PDEGYM_MLP_MAX_INPUT for the forward, <= 1024 for the backward
+ *          passes; 64 units per layer for pdegym_mlp_backward_cat, 256 for pdegym_mlp_backward_wide_cat; up to 4 layers.
+ * Bits     y, dw, db, dx and dx2 equal, BIT FOR BIT, y, dw, db, dx[:, :D] and dx[:, D:] of pdegym_mlp_forward / pdegym_mlp_backward /
+ *          pdegym_mlp_backward_wide on the materialised rows with the same `slabs`: the same operands meet the same accumulator chains.
+ * Forward  every head, clamp and noise option of pdegym_mlp_forward; one launch.
+ * Backward pdegym_mlp_backward_cat_args holds the fields of pdegym_mlp_backward_args and the second part.  dx is the gradient of the
+ *          FIRST D columns, [B, D] (dx_stride >= D) or NULL, only with float32 x; dx2 that of the tail, [B, n2] (dx2_stride >= n2) or
+ *          NULL.  params != 0: the three launches, the workspace and the slabs of the shadowed pass; dw and db are written.
+ *          params == 0: the input gradient alone in ONE launch -- the tile kernel instantiated without the dW / db products, without
+ *          their partial stores and without the dZ / H workspace traffic of the wide pass.  dw[] and db[] must all be NULL (else -2),
+ *          workspace may be NULL, slabs is ignored, and at least one of dx and dx2 is required (else -3).  dx and dx2 carry the bits
+ *          of params != 0: dH = dZ W runs over the units in blocks of 16 in one chain, whatever the slabs.  With dx == NULL only the
+ *          16-column blocks of dZ_0 W_0 that meet the tail are formed (with dx2 == NULL only those that meet the first part).
+ * Rows >= B of the last tile are never read from x or x2 and never written to dx or dx2 (selected to zero, not multiplied by it).
+ * Non-finite data: a NaN in x2[i] reaches row i of y, dx, dx2 and the weight gradients, and no other row of y, dx or dx2.
+ * Errors   as the shadowed entry points: -1 null descriptor / arguments; -2 a limit, n2 out of range or not below in_dim, a stride
+ *          shorter than its row, dx with x_f64, dw / db given with params == 0, dx2 given with n2 == 0, and everything the shadowed
+ *          pass answers -2 to; -3 a required pointer is NULL (x, x2 with n2 >= 1, y / dy, with params != 0 dw, db of a layer with
+ *          bias and the workspace, with params == 0 both of dx and dx2), or an output (dx2 and the workspace included) that
+ *          overlaps an input (x2 included) or another output as byte ranges. */
+int pdegym_mlp_forward_cat(const pdegym_mlp* net, const void* x, int64_t x_stride, const float* x2, int64_t x2_stride, int32_t n2,
+                           void* y, int64_t y_stride, int32_t B, void* stream);
+
+typedef struct pdegym_mlp_backward_cat_args {
+  const void* x;       /* [B, D], D = in_dim - n2 */
+  int64_t x_stride;
+  const float* dy;
+  int64_t dy_stride;
+  const float* w[PDEGYM_MLP_MAX_LAYERS];
+  float* dw[PDEGYM_MLP_MAX_LAYERS];
+  float* db[PDEGYM_MLP_MAX_LAYERS];
+  float* dx;           /* [B, D] or NULL */
+  int64_t dx_stride;
+  int32_t slabs;
+  int32_t params;      /* 0: dx / dx2 alone, one launch */
+  void* workspace;
+  int64_t workspace_bytes;
+  const float* x2;     /* [B, n2] float32 */
+  int64_t x2_stride;
+  float* dx2;          /* [B, n2] or NULL */
+  int64_t dx2_stride;
+  int32_t n2;          /* 0 .. 8 */
+  int32_t reserved_;
+} pdegym_mlp_backward_cat_args;
+/* (the workspace of params != 0 is that of pdegym_mlp_backward_workspace / pdegym_mlp_backward_wide_workspace) */
+int pdegym_mlp_backward_cat(const pdegym_mlp* net, const pdegym_mlp_backward_cat_args* a, int32_t B, void* stream);
+int pdegym_mlp_backward_wide_cat(const pdegym_mlp* net, const pdegym_mlp_backward_cat_args* a, int32_t B, void* stream);
+
 /* ---- backstepping baseline (the controller every result table of the reference compares the learned policies against) ------
  * Gains: theta [R, m] float32 rows, sampled by the caller (the examples use linspace(dx, X, m), NOT the plant's grid) -> gain [R, m]
  * float64, one wave per row, 2 <= m <= PDEGYM_MAX_N1D; dx is the Python double.  Both are BIT-IDENTICAL to the reference under

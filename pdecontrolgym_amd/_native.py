@@ -41,6 +41,7 @@ EXPORTS = [
     "pdegym_squashed_gaussian_sample", "pdegym_squashed_gaussian_sample_backward", "pdegym_sac_critic_loss", "pdegym_sac_actor_loss",
     "pdegym_sac_loss_workspace", "pdegym_mlp_backward_wide", "pdegym_mlp_backward_wide_workspace",
     "pdegym_fused_adam", "pdegym_fused_adam_workspace",
+    "pdegym_mlp_forward_cat", "pdegym_mlp_backward_cat", "pdegym_mlp_backward_wide_cat",
 ]
 # keys of pdegym_debug_set (test-only dispatch overrides, include/pdegym.h)
 DEBUG_NS_GENERIC, DEBUG_NS_NO_COL, DEBUG_NS_COL_MIN_BATCH, DEBUG_NS_NO_LDS_JACOBI = range(4)
@@ -185,6 +186,16 @@ class MlpBackward(C.Structure):
                 ("w", C.c_void_p * MLP_MAX_LAYERS), ("dw", C.c_void_p * MLP_MAX_LAYERS), ("db", C.c_void_p * MLP_MAX_LAYERS),
                 ("dx", C.c_void_p), ("dx_stride", C.c_int64), ("slabs", C.c_int32), ("reserved_", C.c_int32),
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
+class MlpBackwardCat(C.Structure):
+    """pdegym_mlp_backward_cat_args: ``MlpBackward`` with ``params`` in its reserved word, then the second part of the rows."""
+    _fields_ = [("x", C.c_void_p), ("x_stride", C.c_int64), ("dy", C.c_void_p), ("dy_stride", C.c_int64),
+                ("w", C.c_void_p * MLP_MAX_LAYERS), ("dw", C.c_void_p * MLP_MAX_LAYERS), ("db", C.c_void_p * MLP_MAX_LAYERS),
+                ("dx", C.c_void_p), ("dx_stride", C.c_int64), ("slabs", C.c_int32), ("params", C.c_int32),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+                ("x2", C.c_void_p), ("x2_stride", C.c_int64), ("dx2", C.c_void_p), ("dx2_stride", C.c_int64),
+                ("n2", C.c_int32), ("reserved_", C.c_int32)]
 
 
 class Backstep(C.Structure):
@@ -354,6 +365,12 @@ def load():
     lib.pdegym_mlp_backward_wide_workspace.restype = C.c_int64
     lib.pdegym_mlp_backward_wide.argtypes = [C.POINTER(Mlp), C.POINTER(MlpBackward), C.c_int32, C.c_void_p]
     lib.pdegym_mlp_backward_wide.restype = C.c_int
+    lib.pdegym_mlp_forward_cat.argtypes = [C.POINTER(Mlp), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64,
+                                           C.c_int32, C.c_void_p]
+    lib.pdegym_mlp_forward_cat.restype = C.c_int
+    for f in (lib.pdegym_mlp_backward_cat, lib.pdegym_mlp_backward_wide_cat):
+        f.argtypes = [C.POINTER(Mlp), C.POINTER(MlpBackwardCat), C.c_int32, C.c_void_p]
+        f.restype = C.c_int
     lib.pdegym_ppo_loss_workspace.argtypes = [C.c_int32, C.c_int32]
     lib.pdegym_ppo_loss_workspace.restype = C.c_int64
     lib.pdegym_ppo_loss.argtypes = [C.POINTER(PpoLoss), C.c_int32, C.c_void_p]

@@ -501,6 +501,80 @@ class HipBackend:
         a.slabs, a.workspace, a.workspace_bytes = int(slabs), ws.data_ptr(), ws.numel()
         N.check(call(C.byref(net), C.byref(a), B, N.current_stream_ptr(x.device)), f"pdegym_{entry}")
 
+    @_on_device_of("x")
+    def mlp_forward_cat(self, net: N.Mlp, x, x2, y, B: int):
+        """``mlp_forward`` on rows in two parts (pdegym_mlp_forward_cat): row b is ``[x[b] | x2[b]]``, ``x`` [B, D] float32 or float64
+        (``net.x_f64``), ``x2`` [B, n2] float32 with 1 <= n2 <= 8 and D + n2 == the first layer's in_dim; the bits of ``mlp_forward`` on
+        the concatenated rows, without the concatenation."""
+        import torch
+        for t_, name, want in ((x, "x", torch.float64 if net.x_f64 else torch.float32), (x2, "x2", torch.float32),
+                               (y, "y", torch.float64 if net.y_f64 else torch.float32)):
+            if (not torch.is_tensor(t_) or not t_.is_cuda or t_.device != x.device or t_.dtype != want or t_.dim() != 2
+                    or t_.shape[0] != B or t_.stride(1) != 1):
+                raise N.NativeError(f"mlp_forward_cat: {name} must be a {want} HIP tensor [{B}, width] with unit inner stride on x's device")
+        n2 = int(x2.shape[1])
+        if int(x.shape[1]) + n2 != int(net.layer[0].in_dim):
+            raise N.NativeError(f"mlp_forward_cat: x has {int(x.shape[1])} columns and x2 {n2}, the network takes {int(net.layer[0].in_dim)}")
+        stride = lambda t_: t_.stride(0) if B > 1 else t_.shape[1]      # noqa: E731
+        N.check(self.lib.pdegym_mlp_forward_cat(C.byref(net), x.data_ptr(), stride(x), x2.data_ptr(), stride(x2), n2, y.data_ptr(), stride(y),
+                                                B, N.current_stream_ptr(x.device)), "pdegym_mlp_forward_cat")
+
+    @_on_device_of("x")
+    def mlp_backward_cat(self, net: N.Mlp, x, x2, dy, weights, dw=None, db=None, dx=None, dx2=None, params: bool = True,
+                         slabs: int = 0, wide: bool = False):
+        """``mlp_backward`` (``wide``: ``mlp_backward_wide``) on rows in two parts (pdegym_mlp_backward_cat / _wide_cat): ``x`` [B, D],
+        ``x2`` [B, n2] float32 or None (n2 = 0: the plain row), ``dx`` [B, D] and ``dx2`` [B, n2] float32 or None.  ``params`` true:
+        the three launches, ``dw`` / ``db`` as for ``mlp_backward``; false: ONE launch for ``dx`` / ``dx2`` alone -- ``dw`` and ``db``
+        must be None (or lists of None), no workspace is touched.  Bits: those of the shadowed pass on the concatenated rows."""
+        import torch
+        entry = "mlp_backward_wide_cat" if wide else "mlp_backward_cat"
+        B, nl = int(x.shape[0]) if x.dim() == 2 else -1, int(net.n_layers)
+        n2 = 0 if x2 is None else (int(x2.shape[1]) if torch.is_tensor(x2) and x2.dim() == 2 else -1)
+        D = int(net.layer[0].in_dim) - n2
+        want_x = torch.float64 if net.x_f64 else torch.float32
+        rows = (("x", x, want_x, D), ("x2", x2, torch.float32, n2), ("dy", dy, torch.float32, int(net.layer[nl - 1].out_dim)),
+                ("dx", dx, torch.float32, D), ("dx2", dx2, torch.float32, n2))
+        for name, t_, dtype, width in rows:
+            if t_ is None and name in ("x2", "dx", "dx2"):
+                continue
+            if (not torch.is_tensor(t_) or not t_.is_cuda or t_.device != x.device or t_.dtype != dtype or t_.dim() != 2
+                    or tuple(t_.shape) != (B, width) or (width > 1 and t_.stride(1) != 1) or (B > 1 and t_.stride(0) < width)):
+                raise N.NativeError(f"{entry}: {name} must be a {dtype} HIP tensor [{B}, {width}] with unit inner stride on x's device")
+        dw = [None] * nl if dw is None else dw
+        db = [None] * nl if db is None else db
+        if not (len(weights) == len(dw) == len(db) == nl):
+            raise N.NativeError(f"{entry}: weights, dw and db must have one entry per layer ({nl})")
+        if not params and any(t_ is not None for t_ in list(dw) + list(db)):
+            raise N.NativeError(f"{entry}: params=False takes no dw and no db")
+        a = N.MlpBackwardCat()
+        for l in range(nl):
+            shape = (int(net.layer[l].out_dim), int(net.layer[l].in_dim))
+            for name, t_, shp in (("weights", weights[l], shape), ("dw", dw[l], shape), ("db", db[l], shape[:1])):
+                if t_ is None and (name == "db" or not params):
+                    continue
+                if (not torch.is_tensor(t_) or not t_.is_cuda or t_.device != x.device or t_.dtype != torch.float32
+                        or tuple(t_.shape) != shp or not t_.is_contiguous()):
+                    raise N.NativeError(f"{entry}: {name}[{l}] must be a contiguous float32 HIP tensor {shp} on x's device")
+            a.w[l] = weights[l].data_ptr()
+            a.dw[l], a.db[l] = (None if dw[l] is None else dw[l].data_ptr()), (None if db[l] is None else db[l].data_ptr())
+        stride = lambda t_: t_.stride(0) if B > 1 else t_.shape[1]      # noqa: E731
+        a.x, a.x_stride, a.dy, a.dy_stride = x.data_ptr(), stride(x), dy.data_ptr(), stride(dy)
+        if x2 is not None:
+            a.x2, a.x2_stride, a.n2 = x2.data_ptr(), stride(x2), n2
+        if dx is not None:
+            a.dx, a.dx_stride = dx.data_ptr(), stride(dx)
+        if dx2 is not None:
+            a.dx2, a.dx2_stride = dx2.data_ptr(), stride(dx2)
+        a.params, a.slabs = int(bool(params)), int(slabs)
+        if params:
+            shadowed = "mlp_backward_wide" if wide else "mlp_backward"
+            need = int(getattr(self.lib, f"pdegym_{shadowed}_workspace")(C.byref(net), B, int(slabs)))
+            if need < 0:
+                N.check(need, f"pdegym_{shadowed}_workspace")
+            ws = (self._mlp_backward_wide_workspace if wide else self._mlp_backward_workspace)(x.device, need)
+            a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+        N.check(getattr(self.lib, f"pdegym_{entry}")(C.byref(net), C.byref(a), B, N.current_stream_ptr(x.device)), f"pdegym_{entry}")
+
     def _mlp_backward_workspace(self, device, nbytes: int):
         """The workspace of ``mlp_backward``: one uint8 tensor per (device, size), kept (every launch of one stream uses it in turn)."""
         import torch

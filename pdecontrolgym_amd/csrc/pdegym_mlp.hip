@@ -37,9 +37,12 @@ constexpr int kXChunk = 512;                // observation entries per row stage
 // loads in flight per CU than fewer waves with more tiles each (257-256-256-1 at B = 4096: 27.7 us with 4 waves x 4 tiles,
 // 21.4 with 8 x 2, 19.2 with 16 x 1).
 // GAUSS: the squashed-Gaussian head's epilogue, compiled apart -- as a run-time branch it cost the plain head 1 %
-template <int NT, int WV, typename TX, typename TY, bool GAUSS>
+// CAT: rows in two parts (pdegym_mlp_forward_cat), columns 0 .. D-1 from x and D .. in_dim-1 from the float32 x2; compiled apart as
+// well, so that pdegym_mlp_forward's staging loop stays the code it was
+template <int NT, int WV, typename TX, typename TY, bool GAUSS, bool CAT>
 __global__ __launch_bounds__(64 * WV) void mlp_forward_kernel(pdegym_mlp N, const TX* __restrict__ x, long long x_stride,
-                                                          TY* __restrict__ y, long long y_stride, int B, int ldx) {
+                                                          TY* __restrict__ y, long long y_stride, int B, int ldx,
+                                                          const float* __restrict__ x2, long long x2_stride, int D) {
   // LDS: activations ping-pong between hb0 and hb1; the staged observation chunk shares its space with hb1 (first written
   // by the second layer, when the observations are no longer needed)
   extern __shared__ __attribute__((aligned(16))) float mlp_smem[];
@@ -116,10 +119,16 @@ __global__ __launch_bounds__(64 * WV) void mlp_forward_kernel(pdegym_mlp N, cons
             const int r = kRowsPerWave * wave + rr;
             const bool row_ok = row0 + r < B;
             const TX* src = x + (long long)(row_ok ? row0 + r : 0) * x_stride + c0;
+            const float* tail = CAT ? x2 + (long long)(row_ok ? row0 + r : 0) * x2_stride : nullptr;
 #pragma unroll
             for (int i = 0; i < kXChunk / 64; ++i) {
               const int c = lane + 64 * i;
-              v[rr][i] = (row_ok && c < clen) ? (float)src[c] : 0.f;
+              if (CAT) {      // column c0 + c of the row: the first part, or entry c0 + c - D of the tail
+                v[rr][i] = 0.f;
+                if (row_ok && c < clen) v[rr][i] = c0 + c < D ? (float)src[c] : tail[c0 + c - D];
+              } else {
+                v[rr][i] = (row_ok && c < clen) ? (float)src[c] : 0.f;
+              }
             }
           }
           if (c0 > 0 && any_tile) load_w<NT>(wfirst, wq, H, ngroups, c0 / 16, lg, col);
@@ -181,33 +190,47 @@ __global__ __launch_bounds__(64 * WV) void mlp_forward_kernel(pdegym_mlp N, cons
 
 }  // namespace
 
+// the second part of a two-part row (pdegym_mlp_forward_cat); x2 == nullptr: the plain row of pdegym_mlp_forward
+struct Tail {
+  const float* x2;
+  long long x2_stride;
+  int D;
+};
+
 template <int NT, int WV, typename TX, typename TY, bool GAUSS>
-static void launch_mlp_nt(const pdegym_mlp* net, const TX* xp, long long xs, TY* yp, long long ys, int B, hipStream_t st) {
+static void launch_mlp_nt(const pdegym_mlp* net, const TX* xp, long long xs, TY* yp, long long ys, int B, const Tail& tl, hipStream_t st) {
   const int kin = net->layer[0].in_dim < kXChunk ? net->layer[0].in_dim : kXChunk;
   const int ldh = lds_stride(16 * WV * NT);
   const int ldx = lds_stride(kin) > ldh ? lds_stride(kin) : ldh;
   const size_t lds_bytes = (size_t)kRows * (ldh + ldx) * sizeof(float);         // <= 50 KB: below the 64 KB that need no opt-in
-  hipLaunchKernelGGL((mlp_forward_kernel<NT, WV, TX, TY, GAUSS>), dim3((B + kRows - 1) / kRows), dim3(64 * WV), lds_bytes, st, *net, xp, xs, yp, ys,
-                     B, ldx);
+  const dim3 grid((B + kRows - 1) / kRows), block(64 * WV);
+  if (tl.x2)
+    hipLaunchKernelGGL((mlp_forward_kernel<NT, WV, TX, TY, GAUSS, true>), grid, block, lds_bytes, st, *net, xp, xs, yp, ys, B, ldx, tl.x2,
+                       tl.x2_stride, tl.D);
+  else
+    hipLaunchKernelGGL((mlp_forward_kernel<NT, WV, TX, TY, GAUSS, false>), grid, block, lds_bytes, st, *net, xp, xs, yp, ys, B, ldx, nullptr, 0LL, 0);
 }
 
 template <typename TX, typename TY, bool GAUSS>
-static void launch_mlp_head(const pdegym_mlp* net, const TX* xp, long long xs, TY* yp, long long ys, int B, int width, hipStream_t st) {
-  if (width <= 64) launch_mlp_nt<1, 4, TX, TY, GAUSS>(net, xp, xs, yp, ys, B, st);
-  else if (width <= 128) launch_mlp_nt<1, 8, TX, TY, GAUSS>(net, xp, xs, yp, ys, B, st);
-  else launch_mlp_nt<1, 16, TX, TY, GAUSS>(net, xp, xs, yp, ys, B, st);
+static void launch_mlp_head(const pdegym_mlp* net, const TX* xp, long long xs, TY* yp, long long ys, int B, int width, const Tail& tl,
+                            hipStream_t st) {
+  if (width <= 64) launch_mlp_nt<1, 4, TX, TY, GAUSS>(net, xp, xs, yp, ys, B, tl, st);
+  else if (width <= 128) launch_mlp_nt<1, 8, TX, TY, GAUSS>(net, xp, xs, yp, ys, B, tl, st);
+  else launch_mlp_nt<1, 16, TX, TY, GAUSS>(net, xp, xs, yp, ys, B, tl, st);
 }
 
 template <typename TX, typename TY>
-static void launch_mlp(const pdegym_mlp* net, const void* x, long long xs, void* y, long long ys, int B, int width, hipStream_t st) {
+static void launch_mlp(const pdegym_mlp* net, const void* x, long long xs, void* y, long long ys, int B, int width, const Tail& tl,
+                       hipStream_t st) {
   const TX* xp = static_cast<const TX*>(x);
   TY* yp = static_cast<TY*>(y);
-  if (net->head == PDEGYM_MLP_HEAD_SQUASHED_GAUSSIAN) launch_mlp_head<TX, TY, true>(net, xp, xs, yp, ys, B, width, st);
-  else launch_mlp_head<TX, TY, false>(net, xp, xs, yp, ys, B, width, st);
+  if (net->head == PDEGYM_MLP_HEAD_SQUASHED_GAUSSIAN) launch_mlp_head<TX, TY, true>(net, xp, xs, yp, ys, B, width, tl, st);
+  else launch_mlp_head<TX, TY, false>(net, xp, xs, yp, ys, B, width, tl, st);
 }
 
-extern "C" int pdegym_mlp_forward(const pdegym_mlp* net, const void* x, int64_t x_stride, void* y, int64_t y_stride, int32_t B,
-                                  void* stream) {
+// pdegym_mlp_forward (n2 == 0, x2 == nullptr) and pdegym_mlp_forward_cat (n2 >= 1): one set of checks, one dispatch
+static int mlp_forward_rows(const pdegym_mlp* net, const void* x, int64_t x_stride, const float* x2, int64_t x2_stride, int32_t n2,
+                            void* y, int64_t y_stride, int32_t B, void* stream) {
   if (!net || !x || !y) return pdegym::fail(-3, "null pointer");
   if (B < 0) return pdegym::fail(-2, "B must be >= 0");
   if (net->n_layers < 1 || net->n_layers > PDEGYM_MLP_MAX_LAYERS) return pdegym::fail(-2, "n_layers must be 1..4");
@@ -232,7 +255,9 @@ extern "C" int pdegym_mlp_forward(const pdegym_mlp* net, const void* x, int64_t 
   } else if (net->head != PDEGYM_MLP_HEAD_PLAIN) {
     return pdegym::fail(-2, "unknown head");
   }
-  if (x_stride < net->layer[0].in_dim || y_stride < n_out) return pdegym::fail(-2, "row stride shorter than the row");
+  if (x_stride < net->layer[0].in_dim - n2 || y_stride < n_out) return pdegym::fail(-2, "row stride shorter than the row");
+  if (n2 >= net->layer[0].in_dim) return pdegym::fail(-2, "mlp_forward_cat: n2 must be below the first layer's in_dim (D >= 1)");
+  if (n2 && x2_stride < n2) return pdegym::fail(-2, "mlp_forward_cat: x2 row stride shorter than the row");
   if (net->clamp && !(net->lo <= net->hi)) return pdegym::fail(-2, "clamp bounds must satisfy lo <= hi");
   if (net->noise && net->noise_stride < n_out) return pdegym::fail(-2, "noise row stride shorter than the row");
   if (B == 0) return 0;
@@ -240,9 +265,23 @@ extern "C" int pdegym_mlp_forward(const pdegym_mlp* net, const void* x, int64_t 
   for (int l = 0; l < net->n_layers; ++l) width = net->layer[l].out_dim > width ? net->layer[l].out_dim : width;
   hipStream_t st = (hipStream_t)stream;
   const long long xs = x_stride, ys = y_stride;
-  if (net->x_f64 && net->y_f64) launch_mlp<double, double>(net, x, xs, y, ys, B, width, st);
-  else if (net->x_f64) launch_mlp<double, float>(net, x, xs, y, ys, B, width, st);
-  else if (net->y_f64) launch_mlp<float, double>(net, x, xs, y, ys, B, width, st);
-  else launch_mlp<float, float>(net, x, xs, y, ys, B, width, st);
-  return pdegym::check_launch("mlp_forward");
+  const Tail tl = {x2, x2_stride, net->layer[0].in_dim - n2};
+  if (net->x_f64 && net->y_f64) launch_mlp<double, double>(net, x, xs, y, ys, B, width, tl, st);
+  else if (net->x_f64) launch_mlp<double, float>(net, x, xs, y, ys, B, width, tl, st);
+  else if (net->y_f64) launch_mlp<float, double>(net, x, xs, y, ys, B, width, tl, st);
+  else launch_mlp<float, float>(net, x, xs, y, ys, B, width, tl, st);
+  return pdegym::check_launch(n2 ? "mlp_forward_cat" : "mlp_forward");
+}
+
+extern "C" int pdegym_mlp_forward(const pdegym_mlp* net, const void* x, int64_t x_stride, void* y, int64_t y_stride, int32_t B,
+                                  void* stream) {
+  return mlp_forward_rows(net, x, x_stride, nullptr, 0, 0, y, y_stride, B, stream);
+}
+
+extern "C" int pdegym_mlp_forward_cat(const pdegym_mlp* net, const void* x, int64_t x_stride, const float* x2, int64_t x2_stride,
+                                      int32_t n2, void* y, int64_t y_stride, int32_t B, void* stream) {
+  if (n2 < 1 || n2 > 8) return pdegym::fail(-2, "mlp_forward_cat: n2 must be 1..8");
+  if (!x2) return pdegym::fail(-3, "null pointer");
+  if (!pdegym::is_aligned(x2, 4)) return pdegym::fail(-2, "mlp_forward_cat: x2 must be 4-byte aligned");
+  return mlp_forward_rows(net, x, x_stride, x2, x2_stride, n2, y, y_stride, B, stream);
 }

@@ -18,6 +18,10 @@
 // All three products run on v_mfma_f32_16x16x4_f32 (float32 in, float32 accumulate: an exact fmaf chain), so the order of every sum
 // is fixed by the code: rows ascending within a slab, slabs ascending, a layer's units in blocks of 16 (four MFMAs per block, unit 16 kb + 4 lg + c in the c-th).  Rows >= B of
 // the last tile are selected to zero (never multiplied by zero: a non-finite weight would turn that into NaN) and never read.
+//
+// pdegym_mlp_backward_cat (rows in two parts, the critic(obs, action) call) launches the same kernels,
+// instantiated with CAT (two-part addressing of the first layer's input and of dx) and, for params == 0, without PARAMS (the tile
+// kernel alone: no dW / db products, no workspace).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -53,6 +57,13 @@ struct Plan {
   int off_w[kLayers], off_b[kLayers];
   int in[kLayers], out[kLayers];
   int per_slab, n_layers, B, tiles, slabs;
+  // rows in two parts (pdegym_mlp_backward_cat; read by the CAT instantiations alone): columns 0 .. D-1 of the first layer's input
+  // come from x, columns D .. in[0]-1 from x2; dx holds the first D columns of dZ_0 W_0, dx2 the others
+  const float* x2;
+  long long x2_stride;
+  float* dx2;
+  long long dx2_stride;
+  int D;
 };
 
 __device__ __forceinline__ v4f mma(float a, float b, v4f acc) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0); }
@@ -66,7 +77,9 @@ __device__ __forceinline__ float act_backward(float dh, float h, int act) {
   return dh;
 }
 
-template <typename TX>
+// CAT: rows in two parts.  PARAMS false: the input gradient alone -- no dW / db products, no dZ_0 in the workspace, no partial stores
+// (pdegym_mlp_backward_cat with params == 0; the only launch of that call).  pdegym_mlp_backward runs <TX, false, true>, the code it was.
+template <typename TX, bool CAT, bool PARAMS>
 __global__ __launch_bounds__(256) void mlp_backward_tiles(pdegym_mlp N, Plan P, int ldx) {
   extern __shared__ __attribute__((aligned(16))) float bw_smem[];
   float* const hs = bw_smem;                                   // [kLayers][16][kLdh]: the activations of every layer
@@ -109,7 +122,16 @@ __global__ __launch_bounds__(256) void mlp_backward_tiles(pdegym_mlp N, Plan P, 
             const int r = 4 * wave + rr;
             const bool row_ok = row0 + r < B;
             const TX* src = x + (long long)(row_ok ? row0 + r : 0) * P.x_stride + c0;
-            for (int c = lane; c < cpad; c += 64) xs[r * ldx + c] = (row_ok && c < clen) ? (float)src[c] : 0.f;
+            if (CAT) {      // column c0 + c: the first part, or entry c0 + c - D of the tail
+              const float* tail = P.x2 + (long long)(row_ok ? row0 + r : 0) * P.x2_stride;
+              for (int c = lane; c < cpad; c += 64) {
+                float v = 0.f;
+                if (row_ok && c < clen) v = c0 + c < P.D ? (float)src[c] : tail[c0 + c - P.D];
+                xs[r * ldx + c] = v;
+              }
+            } else {
+              for (int c = lane; c < cpad; c += 64) xs[r * ldx + c] = (row_ok && c < clen) ? (float)src[c] : 0.f;
+            }
           }
           if (any_tile) load_w<1>(wfirst, wq, H, ngroups, c0 / 16, lg, col);
           __syncthreads();
@@ -155,11 +177,11 @@ __global__ __launch_bounds__(256) void mlp_backward_tiles(pdegym_mlp N, Plan P, 
         const bool ok = row0 + er < B && c < H;
         const float dz = ok ? act_backward(g[er * kLdh + c], hs[(l * kRows + er) * kLdh + c], act) : 0.f;
         g[er * kLdh + c] = dz;
-        if (l == 0) P.dz0[(long long)(row0 + er) * kWidth + c] = dz;
+        if (PARAMS && l == 0) P.dz0[(long long)(row0 + er) * kWidth + c] = dz;
       }
       __syncthreads();
       // db_l += sum_rows dZ_l, dW_l += dZ_l^T H_{l-1}: A[unit][row] = dZ, B[row][input] = H (or ones); rows in four groups of four
-      if (16 * wave < H) {
+      if (PARAMS && 16 * wave < H) {
         float a[4];
 #pragma unroll
         for (int s = 0; s < 4; ++s) a[s] = g[(4 * s + lg) * kLdh + n];
@@ -177,10 +199,13 @@ __global__ __launch_bounds__(256) void mlp_backward_tiles(pdegym_mlp N, Plan P, 
         }
       }
       // dH_{l-1} = dZ_l W_l (into dx for the first layer): A[row][unit] = dZ, B[unit][input] = W row-major, units in blocks of 16
-      if (l >= 1 || P.dx) {
+      if (l >= 1 || P.dx || (CAT && P.dx2)) {
         const float* __restrict__ W = P.w[l];
         const int in_tiles = (K + 15) >> 4, unit_blocks = (H + 15) >> 4;
-        for (int t = wave; t < in_tiles; t += 4) {
+        // two-part rows, first layer: only the 16-column tiles that meet a part someone asked for
+        const int t_first = (CAT && l == 0 && !P.dx) ? P.D >> 4 : 0;
+        const int t_last = (CAT && l == 0 && !P.dx2) ? (P.D + 15) >> 4 : in_tiles;
+        for (int t = t_first + wave; t < t_last; t += 4) {
           const int i = 16 * t + li, ic = i < K ? i : K - 1;
           v4f d = {0.f, 0.f, 0.f, 0.f};
           for (int kb = 0; kb < unit_blocks; ++kb) {
@@ -202,7 +227,15 @@ __global__ __launch_bounds__(256) void mlp_backward_tiles(pdegym_mlp N, Plan P, 
           for (int v = 0; v < 4; ++v) {
             const int r = 4 * lg + v;
             if (l >= 1) gn[r * kLdh + i] = dv[v];                  // (i < 64: in_tiles <= 4)
-            else if (i < K && row0 + r < B) P.dx[(long long)(row0 + r) * P.dx_stride + i] = dv[v];
+            else if (!CAT) {
+              if (i < K && row0 + r < B) P.dx[(long long)(row0 + r) * P.dx_stride + i] = dv[v];
+            } else if (i < K && row0 + r < B) {
+              if (i < P.D) {
+                if (P.dx) P.dx[(long long)(row0 + r) * P.dx_stride + i] = dv[v];
+              } else if (P.dx2) {
+                P.dx2[(long long)(row0 + r) * P.dx2_stride + (i - P.D)] = dv[v];
+              }
+            }
           }
         }
       }
@@ -213,6 +246,7 @@ __global__ __launch_bounds__(256) void mlp_backward_tiles(pdegym_mlp N, Plan P, 
   }
 
   // ---- the slab's partial sums --------------------------------------------------------------------------------------------------------
+  if (!PARAMS) return;
   float* const part = P.part + (long long)blockIdx.x * P.per_slab;
 #pragma unroll
   for (int l = 0; l < kLayers; ++l) {
@@ -241,7 +275,7 @@ __global__ __launch_bounds__(256) void mlp_backward_tiles(pdegym_mlp N, Plan P, 
 }
 
 // dW_0 partial of (64 input columns blockIdx.x, slab blockIdx.y) = dZ_0^T X over the slab's rows, ascending.  No LDS, no barrier.
-template <typename TX>
+template <typename TX, bool CAT>
 __global__ __launch_bounds__(256) void mlp_backward_dw0(Plan P) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int li = lane & 15, lg = lane >> 4;
@@ -264,8 +298,13 @@ __global__ __launch_bounds__(256) void mlp_backward_dw0(Plan P) {
       for (int s = 0; s < 4; ++s) {
         const int r = row0 + 4 * s + lg, i = i0 + 16 * t + li;
         const bool ok = r < B && i < K;
-        const TX v = x[ok ? (long long)r * P.x_stride + i : 0];
-        b[t][s] = ok ? (float)v : 0.f;
+        if (CAT) {
+          b[t][s] = 0.f;
+          if (ok) b[t][s] = i < P.D ? (float)x[(long long)r * P.x_stride + i] : P.x2[(long long)r * P.x2_stride + (i - P.D)];
+        } else {
+          const TX v = x[ok ? (long long)r * P.x_stride + i : 0];
+          b[t][s] = ok ? (float)v : 0.f;
+        }
       }
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
@@ -435,14 +474,114 @@ int pdegym_mlp_backward(const pdegym_mlp* net, const pdegym_mlp_backward_args* a
   const dim3 grid0((unsigned)((K0 + 63) / 64), (unsigned)slabs);
   const dim3 block(256), grid_reduce((unsigned)((P.per_slab + 255) / 256));
   if (net->x_f64) {
-    mlp_backward_tiles<double><<<dim3(slabs), block, lds_bytes, st>>>(*net, P, ldx);
-    mlp_backward_dw0<double><<<grid0, block, 0, st>>>(P);
+    mlp_backward_tiles<double, false, true><<<dim3(slabs), block, lds_bytes, st>>>(*net, P, ldx);
+    mlp_backward_dw0<double, false><<<grid0, block, 0, st>>>(P);
   } else {
-    mlp_backward_tiles<float><<<dim3(slabs), block, lds_bytes, st>>>(*net, P, ldx);
-    mlp_backward_dw0<float><<<grid0, block, 0, st>>>(P);
+    mlp_backward_tiles<float, false, true><<<dim3(slabs), block, lds_bytes, st>>>(*net, P, ldx);
+    mlp_backward_dw0<float, false><<<grid0, block, 0, st>>>(P);
   }
   mlp_backward_reduce<<<grid_reduce, block, 0, st>>>(P);
   return pdegym::check_launch("mlp_backward");
+}
+
+// Rows in two parts, the parameter gradients on request (include/pdegym.h).  params != 0: the three launches above on the CAT
+// instantiations; params == 0: the tile kernel alone, without its dW / db half, over the library's own slabs (a partition of the
+// tiles among workgroups that no result depends on).
+int pdegym_mlp_backward_cat(const pdegym_mlp* net, const pdegym_mlp_backward_cat_args* a, int32_t B, void* stream) {
+  if (int rc = check_net(net)) return rc;
+  if (!a) return pdegym::fail(-1, "null arguments");
+  const bool params = a->params != 0;
+  const int slabs = resolve_slabs(B, params ? a->slabs : 0);
+  if (slabs < 0) return slabs;
+  const int nl = net->n_layers, K0 = net->layer[0].in_dim, n_out = net->layer[nl - 1].out_dim, n2 = a->n2;
+  if (n2 < 0 || n2 > 8) return pdegym::fail(-2, "mlp_backward_cat: n2 must be 0..8");
+  if (n2 >= K0) return pdegym::fail(-2, "mlp_backward_cat: n2 must be below the first layer's in_dim (D >= 1)");
+  const int D = K0 - n2;
+  if (!a->x || !a->dy) return pdegym::fail(-3, "null x/dy");
+  if (n2 && !a->x2) return pdegym::fail(-3, "null x2");
+  if (!n2 && a->dx2) return pdegym::fail(-2, "mlp_backward_cat: dx2 given with n2 == 0");
+  if (n2 && !pdegym::is_aligned(a->x2, 4)) return pdegym::fail(-2, "x2 must be 4-byte aligned");
+  if (a->dx2 && !pdegym::is_aligned(a->dx2, 4)) return pdegym::fail(-2, "dx2 must be 4-byte aligned");
+  if (params) {
+    if (!a->workspace) return pdegym::fail(-3, "null workspace");
+    if (!pdegym::is_aligned(a->workspace, 4)) return pdegym::fail(-2, "workspace must be 4-byte aligned");
+  } else if (!a->dx && !a->dx2) {
+    return pdegym::fail(-3, "params == 0: one of dx and dx2 is required");
+  }
+  const bool want_dx = a->dx || a->dx2;
+  for (int l = 0; l < nl; ++l) {
+    if (params) {
+      if (!a->dw[l]) return pdegym::fail(-3, "null dw");
+      if (a->db[l] && !net->layer[l].b) return pdegym::fail(-3, "db given for a layer without bias");
+      if (!a->db[l] && net->layer[l].b) return pdegym::fail(-3, "null db for a layer with bias");
+    } else if (a->dw[l] || a->db[l]) {
+      return pdegym::fail(-2, "params == 0: dw and db must all be NULL");
+    }
+    if (!a->w[l] && (l > 0 || want_dx)) return pdegym::fail(-3, "null row-major weights (w[0] is needed with dx / dx2, the others always)");
+  }
+  if (a->dx && net->x_f64) return pdegym::fail(-2, "dx needs float32 x");
+  if (a->x_stride < D || a->dy_stride < n_out || (a->dx && a->dx_stride < D) || (n2 && a->x2_stride < n2) || (a->dx2 && a->dx2_stride < n2))
+    return pdegym::fail(-2, "row stride shorter than the row");
+  const int64_t need = params ? (dz0_floats(B) + (int64_t)slabs * per_slab_floats(net)) * (int64_t)sizeof(float) : 0;
+  if (params && a->workspace_bytes < need) return pdegym::fail(-2, "workspace smaller than pdegym_mlp_backward_workspace answers");
+
+  Range in[3 + 3 * kLayers], out[3 + 2 * kLayers];
+  int n_in = 0, n_outr = 0;
+  in[n_in++] = extent(a->x, B, a->x_stride, D, net->x_f64 ? 8 : 4);
+  in[n_in++] = extent(n2 ? a->x2 : nullptr, B, a->x2_stride, n2, 4);
+  in[n_in++] = extent(a->dy, B, a->dy_stride, n_out, 4);
+  for (int l = 0; l < nl; ++l) {
+    const pdegym_mlp_layer& L = net->layer[l];
+    const int64_t cells = (int64_t)L.out_dim * L.in_dim;
+    in[n_in++] = extent(a->w[l], 1, cells, cells, 4);
+    in[n_in++] = extent(L.w, 1, 0, (int64_t)((L.in_dim + 3) / 4) * L.out_dim * 4, 4);
+    in[n_in++] = extent(L.b, 1, L.out_dim, L.out_dim, 4);
+    out[n_outr++] = extent(a->dw[l], 1, cells, cells, 4);
+    out[n_outr++] = extent(a->db[l], 1, L.out_dim, L.out_dim, 4);
+  }
+  out[n_outr++] = extent(a->dx, B, a->dx_stride, D, 4);
+  out[n_outr++] = extent(a->dx2, B, a->dx2_stride, n2, 4);
+  out[n_outr++] = extent(params ? a->workspace : nullptr, 1, need, need, 1);
+  for (int i = 0; i < n_outr; ++i) {
+    for (int j = 0; j < n_in; ++j)
+      if (out[i].overlaps(in[j])) return pdegym::fail(-3, "an output or the workspace overlaps an input");
+    for (int j = i + 1; j < n_outr; ++j)
+      if (out[i].overlaps(out[j])) return pdegym::fail(-3, "two outputs overlap (the workspace counts as one)");
+  }
+
+  Plan P = {};
+  P.x = a->x, P.x_stride = a->x_stride, P.dy = a->dy, P.dy_stride = a->dy_stride, P.dx = a->dx, P.dx_stride = a->dx_stride;
+  P.x2 = a->x2, P.x2_stride = a->x2_stride, P.dx2 = a->dx2, P.dx2_stride = a->dx2_stride, P.D = D;
+  P.dz0 = params ? static_cast<float*>(a->workspace) : nullptr;
+  P.part = params ? P.dz0 + dz0_floats(B) : nullptr;
+  int at = 0;
+  for (int l = 0; l < nl; ++l) {
+    const pdegym_mlp_layer& L = net->layer[l];
+    P.w[l] = a->w[l], P.dw[l] = a->dw[l], P.db[l] = a->db[l], P.in[l] = L.in_dim, P.out[l] = L.out_dim;
+    P.off_w[l] = at, at += L.out_dim * L.in_dim;
+    P.off_b[l] = at, at += L.out_dim;
+  }
+  P.per_slab = at, P.n_layers = nl, P.B = B, P.tiles = (int)(((int64_t)B + kRows - 1) / kRows), P.slabs = slabs;
+  hipStream_t st = (hipStream_t)stream;
+  const int kin = ((K0 < kXChunk ? K0 : kXChunk) + 15) & ~15;
+  const int ldx = lds_stride(kin);
+  const size_t lds_bytes = (size_t)((kLayers + 2) * kRows * kLdh + kRows * ldx) * sizeof(float);
+  const dim3 grid0((unsigned)((K0 + 63) / 64), (unsigned)slabs);
+  const dim3 block(256), grid_reduce((unsigned)((P.per_slab + 255) / 256));
+  if (!params) {
+    if (net->x_f64) mlp_backward_tiles<double, true, false><<<dim3(slabs), block, lds_bytes, st>>>(*net, P, ldx);
+    else mlp_backward_tiles<float, true, false><<<dim3(slabs), block, lds_bytes, st>>>(*net, P, ldx);
+    return pdegym::check_launch("mlp_backward_cat");
+  }
+  if (net->x_f64) {
+    mlp_backward_tiles<double, true, true><<<dim3(slabs), block, lds_bytes, st>>>(*net, P, ldx);
+    mlp_backward_dw0<double, true><<<grid0, block, 0, st>>>(P);
+  } else {
+    mlp_backward_tiles<float, true, true><<<dim3(slabs), block, lds_bytes, st>>>(*net, P, ldx);
+    mlp_backward_dw0<float, true><<<grid0, block, 0, st>>>(P);
+  }
+  mlp_backward_reduce<<<grid_reduce, block, 0, st>>>(P);
+  return pdegym::check_launch("mlp_backward_cat");
 }
 
 }  // extern "C"

@@ -18,6 +18,11 @@ the same kernels (include/pdegym.h: PDEGYM_MLP_HEAD_SQUASHED_GAUSSIAN).
 (csrc/pdegym_mlp_backward.hip) for layers of at most 64 units and ``pdegym_mlp_backward_wide``
 (csrc/pdegym_mlp_backward_wide.hip) for layers of up to 256 -- SB3's SAC networks --, and fills the ``.grad`` of the wrapped module's
 Parameters.
+
+``policy(obs, tail)`` / ``forward_into(obs, out, tail=...)`` / ``with_grad(obs, tail, params=...)``: SB3's ``critic(obs, actions)`` call
+form -- the first layer reads its row from the two tensors (pdegym_mlp_forward_cat: no ``torch.cat``), the gradient goes back to
+``tail`` (and to a float32 ``obs`` that asks for it) as ``[B, n2]`` / ``[B, D]`` tensors of their own, and ``params=False`` -- the critic
+pass of SAC's actor step -- runs the backward as ONE launch that forms no parameter gradient (pdegym_mlp_backward_cat / _wide_cat).
 """
 from __future__ import annotations
 
@@ -258,8 +263,28 @@ class FusedMLP:
             net.noise, net.noise_stride = noise.data_ptr(), (1 if actions.dim() == 2 else int(actions.shape[2]))
         return net
 
-    def forward_into(self, obs, out, clamp="default", noise=None):
-        """out[b, :] = net(obs[b, :]); ``obs`` [B, in_dim] (any trailing shape that flattens to in_dim), ``out`` [B, out_dim]
+    def _check_tail(self, x, tail, what):
+        """``tail`` as the second part of the rows whose first part is ``x`` [B, D]: float32 [B, n2] on x's device, 1 <= n2 <= 8, the
+        widths adding up to ``in_dim``; on a backend with the two-part entry points.  ``ValueError`` otherwise."""
+        import torch
+        if not (hasattr(self.backend, "mlp_forward_cat") and hasattr(self.backend, "mlp_backward_cat")):
+            raise ValueError(f"FusedMLP.{what}: tail= needs a backend with mlp_forward_cat / mlp_backward_cat, {type(self.backend).__name__} has none")
+        if not torch.is_tensor(tail) or tail.dim() != 2 or tail.shape[0] != x.shape[0]:
+            raise ValueError(f"FusedMLP.{what}: tail must be a [B, n2] tensor with the observations' B = {x.shape[0]}")
+        if tail.dtype != torch.float32:
+            raise ValueError(f"FusedMLP.{what}: tail must be float32, got {tail.dtype}")
+        if tail.device != x.device:
+            raise ValueError(f"FusedMLP.{what}: tail is on {tail.device}, the observations on {x.device}")
+        if not 1 <= tail.shape[1] <= 8:
+            raise ValueError(f"FusedMLP.{what}: tail must have 1..8 columns, got {tail.shape[1]}")
+        if x.shape[1] + tail.shape[1] != self.in_dim:
+            raise ValueError(f"observation rows have {x.shape[1]} entries and tail rows {tail.shape[1]}, the network takes {self.in_dim}")
+
+    def forward_into(self, obs, out, clamp="default", noise=None, tail=None):
+        """``tail`` (float32 [B, n2], n2 <= 8): the rows are ``[obs | tail]``, read from the two tensors as they are -- SB3's
+        ``critic(obs, actions)`` -- with the bits of the call on ``torch.cat([obs, tail], 1)``.  Without it:
+
+        out[b, :] = net(obs[b, :]); ``obs`` [B, in_dim] (any trailing shape that flattens to in_dim), ``out`` [B, out_dim]
         or [B] when out_dim == 1, on the parameters' device.  float64 observations (traffic, tumour, float64 Navier-Stokes)
         are rounded to float32 as they are read and a float64 ``out`` receives the widened float32 result -- the casts SB3
         makes around its float32 policy.  ``noise`` (float32, same shape as the action): added to the network output before
@@ -270,7 +295,9 @@ class FusedMLP:
         ``out_dim`` <= 8."""
         B = obs.shape[0]
         x = obs.reshape(B, -1)
-        if x.shape[1] != self.in_dim:
+        if tail is not None:
+            self._check_tail(x, tail, "forward_into")
+        elif x.shape[1] != self.in_dim:
             raise ValueError(f"observation rows have {x.shape[1]} entries, the network takes {self.in_dim}")
         y = out.reshape(B, self.out_dim)
         if y.data_ptr() != out.data_ptr():
@@ -286,7 +313,10 @@ class FusedMLP:
             if nz.dtype != torch.float32 or nz.device != x.device or nz.stride(1) != 1 or nz.data_ptr() != noise.data_ptr():
                 raise ValueError("noise must be a float32 tensor on the observations' device, viewable as [B, out_dim]")
             net.noise, net.noise_stride = nz.data_ptr(), nz.stride(0)
-        self.backend.mlp_forward(net, x, y, B)
+        if tail is not None:
+            self.backend.mlp_forward_cat(net, x, _rows(tail), y, B)
+        else:
+            self.backend.mlp_forward(net, x, y, B)
         return out
 
     # ---- the differentiable evaluation (pdegym_mlp_forward + pdegym_mlp_backward / _wide) ---------------------------------------------
@@ -334,8 +364,14 @@ class FusedMLP:
             ps += [p for m in self._heads for p in (m.weight, m.bias) if p is not None]
         return ps
 
-    def with_grad(self, obs):
-        """``[B, n]`` float32 WITH a ``grad_fn``: the last layer's output (no clamp, no noise, no head: a squashed-Gaussian wrapper
+    def with_grad(self, obs, tail=None, params=True):
+        """``tail`` (float32 [B, n2], n2 <= 8): the rows are ``[obs | tail]`` -- SB3's ``critic(obs, actions)`` -- and ``tail`` receives its
+        own ``[B, n2]`` gradient when it requires grad (``obs``, float32 and requiring grad, the ``[B, D]`` one of the first part: no
+        full-width dx exists).  ``params=False``: no gradient goes to ``grad_parameters()`` and the backward is ONE launch that forms
+        none (the critic pass of SAC's actor step); the same pass runs when no parameter requires grad.  Bits: those of the call on
+        ``torch.cat([obs, tail], 1)``.  ``ValueError`` on a backend without the two-part entry points.  Without the two arguments:
+
+        ``[B, n]`` float32 WITH a ``grad_fn``: the last layer's output (no clamp, no noise, no head: a squashed-Gaussian wrapper
         returns the raw ``[B, 2A]`` rows -- mu columns, then log_std columns -- and SAC's torch code applies clip / exp / tanh under
         autograd).  Forward: one ``pdegym_mlp_forward`` launch after ``refresh()``; backward: ``pdegym_mlp_backward`` for a network
         that ``fits_backward()``, ``pdegym_mlp_backward_wide`` for a wider one that ``fits_backward_wide()``; either returns the
@@ -350,31 +386,50 @@ class FusedMLP:
             raise ValueError(f"FusedMLP.with_grad: {self.backward_limit()}")
         B = obs.shape[0]
         x = obs.reshape(B, -1)
-        if x.shape[1] != self.in_dim:
+        if tail is not None:
+            self._check_tail(x, tail, "with_grad")
+        elif x.shape[1] != self.in_dim:
             raise ValueError(f"observation rows have {x.shape[1]} entries, the network takes {self.in_dim}")
         if x.dtype not in (torch.float32, torch.float64):
             raise ValueError(f"FusedMLP.with_grad: obs must be float32 or float64, got {x.dtype}")
+        two_part = hasattr(self.backend, "mlp_forward_cat") and hasattr(self.backend, "mlp_backward_cat")
+        if not params and not two_part:
+            raise ValueError(f"FusedMLP.with_grad: params=False needs a backend with mlp_backward_cat, {type(self.backend).__name__} has none")
         if x.is_cuda and torch.cuda.is_current_stream_capturing():
             if self._optimizer is None:      # (attached: the optimiser's own launch writes the copies, there is nothing to refresh)
                 raise RuntimeError("FusedMLP.with_grad cannot run inside a stream capture: refresh() has to see the optimiser's last step")
         else:
             self.refresh()
-        return _with_grad_function().apply(self, x, *self.grad_parameters())
+        ps = self.grad_parameters()
+        if tail is not None or not params or (two_part and not any(p.requires_grad for p in ps)):
+            if not params:      # detached: no edge to the parameters (saved all the same: a backward after an in-place step is refused)
+                ps = [p.detach() for p in ps]
+            return _with_grad_function(cat=True).apply(self, bool(params), x, tail, *ps)
+        return _with_grad_function().apply(self, x, *ps)
 
-    def __call__(self, obs):
+    def __call__(self, obs, tail=None):
         import torch
         out = torch.empty(obs.shape[0], self.out_dim, dtype=obs.dtype, device=obs.device)
-        return self.forward_into(obs, out)      # (squashed-Gaussian head: a ValueError -- it has no default box; use forward_into)
+        return self.forward_into(obs, out, tail=tail)      # (squashed-Gaussian head: a ValueError -- it has no default box; use forward_into)
 
 
-_function = None
+def _rows(t):
+    """``t`` [B, n] detached, with unit inner stride and rows that do not overlap (what the entry points take), copied only if not."""
+    t = t.detach()
+    if t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        t = t.contiguous()
+    return t
 
 
-def _with_grad_function():
-    """The ``torch.autograd.Function`` behind ``FusedMLP.with_grad`` (built on first use: this module imports torch lazily)."""
-    global _function
+_function = _cat_function = None
+
+
+def _with_grad_function(cat=False):
+    """The ``torch.autograd.Function`` behind ``FusedMLP.with_grad`` (built on first use: this module imports torch lazily).  ``cat``:
+    the one behind ``with_grad(obs, tail, params)``, on the two-part entry points."""
+    global _function, _cat_function
     if _function is not None:
-        return _function
+        return _cat_function if cat else _function
     import torch
 
     class FusedMLPFunction(torch.autograd.Function):
@@ -409,5 +464,51 @@ def _with_grad_function():
             wanted = ctx.needs_input_grad[2:]
             return (None, dx) + tuple(g if need else None for g, need in zip(grads, wanted))
 
-    _function = FusedMLPFunction
-    return _function
+    class FusedMLPCatFunction(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, policy, params, x, tail, *ps):
+            xd, td = _rows(x), (None if tail is None else _rows(tail))
+            n_out = int(policy.layers[-1][0].shape[0])
+            y = torch.empty(xd.shape[0], n_out, dtype=torch.float32, device=xd.device)
+            net = policy._net(None, xd.dtype == torch.float64, plain=True)
+            if td is None:
+                policy.backend.mlp_forward(net, xd, y, xd.shape[0])
+            else:
+                policy.backend.mlp_forward_cat(net, xd, td, y, xd.shape[0])
+            ctx.policy = policy
+            ctx.want_dx = bool(ctx.needs_input_grad[2]) and x.dtype == torch.float32
+            ctx.want_dx2 = td is not None and bool(ctx.needs_input_grad[3])
+            ctx.want_params = params and any(ctx.needs_input_grad[4:])
+            ctx.has_tail = td is not None
+            ctx.save_for_backward(xd, *(() if td is None else (td,)), *ps)
+            return y
+
+        @staticmethod
+        def backward(ctx, dy):
+            policy = ctx.policy
+            xd, td = ctx.saved_tensors[0], (ctx.saved_tensors[1] if ctx.has_tail else None)
+            none = (None,) * (4 + len(ctx.needs_input_grad[4:]))
+            if not (ctx.want_params or ctx.want_dx or ctx.want_dx2):
+                return none
+            dy = dy.to(torch.float32).contiguous()
+            weights = [w.detach() for w, _, _ in policy.layers]
+            dw = db = None
+            if ctx.want_params:
+                dw = [torch.empty_like(w) for w in weights]
+                db = [None if b is None else torch.empty_like(b.detach()) for _, b, _ in policy.layers]
+            dx = torch.empty(xd.shape, dtype=torch.float32, device=xd.device) if ctx.want_dx else None
+            dx2 = torch.empty(td.shape, dtype=torch.float32, device=td.device) if ctx.want_dx2 else None
+            policy.backend.mlp_backward_cat(policy._net(None, xd.dtype == torch.float64, plain=True), xd, td, dy, weights, dw, db, dx, dx2,
+                                            params=ctx.want_params, wide=not policy.fits_backward())
+            if not ctx.want_params:
+                return (None, None, dx, dx2) + none[4:]
+            heads = policy._heads is not None
+            grads = [g for w_, b_ in zip(dw[:-1] if heads else dw, db[:-1] if heads else db) for g in (w_, b_) if g is not None]
+            if heads:      # rows 0 .. A-1 of the fused last layer are mu's, rows A .. 2A-1 log_std's
+                A = dw[-1].shape[0] // 2
+                for rows in (slice(0, A), slice(A, 2 * A)):
+                    grads += [dw[-1][rows]] + ([db[-1][rows]] if db[-1] is not None else [])
+            return (None, None, dx, dx2) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[4:]))
+
+    _function, _cat_function = FusedMLPFunction, FusedMLPCatFunction
+    return _cat_function if cat else _function

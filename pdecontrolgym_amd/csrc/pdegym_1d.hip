@@ -18,6 +18,9 @@
 //       transport  environments1d/hyperbolic.py:143-155
 //       parabolic  environments1d/parabolic.py:138-150
 //       reward     rewards/tuned_reward_1d.py:25-40 (streaming form, see docs/HISTORY.md section 3.3)
+//   * the one place a fused multiply-add replaces two of the reference's roundings: the headline instantiation (nx = 256 parabolic)
+//     folds a power-of-two F into x + F*lap, which is exact unless F*lap underflows; one v_min3_f32 per sub-step guards the rows
+//     where it could (pdegym_1d_body.h: run_substeps, FOLD; tests/test_fold_lemma.py)
 #ifdef PDEGYM_HEAD_STAMPS
 // Diagnostic build (tools/head_stamps.py; 1 = the kernels as launched, 2 = every launch through step1d_kernel): three 100 MHz
 // real-time stamps per wave -- 0 at wave entry, 1 when the head's pointers are in SGPRs, 2 when the row, beta and the per-instance
@@ -41,6 +44,8 @@ __device__ unsigned long long pdegym_head_stamp_buf[3 * 65536];
 #define PDEGYM_HEAD_STAMPS_OUT(inst)
 #endif
 #include "pdegym_1d_body.h"
+
+#include <cstring>
 
 namespace {
 
@@ -72,6 +77,10 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void step1d_kernel(pdegym_pa
 // with kernel-argument preloading (build.py: FILE_OPTS), which hands exactly these 14 dwords to the wave in SGPRs at launch: then
 // not even that fetch stands in front of the loads (C2 15.59 -> 15.22 us, S = 1 4.52 -> 4.15 us: profiles/r08_ab_notes.txt).
 struct HeadArgs {};      // names the overload: step1d_kernel<HeadArgs, ...> is the fast path with leading head arguments
+// ... and the same launch with the folded sub-step (run_substeps: FOLD), for the headline shape only.  A kernel of its own, chosen by
+// launch_epl when F is a power of two and an env-step has more than one sub-step: compiled into the HeadArgs kernel, the second loop
+// moved the S = 1 launch from 4.15 to 4.45 us (profiles/r19_ab_notes.txt), so that launch keeps the kernel it had.
+struct HeadArgsFold {};
 template <typename LEAD, int EPL, bool PARABOLIC, bool BURGERS, bool FULL>
 __global__ __launch_bounds__(kWave* kWavesPerBlock) void step1d_kernel(const float* row_in, const void* beta, int32_t* time_index,
                                                                              const void* action, double* bsum, float* ring,
@@ -95,7 +104,10 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void step1d_kernel(const flo
   L.action = action;
   L.bsum = bsum;
   L.ring = ring;
-  step1d_body<EPL, PARABOLIC, false, false, BURGERS, false, false, false, FULL, false, true>(P, L, B, inst, lane);
+  // the headline shape alone (nx = 256 parabolic, the row fills the wave) folds a power-of-two F into one fma per slot (run_substeps: FOLD)
+  constexpr bool kFold = std::is_same_v<LEAD, HeadArgsFold>;
+  static_assert(!kFold || (EPL == 4 && PARABOLIC && !BURGERS && FULL), "the fold is the headline shape's");
+  step1d_body<EPL, PARABOLIC, false, false, BURGERS, false, false, false, FULL, false, true, kFold>(P, L, B, inst, lane);
   PDEGYM_HEAD_STAMPS_OUT(inst);
 }
 
@@ -422,6 +434,13 @@ __global__ void selftest_quotient_kernel(SelftestQuotientArgs A) {
   }
 }
 
+// F = 2^-1 ... 2^-24 exactly and more than one sub-step per env-step: the launches the folded kernel serves (it tests the same itself)
+inline bool fold_serves(const pdegym_params1d& P) {
+  unsigned int fbits;
+  std::memcpy(&fbits, &P.F, sizeof fbits);
+  return P.substeps > 1 && (fbits & 0x7fffffu) == 0u && (fbits >> 23) >= 103u && (fbits >> 23) <= 126u;
+}
+
 template <int EPL, bool PARABOLIC, bool BURGERS = false>
 int launch_epl(const pdegym_params1d& P, const pdegym_bufs1d& Bf, int B, hipStream_t st) {
   const dim3 grid((B + kWavesPerBlock - 1) / kWavesPerBlock), block(kWave * kWavesPerBlock);
@@ -453,7 +472,11 @@ int launch_epl(const pdegym_params1d& P, const pdegym_bufs1d& Bf, int B, hipStre
     if (kHead && Bf.beta_stride >= 0 && Bf.beta_stride <= INT32_MAX) {      // step1d_kernel<HeadArgs, ...>: the head's arguments lead
       const float* row_in = Bf.state_in ? Bf.state_in : Bf.u;
       const int bstride = (int)Bf.beta_stride;
-      if (full)
+      constexpr bool kHasFold = EPL == 4 && PARABOLIC && !BURGERS && kHasFull;
+      if (full && kHasFold && fold_serves(P))
+        hipLaunchKernelGGL((step1d_kernel<std::conditional_t<kHasFold, HeadArgsFold, HeadArgs>, EPL, PARABOLIC, BURGERS, kHasFull>), grid, block,
+                           lds, st, row_in, Bf.beta, Bf.time_index, Bf.action, Bf.bsum, Bf.ring, bstride, B, P, Bf);
+      else if (full)
         hipLaunchKernelGGL((step1d_kernel<HeadArgs, EPL, PARABOLIC, BURGERS, kHasFull>), grid, block, lds, st, row_in, Bf.beta, Bf.time_index,
                            Bf.action, Bf.bsum, Bf.ring, bstride, B, P, Bf);
       else

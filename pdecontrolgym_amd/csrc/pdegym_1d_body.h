@@ -283,11 +283,23 @@ __device__ __forceinline__ float kind_norm(const float (&x)[EPL], float bl, int 
 // sub-step, i.e. parabolic Neumann control).
 // M64: float64 beta and/or float64 / Python-float control (pdegym_params1d.beta_f64 / action_kind): the select form with the
 // reference's mixed-precision expressions (see step1d_wide_kernel for the same arithmetic on LDS-resident rows).
+// FOLD (step1d_kernel<HeadArgsFold, 4, true, false, true> only, the headline shape): when the caller says fold_ok -- F = 2^-k, 1 <= k <= 24,
+// more than one sub-step -- the sub-steps behind the peeled first one form t5 = fma(F, t3, x) instead of x + RN(F * t3): F * t3 is exact
+// unless it underflows, and then the two agree bit for bit.  The guard (tests/test_fold_lemma.py): a slot can differ only
+// where |x| < 2^-100 AND a neighbour is below 2^-78; of two adjacent slots one is even, so a row whose EVEN slots (e = 0 and 2 of every
+// lane; the frozen boundary slot 255 and node 0 are odd / outside) all hold |x| >= 2^-78 is folded exactly.  One v_min3_f32 per sub-step
+// keeps the running minimum of the even slots' magnitudes of every row a fold sub-step reads, against the floor 2^-64.  A row below the
+// floor after the peeled sub-step (zeros, compact support, denormals) never enters the fold loop; one that sinks below it later makes
+// the caller run the whole call again in the plain form (*fold_redo).  NaN compares as not-below in v_min3_f32 and is left to the
+// caller's non-finite test, like today.
+constexpr float kFoldFloor = 5.421010862427522e-20f;      // 2^-64
 template <int EPL, bool PARABOLIC, bool NEUMANN, bool FAST, bool HIST, bool BURGERS = false, bool M64 = false, bool ROLL = false,
-          typename RingT = RingMem, bool FULL = false>
+          typename RingT = RingMem, bool FULL = false, bool FOLD = false>
 __device__ __forceinline__ void run_substeps(Row<EPL>& R, const float (&beta)[EPL], const pdegym_params1d& P, int nsub,
                                              float a, RingT& ring, float* hist, int lane, const double* b64 = nullptr, double a64 = 0.0,
-                                             float* xprev = nullptr, float* blprev = nullptr, int thor_k = 0) {
+                                             float* xprev = nullptr, float* blprev = nullptr, int thor_k = 0, bool fold_ok = false,
+                                             bool* fold_redo = nullptr) {
+  static_assert(!FOLD || (FAST && PARABOLIC && FULL && !HIST && !ROLL && EPL == 4), "the fold is the headline instantiation's");
   // xprev/blprev (select form only): the row BEFORE the last sub-step, for NormReward's "differential" horizon
   // thor_k (select form only): NormReward "t-horizon" of length thor_k -- the reward's norm of each of the last thor_k - 1 rows
   // before the final one goes into the ring (the final row's is the epilogue's)
@@ -332,11 +344,20 @@ __device__ __forceinline__ void run_substeps(Row<EPL>& R, const float (&beta)[EP
     }
   }
 
+  // FOLD: running minimum of the even slots' magnitudes (one instruction; the compiler's fminf would canonicalise the carried value)
+  float fold_min = __builtin_inff();
+  auto fold_track = [&]() {
+    if constexpr (FOLD) asm("v_min3_f32 %0, %1, |%2|, |%3|" : "=v"(fold_min) : "v"(fold_min), "v"(R.x[0]), "v"(R.x[2 % EPL]));
+  };
+  auto fold_below = [&]() { return __builtin_amdgcn_ballot_w64(!(fold_min >= kFoldFloor)) != 0ull; };     // wave-uniform
+
   // one PDE sub-step on the register-resident row (no bookkeeping).  GENERAL_EDGE: node 0 may be non-zero (first
   // sub-step after a reset) and, on the fast path, the frozen boundary slot takes the new control value.
+  // pow2_tag: transport -- dx is a power of two; parabolic with FOLD -- the folded form (F is a power of two, see above).
   auto pde_substep = [&](auto general_edge, auto pow2_tag) {
     constexpr bool GENERAL_EDGE = decltype(general_edge)::value;
-    constexpr bool POW2_DX = decltype(pow2_tag)::value;
+    constexpr bool POW2_DX = !PARABOLIC && decltype(pow2_tag)::value;
+    constexpr bool FOLDED = FOLD && PARABOLIC && decltype(pow2_tag)::value && !GENERAL_EDGE;
     // p[first slot - 1]; after the first sub-step node 0 is identically 0, so the shift needs no fill operand
     const float xl = PARABOLIC ? from_left_lane(R.x[EPL - 1], GENERAL_EDGE ? R.bl : 0.0f) : 0.0f;
     const float xr = from_right_lane(R.x[0], 0.0f);                          // p[last slot + 1]
@@ -380,10 +401,16 @@ __device__ __forceinline__ void run_substeps(Row<EPL>& R, const float (&beta)[EP
       }
 #pragma unroll
       for (int e = 0; e < EPL; ++e) t7[e] = c[e] * R.x[e];
+      if constexpr (FOLDED) {
 #pragma unroll
-      for (int e = 0; e < EPL; ++e) t4[e] = fe[e] * t3[e];
+        for (int e = 0; e < EPL; ++e) t5[e] = __builtin_fmaf(fe[e], t3[e], R.x[e]);
+        (void)t4;
+      } else {
 #pragma unroll
-      for (int e = 0; e < EPL; ++e) t5[e] = R.x[e] + t4[e];
+        for (int e = 0; e < EPL; ++e) t4[e] = fe[e] * t3[e];
+#pragma unroll
+        for (int e = 0; e < EPL; ++e) t5[e] = R.x[e] + t4[e];
+      }
 #pragma unroll
       for (int e = 0; e < EPL; ++e) y[e] = t5[e] + t7[e];
     } else if constexpr (FAST && !PARABOLIC) {
@@ -483,6 +510,7 @@ __device__ __forceinline__ void run_substeps(Row<EPL>& R, const float (&beta)[EP
       for (int e = 0; e < EPL; ++e) R.x[e] = (s0 + e == ns - 1) ? bval : R.x[e];
     }
     R.bl = 0.0f;  // parabolic.py:146  u(0,t) = 0
+    if constexpr (FOLDED) fold_track();      // the row the next fold sub-step reads
   };
   // rows whose norm a later reward call looks back at (tuned_reward_1d.py:40): r+100 is a step end
   auto record_norm = [&](int done) {
@@ -552,6 +580,13 @@ __device__ __forceinline__ void run_substeps(Row<EPL>& R, const float (&beta)[EP
       if (HIST && hrow) store_row(std::true_type{});
       record_norm(s);
     }
+    bool folding = false;      // wave-uniform
+    if constexpr (FOLD) {
+      if (fold_ok) {           // (implies nsub > 1: the peeled sub-step has run)
+        fold_track();
+        folding = !fold_below();
+      }
+    }
     while (s < nsub) {
       int run = nsub - s;
       if (rec_all) {
@@ -573,6 +608,9 @@ __device__ __forceinline__ void run_substeps(Row<EPL>& R, const float (&beta)[EP
           if (any_part) run_of(run, std::false_type{}, std::true_type{});
           else run_of(run, std::false_type{}, std::false_type{});
         }
+      } else if constexpr (FOLD) {
+        if (folding) for (int i = 0; i < run; ++i) pde_substep(std::false_type{}, std::true_type{});
+        else for (int i = 0; i < run; ++i) pde_substep(std::false_type{}, std::false_type{});
       } else {
         if (pow2_dx) for (int i = 0; i < run; ++i) pde_substep(std::false_type{}, std::true_type{});
         else for (int i = 0; i < run; ++i) pde_substep(std::false_type{}, std::false_type{});
@@ -582,6 +620,9 @@ __device__ __forceinline__ void run_substeps(Row<EPL>& R, const float (&beta)[EP
       if (R.k >= S) R.k -= S;
       s += run;
       record_norm(s);
+    }
+    if constexpr (FOLD) {
+      if (folding) *fold_redo = fold_below();      // some row a fold sub-step read was below the floor: the caller starts over
     }
   } else {
     for (int s = 0; s < nsub; ++s) {
@@ -632,7 +673,7 @@ __device__ __forceinline__ void load_row(Row<EPL>& R, float (&beta)[EPL], const 
 // HFAST (round 6, with HIST): the fast sub-step loop storing every row into the trajectory buffer (bufs.history must be given; the
 // launcher keeps the NormReward "differential" / "t-horizon" requests on the select form).
 template <int EPL, bool PARABOLIC, bool NEUMANN, bool HIST, bool BURGERS = false, bool M64 = false, bool ROLL = false,
-          bool CARRY = false, bool FULL = false, bool HFAST = false, bool STEP_KERNEL = false>
+          bool CARRY = false, bool FULL = false, bool HFAST = false, bool STEP_KERNEL = false, bool FOLD = false>
 __device__ __forceinline__ void step1d_body(const pdegym_params1d& P, const pdegym_bufs1d& Bf, const int B, const int inst,
                                             const int lane, const float* command = nullptr, Carry<EPL>* carry = nullptr,
                                             const bool store_state = true) {
@@ -775,7 +816,26 @@ __device__ __forceinline__ void step1d_body(const pdegym_params1d& P, const pdeg
     }
     norm_now = 0.f;
     if (!exact) {
-      run_substeps<EPL, PARABOLIC, false, true, HFAST, BURGERS, false, ROLL, RingT, FULL>(R, beta, P, nsub, a, ring, hist, lane);
+      if constexpr (FOLD) {
+        // F = 2^-1 ... 2^-24 exactly (positive, zero mantissa, biased exponent 103 ... 126) and more than one sub-step: scalar tests
+        // (run_substeps: FOLD).  The second pass, if the guard tripped inside the call, is the plain fast loop from the untouched input
+        // row, set up like the exact redo below: it rewrites the ring slots of the first pass, same lane, program order.
+        const unsigned int fbits = __float_as_uint(P.F);
+        const bool fold_ok = nsub > 1 && (fbits & 0x7fffffu) == 0u && (fbits >> 23) >= 103u && (fbits >> 23) <= 126u;
+        bool fold_redo = false;
+        run_substeps<EPL, PARABOLIC, false, true, HFAST, BURGERS, false, ROLL, RingT, FULL, true>(
+            R, beta, P, nsub, a, ring, hist, lane, nullptr, 0.0, nullptr, nullptr, 0, fold_ok, &fold_redo);
+        if (fold_redo) {      // wave-uniform
+          load_row<EPL, PARABOLIC>(R, beta, urow_in, brow, n, lane);
+          R.t = t_in;
+          R.k = (t_in + PDEGYM_LOOKBACK) % S;
+          R.bsum = bsum_in;
+          R.back_norm = 0.f;
+          run_substeps<EPL, PARABOLIC, false, true, HFAST, BURGERS, false, ROLL, RingT, FULL>(R, beta, P, nsub, a, ring, hist, lane);
+        }
+      } else {
+        run_substeps<EPL, PARABOLIC, false, true, HFAST, BURGERS, false, ROLL, RingT, FULL>(R, beta, P, nsub, a, ring, hist, lane);
+      }
       if constexpr (kObsEarly) {
         if (Bf.state_in && P.sensing == PDEGYM_SENSE_FULL) {
           float* orow = Bf.obs + (size_t)inst * n;

@@ -37,11 +37,16 @@ algorithm in plain torch on the batched engine:
                 old log-probabilities are copied into static tensors outside the graph (``randperm`` stays outside as well), the
                 attached wrappers need no ``refresh()`` and the optimiser no host work.  The numbers are those of ``fused_opt``.
 
+``bootstrap`` (off by default: the histories printed without it are unchanged): an episode that is cut off (``limit_pde_state_size``:
+``truncated and not terminated``) is handled as SB3 handles ``infos[i]["TimeLimit.truncated"]`` -- ``DeviceRollout(terminal_obs=True)``
+keeps the terminal observation of every step, and ``DeviceRolloutBuffer.compute`` adds ``gamma * V(terminal observation)`` to that
+step's reward.  Without it every cut-off is treated as a termination.
+
 The plant is the reference's unstable reaction-diffusion benchmark u_t = u_xx + beta(x) u with boundary actuation
 (ReactionDiffusionPDE1D, Dirichlet control at x = 1).  Uncontrolled, ||u|| grows; the printed mean ||u|| over an episode falls
 as the policy learns to damp it.
 
-    python examples/train_ppo_device.py [iterations] [num_envs] [hidden units per layer: 64] [fused_grad: 0] [fused_loss: 0] [fused_opt: 0] [graph_update: 0]
+    python examples/train_ppo_device.py [iterations] [num_envs] [hidden units per layer: 64] [fused_grad: 0] [fused_loss: 0] [fused_opt: 0] [graph_update: 0] [bootstrap: 0]
 """
 import os
 import sys
@@ -86,7 +91,8 @@ def mlp(sizes, out_tanh=False):
 nmb_of_update = 4      # minibatches per epoch
 
 
-def main(iterations=30, B=2048, T=64, quiet=False, hidden=64, fused_grad=False, fused_loss=False, fused_opt=False, graph_update=False):
+def main(iterations=30, B=2048, T=64, quiet=False, hidden=64, fused_grad=False, fused_loss=False, fused_opt=False, graph_update=False,
+         bootstrap=False):
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
     venv = make_env(B, horizon=T)        # one rollout = one episode of every environment
@@ -104,7 +110,7 @@ def main(iterations=30, B=2048, T=64, quiet=False, hidden=64, fused_grad=False, 
     log_std = torch.nn.Parameter(torch.full((1,), -0.7, device=dev))
     opt = torch.optim.Adam(list(actor.parameters()) + list(critic.parameters()) + [log_std], lr=1e-3)
     policy = FusedMLP(actor)
-    rollout = DeviceRollout(venv, policy, T, action_noise=True)
+    rollout = DeviceRollout(venv, policy, T, action_noise=True, terminal_obs=bool(bootstrap))
     # the networks of the update: the modules themselves under torch autograd, or their fused forward + backward launches
     actor_fn, critic_fn = actor, critic
     fused_nets = [policy]
@@ -126,7 +132,7 @@ def main(iterations=30, B=2048, T=64, quiet=False, hidden=64, fused_grad=False, 
                   "lp": torch.empty(T * B, device=dev)}
     start = {"actor": [p.detach().clone() for p in actor.parameters()], "critic": [p.detach().clone() for p in critic.parameters()]}
     gamma, lam, clip, epochs, nmb = 0.99, 0.95, 0.2, 6, nmb_of_update
-    buffer = DeviceRolloutBuffer(rollout, gamma=gamma, gae_lambda=lam)
+    buffer = DeviceRolloutBuffer(rollout, gamma=gamma, gae_lambda=lam)      # (bootstrap: boot = V(terminal rows) where cut off)
     head = PPOLoss(clip_range=clip, ent_coef=1e-3, vf_coef=0.25, normalize_advantage=True) if fused_loss else None
     history = []
     t_roll = t_upd = 0.0
@@ -226,4 +232,5 @@ if __name__ == "__main__":
          hidden=int(sys.argv[3]) if len(sys.argv) > 3 else 64, fused_grad=bool(int(sys.argv[4])) if len(sys.argv) > 4 else False,
          fused_loss=bool(int(sys.argv[5])) if len(sys.argv) > 5 else False,
          fused_opt=bool(int(sys.argv[6])) if len(sys.argv) > 6 else False,
-         graph_update=bool(int(sys.argv[7])) if len(sys.argv) > 7 else False)
+         graph_update=bool(int(sys.argv[7])) if len(sys.argv) > 7 else False,
+         bootstrap=bool(int(sys.argv[8])) if len(sys.argv) > 8 else False)

@@ -16,7 +16,11 @@ batched engine, on the plant of examples/train_ppo_device.py:
                 ``run()``).
 
     python examples/train_sac_device.py [iterations] [num_envs] [hidden units per layer: 64] [fused_grad: 0] [fused_loss: 0] [fused_opt: 0]
-                                        [fused_critic: 0]
+                                        [fused_critic: 0] [terminal_obs: 0]
+
+``terminal_obs`` (off by default: the histories printed without it are unchanged) stores transitions as SB3's replay buffer does:
+``DeviceRollout(terminal_obs=True)`` keeps the terminal observation of every step that ended an episode, ``next`` takes it there and
+``obs[t + 1]`` elsewhere, and ``term`` is ``terminated`` alone -- a cut-off episode (``limit_pde_state_size``) keeps its bootstrap.
 
 ``fused_loss`` sends the three sample / loss blocks of the update through ``pde_control_gym.SACLoss`` (pdegym_squashed_gaussian_sample
 and its backward, pdegym_sac_critic_loss, pdegym_sac_actor_loss): ``head.sample`` writes ``[obs | action]`` and the log-probability in
@@ -87,7 +91,7 @@ def sample(latent, mu, log_std, obs, raw=None):
 
 
 def main(iterations=30, num_envs=1024, n_steps=32, hidden=64, one_launch=None, quiet=False, updates=8, batch=2048, fused_grad=False,
-         fused_loss=False, fused_opt=False, fused_critic=False):
+         fused_loss=False, fused_opt=False, fused_critic=False, terminal_obs=False):
     if fused_critic and not (fused_grad and fused_loss and fused_opt and hidden <= 256):
         raise ValueError("fused_critic needs fused_grad, fused_loss and fused_opt, and layers of at most 256 units")
     dev = torch.device("cuda", 0)
@@ -114,7 +118,8 @@ def main(iterations=30, num_envs=1024, n_steps=32, hidden=64, one_launch=None, q
     opt_alpha = torch.optim.Adam([log_alpha], lr=3e-4)
     start = {k: [p.detach().clone() for p in ps] for k, ps in (("actor", actor_params), ("q1", list(q1.parameters())), ("q2", list(q2.parameters())))}
     policy = FusedMLP.squashed_gaussian(latent, mu, log_std, (LOG_STD_MIN, LOG_STD_MAX))
-    rollout = DeviceRollout(venv, policy, T, action_low=lo, action_high=hi, action_noise=True, one_launch=one_launch)
+    rollout = DeviceRollout(venv, policy, T, action_low=lo, action_high=hi, action_noise=True, one_launch=one_launch,
+                            terminal_obs=bool(terminal_obs))
     # the networks of the update: the modules under torch autograd, or (fused_grad, layers of at most 256 units -- SB3's own 256-256
     # among them) FusedMLP.with_grad -- the critics' gradient with respect to the action column is the dx of pdegym_mlp_backward
     # (layers of at most 64 units) or of pdegym_mlp_backward_wide
@@ -158,11 +163,18 @@ def main(iterations=30, num_envs=1024, n_steps=32, hidden=64, one_launch=None, q
         t_roll += time.perf_counter() - t0
         t0 = time.perf_counter()
         idx = (head + torch.arange(T * B, device=dev)) % cap
-        # (after a restart obs[t + 1] is the new episode's first row: the bootstrap of such a transition is cut like a termination's,
-        # the engines keep no terminal-observation buffer)
-        ended = (rollout.terminated | rollout.truncated).reshape(-1, 1).float()
+        ended = (rollout.terminated | rollout.truncated).reshape(-1, 1)
         buf["obs"][idx] = rollout.obs[:T].reshape(-1, D)
-        buf["next"][idx] = rollout.obs[1:].reshape(-1, D)
+        if terminal_obs:
+            # SB3's replay buffer: next_obs of a step that ended an episode is its terminal observation (obs[t + 1] is the new
+            # episode's first row), and only a termination cuts the bootstrap -- a cut-off episode bootstraps from that row
+            buf["next"][idx] = torch.where(ended.bool(), rollout.terminal_obs.reshape(-1, D), rollout.obs[1:].reshape(-1, D))
+            ended = rollout.terminated.reshape(-1, 1)
+        else:
+            # (after a restart obs[t + 1] is the new episode's first row: the bootstrap of such a transition is cut like a
+            # termination's)
+            buf["next"][idx] = rollout.obs[1:].reshape(-1, D)
+        ended = ended.float()
         buf["act"][idx] = (2.0 * (rollout.actions.reshape(-1, 1) - lo) / (hi - lo) - 1.0).clamp(-1.0, 1.0)
         buf["rew"][idx] = rollout.rewards.reshape(-1, 1)
         buf["term"][idx] = ended
@@ -253,4 +265,5 @@ if __name__ == "__main__":
          hidden=int(sys.argv[3]) if len(sys.argv) > 3 else 64, fused_grad=bool(int(sys.argv[4])) if len(sys.argv) > 4 else False,
          fused_loss=bool(int(sys.argv[5])) if len(sys.argv) > 5 else False,
          fused_opt=bool(int(sys.argv[6])) if len(sys.argv) > 6 else False,
-         fused_critic=bool(int(sys.argv[7])) if len(sys.argv) > 7 else False)
+         fused_critic=bool(int(sys.argv[7])) if len(sys.argv) > 7 else False,
+         terminal_obs=bool(int(sys.argv[8])) if len(sys.argv) > 8 else False)

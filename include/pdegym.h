@@ -40,6 +40,11 @@
  *   pdegym_fused_adam       replaces the tail of every gradient step of those scripts (torch.nn.utils.clip_grad_norm_, torch.optim.Adam
  *                           and, for SAC, stable_baselines3/common/utils.py: polyak_update) and writes the blocked weight copies of
  *                           pdegym_mlp_forward while it is there
+ *   PDEGYM_ROLLOUT_FINAL_OBS_PER_STEP (a bit of the rollout descriptors' reserved_) keeps what SB3's VecEnv hands on as
+ *                           infos[i]["terminal_observation"] for EVERY step of a one-launch rollout (final_obs becomes [T, B, obs_dim]),
+ *                           and pdegym_mlp_forward_masked evaluates V(terminal_observation) on the rows with
+ *                           infos[i]["TimeLimit.truncated"] only: the two halves of the truncation bootstrap of
+ *                           stable_baselines3/common/on_policy_algorithm.py: collect_rollouts
  *
  * One call advances EVERY instance of a batch by one env-step (S PDE sub-steps for the 1D envs, one
  * Chorin projection step with K Jacobi sweeps for NS2D).  Instances are independent.
@@ -82,6 +87,14 @@ extern "C" {
 #endif
 
 #define PDEGYM_ABI_VERSION 21
+/* Bit 0 of pdegym_rollout1d.reserved_, pdegym_rollout_traffic.reserved_ and pdegym_rollout_tumor.reserved_ (the other bits are ignored):
+ * the final_obs of the call (pdegym_bufs1d.final_obs, pdegym_bufs_traffic.final_obs, pdegym_wrap_tumor.final_obs) is an array
+ * [T, B, obs_dim] instead of [B, obs_dim].  Row (t, b) receives what final_obs[b] would hold after the t-th of T consecutive step
+ * calls -- the last observation of the finished episode -- and is written ONLY where step t ended the episode of instance b
+ * (terminated | truncated) and the fused auto-reset restarted it; no other row is touched, and the engine's own [B, obs_dim] final_obs
+ * is NOT written by such a call.  Every other output and the state left behind keep their bits.  With the bit set, final_obs == NULL
+ * is refused with -3 and a call without an auto-reset pool (reset_init / reset_rs) with -2, before anything is launched. */
+#define PDEGYM_ROLLOUT_FINAL_OBS_PER_STEP 1
 #define PDEGYM_RING 128          /* slots of the per-instance row-norm ring (look-back is 100 rows) */
 #define PDEGYM_LOOKBACK 100      /* tuned_reward_1d.py:25,40: int(1/0.01) rows */
 #define PDEGYM_MAX_N1D 2048      /* nodes per 1D row kept in registers by the wave-per-instance kernels */
@@ -181,7 +194,8 @@ typedef struct pdegym_bufs1d {
                                step ends terminated|truncated is restarted INSIDE the same launch (state := pool row,
                                time_index := 0) and obs[b] is the first observation of the new episode            */
   float* final_obs;         /* optional [B, obs_dim]: last observation of the finished episode (written only for
-                               instances that were auto-reset in this call; SB3's "terminal_observation")          */
+                               instances that were auto-reset in this call; SB3's "terminal_observation"); [T, B, obs_dim]
+                               in a rollout call with PDEGYM_ROLLOUT_FINAL_OBS_PER_STEP                             */
   /* The reference redraws BOTH the initial condition and beta at every reset (hyperbolic.py:207-209).  With a pool of
    * reset_pool_rows >= B rows, the k-th restart of instance b takes pool row (b + k*B) mod reset_pool_rows, so consecutive
    * episodes of one instance start from different rows without any host work; reset_pool_rows == 0 means B (row b always). */
@@ -220,7 +234,8 @@ int pdegym_parabolic_step(const pdegym_params1d* prm, const pdegym_bufs1d* buf, 
  * Needs float32 beta and actions, the temporal reward horizon, n <= 2048. */
 typedef struct pdegym_rollout1d {
   int32_t T;                /* env-steps per call                                                              */
-  int32_t reserved_;
+  int32_t reserved_;        /* bit 0: PDEGYM_ROLLOUT_FINAL_OBS_PER_STEP (bufs->final_obs is [T, B, obs_dim]; with scalar sensing
+                               obs_dim == 1); other bits ignored                                               */
   float* obs;               /* [T + 1, B, n]  slot 0 = the input rows; slots 1 .. T are written                 */
   float* actions;           /* [T, B]  read; with a policy: WRITTEN (the command the policy issued, after noise and clamp) */
   float* rewards;           /* [T, B]  (may be NULL with PDEGYM_REWARD_NONE)                                   */
@@ -394,7 +409,8 @@ typedef struct pdegym_bufs_traffic {
    * reward still report the finished step.  qs_clip (the construction-time action bounds) is left alone. */
   const double* reset_rs;      /* optional [reset_pool_rows] steady-state densities of the coming episodes              */
   const double* reset_profile; /* [M] sin(3 x/L pi)*0.1 + 1 as for pdegym_traffic_reset_masked (required with reset_rs)  */
-  double* final_obs;           /* optional [B, 2M]: last observation of the finished episode ("terminal_observation")   */
+  double* final_obs;           /* optional [B, 2M]: last observation of the finished episode ("terminal_observation");
+                                  [T, B, 2M] in a rollout call with PDEGYM_ROLLOUT_FINAL_OBS_PER_STEP                    */
   int32_t* reset_count;        /* optional [B] in/out: restarts so far; NULL = always pool row b mod reset_pool_rows     */
   int32_t reset_pool_rows;     /* rows of reset_rs (0 = B)                                                              */
   int32_t reserved2_;
@@ -412,7 +428,8 @@ int pdegym_traffic_step(const pdegym_params_traffic* prm, const pdegym_bufs_traf
  * rounded to float32, plus noise [T, B, action_stride] (row stride noise_stride), clamped, widened and stored to actions. */
 typedef struct pdegym_rollout_traffic {
   int32_t T;
-  int32_t reserved_;
+  int32_t reserved_;        /* bit 0: PDEGYM_ROLLOUT_FINAL_OBS_PER_STEP (bufs->final_obs is double [T, B, 2M]); other bits ignored;
+                               pdegym_traffic_backstep_rollout takes it too                                     */
   double* obs;              /* [T + 1, B, 2M]  slot 0 is read only by a policy; slots 1 .. T are written         */
   double* actions;          /* [T, B, action_stride]  read, or written when a policy is given                   */
   double* rewards;          /* [T, B]                                                                          */
@@ -513,7 +530,8 @@ typedef struct pdegym_wrap_tumor {
   int64_t* treatment_calls;             /* [B] in/out Therapy-stage wrapper steps                                          */
   int64_t* soft_constraint_violations;  /* [B] in/out Therapy-stage wrapper steps whose reward was negative                */
   double* final_obs;                    /* [B, nx] or NULL: the last row of an episode that ended in this launch (rows of
-                                           other patients are left untouched)                                              */
+                                           other patients are left untouched); [T, B, nx] in a pdegym_tumor_rollout call with
+                                           PDEGYM_ROLLOUT_FINAL_OBS_PER_STEP                                               */
   double* obs;                          /* pdegym_tumor_therapy_step only: [B, nx] receives the returned observation, or NULL:
                                            the observation is buf->u (not with weekends)                                   */
 } pdegym_wrap_tumor;
@@ -548,7 +566,7 @@ int pdegym_tumor_therapy_step(const pdegym_params_tumor* prm, const pdegym_bufs_
  * is refused.                                                                                                                     */
 typedef struct pdegym_rollout_tumor {
   int32_t T;
-  int32_t reserved_;
+  int32_t reserved_;        /* bit 0: PDEGYM_ROLLOUT_FINAL_OBS_PER_STEP (wrap->final_obs is [T, B, nx]); other bits ignored */
   double* obs;              /* [T + 1, B, nx]  slot 0 is read only by a policy; slots 1 .. T are written        */
   double* actions;          /* [T, B]  read, or written when a policy is given                                  */
   double* rewards;          /* [T, B]                                                                           */
@@ -635,6 +653,17 @@ enum { PDEGYM_MLP_HEAD_PLAIN = 0, PDEGYM_MLP_HEAD_SQUASHED_GAUSSIAN = 1 };
 /* y[b, :] = net(x[b, :]) for b < B; x_stride / y_stride = ELEMENTS between consecutive rows (>= the row lengths). */
 int pdegym_mlp_forward(const pdegym_mlp* net, const void* x, int64_t x_stride, void* y, int64_t y_stride, int32_t B,
                        void* stream);
+
+/* The same launch on the LIVE rows only: row r is live when rows[r] != 0 and (rows_not == NULL or rows_not[r] == 0) -- e.g.
+ * rows = truncated, rows_not = terminated of a rollout, x = its terminal observations: SB3's V(terminal_observation) where
+ * infos[i]["TimeLimit.truncated"], with no compaction, no allocation and no synchronisation (the call can be captured in a graph).
+ * rows (required, else -1) and rows_not are uint8 [B] device arrays.  y is stored for live rows only: dead rows of y are NOT
+ * touched.  A live row carries the BITS of pdegym_mlp_forward on the same row (the rows of a 16-row tile are independent in the
+ * matrix-core reduction), whatever the dead rows of x hold -- NaN included.  A workgroup whose 16 rows are all dead returns
+ * before it loads a weight.  Plain head only (head == PLAIN, else -2), noise == NULL (else -2); float32 or float64 x (x_f64),
+ * float32 y (y_f64 is refused); clamp as in pdegym_mlp_forward; both tile plans (layers of <= 64 and of <= 256 units). */
+int pdegym_mlp_forward_masked(const pdegym_mlp* net, const void* x, int64_t x_stride, void* y, int64_t y_stride, const uint8_t* rows,
+                              const uint8_t* rows_not, int32_t B, void* stream);
 
 /* ---- backward pass of the same network (the gradient step of the reference's PPO / SAC training scripts) ------------------------
  * Given dy = dLoss/dy [B, out_dim], pdegym_mlp_backward writes dLoss/dW and dLoss/db of every layer, and optionally dLoss/dx, in three

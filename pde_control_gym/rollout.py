@@ -28,10 +28,15 @@ class DeviceRollout:
     env-step (timings: DESIGN.md section 4.9); ``sensing_noise=True`` keeps its two launches (the traffic kernels take no observation
     noise).  ``one_launch=True`` on a BrainTumor1D environment (``TumorVecEnv``) runs the T ``TherapyWrapper`` steps -- treatment
     days, weekend days, post-therapy and growth runs, restarts -- and a ``FusedMLP`` that fits, or commands given ahead
-    (``policy=None``, fill ``ro.actions``), in one launch: opt-in, bit-identical to the default path."""
+    (``policy=None``, fill ``ro.actions``), in one launch: opt-in, bit-identical to the default path.
+    ``terminal_obs=True`` (after ``venv.enable_fused_auto_reset()``; not on NavierStokes2D, not with sensing noise): ``terminal_obs``
+    ``[T, B, D]``, zero-filled once, keeps SB3's ``infos[b]["terminal_observation"]`` of every step -- row (t, b) receives the last
+    observation of the episode that step t ended (``terminated[t, b] | truncated[t, b]``) while ``obs[t + 1, b]`` is the first of the
+    next one; rows of steps that ended nothing are never written.  Every run path fills it with the same bits (DESIGN.md section
+    4.21); ``DeviceRolloutBuffer`` bootstraps truncated steps from it."""
 
     def __init__(self, venv, policy, n_steps: int, use_graph: bool = True, action_low: float = -1.0, action_high: float = 1.0,
-                 action_noise: bool = False, one_launch=None, sensing_noise: bool = False):
+                 action_noise: bool = False, one_launch=None, sensing_noise: bool = False, terminal_obs: bool = False):
         import torch
         self.venv, self.policy, self.T = venv, policy, int(n_steps)
         self.lo, self.hi = float(action_low), float(action_high)
@@ -97,6 +102,17 @@ class DeviceRollout:
             self.one_launch = False
         if self.sensing_noise is not None and not venv.one_launch_obs_noise:
             self.one_launch = False          # (the traffic rollout kernel has no obs_noise input)
+        # terminal_obs=True: what SB3's VecEnv hands on as infos[b]["terminal_observation"], for every step of the rollout
+        self.terminal_obs = None
+        if terminal_obs:
+            if sensing_noise or self._noise_f is not None:
+                raise ValueError("terminal_obs=True cannot be combined with sensing_noise=True / sensing_noise_tensor_func: the agent "
+                                 "would see the NOISY terminal observation, and the rollout has no noise slot for a terminal row "
+                                 "(sensing_noise is [T + 1, B, ...], one slot per observation slot)")
+            gap = venv.terminal_obs_gap()
+            if gap is not None:
+                raise ValueError("terminal_obs=True: " + gap)
+            self.terminal_obs = torch.zeros_like(self.obs[:self.T])
         self.use_graph = bool(use_graph) and dev.type == "cuda"
         self._graph = None
         self._state_buf = None     # observation tensor the captured graph leaves the end state in (see adopt_rollout_obs)
@@ -107,6 +123,8 @@ class DeviceRollout:
             extra = {}
             if self.sensing_noise is not None:
                 extra = dict(obs_noise=self.sensing_noise[:self.T], obs_seen=self.obs_seen[:self.T])
+            if self.terminal_obs is not None:
+                extra = dict(final_obs_steps=self.terminal_obs)
             self.venv.rollout_one_launch(self.obs, self.actions, self.rewards, self.terminated, self.truncated, policy=self.policy,
                                          clamp=(self.lo, self.hi), noise=self.action_noise, **extra)
             if self.sensing_noise is not None:
@@ -132,6 +150,8 @@ class DeviceRollout:
                         a = a.clamp(self.lo, self.hi)
                     self.actions[t].copy_(a)
                 self.venv.rollout_step(t, self.obs, self.actions, self.rewards, self.terminated, self.truncated)
+                if self.terminal_obs is not None:       # the rows this step ended: engine's final_obs -> row t (no other row is written)
+                    self.venv.rollout_keep_terminal(self.terminal_obs[t], self.terminated[t], self.truncated[t])
             if self.obs_seen is not None:
                 with torch.no_grad():
                     self._see(self.T, torch)

@@ -20,15 +20,22 @@ class DeviceRolloutBuffer:
     ``episode_return[T, B]`` (float64) and ``episode_length[T, B]`` (int32) -- where an episode ended at ``(t, b)`` its return and
     length, else 0 -- and the ``[B]`` accumulators ``ep_return_acc`` / ``ep_length_acc`` of the episodes still running, which
     persist from one rollout to the next (auto-reset ends episodes anywhere in the buffer).  ``boot``: None, or a float32
-    ``[T, B]`` tensor the caller assigns -- V(terminal observation), added as ``gamma * boot`` to the reward of steps that were
-    truncated and not terminated (SB3's time-limit bootstrap); other entries are never used.  Rewards and flags are the rollout's
+    ``[T, B]`` tensor -- V(terminal observation), added as ``gamma * boot`` to the reward of steps that were
+    truncated and not terminated (SB3's time-limit bootstrap, on_policy_algorithm.py: collect_rollouts); other entries are never used.
+    On a rollout built with ``terminal_obs=True`` it is allocated here and ``compute(critic=...)`` fills it before the GAE launch:
+    ``boot[t, b] = critic(rollout.terminal_obs[t, b])`` where ``truncated[t, b] & ~terminated[t, b]`` -- a ``FusedMLP`` critic in one
+    masked launch over the T * B rows (no compaction, no allocation, no synchronisation; the other entries keep what they held), any
+    other module on all T * B rows.  ``bootstrap_truncated=False`` keeps ``boot = None`` (every cut-off treated as SB3 treats a
+    VecEnv without the ``TimeLimit.truncated`` key); ``compute(values=...)`` leaves ``boot`` to the caller, as on any other rollout,
+    where it stays a tensor the caller assigns.  Rewards and flags are the rollout's
     own buffers, the rewards in the engine's dtype (float64 ones are rounded once to float32 as they are read, SB3's storage).
 
     ``compute`` makes no host synchronisation and, with a ``FusedMLP`` critic or ``values=``, no allocation: ``rollout.run()`` and
     ``buf.compute(...)`` can be captured together in one ``torch.cuda.graph`` (build the rollout with ``use_graph=False``, and call
     ``critic.refresh()`` / ``policy.refresh()`` before a replay that follows an optimizer step)."""
 
-    def __init__(self, rollout, gamma: float = 0.99, gae_lambda: float = 0.95, episode_stats: bool = True, backend=None):
+    def __init__(self, rollout, gamma: float = 0.99, gae_lambda: float = 0.95, episode_stats: bool = True, backend=None,
+                 bootstrap_truncated: bool = True):
         import torch
         self.rollout, self.gamma, self.gae_lambda = rollout, float(gamma), float(gae_lambda)
         self.T, self.B = (int(s) for s in rollout.rewards.shape)
@@ -38,6 +45,9 @@ class DeviceRolloutBuffer:
         self.advantages = torch.zeros(T, B, dtype=torch.float32, device=dev)
         self.returns = torch.zeros(T, B, dtype=torch.float32, device=dev)
         self.boot = None
+        self.bootstrap_truncated = bool(bootstrap_truncated) and getattr(rollout, "terminal_obs", None) is not None
+        if self.bootstrap_truncated:
+            self.boot = torch.zeros(T, B, dtype=torch.float32, device=dev)
         self.episode_return = self.episode_length = self.ep_return_acc = self.ep_length_acc = None
         if episode_stats:
             self.episode_return = torch.zeros(T, B, dtype=torch.float64, device=dev)
@@ -71,6 +81,24 @@ class DeviceRolloutBuffer:
                 raise ValueError(f"the critic must return one value per row, got {tuple(v.shape)} for {x.shape[0]} rows")
             out.copy_(v.reshape(-1))
 
+    def _bootstrap(self, critic):
+        """boot[t, b] = critic(terminal observation of step t, environment b) where that step was truncated and not terminated."""
+        import torch
+        ro = self.rollout
+        boot = self.boot
+        if (not torch.is_tensor(boot) or tuple(boot.shape) != (self.T, self.B) or boot.dtype != torch.float32 or not boot.is_contiguous()):
+            raise ValueError(f"boot must stay the contiguous float32 [{self.T}, {self.B}] tensor the constructor allocated")
+        x = ro.terminal_obs.reshape(self.T * self.B, -1)
+        out = boot.view(-1)
+        if hasattr(critic, "forward_into"):          # one masked launch: only the truncated-and-not-terminated rows are evaluated and stored
+            critic.forward_into(x, out, clamp=None, rows=ro.truncated.view(-1), rows_not=ro.terminated.view(-1))
+            return
+        with torch.no_grad():
+            p = next(iter(critic.parameters()), None) if hasattr(critic, "parameters") else None
+            if p is not None and p.dtype != x.dtype:
+                x = x.to(p.dtype)
+            out.copy_(critic(x).reshape(-1))
+
     def compute(self, critic=None, values=None):
         """Fill ``values`` -- from ``critic`` (a ``FusedMLP`` or any torch module mapping ``[N, obs_dim]`` to ``[N, 1]``) or from
         the tensor ``values`` ``[T + 1, B]`` (slot T: SB3's ``last_values``) -- then ``advantages``, ``returns`` and the episode
@@ -80,6 +108,8 @@ class DeviceRolloutBuffer:
             raise ValueError("give exactly one of critic= and values=")
         if critic is not None:
             self._evaluate(critic)
+            if self.bootstrap_truncated:
+                self._bootstrap(critic)
         else:
             if tuple(values.shape) != (self.T + 1, self.B):
                 raise ValueError(f"values must be [{self.T + 1}, {self.B}] (T + 1 observation slots), got {tuple(values.shape)}")

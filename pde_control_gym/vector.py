@@ -132,6 +132,10 @@ class BatchedVecEnv(VecEnv):
     #   adopt_rollout_obs(buf)    after a graph replay (PDEVecEnv below)
     #   one_launch_fits(policy)   whether the whole rollout with the policy inside is ONE kernel launch, rollout_one_launch(*buffers,
     #                             policy=, clamp=, noise=[, obs_noise=, obs_seen=]); one_launch_obs_noise: it takes pre-drawn sensing noise
+    #   terminal_obs_gap()        what keeps DeviceRollout(terminal_obs=True) off this environment, as a sentence, or None;
+    #                             rollout_one_launch(..., final_obs_steps=[T, B, ...]) then keeps the last observation of every episode
+    #                             that ended at (t, b) in row (t, b), and rollout_keep_terminal(slot, terminated, truncated) copies the
+    #                             rows the step just made ended from rollout_final_obs() into ``slot`` on the launch-per-step path
     #   one_launch_law_fits(law)  the same question for a controller evaluated inside the launch (BacksteppingController: opt-in,
     #                             DeviceRollout(one_launch=True)); one_launch_law_gap(law): what is missing, or None
     _rollout_state_keys = None
@@ -160,6 +164,22 @@ class BatchedVecEnv(VecEnv):
 
     def one_launch_fits(self, policy):
         return False
+
+    def terminal_obs_gap(self):
+        if not self._fused_reset:
+            return ("the terminal observation is what the fused auto-reset keeps when it restarts an instance inside the launch: call "
+                    "venv.enable_fused_auto_reset() first")
+        if self.core.t.get("final_obs") is None:
+            return "the engine keeps no final_obs (enable_auto_reset(..., keep_final_obs=False))"
+        return None
+
+    def rollout_final_obs(self):
+        return self.core.t["final_obs"]
+
+    def rollout_keep_terminal(self, slot, terminated, truncated):
+        import torch
+        ended = ((terminated | truncated) != 0).reshape((-1,) + (1,) * (slot.dim() - 1))
+        torch.where(ended, self.rollout_final_obs(), slot, out=slot)
 
     def one_launch_law_gap(self, law):
         return f"{type(self).__name__} has no rollout kernel with a control law inside"
@@ -639,6 +659,10 @@ class NSVecEnv(PDEVecEnv):
     def rollout_body(self, obs):
         with self.core.single_pressure_buffer(), self._rollout_into(obs, ("obs", "reward", "terminated"), True):
             yield
+
+    def terminal_obs_gap(self):
+        return ("NavierStokes2D never truncates (navier_stokes2D.py:155) and the bootstrap of a terminated transition is cut whatever "
+                "its next observation holds: there is no terminal observation to keep")
 
 
 class TrafficVecEnv(PDEVecEnv):

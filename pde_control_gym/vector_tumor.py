@@ -168,15 +168,25 @@ class TumorVecEnv(BatchedVecEnv):
                     f"two float64 rows of {self.core.nx} nodes for 16 patients within 160 KB (TumorBatch.policy_fits_rollout)")
         return None
 
-    def rollout_one_launch(self, obs, actions, rewards, terminated, truncated, policy=None, clamp="default", noise=None, **kw):
+    def rollout_one_launch(self, obs, actions, rewards, terminated, truncated, policy=None, clamp="default", noise=None,
+                           final_obs_steps=None, **kw):
         """T wrapper steps (and the policy) in ONE launch; ``terminal_obs`` holds the last row of every episode that ended in it
-        (the latest one per patient)."""
+        (the latest one per patient) -- or, with ``final_obs_steps`` [T, B, nx], row (t, b) of that tensor holds the last row of the
+        episode that step t ended, and ``terminal_obs`` is left as it was."""
         if kw:
             raise ValueError(f"the tumour rollout kernel takes no {sorted(kw)}")
         W = self._wrapper_state()
+        extra = {} if final_obs_steps is None else {"final_obs_steps": final_obs_steps}
         self.core.rollout(obs, actions, rewards, terminated, truncated, policy=policy, clamp=clamp,
-                          noise=noise if policy is not None else None, wrap_state=W)
-        self.terminal_obs = W["final_obs"]
+                          noise=noise if policy is not None else None, wrap_state=W, **extra)
+        if final_obs_steps is None:
+            self.terminal_obs = W["final_obs"]
+
+    def terminal_obs_gap(self):          # (the wrapper restarts every finished patient itself: nothing to enable)
+        return None
+
+    def rollout_final_obs(self):
+        return self.terminal_obs
 
     # ---- SB3 VecEnv face ------------------------------------------------------------------------------------------------
     def step_wait(self):

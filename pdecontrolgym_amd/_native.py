@@ -42,7 +42,10 @@ EXPORTS = [
     "pdegym_sac_loss_workspace", "pdegym_mlp_backward_wide", "pdegym_mlp_backward_wide_workspace",
     "pdegym_fused_adam", "pdegym_fused_adam_workspace",
     "pdegym_mlp_forward_cat", "pdegym_mlp_backward_cat", "pdegym_mlp_backward_wide_cat",
+    "pdegym_mlp_forward_masked",
 ]
+# bit 0 of Rollout1D / RolloutTraffic / RolloutTumor .reserved_ (PDEGYM_ROLLOUT_FINAL_OBS_PER_STEP): final_obs of the call is [T, B, obs_dim]
+ROLLOUT_FINAL_OBS_PER_STEP = 1
 # keys of pdegym_debug_set (test-only dispatch overrides, include/pdegym.h)
 DEBUG_NS_GENERIC, DEBUG_NS_NO_COL, DEBUG_NS_COL_MIN_BATCH, DEBUG_NS_NO_LDS_JACOBI = range(4)
 MLP_MAX_LAYERS, MLP_MAX_WIDTH, MLP_MAX_INPUT = 4, 256, 8192
@@ -339,6 +342,9 @@ def load():
     lib.pdegym_tumor_rollout.restype = C.c_int
     lib.pdegym_mlp_forward.argtypes = [C.POINTER(Mlp), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
     lib.pdegym_mlp_forward.restype = C.c_int
+    lib.pdegym_mlp_forward_masked.argtypes = [C.POINTER(Mlp), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
+                                              C.c_void_p]
+    lib.pdegym_mlp_forward_masked.restype = C.c_int
     for f in (lib.pdegym_backstep_gain_parabolic, lib.pdegym_backstep_gain_transport):
         f.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_void_p]
         f.restype = C.c_int

@@ -53,6 +53,17 @@ def _prepared(fn, pP, pB, B, dev, what, keep):
     return call
 
 
+def _final_obs_steps(prefix, x, shape, dtype, like):
+    """The per-step terminal observations of a one-launch rollout (PDEGYM_ROLLOUT_FINAL_OBS_PER_STEP), checked where the other rollout
+    buffers are: a contiguous ``dtype`` tensor of ``shape`` on the device of ``like``.  Returns the flag word of the descriptor."""
+    if x is None:
+        return 0
+    _check_shapes(prefix, {"final_obs_steps": (x, shape, dtype)})
+    if x.device != like.device:
+        raise N.NativeError(f"{prefix} final_obs_steps must live on {like.device}, got {x.device}")
+    return N.ROLLOUT_FINAL_OBS_PER_STEP
+
+
 def _check_shapes(prefix, wanted):
     """``wanted``: name -> (tensor | None, shape[, dtype]).  Every tensor given must be contiguous and have that shape (and dtype)."""
     for name, (x, shape, *dtype) in wanted.items():
@@ -136,12 +147,13 @@ class HipBackend:
 
     @_on_device_of("obs")
     def rollout1d(self, kind: str, P: N.Params1D, T: dict, obs, actions, rewards, terminated, truncated, B: int, policy=None,
-                  obs_noise=None, obs_seen=None):
+                  obs_noise=None, obs_seen=None, final_obs_steps=None):
         """T env-steps in one launch (pdegym_*_rollout): ``obs`` [T+1, B, obs_dim] (slot 0 = input rows with full-state sensing;
         with scalar sensing the state is ``T["u"]``, advanced in place), ``actions`` / ``rewards`` / ``terminated`` /
         ``truncated`` [T, B].  ``policy``: an ``N.Mlp`` descriptor evaluated inside the launch (``actions`` is then an output;
         its ``noise``, if set, is [T, B]); ``obs_noise`` / ``obs_seen`` [T, B, obs_dim]: the policy reads obs[t] + obs_noise[t],
-        which obs_seen[t] receives."""
+        which obs_seen[t] receives.  ``final_obs_steps`` [T, B, obs_dim]: row (t, b) receives the last observation of the episode
+        that step t ended (no other row is written, and ``T["final_obs"]`` is not)."""
         import torch
         fn = self.lib.pdegym_transport_rollout if kind == "transport" else self.lib.pdegym_parabolic_rollout
         steps = int(actions.shape[0])
@@ -151,8 +163,11 @@ class HipBackend:
                                   "terminated": (terminated, (steps, B)), "truncated": (truncated, (steps, B)),
                                   "obs_noise": (obs_noise, (steps, B, od), torch.float32),
                                   "obs_seen": (obs_seen, (steps, B, od), torch.float32)})
-        bufs = self._bufs1d({**T, "state_in": None, "u": None if full else T["u"], "history": None})
+        flags = _final_obs_steps("rollout", final_obs_steps, (steps, B, od), torch.float32, obs)
+        bufs = self._bufs1d({**T, "state_in": None, "u": None if full else T["u"], "history": None,
+                             **({"final_obs": final_obs_steps} if flags else {})})
         ro = self._rollout1d_desc(obs, actions, rewards, terminated, truncated, obs_noise, obs_seen, policy)
+        ro.reserved_ = flags
         N.check(fn(C.byref(P), C.byref(bufs), C.byref(ro), B, N.current_stream_ptr(obs.device)), f"pdegym_{kind}_rollout")
 
     @_on_device_of("bsum")
@@ -294,17 +309,23 @@ class HipBackend:
         return ro
 
     @_on_device_of("r")
-    def traffic_rollout(self, P: N.ParamsTraffic, T: dict, obs, actions, rewards, done, truncated, B: int, policy=None):
+    def traffic_rollout(self, P: N.ParamsTraffic, T: dict, obs, actions, rewards, done, truncated, B: int, policy=None,
+                        final_obs_steps=None):
         """T env-steps in one launch (pdegym_traffic_rollout): ``obs`` [T+1, B, 2M], ``actions`` [T, B, A] (A = 1 or 2; an output
-        when ``policy`` -- an ``N.Mlp`` descriptor, its ``noise`` [T, B, A] -- is given), ``rewards`` / ``done`` / ``truncated`` [T, B]."""
+        when ``policy`` -- an ``N.Mlp`` descriptor, its ``noise`` [T, B, A] -- is given), ``rewards`` / ``done`` / ``truncated`` [T, B].
+        ``final_obs_steps`` float64 [T, B, 2M]: row (t, b) receives the last observation of the episode that step t ended (no other
+        row is written, and ``T["final_obs"]`` is not)."""
+        import torch
         steps = int(actions.shape[0])
         A = int(actions.shape[2])
         if A not in (1, 2):
             raise N.NativeError(f"rollout actions must be a contiguous [{steps}, {B}, 1 or 2] tensor, got {tuple(actions.shape)}")
         _check_shapes("rollout", {"obs": (obs, (steps + 1, B, 2 * P.M)), "actions": (actions, (steps, B, A)), "rewards": (rewards, (steps, B)),
                                   "done": (done, (steps, B)), "truncated": (truncated, (steps, B))})
-        bufs = self._bufs_traffic({**T, "action": actions[0]})
+        flags = _final_obs_steps("rollout", final_obs_steps, (steps, B, 2 * P.M), torch.float64, obs)
+        bufs = self._bufs_traffic({**T, "action": actions[0], **({"final_obs": final_obs_steps} if flags else {})})
         ro = self._rollout_traffic_desc(obs, actions, rewards, done, truncated, policy)
+        ro.reserved_ = flags
         N.check(self.lib.pdegym_traffic_rollout(C.byref(P), C.byref(bufs), C.byref(ro), B, N.current_stream_ptr(obs.device)),
                 "pdegym_traffic_rollout")
 
@@ -328,16 +349,20 @@ class HipBackend:
                 "pdegym_traffic_backstep_control")
 
     @_on_device_of("r")
-    def traffic_backstep_rollout(self, P: N.ParamsTraffic, T: dict, obs, actions, rewards, done, truncated, B: int, law: N.TrafficBackstep):
+    def traffic_backstep_rollout(self, P: N.ParamsTraffic, T: dict, obs, actions, rewards, done, truncated, B: int, law: N.TrafficBackstep,
+                                 final_obs_steps=None):
         """T env-steps with the backstepping law inside, in one launch (pdegym_traffic_backstep_rollout): the buffers of
         ``traffic_rollout`` with ``actions`` [T, B, commands] an output; ``law``: an ``N.TrafficBackstep`` descriptor
-        (``TrafficBacksteppingController.rollout_law``; its ``noise`` [T, B, commands])."""
+        (``TrafficBacksteppingController.rollout_law``; its ``noise`` [T, B, commands]); ``final_obs_steps`` as there."""
+        import torch
         steps = int(actions.shape[0])
         A = 2 if P.sim == N.TRAFFIC_SIM["both"] else 1
         _check_shapes("backstep rollout", {"obs": (obs, (steps + 1, B, 2 * P.M)), "actions": (actions, (steps, B, A)),
                                            "rewards": (rewards, (steps, B)), "done": (done, (steps, B)), "truncated": (truncated, (steps, B))})
-        bufs = self._bufs_traffic({**T, "action": actions[0]})
+        flags = _final_obs_steps("backstep rollout", final_obs_steps, (steps, B, 2 * P.M), torch.float64, obs)
+        bufs = self._bufs_traffic({**T, "action": actions[0], **({"final_obs": final_obs_steps} if flags else {})})
         ro = self._rollout_traffic_desc(obs, actions, rewards, done, truncated)
+        ro.reserved_ = flags
         N.check(self.lib.pdegym_traffic_backstep_rollout(C.byref(P), C.byref(bufs), C.byref(ro), C.byref(law), B,
                                                          N.current_stream_ptr(obs.device)), "pdegym_traffic_backstep_rollout")
 
@@ -417,17 +442,23 @@ class HipBackend:
                 "pdegym_tumor_therapy_step")
 
     @_on_device_of("u")
-    def tumor_rollout(self, P: N.ParamsTumor, T: dict, W: dict, obs, actions, rewards, terminated, truncated, B: int, policy=None):
+    def tumor_rollout(self, P: N.ParamsTumor, T: dict, W: dict, obs, actions, rewards, terminated, truncated, B: int, policy=None,
+                      final_obs_steps=None):
         """T wrapper steps in one launch (pdegym_tumor_rollout): ``obs`` [T+1, B, nx], ``actions`` [T, B] (an output when ``policy`` --
-        an ``N.Mlp`` descriptor, its ``noise`` [T, B] -- is given), ``rewards`` / ``terminated`` / ``truncated`` [T, B]."""
+        an ``N.Mlp`` descriptor, its ``noise`` [T, B] -- is given), ``rewards`` / ``terminated`` / ``truncated`` [T, B].
+        ``final_obs_steps`` float64 [T, B, nx]: row (t, b) receives the last row of the episode that step t ended (no other row is
+        written, and ``W["final_obs"]`` is not)."""
         import torch
         steps = int(actions.shape[0])
         _check_shapes("rollout", {"obs": (obs, (steps + 1, B, P.nx)), "actions": (actions, (steps, B)), "rewards": (rewards, (steps, B)),
                                   "terminated": (terminated, (steps, B)), "truncated": (truncated, (steps, B))})
         bufs = self._bufs_tumor({**T, "kill": None, "active": None})
-        wrap = self._wrap_tumor(T, {**W, "obs": None}, B)
+        flags = _final_obs_steps("rollout", final_obs_steps, (steps, B, P.nx), torch.float64, obs)
+        wrap = self._wrap_tumor(T, {**W, "obs": None, **({"final_obs": None} if flags else {})}, B)
+        if flags:
+            wrap.final_obs = N.dptr(final_obs_steps, torch.float64)
         ro = N.RolloutTumor()
-        ro.T = steps
+        ro.T, ro.reserved_ = steps, flags
         ro.obs, ro.actions, ro.rewards = N.dptr(obs, torch.float64), N.dptr(actions, torch.float64), N.dptr(rewards, torch.float64)
         ro.terminated, ro.truncated = N.dptr(terminated, torch.uint8), N.dptr(truncated, torch.uint8)
         ro.policy = C.addressof(policy) if policy is not None else None
@@ -436,14 +467,27 @@ class HipBackend:
 
     # ---- policy network ----------------------------------------------------------------------------
     @_on_device_of("x")
-    def mlp_forward(self, net: N.Mlp, x, y, B: int):
+    def mlp_forward(self, net: N.Mlp, x, y, B: int, rows=None, rows_not=None):
         """y[b] = net(x[b]) for b < B: x [B, in_dim], y [B, out_dim] rows (row stride = stride(0)); float32, or float64 with
-        net.x_f64 / net.y_f64 set (the caller sets them from the tensors' dtypes)."""
+        net.x_f64 / net.y_f64 set (the caller sets them from the tensors' dtypes).  ``rows`` (uint8 [B], with ``rows_not`` uint8 [B] or
+        None): pdegym_mlp_forward_masked -- only rows with rows[b] != 0 and rows_not[b] == 0 are evaluated and stored, the others of
+        ``y`` are left as they are."""
         import torch
         for t_, name, f64 in ((x, "x", net.x_f64), (y, "y", net.y_f64)):
             want = torch.float64 if f64 else torch.float32
             if not t_.is_cuda or t_.dtype != want or t_.dim() != 2 or t_.stride(1) != 1:
                 raise N.NativeError(f"mlp_forward: {name} must be a {want} HIP tensor [B, width] with unit inner stride")
+        if rows is None and rows_not is not None:
+            raise N.NativeError("mlp_forward: rows_not knocks rows out of `rows`, which is missing")
+        if rows is not None:
+            _check_shapes("mlp_forward", {"rows": (rows, (B,), torch.uint8), "rows_not": (rows_not, (B,), torch.uint8)})
+            for m, name in ((rows, "rows"), (rows_not, "rows_not")):
+                if m is not None and m.device != x.device:
+                    raise N.NativeError(f"mlp_forward: {name} must live on {x.device}, got {m.device}")
+            N.check(self.lib.pdegym_mlp_forward_masked(C.byref(net), x.data_ptr(), x.stride(0), y.data_ptr(), y.stride(0),
+                                                       N.dptr(rows, torch.uint8), N.dptr(rows_not, torch.uint8), B,
+                                                       N.current_stream_ptr(x.device)), "pdegym_mlp_forward_masked")
+            return
         N.check(self.lib.pdegym_mlp_forward(C.byref(net), x.data_ptr(), x.stride(0), y.data_ptr(), y.stride(0), B,
                                             N.current_stream_ptr(x.device)), "pdegym_mlp_forward")
 
@@ -972,10 +1016,11 @@ class HipBackend:
 
     @_on_device_of("obs")
     def backstep_rollout1d(self, kind: str, P: N.Params1D, T: dict, obs, actions, rewards, terminated, truncated, B: int, law: N.Backstep,
-                           obs_noise=None, obs_seen=None):
+                           obs_noise=None, obs_seen=None, final_obs_steps=None):
         """T env-steps with the backstepping law inside, in one launch (pdegym_*_backstep_rollout): the buffers of ``rollout1d``
         (full-state sensing: ``obs`` [T+1, B, n]); ``actions`` is an output.  ``law``: an ``N.Backstep`` descriptor with gains,
-        length, order, scale, ``noise`` [T, B], clamp (``BacksteppingController.rollout_law``; obs / out64 / out32 unset)."""
+        length, order, scale, ``noise`` [T, B], clamp (``BacksteppingController.rollout_law``; obs / out64 / out32 unset).
+        ``final_obs_steps`` [T, B, n]: as in ``rollout1d``."""
         import torch
         fn = self.lib.pdegym_transport_backstep_rollout if kind == "transport" else self.lib.pdegym_parabolic_backstep_rollout
         steps = int(actions.shape[0])
@@ -983,8 +1028,10 @@ class HipBackend:
                                            "terminated": (terminated, (steps, B)), "truncated": (truncated, (steps, B)),
                                            "obs_noise": (obs_noise, (steps, B, P.n), torch.float32),
                                            "obs_seen": (obs_seen, (steps, B, P.n), torch.float32)})
-        bufs = self._bufs1d({**T, "state_in": None, "u": None, "history": None})
+        flags = _final_obs_steps("backstep rollout", final_obs_steps, (steps, B, P.n), torch.float32, obs)
+        bufs = self._bufs1d({**T, "state_in": None, "u": None, "history": None, **({"final_obs": final_obs_steps} if flags else {})})
         ro = self._rollout1d_desc(obs, actions, rewards, terminated, truncated, obs_noise, obs_seen)
+        ro.reserved_ = flags
         N.check(fn(C.byref(P), C.byref(bufs), C.byref(ro), C.byref(law), B, N.current_stream_ptr(obs.device)),
                 f"pdegym_{kind}_backstep_rollout")
 

@@ -345,7 +345,7 @@ class PDEBatch1D(EngineCheckpoint):
         return self.law_rollout_gap(law) is None
 
     def rollout(self, obs, actions, rewards, terminated, truncated, policy=None, clamp="default", noise=None, obs_noise=None,
-                obs_seen=None):
+                obs_seen=None, final_obs_steps=None):
         """T env-steps in ONE launch (include/pdegym.h: pdegym_*_rollout): step t takes the commands from ``actions[t]`` and
         writes ``obs[t + 1]`` ([T+1, B, obs_dim]), ``rewards[t]``, ``terminated[t]``, ``truncated[t]`` -- bit-identical to T
         calls of ``step(actions[t], out_obs=obs[t + 1], ...)``, fused auto-reset included.  With full-state sensing ``obs[0]``
@@ -365,18 +365,23 @@ class PDEBatch1D(EngineCheckpoint):
         ``policy`` may also be an attached ``BacksteppingController`` that fits (``law_fits_rollout``): the law is evaluated inside the
         launch on ``obs[t]`` (+ ``obs_noise[t]``), ``actions[t]`` receives the command after ``noise[t]`` and the clamp (``clamp``:
         (lo, hi) or None; "default" = none), and everything is bit-identical to ``controller.forward_into`` + ``step`` per env-step,
-        in both summation orders, with gains that follow the restarts the fused auto-reset makes inside the launch."""
+        in both summation orders, with gains that follow the restarts the fused auto-reset makes inside the launch.
+
+        ``final_obs_steps`` float32 [T, B, obs_dim] (needs ``enable_auto_reset``): row (t, b) receives what ``t['final_obs'][b]`` holds
+        after step t of the step loop -- the last observation of the finished episode -- where step t ended the episode of instance
+        b; no other row is written, and ``t['final_obs']`` itself is not."""
         if not self.can_rollout():
             raise ValueError("rollout needs a state with one home (full-state sensing: state_in_obs; no history) and float32 operands")
         self.params.action_kind = N.ACTION_F32
         net = None
+        extra = {} if final_obs_steps is None else {"final_obs_steps": final_obs_steps}      # (backends without the keyword stay valid)
         if hasattr(policy, "rollout_law"):          # a controller: its descriptor travels with the launch (pdegym_*_backstep_rollout)
             gap = self.law_rollout_gap(policy)
             if gap is not None:
                 raise ValueError("this controller cannot run inside the rollout kernel: " + gap)
             law = policy.rollout_law(actions, None if clamp == "default" else clamp, noise)
             self.backend.backstep_rollout1d(self.kind, self.params, self.t, obs, actions, rewards, terminated, truncated, self.num_envs,
-                                            law, obs_noise=obs_noise, obs_seen=obs_seen)
+                                            law, obs_noise=obs_noise, obs_seen=obs_seen, **extra)
             self.t["obs"].copy_(obs[-1])
             if self.state_in_obs:
                 self.t["u"] = self.t["obs"]
@@ -388,7 +393,7 @@ class PDEBatch1D(EngineCheckpoint):
         elif obs_noise is not None or obs_seen is not None:
             raise ValueError("obs_noise / obs_seen shape the policy's input: they need a policy")
         self.backend.rollout1d(self.kind, self.params, self.t, obs, actions, rewards, terminated, truncated, self.num_envs,
-                               policy=net, obs_noise=obs_noise, obs_seen=obs_seen)
+                               policy=net, obs_noise=obs_noise, obs_seen=obs_seen, **extra)
         self.t["obs"].copy_(obs[-1])
         if self.state_in_obs:
             self.t["u"] = self.t["obs"]

@@ -131,25 +131,28 @@ class TrafficBatch(EngineCheckpoint):
             return f"freeways of {self.M} nodes (the kernel keeps freeways of up to 64 nodes in registers)"
         return controller.rollout_gap(self)
 
-    def rollout(self, obs, actions, rewards, done, truncated, policy=None, clamp="default", noise=None, law=None):
+    def rollout(self, obs, actions, rewards, done, truncated, policy=None, clamp="default", noise=None, law=None, final_obs_steps=None):
         """T env-steps in ONE launch (include/pdegym.h: pdegym_traffic_rollout): step t takes ``actions[t]`` ([T, B, action_dim]),
         writes ``obs[t + 1]`` ([T+1, B, 2M]), ``rewards[t]``, ``done[t]``, ``truncated[t]`` -- bit-identical to T ``step`` calls.
         With ``policy`` (a ``FusedMLP``) the commands are computed inside the launch from ``obs[t]`` (``obs[0]`` = the current
         observation, supplied by the caller) and written to ``actions``; ``noise`` [T, B, action_dim] float32 is added before
         the clamp.  With ``law`` (an ``N.TrafficBackstep`` descriptor: ``TrafficBacksteppingController.rollout_law``) the
         backstepping law forms the commands inside the launch instead (pdegym_traffic_backstep_rollout), bit-identical to control
-        launch + ``step`` per env-step.  The engine's own observation / reward / flag tensors receive the values of the last step."""
+        launch + ``step`` per env-step.  The engine's own observation / reward / flag tensors receive the values of the last step.
+        ``final_obs_steps`` float64 [T, B, 2M] (needs ``enable_auto_reset``): row (t, b) receives the last observation of the episode
+        that step t ended; no other row is written, and ``t['final_obs']`` is not."""
         if not self.can_rollout():
             raise ValueError("rollout needs freeways of at most 64 nodes")
         if law is not None and policy is not None:
             raise ValueError("rollout takes a policy or a law, not both")
         if policy is not None and not self.policy_fits_rollout(policy):
             raise ValueError("this policy cannot run inside the rollout kernel (see policy_fits_rollout)")
+        extra = {} if final_obs_steps is None else {"final_obs_steps": final_obs_steps}      # (backends without the keyword stay valid)
         if law is not None:
-            self.backend.traffic_backstep_rollout(self.params, self.t, obs, actions, rewards, done, truncated, self.num_envs, law)
+            self.backend.traffic_backstep_rollout(self.params, self.t, obs, actions, rewards, done, truncated, self.num_envs, law, **extra)
         else:
             net = policy.rollout_net(obs, actions, clamp, noise) if policy is not None else None
-            self.backend.traffic_rollout(self.params, self.t, obs, actions, rewards, done, truncated, self.num_envs, policy=net)
+            self.backend.traffic_rollout(self.params, self.t, obs, actions, rewards, done, truncated, self.num_envs, policy=net, **extra)
         self.t["obs"].copy_(obs[-1])
         self.t["reward"].copy_(rewards[-1])
         self.t["done"].copy_(done[-1])

@@ -159,15 +159,18 @@ class TumorBatch(EngineCheckpoint):
         obs = W.get("obs")
         return (self.t["u"] if obs is None else obs), self.t["reward"], self.t["terminated"], self.t["truncated"]
 
-    def rollout(self, obs, actions, rewards, terminated, truncated, policy=None, clamp="default", noise=None, wrap_state=None):
+    def rollout(self, obs, actions, rewards, terminated, truncated, policy=None, clamp="default", noise=None, wrap_state=None,
+                final_obs_steps=None):
         """T wrapper steps in ONE launch (pdegym_tumor_rollout): step t takes ``actions[t]`` ([T, B]) and writes ``obs[t + 1]``
         ([T+1, B, nx]), ``rewards[t]``, ``terminated[t]``, ``truncated[t]`` -- bit-identical to T ``therapy_step`` calls.  With
         ``policy`` (a ``FusedMLP``) the commands are computed inside the launch from ``obs[t]`` (``obs[0]`` = the current
         observation, supplied by the caller) and written to ``actions``; ``noise`` [T, B] float32 is added before the clamp.
-        ``wrap_state`` as for ``therapy_step`` (its ``obs`` is not used)."""
+        ``wrap_state`` as for ``therapy_step`` (its ``obs`` is not used).  ``final_obs_steps`` [T, B, nx]: row (t, b) receives the last
+        row of the episode that step t ended; no other row is written, and ``wrap_state["final_obs"]`` is not."""
         W = self._wrap(wrap_state if wrap_state is not None else {})
         if policy is not None and not self.policy_fits_rollout(policy):
             raise ValueError("this policy cannot run inside the rollout kernel (see policy_fits_rollout)")
         net = policy.rollout_net(obs, actions, clamp, noise) if policy is not None else None
-        self.backend.tumor_rollout(self.params, self.t, W, obs, actions, rewards, terminated, truncated, self.num_envs, policy=net)
+        extra = {} if final_obs_steps is None else {"final_obs_steps": final_obs_steps}      # (backends without the keyword stay valid)
+        self.backend.tumor_rollout(self.params, self.t, W, obs, actions, rewards, terminated, truncated, self.num_envs, policy=net, **extra)
         return obs, rewards, terminated, truncated

@@ -39,10 +39,17 @@ __device__ __forceinline__ void stage_carried_row(const Carry<EPL>& C, float* xw
 
 // The buffers as env-step t of a rollout sees them: observation slot t + 1 out (slot = B * observation length, in floats), row t of
 // the [T, B] arrays.  full (full-state sensing): the state comes from slot t; otherwise it lives in bufs.u, advanced in place.
+// PDEGYM_ROLLOUT_FINAL_OBS_PER_STEP: bufs.final_obs is [T, B, observation length] and step t sees slot t of it.  (rollout1d_kernel,
+// whose view advances incrementally, has the mode as a template parameter instead: pdegym_1d_rollout.hip.)
+__device__ __forceinline__ size_t terminal_obs_stride(const pdegym_rollout1d& Ro, size_t slot) {
+  return (Ro.reserved_ & PDEGYM_ROLLOUT_FINAL_OBS_PER_STEP) ? slot : 0;      // uniform over the launch
+}
+
 __device__ __forceinline__ pdegym_bufs1d rollout_step_view(const pdegym_bufs1d& Bf, const pdegym_rollout1d& Ro, int B, size_t slot, int t,
                                                            bool full = true) {
   pdegym_bufs1d S = Bf;
   S.history = nullptr;
+  S.final_obs = Bf.final_obs + (size_t)t * terminal_obs_stride(Ro, slot);      // (NULL stays NULL: the launchers refuse the flag without it)
   if (full) S.u = nullptr;
   S.state_in = full ? Ro.obs + (size_t)t * slot : nullptr;
   S.obs = Ro.obs + (size_t)(t + 1) * slot;
@@ -67,6 +74,10 @@ inline int check_rollout_plant(const pdegym_params1d& P, const pdegym_bufs1d& bu
   if (!buf.beta || !buf.time_index || !buf.bsum || !buf.ring || !buf.norm_now || !buf.norm_back) return fail(-3, "null device buffer");
   if (!ro.obs || !ro.actions || !ro.terminated || !ro.truncated) return fail(-3, "null rollout buffer");
   if (P.reward_kind != PDEGYM_REWARD_NONE && !ro.rewards) return fail(-3, "null reward buffer");
+  if (ro.reserved_ & PDEGYM_ROLLOUT_FINAL_OBS_PER_STEP) {
+    if (!buf.final_obs) return fail(-3, "PDEGYM_ROLLOUT_FINAL_OBS_PER_STEP needs bufs->final_obs [T, B, obs_dim]");
+    if (!buf.reset_init) return fail(-2, "PDEGYM_ROLLOUT_FINAL_OBS_PER_STEP needs the auto-reset pool (reset_init): only a restart keeps a final observation");
+  }
   return 0;
 }
 

@@ -12,7 +12,10 @@ namespace {
 // env-steps: no dispatch gap, no load phase (the state stays in registers, Carry), and the waves of a SIMD drift apart
 // instead of finishing in two generations (docs/HISTORY.md section 3.2).
 // FULL: the row fills the wave exactly (n - J0 == 64 EPL): the slot masks fold away (pdegym_1d_body.h: run_substeps).
-template <int EPL, bool PARABOLIC, bool BURGERS, bool FULL>
+// PER_STEP (PDEGYM_ROLLOUT_FINAL_OBS_PER_STEP): final_obs is [T, B, n] and advances with the view.  Compiled apart: the form without
+// it is the kernel it was, and a stride, a flag or a second advancing pointer in this loop costs the transport FULL form (99 SGPRs) a
+// wave of occupancy.
+template <int EPL, bool PARABOLIC, bool BURGERS, bool FULL, bool PER_STEP = false>
 __global__ __launch_bounds__(kWave* kWavesPerBlock) void rollout1d_kernel(pdegym_params1d P, pdegym_bufs1d Bf, pdegym_rollout1d Ro,
                                                                          int B) {
   const int lane = threadIdx.x & (kWave - 1);
@@ -30,6 +33,7 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void rollout1d_kernel(pdegym
   carry_load<EPL, PARABOLIC, FULL>(C, P, Bf, Ro.obs, inst, lane);
   // the per-step views of the rollout arrays advance by one slot / row per env-step (no 64-bit multiplications in the loop)
   pdegym_bufs1d S = rollout_step_view(Bf, Ro, B, slot, 0);
+  S.final_obs = Bf.final_obs;      // (slot 0 of it, or the [B, n] array: the mode is PER_STEP here, not the descriptor's bit)
   auto command_batch = [&](int t0) { return (t0 + lane < Ro.T) ? Ro.actions[(size_t)(t0 + lane) * B + inst] : 0.f; };
   float a_cur = command_batch(0);
   drain_vmem();
@@ -47,6 +51,7 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void rollout1d_kernel(pdegym
     S.reward += B;
     S.terminated += B;
     S.truncated += B;
+    if constexpr (PER_STEP) S.final_obs += slot;
   }
   carry_store_ring<EPL>(C, Bf, inst, lane);
 }
@@ -210,15 +215,18 @@ int launch_rollout(const pdegym_params1d* prm, const pdegym_bufs1d* buf, const p
   }
   const dim3 grid((B + kWavesPerBlock - 1) / kWavesPerBlock), block(kWave * kWavesPerBlock);
   // the same slots-per-lane choice as launch_step: the norm reductions (hence rewards) depend on the layout
+  const bool per_step = (ro->reserved_ & PDEGYM_ROLLOUT_FINAL_OBS_PER_STEP) != 0;
   with_epl<32>(epl, [&](auto tag) {
     constexpr int E = decltype(tag)::value;
+    auto carried = [&](auto full_tag) {
+      constexpr bool F = decltype(full_tag)::value;
+      if (per_step) hipLaunchKernelGGL((rollout1d_kernel<E, PARABOLIC, BURGERS, F, true>), grid, block, 0, st, P, *buf, *ro, B);
+      else hipLaunchKernelGGL((rollout1d_kernel<E, PARABOLIC, BURGERS, F>), grid, block, 0, st, P, *buf, *ro, B);
+    };
     if constexpr (epl_has_full(E)) {
-      if (!general && nslots == kWave * E) {
-        hipLaunchKernelGGL((rollout1d_kernel<E, PARABOLIC, BURGERS, true>), grid, block, 0, st, P, *buf, *ro, B);
-        return;
-      }
+      if (!general && nslots == kWave * E) return carried(std::true_type{});
     }
-    if (!general) hipLaunchKernelGGL((rollout1d_kernel<E, PARABOLIC, BURGERS, false>), grid, block, 0, st, P, *buf, *ro, B);
+    if (!general) carried(std::false_type{});
     else if (neumann) hipLaunchKernelGGL((rollout1d_general_kernel<E, PARABOLIC, true, BURGERS>), grid, block, 0, st, P, *buf, *ro, B);
     else hipLaunchKernelGGL((rollout1d_general_kernel<E, PARABOLIC, false, BURGERS>), grid, block, 0, st, P, *buf, *ro, B);
   });

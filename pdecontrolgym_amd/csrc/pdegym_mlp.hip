@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "pdegym.h"
 #include "pdegym_common.h"
@@ -39,10 +40,16 @@ constexpr int kXChunk = 512;                // observation entries per row stage
 // GAUSS: the squashed-Gaussian head's epilogue, compiled apart -- as a run-time branch it cost the plain head 1 %
 // CAT: rows in two parts (pdegym_mlp_forward_cat), columns 0 .. D-1 from x and D .. in_dim-1 from the float32 x2; compiled apart as
 // well, so that pdegym_mlp_forward's staging loop stays the code it was
-template <int NT, int WV, typename TX, typename TY, bool GAUSS, bool CAT>
+// MASKED (pdegym_mlp_forward_masked): row r is live when rows[r] != 0 and (rows_not == nullptr or rows_not[r] == 0); only live rows are
+// stored, and a workgroup without one returns before it requests a weight (and before its first barrier: the condition is the same
+// in every wave).  Dead rows are staged and reduced like any other -- the rows of a tile are independent in the MFMA, so a live row's
+// bits do not depend on them -- which keeps the reduction the unmasked kernel's, instruction for instruction.  Compiled apart as well.
+template <int NT, int WV, typename TX, typename TY, bool GAUSS, bool CAT, bool MASKED = false>
 __global__ __launch_bounds__(64 * WV) void mlp_forward_kernel(pdegym_mlp N, const TX* __restrict__ x, long long x_stride,
                                                           TY* __restrict__ y, long long y_stride, int B, int ldx,
-                                                          const float* __restrict__ x2, long long x2_stride, int D) {
+                                                          const float* __restrict__ x2, long long x2_stride, int D,
+                                                          const uint8_t* __restrict__ rows, const uint8_t* __restrict__ rows_not) {
+  static_assert(!MASKED || (!GAUSS && !CAT), "the masked launch takes plain rows and the plain head");
   // LDS: activations ping-pong between hb0 and hb1; the staged observation chunk shares its space with hb1 (first written
   // by the second layer, when the observations are no longer needed)
   extern __shared__ __attribute__((aligned(16))) float mlp_smem[];
@@ -55,6 +62,14 @@ __global__ __launch_bounds__(64 * WV) void mlp_forward_kernel(pdegym_mlp N, cons
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int li = lane & 15, lg = lane >> 4;      // MFMA operand lane = (row or neuron li, k-slot lg)
   const int row0 = blockIdx.x * kRows;
+  // bit r: row row0 + r is live.  Lane l looks at row l % 16, so every wave of the workgroup forms the same 16 bits.
+  unsigned live_rows = 0xffffu;
+  if constexpr (MASKED) {
+    const int r = row0 + li;
+    const bool live = r < B && rows[r] != 0 && !(rows_not && rows_not[r] != 0);
+    live_rows = (unsigned)__ballot(live) & 0xffffu;
+    if (live_rows == 0) return;      // workgroup-uniform
+  }
 
   // weights of the first pipeline stage of the coming layer: requested before the barrier that publishes its inputs
   v4f wfirst[kStage][NT];
@@ -177,7 +192,7 @@ __global__ __launch_bounds__(64 * WV) void mlp_forward_kernel(pdegym_mlp N, cons
           } else if (last) {
             if (N.noise && n < H && row0 + r < B) o += N.noise[(long long)(row0 + r) * N.noise_stride + n];
             if (N.clamp) o = pdegym::clip_keep_nan(o, N.lo, N.hi);
-            if (n < H && row0 + r < B) y[(long long)(row0 + r) * y_stride + n] = (TY)o;
+            if (n < H && row0 + r < B && (!MASKED || ((live_rows >> r) & 1u))) y[(long long)(row0 + r) * y_stride + n] = (TY)o;
           } else {
             hout[r * kLdh + n] = o;
           }
@@ -191,10 +206,13 @@ __global__ __launch_bounds__(64 * WV) void mlp_forward_kernel(pdegym_mlp N, cons
 }  // namespace
 
 // the second part of a two-part row (pdegym_mlp_forward_cat); x2 == nullptr: the plain row of pdegym_mlp_forward
+// rows / rows_not: the row mask of pdegym_mlp_forward_masked (plain head, float32 y, no second part); rows == nullptr: every row
 struct Tail {
   const float* x2;
   long long x2_stride;
   int D;
+  const uint8_t* rows;
+  const uint8_t* rows_not;
 };
 
 template <int NT, int WV, typename TX, typename TY, bool GAUSS>
@@ -206,9 +224,15 @@ static void launch_mlp_nt(const pdegym_mlp* net, const TX* xp, long long xs, TY*
   const dim3 grid((B + kRows - 1) / kRows), block(64 * WV);
   if (tl.x2)
     hipLaunchKernelGGL((mlp_forward_kernel<NT, WV, TX, TY, GAUSS, true>), grid, block, lds_bytes, st, *net, xp, xs, yp, ys, B, ldx, tl.x2,
-                       tl.x2_stride, tl.D);
-  else
-    hipLaunchKernelGGL((mlp_forward_kernel<NT, WV, TX, TY, GAUSS, false>), grid, block, lds_bytes, st, *net, xp, xs, yp, ys, B, ldx, nullptr, 0LL, 0);
+                       tl.x2_stride, tl.D, nullptr, nullptr);
+  else if constexpr (!GAUSS && std::is_same<TY, float>::value) {
+    if (tl.rows)
+      hipLaunchKernelGGL((mlp_forward_kernel<NT, WV, TX, TY, false, false, true>), grid, block, lds_bytes, st, *net, xp, xs, yp, ys, B, ldx,
+                         nullptr, 0LL, 0, tl.rows, tl.rows_not);
+    else
+      hipLaunchKernelGGL((mlp_forward_kernel<NT, WV, TX, TY, GAUSS, false>), grid, block, lds_bytes, st, *net, xp, xs, yp, ys, B, ldx, nullptr, 0LL, 0, nullptr, nullptr);
+  } else
+    hipLaunchKernelGGL((mlp_forward_kernel<NT, WV, TX, TY, GAUSS, false>), grid, block, lds_bytes, st, *net, xp, xs, yp, ys, B, ldx, nullptr, 0LL, 0, nullptr, nullptr);
 }
 
 template <typename TX, typename TY, bool GAUSS>
@@ -228,10 +252,14 @@ static void launch_mlp(const pdegym_mlp* net, const void* x, long long xs, void*
   else launch_mlp_head<TX, TY, false>(net, xp, xs, yp, ys, B, width, tl, st);
 }
 
-// pdegym_mlp_forward (n2 == 0, x2 == nullptr) and pdegym_mlp_forward_cat (n2 >= 1): one set of checks, one dispatch
+// pdegym_mlp_forward (n2 == 0, x2 == nullptr), pdegym_mlp_forward_cat (n2 >= 1) and pdegym_mlp_forward_masked (rows): one set of checks,
+// one dispatch
 static int mlp_forward_rows(const pdegym_mlp* net, const void* x, int64_t x_stride, const float* x2, int64_t x2_stride, int32_t n2,
-                            void* y, int64_t y_stride, int32_t B, void* stream) {
+                            void* y, int64_t y_stride, int32_t B, void* stream, const uint8_t* rows = nullptr,
+                            const uint8_t* rows_not = nullptr) {
   if (!net || !x || !y) return pdegym::fail(-3, "null pointer");
+  if (rows && (net->head != PDEGYM_MLP_HEAD_PLAIN || net->noise || net->y_f64))
+    return pdegym::fail(-2, "mlp_forward_masked: the plain head, no noise and float32 y");
   if (B < 0) return pdegym::fail(-2, "B must be >= 0");
   if (net->n_layers < 1 || net->n_layers > PDEGYM_MLP_MAX_LAYERS) return pdegym::fail(-2, "n_layers must be 1..4");
   for (int l = 0; l < net->n_layers; ++l) {
@@ -265,17 +293,23 @@ static int mlp_forward_rows(const pdegym_mlp* net, const void* x, int64_t x_stri
   for (int l = 0; l < net->n_layers; ++l) width = net->layer[l].out_dim > width ? net->layer[l].out_dim : width;
   hipStream_t st = (hipStream_t)stream;
   const long long xs = x_stride, ys = y_stride;
-  const Tail tl = {x2, x2_stride, net->layer[0].in_dim - n2};
+  const Tail tl = {x2, x2_stride, net->layer[0].in_dim - n2, rows, rows_not};
   if (net->x_f64 && net->y_f64) launch_mlp<double, double>(net, x, xs, y, ys, B, width, tl, st);
   else if (net->x_f64) launch_mlp<double, float>(net, x, xs, y, ys, B, width, tl, st);
   else if (net->y_f64) launch_mlp<float, double>(net, x, xs, y, ys, B, width, tl, st);
   else launch_mlp<float, float>(net, x, xs, y, ys, B, width, tl, st);
-  return pdegym::check_launch(n2 ? "mlp_forward_cat" : "mlp_forward");
+  return pdegym::check_launch(n2 ? "mlp_forward_cat" : (rows ? "mlp_forward_masked" : "mlp_forward"));
 }
 
 extern "C" int pdegym_mlp_forward(const pdegym_mlp* net, const void* x, int64_t x_stride, void* y, int64_t y_stride, int32_t B,
                                   void* stream) {
   return mlp_forward_rows(net, x, x_stride, nullptr, 0, 0, y, y_stride, B, stream);
+}
+
+extern "C" int pdegym_mlp_forward_masked(const pdegym_mlp* net, const void* x, int64_t x_stride, void* y, int64_t y_stride,
+                                         const uint8_t* rows, const uint8_t* rows_not, int32_t B, void* stream) {
+  if (!rows) return pdegym::fail(-1, "mlp_forward_masked: null rows (pdegym_mlp_forward evaluates every row)");
+  return mlp_forward_rows(net, x, x_stride, nullptr, 0, 0, y, y_stride, B, stream, rows, rows_not);
 }
 
 extern "C" int pdegym_mlp_forward_cat(const pdegym_mlp* net, const void* x, int64_t x_stride, const float* x2, int64_t x2_stride,

@@ -37,7 +37,7 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void traffic_step_kernel(pde
   const TrafficStepOut o = traffic_step_wave(P, K, r, y, time, rs, Bf.qs_clip[inst], a0, a1, lane);
   double* ob = Bf.obs + (size_t)inst * 2 * M;
   if (Bf.reset_rs && (o.done || o.trunc)) {       // wave-uniform
-    traffic_auto_reset(P, Bf, inst, B, 0, in ? Bf.reset_profile[lane] : 1.0, r, y, rs, o.v, o.vs, ob, lane);
+    traffic_auto_reset(P, Bf, Bf.final_obs, inst, B, 0, in ? Bf.reset_profile[lane] : 1.0, r, y, rs, o.v, o.vs, ob, lane);
     time = 0.0;
     if (lane == 0) {
       Bf.rs[inst] = rs;
@@ -141,7 +141,7 @@ __global__ __launch_bounds__(kWave* pdegym_policy::kWaves) void traffic_rollout_
     const TrafficStepOut o = traffic_step_wave(P, K, r, y, time, rs, qc, a0, a1, lane);
     double* onext = Ro.obs + (size_t)(t + 1) * slot + (size_t)inst * D;
     if (Bf.reset_rs && (o.done || o.trunc)) {     // wave-uniform
-      traffic_auto_reset(P, Bf, inst, B, restarts, prof, r, y, rs, o.v, o.vs, onext, lane);
+      traffic_auto_reset(P, Bf, traffic_terminal_slot(Bf, Ro, slot, t), inst, B, restarts, prof, r, y, rs, o.v, o.vs, onext, lane);
       ++restarts;
       time = 0.0;
       if constexpr (!has_policy) drain_vmem();
@@ -349,6 +349,7 @@ int pdegym_traffic_rollout(const pdegym_params_traffic* prm, const pdegym_bufs_t
   if (B <= 0 || ro->T <= 0) return 0;
   if (prm->M > kWave) return pdegym::fail(-2, "traffic rollout: freeways of up to 64 nodes (the register-resident kernel)");
   if (!ro->obs || !ro->actions || !ro->rewards || !ro->done || !ro->truncated) return pdegym::fail(-3, "null rollout buffer");
+  if (int rc = check_terminal_slots(*buf, *ro, "traffic rollout")) return rc;
   const int A = buf->action_stride > 0 ? buf->action_stride : 2;
   if (A > 2) return pdegym::fail(-2, "action_stride must be 1 or 2");
   if (ro->policy && A > pdegym_policy::kWideOut) return pdegym::fail(-2, "policy: at most two commands");

@@ -203,7 +203,7 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void traffic_backstep_rollou
     const TrafficStepOut o = traffic_step_wave(P, K, r, y, time, rs, qc, a0, a1, lane);
     double* onext = Ro.obs + (size_t)(t + 1) * slot + (size_t)inst * D;
     if (Bf.reset_rs && (o.done || o.trunc)) {     // wave-uniform
-      traffic_auto_reset(P, Bf, inst, B, restarts, prof, r, y, rs, o.v, o.vs, onext, lane);
+      traffic_auto_reset(P, Bf, traffic_terminal_slot(Bf, Ro, slot, t), inst, B, restarts, prof, r, y, rs, o.v, o.vs, onext, lane);
       ++restarts;
       time = 0.0;
       lv = y / r + Veq(P.vm, P.rm, r);            // traffic_restart_node's speed: what the slot just received
@@ -289,6 +289,7 @@ int pdegym_traffic_backstep_rollout(const pdegym_params_traffic* prm, const pdeg
   if (buf->reset_rs && !buf->reset_profile) return pdegym::fail(-3, "reset_rs needs reset_profile");
   if (buf->reset_pool_rows < 0) return pdegym::fail(-2, "reset_pool_rows must be >= 0");
   if (!ro->obs || !ro->actions || !ro->rewards || !ro->done || !ro->truncated) return pdegym::fail(-3, "null rollout buffer");
+  if (int rc = check_terminal_slots(*buf, *ro, "traffic backstep rollout")) return rc;
   const int ncmd = prm->sim == PDEGYM_TRAFFIC_BOTH ? 2 : 1;
   if ((buf->action_stride > 0 ? buf->action_stride : 2) != ncmd)
     return pdegym::fail(-2, "action_stride must be the number of commands (1; 2 for 'both'): every column of actions is written");

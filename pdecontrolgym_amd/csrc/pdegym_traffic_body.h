@@ -8,6 +8,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cstdio>
+
 #include "pdegym.h"
 #include "pdegym_common.h"
 
@@ -150,14 +152,31 @@ __device__ __forceinline__ void traffic_restart_node(const pdegym_params_traffic
   v = y / r + Veq(P.vm, P.rm, r);
 }
 
+// Where env-step t of a rollout keeps the final observation: bufs.final_obs itself, or slot t of it when it is [T, B, 2M]
+// (PDEGYM_ROLLOUT_FINAL_OBS_PER_STEP).  Evaluated on the restart path only.
+__device__ __forceinline__ double* traffic_terminal_slot(const pdegym_bufs_traffic& Bf, const pdegym_rollout_traffic& Ro, size_t slot, int t) {
+  return (Ro.reserved_ & PDEGYM_ROLLOUT_FINAL_OBS_PER_STEP) ? Bf.final_obs + (size_t)t * slot : Bf.final_obs;
+}
+
+// The flag asks for something to keep and a restart to keep it at: 0, or the code to return (message in the error slot).
+inline int check_terminal_slots(const pdegym_bufs_traffic& buf, const pdegym_rollout_traffic& ro, const char* who) {
+  if (!(ro.reserved_ & PDEGYM_ROLLOUT_FINAL_OBS_PER_STEP)) return 0;
+  auto fail = [who](int code, const char* msg) { return std::snprintf(pdegym::error_slot(), 512, "%s: %s", who, msg), code; };
+  if (!buf.final_obs) return fail(-3, "PDEGYM_ROLLOUT_FINAL_OBS_PER_STEP needs bufs->final_obs [T, B, 2M]");
+  if (!buf.reset_rs) return fail(-2, "PDEGYM_ROLLOUT_FINAL_OBS_PER_STEP needs the auto-reset pool (reset_rs): only a restart keeps a final observation");
+  return 0;
+}
+
 // Fused auto-reset of a freeway held in registers (wave-uniform): the final observation, rs of the pool row of this restart
 // (`extra`: restarts made inside the launch and not yet in reset_count), the nodes restarted with profile value `prof`, the
 // observation of the restarted state into `obs`.  What goes back to memory besides is each kernel's own business.
-__device__ __forceinline__ void traffic_auto_reset(const pdegym_params_traffic& P, const pdegym_bufs_traffic& Bf, int inst, int B, int extra,
-                                                   double prof, double& r, double& y, double& rs, double v, double vs, double* obs,
-                                                   int lane) {
+// final_obs: the [B, 2M] array that keeps the final observation, or NULL -- bufs.final_obs, or the slot of this env-step of it
+// (traffic_terminal_slot).
+__device__ __forceinline__ void traffic_auto_reset(const pdegym_params_traffic& P, const pdegym_bufs_traffic& Bf, double* final_obs, int inst,
+                                                   int B, int extra, double prof, double& r, double& y, double& rs, double v, double vs,
+                                                   double* obs, int lane) {
   const int M = P.M;
-  if (Bf.final_obs) traffic_emit_obs(P, Bf.final_obs + (size_t)inst * 2 * M, r, v, rs, vs, lane);
+  if (final_obs) traffic_emit_obs(P, final_obs + (size_t)inst * 2 * M, r, v, rs, vs, lane);
   rs = Bf.reset_rs[pool_row(Bf.reset_pool_rows, Bf.reset_count, inst, B, extra)];
   if (lane < M) {
     double v0;

@@ -26,8 +26,10 @@ namespace pol = pdegym_policy;
 
 // obs0: observation slot 0 (read by a policy only); obs1: slot 1 (slot t + 1 = obs1 + t * B * nx) or nullptr (the observation is
 // the live row, written once at the end); actions / rewards / terminated / truncated: rows of B, row t per wrapper step.
+// final_stride: 0, or B * nx when wrap.final_obs is [T, B, nx] and step t keeps its last row in slot t (PDEGYM_ROLLOUT_FINAL_OBS_PER_STEP).
 struct Slots {
   int T;
+  int64_t final_stride;
   const double* obs0;
   double* obs1;
   double* actions;
@@ -172,7 +174,7 @@ __global__ __launch_bounds__(kWave* pol::kWaves) void tumor_rollout_kernel(pdegy
         if (rep_term || rep_lethal) {                                   // SB3 auto-reset: keep the last row, restart, growth run
           wave_lds_sync();
           if (Wr.final_obs) {
-            double* fo = Wr.final_obs + (size_t)inst * nx;
+            double* fo = Wr.final_obs + (size_t)t * (size_t)Ro.final_stride + (size_t)inst * nx;
             for (int i = lane; i < nx; i += kWave) fo[i] = cur[i];
           }
           tumor_stage_row(P, init_row, cur, lane, S.t2_idx);
@@ -255,7 +257,7 @@ int pdegym_tumor_therapy_step(const pdegym_params_tumor* prm, const pdegym_bufs_
   if (wrap->weekends && !wrap->obs)
     return pdegym::fail(-2, "tumor wrapper step: weekends needs an obs row per patient (a resting patient returns the treatment day's row, not the live one)");
   if (B <= 0) return 0;
-  const Slots ro = {1, nullptr, wrap->obs, const_cast<double*>(buf->control), buf->reward, buf->terminated, buf->truncated};
+  const Slots ro = {1, 0, nullptr, wrap->obs, const_cast<double*>(buf->control), buf->reward, buf->terminated, buf->truncated};
   return launch(prm, buf, wrap, ro, nullptr, B, stream, "tumor_therapy_step");
 }
 
@@ -265,7 +267,9 @@ int pdegym_tumor_rollout(const pdegym_params_tumor* prm, const pdegym_bufs_tumor
   if (!ro) return pdegym::fail(-1, "null rollout descriptor");
   if (B <= 0 || ro->T <= 0) return 0;
   if (!ro->obs || !ro->actions || !ro->rewards || !ro->terminated || !ro->truncated) return pdegym::fail(-3, "null rollout buffer");
-  const Slots s = {ro->T, ro->obs, ro->obs + (size_t)B * prm->nx, ro->actions, ro->rewards, ro->terminated, ro->truncated};
+  const bool per_step = (ro->reserved_ & PDEGYM_ROLLOUT_FINAL_OBS_PER_STEP) != 0;
+  if (per_step && !wrap->final_obs) return pdegym::fail(-3, "tumor rollout: PDEGYM_ROLLOUT_FINAL_OBS_PER_STEP needs wrap->final_obs [T, B, nx]");
+  const Slots s = {ro->T, per_step ? (int64_t)B * prm->nx : 0, ro->obs, ro->obs + (size_t)B * prm->nx, ro->actions, ro->rewards, ro->terminated, ro->truncated};
   return launch(prm, buf, wrap, s, ro->policy, B, stream, "tumor_rollout");
 }
 

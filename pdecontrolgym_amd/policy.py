@@ -280,7 +280,7 @@ class FusedMLP:
         if x.shape[1] + tail.shape[1] != self.in_dim:
             raise ValueError(f"observation rows have {x.shape[1]} entries and tail rows {tail.shape[1]}, the network takes {self.in_dim}")
 
-    def forward_into(self, obs, out, clamp="default", noise=None, tail=None):
+    def forward_into(self, obs, out, clamp="default", noise=None, tail=None, rows=None, rows_not=None):
         """``tail`` (float32 [B, n2], n2 <= 8): the rows are ``[obs | tail]``, read from the two tensors as they are -- SB3's
         ``critic(obs, actions)`` -- with the bits of the call on ``torch.cat([obs, tail], 1)``.  Without it:
 
@@ -292,7 +292,13 @@ class FusedMLP:
         A NaN observation propagates as in PyTorch (the row's output is NaN) and the clamp keeps a NaN like ``torch.clamp`` /
         ``np.clip``; +-Inf is clamped to the bound (include/pdegym.h, conventions).  Squashed-Gaussian head (``squashed_gaussian``):
         ``noise`` is ``eps`` (standard-normal draws; None: the deterministic actor), ``clamp`` the action box (required), and
-        ``out_dim`` <= 8."""
+        ``out_dim`` <= 8.
+
+        ``rows`` (uint8 [B], with ``rows_not`` uint8 [B] or None): only the rows with ``rows[b] != 0 and rows_not[b] == 0`` are
+        evaluated and stored (pdegym_mlp_forward_masked) -- the other rows of ``out`` are left as they are, a stored row has the
+        bits of the unmasked call, and what the other rows of ``obs`` hold (NaN included) does not matter.  No compaction, no
+        allocation, no synchronisation: V(terminal observation) on the truncated rows of a rollout inside a captured graph.  Plain
+        head, float32 ``out``, no ``noise``, no ``tail``."""
         B = obs.shape[0]
         x = obs.reshape(B, -1)
         if tail is not None:
@@ -313,7 +319,16 @@ class FusedMLP:
             if nz.dtype != torch.float32 or nz.device != x.device or nz.stride(1) != 1 or nz.data_ptr() != noise.data_ptr():
                 raise ValueError("noise must be a float32 tensor on the observations' device, viewable as [B, out_dim]")
             net.noise, net.noise_stride = nz.data_ptr(), nz.stride(0)
-        if tail is not None:
+        if rows is not None or rows_not is not None:
+            if rows is None:
+                raise ValueError("rows_not knocks rows out of `rows`: give rows")
+            if tail is not None or noise is not None or net.head != N.MLP_HEAD_PLAIN or y.dtype != torch.float32:
+                raise ValueError("forward_into(rows=...) takes the plain head and a float32 out, without noise or tail")
+            for m, name in ((rows, "rows"), (rows_not, "rows_not")):
+                if m is not None and (m.dtype != torch.uint8 or m.numel() != B or m.device != x.device or not m.is_contiguous()):
+                    raise ValueError(f"{name} must be a contiguous uint8 tensor of {B} flags on the observations' device")
+            self.backend.mlp_forward(net, x, y, B, rows=rows.reshape(B), rows_not=None if rows_not is None else rows_not.reshape(B))
+        elif tail is not None:
             self.backend.mlp_forward_cat(net, x, _rows(tail), y, B)
         else:
             self.backend.mlp_forward(net, x, y, B)

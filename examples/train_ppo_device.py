@@ -37,6 +37,11 @@ algorithm in plain torch on the batched engine:
                 old log-probabilities are copied into static tensors outside the graph (``randperm`` stays outside as well), the
                 attached wrappers need no ``refresh()`` and the optimiser no host work.  The numbers are those of ``fused_opt``.
 
+``gather`` (off by default; needs ``fused_grad`` and ``fused_loss``): the minibatch's observations are not gathered -- ``actor_fn(o_f,
+index=mb)`` and ``critic_fn(o_f, index=mb)`` read row ``mb[b]`` of the rollout's own ``obs`` in place (``FusedMLP.with_grad(..., index=)``:
+pdegym_mlp_forward_gather, pdegym_mlp_backward_gather / _wide_gather), in the eager step and in the ``graph_update`` step.  Every indexed
+call carries the bits of the call on ``o_f[mb]``: the history is identical.
+
 ``bootstrap`` (off by default: the histories printed without it are unchanged): an episode that is cut off (``limit_pde_state_size``:
 ``truncated and not terminated``) is handled as SB3 handles ``infos[i]["TimeLimit.truncated"]`` -- ``DeviceRollout(terminal_obs=True)``
 keeps the terminal observation of every step, and ``DeviceRolloutBuffer.compute`` adds ``gamma * V(terminal observation)`` to that
@@ -46,7 +51,7 @@ The plant is the reference's unstable reaction-diffusion benchmark u_t = u_xx + 
 (ReactionDiffusionPDE1D, Dirichlet control at x = 1).  Uncontrolled, ||u|| grows; the printed mean ||u|| over an episode falls
 as the policy learns to damp it.
 
-    python examples/train_ppo_device.py [iterations] [num_envs] [hidden units per layer: 64] [fused_grad: 0] [fused_loss: 0] [fused_opt: 0] [graph_update: 0] [bootstrap: 0]
+    python examples/train_ppo_device.py [iterations] [num_envs] [hidden units per layer: 64] [fused_grad: 0] [fused_loss: 0] [fused_opt: 0] [graph_update: 0] [bootstrap: 0] [gather: 0]
 """
 import os
 import sys
@@ -92,7 +97,9 @@ nmb_of_update = 4      # minibatches per epoch
 
 
 def main(iterations=30, B=2048, T=64, quiet=False, hidden=64, fused_grad=False, fused_loss=False, fused_opt=False, graph_update=False,
-         bootstrap=False):
+         bootstrap=False, gather=False):
+    if gather and not (fused_grad and fused_loss and hidden <= 256):
+        raise ValueError("gather needs fused_grad and fused_loss, and layers of at most 256 units")
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
     venv = make_env(B, horizon=T)        # one rollout = one episode of every environment
@@ -165,8 +172,12 @@ def main(iterations=30, B=2048, T=64, quiet=False, hidden=64, fused_grad=False, 
             static["lp"].copy_(lp_f)
             if step_fn is None:
                 def step_fn(o_f=o_f, adv_f=adv_f, ret_f=ret_f):      # (views of the rollout's and the buffer's own tensors: fixed addresses)
-                    obs_mb = o_f[static["mb"]]
-                    result = head(actor_fn(obs_mb), log_std, critic_fn(obs_mb), static["a"], static["lp"], adv_f, ret_f, index=static["mb"])
+                    if gather:      # (the address of static["mb"] is what the graph holds: the indices are copied into it)
+                        mean, value = actor_fn(o_f, index=static["mb"]), critic_fn(o_f, index=static["mb"])
+                    else:
+                        obs_mb = o_f[static["mb"]]
+                        mean, value = actor_fn(obs_mb), critic_fn(obs_mb)
+                    result = head(mean, log_std, value, static["a"], static["lp"], adv_f, ret_f, index=static["mb"])
                     result.backward()
                     opt.step()
         for _ in range(epochs):
@@ -189,8 +200,12 @@ def main(iterations=30, B=2048, T=64, quiet=False, hidden=64, fused_grad=False, 
                         graph.replay()
                     continue
                 if fused_loss:
-                    obs_mb = o_f[mb]
-                    result = head(actor_fn(obs_mb), log_std, critic_fn(obs_mb), a_f, lp_f, adv_f, ret_f, index=mb)
+                    if gather:
+                        mean, value = actor_fn(o_f, index=mb), critic_fn(o_f, index=mb)
+                    else:
+                        obs_mb = o_f[mb]
+                        mean, value = actor_fn(obs_mb), critic_fn(obs_mb)
+                    result = head(mean, log_std, value, a_f, lp_f, adv_f, ret_f, index=mb)
                     opt.zero_grad(set_to_none=True)
                     result.backward()
                     if not fused_opt:
@@ -233,4 +248,5 @@ if __name__ == "__main__":
          fused_loss=bool(int(sys.argv[5])) if len(sys.argv) > 5 else False,
          fused_opt=bool(int(sys.argv[6])) if len(sys.argv) > 6 else False,
          graph_update=bool(int(sys.argv[7])) if len(sys.argv) > 7 else False,
-         bootstrap=bool(int(sys.argv[8])) if len(sys.argv) > 8 else False)
+         bootstrap=bool(int(sys.argv[8])) if len(sys.argv) > 8 else False,
+         gather=bool(int(sys.argv[9])) if len(sys.argv) > 9 else False)

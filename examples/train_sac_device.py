@@ -16,7 +16,7 @@ batched engine, on the plant of examples/train_ppo_device.py:
                 ``run()``).
 
     python examples/train_sac_device.py [iterations] [num_envs] [hidden units per layer: 64] [fused_grad: 0] [fused_loss: 0] [fused_opt: 0]
-                                        [fused_critic: 0] [terminal_obs: 0]
+                                        [fused_critic: 0] [terminal_obs: 0] [replay: 0]
 
 ``terminal_obs`` (off by default: the histories printed without it are unchanged) stores transitions as SB3's replay buffer does:
 ``DeviceRollout(terminal_obs=True)`` keeps the terminal observation of every step that ended an episode, ``next`` takes it there and
@@ -50,6 +50,17 @@ three-switch path's, bit for bit (``FusedMLP.with_grad``: the two-part rows give
 drawn by the same two calls in the same order, so the printed history is the same for the same seed.  The critics' ``.grad`` after
 the actor step is no longer produced; nothing read it.  The target critics stay the torch modules on ``head.sample``'s block: their
 float32 sums are torch's GEMM order, which the kernels' order matches only to rounding -- moving them would change the history.
+
+``replay`` (needs the four fused switches) keeps the replay memory in a ``pde_control_gym.DeviceReplayBuffer`` -- ``store.add()`` in place
+of ``fill()``'s seven indexed assignments, ``store.sample(batch)`` in place of the ``randint`` (the same call) -- and runs the SAME update
+body WITHOUT gathering observations or actions: a minibatch is its index ``mb`` and the storages, and the first layer of every fused
+network reads row ``mb[b]`` in place (``FusedMLP.with_grad(..., index=)``: pdegym_mlp_forward_gather, pdegym_mlp_backward_gather /
+_wide_gather): ``q_fn(obs, act, index=mb, tail_indexed=True)`` for the critic step, ``raw_fn(obs, index=mb)`` and
+``q_fn(obs, a_pi, index=mb, params=False)`` for the actor step, ``raw_fn(next, index=mb)`` under ``no_grad`` for the target action.  The
+one gather that stays is ``next[mb]``: the target critics stay the torch modules on ``head.sample(..., obs=o2)``'s block, for the reason
+above.  Every indexed call carries the bits of the call on the gathered rows, the random draws are made by the same calls in the same
+order, and the storages hold the same transitions, so the printed history equals the ``fused_critic`` path's, number for number, for the
+same seed.
 """
 import copy
 import math
@@ -60,7 +71,7 @@ import time
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from pde_control_gym import DeviceRollout, FusedAdam, FusedMLP, SACLoss  # noqa: E402
+from pde_control_gym import DeviceReplayBuffer, DeviceRollout, FusedAdam, FusedMLP, SACLoss  # noqa: E402
 from train_ppo_device import make_env  # noqa: E402
 
 LOG_STD_MIN, LOG_STD_MAX = -20.0, 2.0
@@ -91,7 +102,9 @@ def sample(latent, mu, log_std, obs, raw=None):
 
 
 def main(iterations=30, num_envs=1024, n_steps=32, hidden=64, one_launch=None, quiet=False, updates=8, batch=2048, fused_grad=False,
-         fused_loss=False, fused_opt=False, fused_critic=False, terminal_obs=False):
+         fused_loss=False, fused_opt=False, fused_critic=False, terminal_obs=False, replay=False):
+    if replay and not fused_critic:
+        raise ValueError("replay needs fused_grad, fused_loss, fused_opt and fused_critic")
     if fused_critic and not (fused_grad and fused_loss and fused_opt and hidden <= 256):
         raise ValueError("fused_critic needs fused_grad, fused_loss and fused_opt, and layers of at most 256 units")
     dev = torch.device("cuda", 0)
@@ -132,7 +145,11 @@ def main(iterations=30, num_envs=1024, n_steps=32, hidden=64, one_launch=None, q
         print(f"fused_grad: layers of {hidden} units are wider than the 256 the fused backward passes take; the update uses torch autograd")
     # the replay buffer: device tensors, a ring of `cap` transitions filled T * B at a time
     cap = max(16 * T * B, batch)
-    buf = {k: torch.zeros(cap, n, device=dev) for k, n in (("obs", D), ("next", D), ("act", 1), ("rew", 1), ("term", 1))}
+    if replay:      # the class's storages under the names of the dict; add() fills them, the update reads them by index
+        store = DeviceReplayBuffer(rollout, cap, lo, hi)
+        buf = {"obs": store.observations, "next": store.next_observations, "act": store.actions, "rew": store.rewards, "term": store.dones}
+    else:
+        buf = {k: torch.zeros(cap, n, device=dev) for k, n in (("obs", D), ("next", D), ("act", 1), ("rew", 1), ("term", 1))}
     head, filled = 0, 0
     gamma, tau, target_entropy = 0.99, 0.005, -1.0
     loss_head = SACLoss(gamma, target_entropy, (LOG_STD_MIN, LOG_STD_MAX)) if fused_loss else None
@@ -146,22 +163,14 @@ def main(iterations=30, num_envs=1024, n_steps=32, hidden=64, one_launch=None, q
         opt_alpha = FusedAdam([log_alpha], lr=3e-4)
         q_step = lambda: opt_q.step(polyak=True)      # noqa: E731
 
-    def raw_of(x):
+    def raw_of(x, **rows):
         """The rows [mu, log_std] of the actor: the fused last layer of ``with_grad``, or the modules' outputs side by side."""
         if raw_fn is not None:
-            return raw_fn(x)
+            return raw_fn(x, **rows)
         h = latent(x)
         return torch.cat([mu(h), log_std(h)], 1)
-    history = {"q_loss": [], "actor_loss": [], "alpha": [], "mean_reward": [], "mean_norm": []}
-    t_roll = t_upd = 0.0
-    for it in range(iterations):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        rollout.action_noise.normal_()                   # eps: standard normal, scaled by the state's sigma inside the kernel
-        rollout.run()
-        torch.cuda.synchronize()
-        t_roll += time.perf_counter() - t0
-        t0 = time.perf_counter()
+    def fill(head):
+        """The rollout's T * B transitions into the dict's ring at ``head`` (what ``DeviceReplayBuffer.add`` does for ``replay``)."""
         idx = (head + torch.arange(T * B, device=dev)) % cap
         ended = (rollout.terminated | rollout.truncated).reshape(-1, 1)
         buf["obs"][idx] = rollout.obs[:T].reshape(-1, D)
@@ -178,17 +187,44 @@ def main(iterations=30, num_envs=1024, n_steps=32, hidden=64, one_launch=None, q
         buf["act"][idx] = (2.0 * (rollout.actions.reshape(-1, 1) - lo) / (hi - lo) - 1.0).clamp(-1.0, 1.0)
         buf["rew"][idx] = rollout.rewards.reshape(-1, 1)
         buf["term"][idx] = ended
+    history = {"q_loss": [], "actor_loss": [], "alpha": [], "mean_reward": [], "mean_norm": []}
+
+    def record(q_loss, actor_loss, it):
+        for k, v in (("q_loss", q_loss), ("actor_loss", actor_loss), ("alpha", log_alpha.exp()), ("mean_reward", rollout.rewards.mean()),
+                     ("mean_norm", rollout.obs[:T].norm(dim=2).mean())):
+            history[k].append(float(v.detach()))
+        if not quiet and (it % 5 == 0 or it == iterations - 1):
+            print(f"iter {it:3d}  mean reward {history['mean_reward'][-1]:+8.4f}  mean ||u|| {history['mean_norm'][-1]:7.3f}  "
+                  f"Q loss {history['q_loss'][-1]:9.4g}  actor loss {history['actor_loss'][-1]:+9.4g}  alpha {history['alpha'][-1]:.3f}")
+    t_roll = t_upd = 0.0
+    for it in range(iterations):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        rollout.action_noise.normal_()                   # eps: standard normal, scaled by the state's sigma inside the kernel
+        rollout.run()
+        torch.cuda.synchronize()
+        t_roll += time.perf_counter() - t0
+        t0 = time.perf_counter()
+        if replay:
+            store.add()
+        else:
+            fill(head)
         head, filled = (head + T * B) % cap, min(filled + T * B, cap)
         for _ in range(updates):
-            mb = torch.randint(0, filled, (min(batch, filled),), device=dev)
+            mb = store.sample(batch).index if replay else torch.randint(0, filled, (min(batch, filled),), device=dev)
             if loss_head is not None:
-                o, o2, a = (buf[k][mb] for k in ("obs", "next", "act"))          # (rewards and terminations: gathered in the kernel)
+                if replay:      # the storages themselves: every fused network reads row mb[b] in place; one gather for the torch targets
+                    o, nxt, a, rows, stored = buf["obs"], buf["next"], buf["act"], {"index": mb}, {"index": mb, "tail_indexed": True}
+                    o2 = nxt[mb]
+                else:
+                    o, o2, a = (buf[k][mb] for k in ("obs", "next", "act"))      # (rewards and terminations: gathered in the kernel)
+                    nxt, rows, stored = o2, {}, {}
                 eps2, eps = torch.randn(2, mb.shape[0], 1, device=dev)
                 with torch.no_grad():
-                    block2, logp2 = loss_head.sample(raw_of(o2), eps2, obs=o2)        # [o2 | a2], log pi(a2 | o2)
+                    block2, logp2 = loss_head.sample(raw_of(nxt, **rows), eps2, obs=o2)        # [o2 | a2], log pi(a2 | o2)
                     q1_next, q2_next = q1_t(block2), q2_t(block2)
                 if fused_critic:                                                      # critic(obs, actions): the row in two parts
-                    q1_now, q2_now = q1_fn(o, a), q2_fn(o, a)
+                    q1_now, q2_now = q1_fn(o, a, **stored), q2_fn(o, a, **stored)
                 else:
                     oa = torch.cat([o, a], 1)
                     q1_now, q2_now = q1_fn(oa), q2_fn(oa)
@@ -198,8 +234,8 @@ def main(iterations=30, num_envs=1024, n_steps=32, hidden=64, one_launch=None, q
                 q_step()
                 q_loss = result.critic_loss
                 if fused_critic:      # plain actions; one backward launch per critic, for the action's gradient alone
-                    a_pi, logp = loss_head.sample(raw_of(o), eps)
-                    result = loss_head.actor(q1_fn(o, a_pi, params=False), q2_fn(o, a_pi, params=False), logp, log_alpha)
+                    a_pi, logp = loss_head.sample(raw_of(o, **rows), eps)
+                    result = loss_head.actor(q1_fn(o, a_pi, params=False, **rows), q2_fn(o, a_pi, params=False, **rows), logp, log_alpha)
                 else:
                     block, logp = loss_head.sample(raw_of(o), eps, obs=o)             # [o | a_pi]: the critics' input, no cat
                     result = loss_head.actor(q1_fn(block), q2_fn(block), logp, log_alpha)
@@ -245,12 +281,7 @@ def main(iterations=30, num_envs=1024, n_steps=32, hidden=64, one_launch=None, q
                         pt.lerp_(p, tau)
         torch.cuda.synchronize()
         t_upd += time.perf_counter() - t0
-        for k, v in (("q_loss", q_loss), ("actor_loss", actor_loss), ("alpha", log_alpha.exp()), ("mean_reward", rollout.rewards.mean()),
-                     ("mean_norm", rollout.obs[:T].norm(dim=2).mean())):
-            history[k].append(float(v.detach()))
-        if not quiet and (it % 5 == 0 or it == iterations - 1):
-            print(f"iter {it:3d}  mean reward {history['mean_reward'][-1]:+8.4f}  mean ||u|| {history['mean_norm'][-1]:7.3f}  "
-                  f"Q loss {history['q_loss'][-1]:9.4g}  actor loss {history['actor_loss'][-1]:+9.4g}  alpha {history['alpha'][-1]:.3f}")
+        record(q_loss, actor_loss, it)
     now = {"actor": actor_params, "q1": list(q1.parameters()), "q2": list(q2.parameters())}
     history["moved"] = {k: all(not torch.equal(p.detach(), s) for p, s in zip(now[k], start[k])) for k in now}
     history["one_launch"] = rollout.one_launch
@@ -266,4 +297,5 @@ if __name__ == "__main__":
          fused_loss=bool(int(sys.argv[5])) if len(sys.argv) > 5 else False,
          fused_opt=bool(int(sys.argv[6])) if len(sys.argv) > 6 else False,
          fused_critic=bool(int(sys.argv[7])) if len(sys.argv) > 7 else False,
-         terminal_obs=bool(int(sys.argv[8])) if len(sys.argv) > 8 else False)
+         terminal_obs=bool(int(sys.argv[8])) if len(sys.argv) > 8 else False,
+         replay=bool(int(sys.argv[9])) if len(sys.argv) > 9 else False)

@@ -45,6 +45,10 @@
  *                           and pdegym_mlp_forward_masked evaluates V(terminal_observation) on the rows with
  *                           infos[i]["TimeLimit.truncated"] only: the two halves of the truncation bootstrap of
  *                           stable_baselines3/common/on_policy_algorithm.py: collect_rollouts
+ *   pdegym_mlp_forward_gather, pdegym_mlp_backward_gather, pdegym_mlp_backward_wide_gather
+ *                           replace the replay_data.observations[...] / rollout_data minibatch gathers in front of the networks in
+ *                           SAC.train and PPO.train (stable_baselines3/common/buffers.py: ReplayBuffer._get_samples): the first layer
+ *                           reads row index[b] of the storage in place
  *
  * One call advances EVERY instance of a batch by one env-step (S PDE sub-steps for the 1D envs, one
  * Chorin projection step with K Jacobi sweeps for NS2D).  Instances are independent.
@@ -799,6 +803,40 @@ typedef struct pdegym_mlp_backward_cat_args {
 /* (the workspace of params != 0 is that of pdegym_mlp_backward_workspace / pdegym_mlp_backward_wide_workspace) */
 int pdegym_mlp_backward_cat(const pdegym_mlp* net, const pdegym_mlp_backward_cat_args* a, int32_t B, void* stream);
 int pdegym_mlp_backward_wide_cat(const pdegym_mlp* net, const pdegym_mlp_backward_cat_args* a, int32_t B, void* stream);
+
+/* ---- rows by index: the networks read a minibatch out of a storage in place, no [N, D] copy of the rows ------------------------------
+ * A replay buffer (pde_control_gym.DeviceReplayBuffer) or a rollout holds [M, D] observations; an update step draws a minibatch as an
+ * int64 index and, until now, gathered x[index] (and the stored actions) into fresh arrays before a network saw a row.  The three
+ * entry points below read row index[b] of the storage where the shadowed ones read row b of the copy.  They launch the kernels of
+ * pdegym_mlp_forward_cat, pdegym_mlp_backward_cat and pdegym_mlp_backward_wide_cat (new instantiations: no new kernel).
+ *
+ * Row      row b of the first layer's input is [ x[index[b], 0 .. D) | x2[(x2_indexed ? index[b] : b), 0 .. n2) ], 0 <= n2 <= 8,
+ *          D = in_dim - n2 >= 1; n2 == 0 is the plain row (x2 == NULL).  y, dy and dx2 stay dense: row b.  x: float32, or float64 with
+ *          net->x_f64, rounded as it is read.  Duplicated index entries are ordinary (sampling with replacement).
+ * Bits     y, dw, db and dx2 equal, BIT FOR BIT, those of pdegym_mlp_forward / _cat, pdegym_mlp_backward_cat and
+ *          pdegym_mlp_backward_wide_cat on the materialised rows with the same `slabs`: only the address of a row changes.  Every head,
+ *          clamp and noise option of the forward, params 0 / 1 of the backward (one launch, or three) are kept.
+ * Gradients  dx must be NULL (-2): a gradient of gathered rows is a scatter-add over duplicates, and the library has no float atomics.
+ *          dx2 only with x2_indexed == 0 (the actor step: stored observation, fresh action).
+ * Range    UNLIKE the `index` of pdegym_ppo_loss and pdegym_sac_critic_loss, whose range is the caller's to keep, an entry outside
+ *          [0, M) is NEVER DEREFERENCED here (the index addresses a large storage on machines others share): where the row base is
+ *          formed, one comparison per row replaces such an entry by row 0 for the address and selects the whole row to quiet NaN.  Its
+ *          y is NaN and it reaches the weight gradients as a NaN row would; no other row of y or dx2 changes a bit.
+ * Errors   as the shadowed entry points, and: -1 g or g->index NULL; -2 M < 1, index not 8-byte aligned, dx given, dx2 with
+ *          x2_indexed, x2_indexed with n2 == 0.  The overlap checks of the backward passes take M rows for x (and for x2 with
+ *          x2_indexed) and the B entries of index as an input. */
+typedef struct pdegym_mlp_gather {
+  const int64_t* index;   /* [B] device array: row b of the call is row index[b] of x             */
+  int64_t M;              /* rows of x (and of x2 when x2_indexed); >= 1                          */
+  int32_t x2_indexed;     /* 0: the tail of row b is x2[b]; 1: it is x2[index[b]]                */
+  int32_t reserved_;
+} pdegym_mlp_gather;
+int pdegym_mlp_forward_gather(const pdegym_mlp* net, const void* x, int64_t x_stride, const float* x2, int64_t x2_stride,
+                              int32_t n2, const pdegym_mlp_gather* g, void* y, int64_t y_stride, int32_t B, void* stream);
+int pdegym_mlp_backward_gather(const pdegym_mlp* net, const pdegym_mlp_backward_cat_args* a, const pdegym_mlp_gather* g,
+                               int32_t B, void* stream);
+int pdegym_mlp_backward_wide_gather(const pdegym_mlp* net, const pdegym_mlp_backward_cat_args* a, const pdegym_mlp_gather* g,
+                                    int32_t B, void* stream);
 
 /* ---- backstepping baseline (the controller every result table of the reference compares the learned policies against) ------
  * Gains: theta [R, m] float32 rows, sampled by the caller (the examples use linspace(dx, X, m), NOT the plant's grid) -> gain [R, m]

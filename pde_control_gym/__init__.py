@@ -37,6 +37,7 @@ for _id, _entry in _IDS.items():
 from pde_control_gym.vector import PDEVecEnv, make_vec  # noqa: E402
 from pde_control_gym.rollout import DeviceRollout  # noqa: E402
 from pde_control_gym.rollout_buffer import DeviceRolloutBuffer  # noqa: E402
+from pde_control_gym.replay_buffer import DeviceReplayBuffer, ReplaySample  # noqa: E402
 from pde_control_gym.ppo_loss import PPOLoss  # noqa: E402
 from pde_control_gym.sac_loss import SACLoss  # noqa: E402
 from pde_control_gym.fused_adam import FusedAdam  # noqa: E402
@@ -46,4 +47,4 @@ from pde_control_gym.ns_adjoint import NSAdjointOptimizer  # noqa: E402
 from pde_control_gym import export  # noqa: E402
 from pde_control_gym.vector_gymnasium import GymnasiumVectorAdapter  # noqa: E402
 
-__all__ = ["make", "register", "make_vec", "PDEVecEnv", "DeviceRollout", "DeviceRolloutBuffer", "PPOLoss", "SACLoss", "FusedAdam", "FusedMLP", "BacksteppingController", "TrafficBacksteppingController", "NSAdjointOptimizer", "HAVE_GYMNASIUM", "export", "GymnasiumVectorAdapter"]
+__all__ = ["make", "register", "make_vec", "PDEVecEnv", "DeviceRollout", "DeviceRolloutBuffer", "DeviceReplayBuffer", "ReplaySample", "PPOLoss", "SACLoss", "FusedAdam", "FusedMLP", "BacksteppingController", "TrafficBacksteppingController", "NSAdjointOptimizer", "HAVE_GYMNASIUM", "export", "GymnasiumVectorAdapter"]

@@ -43,6 +43,7 @@ EXPORTS = [
     "pdegym_fused_adam", "pdegym_fused_adam_workspace",
     "pdegym_mlp_forward_cat", "pdegym_mlp_backward_cat", "pdegym_mlp_backward_wide_cat",
     "pdegym_mlp_forward_masked",
+    "pdegym_mlp_forward_gather", "pdegym_mlp_backward_gather", "pdegym_mlp_backward_wide_gather",
 ]
 # bit 0 of Rollout1D / RolloutTraffic / RolloutTumor .reserved_ (PDEGYM_ROLLOUT_FINAL_OBS_PER_STEP): final_obs of the call is [T, B, obs_dim]
 ROLLOUT_FINAL_OBS_PER_STEP = 1
@@ -199,6 +200,11 @@ class MlpBackwardCat(C.Structure):
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
                 ("x2", C.c_void_p), ("x2_stride", C.c_int64), ("dx2", C.c_void_p), ("dx2_stride", C.c_int64),
                 ("n2", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class MlpGather(C.Structure):
+    """pdegym_mlp_gather: row b of a call is row ``index[b]`` of the [M, D] storage ``x`` (and of ``x2`` with ``x2_indexed``)."""
+    _fields_ = [("index", C.c_void_p), ("M", C.c_int64), ("x2_indexed", C.c_int32), ("reserved_", C.c_int32)]
 
 
 class Backstep(C.Structure):
@@ -376,6 +382,12 @@ def load():
     lib.pdegym_mlp_forward_cat.restype = C.c_int
     for f in (lib.pdegym_mlp_backward_cat, lib.pdegym_mlp_backward_wide_cat):
         f.argtypes = [C.POINTER(Mlp), C.POINTER(MlpBackwardCat), C.c_int32, C.c_void_p]
+        f.restype = C.c_int
+    lib.pdegym_mlp_forward_gather.argtypes = [C.POINTER(Mlp), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(MlpGather),
+                                              C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
+    lib.pdegym_mlp_forward_gather.restype = C.c_int
+    for f in (lib.pdegym_mlp_backward_gather, lib.pdegym_mlp_backward_wide_gather):
+        f.argtypes = [C.POINTER(Mlp), C.POINTER(MlpBackwardCat), C.POINTER(MlpGather), C.c_int32, C.c_void_p]
         f.restype = C.c_int
     lib.pdegym_ppo_loss_workspace.argtypes = [C.c_int32, C.c_int32]
     lib.pdegym_ppo_loss_workspace.restype = C.c_int64

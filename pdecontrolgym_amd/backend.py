@@ -563,6 +563,52 @@ class HipBackend:
         N.check(self.lib.pdegym_mlp_forward_cat(C.byref(net), x.data_ptr(), stride(x), x2.data_ptr(), stride(x2), n2, y.data_ptr(), stride(y),
                                                 B, N.current_stream_ptr(x.device)), "pdegym_mlp_forward_cat")
 
+    @staticmethod
+    def _mlp_gather_desc(entry: str, x, x2, index, x2_indexed: bool, B: int) -> N.MlpGather:
+        """The checks of ``index`` and the descriptor of the gather calls: ``index`` a contiguous int64 HIP tensor [B] on x's device."""
+        import torch
+        if (not torch.is_tensor(index) or not index.is_cuda or index.device != x.device or index.dtype != torch.int64 or index.dim() != 1
+                or index.shape[0] != B or not index.is_contiguous()):
+            raise N.NativeError(f"{entry}: index must be a contiguous int64 HIP tensor [{B}] on x's device")
+        if x2_indexed and (x2 is None or x2.shape[0] != x.shape[0]):
+            raise N.NativeError(f"{entry}: x2_indexed needs x2 with the {int(x.shape[0])} rows of x")
+        g = N.MlpGather()
+        g.index, g.M, g.x2_indexed = index.data_ptr(), int(x.shape[0]), int(bool(x2_indexed))
+        return g
+
+    @_on_device_of("x")
+    def mlp_forward_gather(self, net: N.Mlp, x, x2, index, y, B: int, x2_indexed: bool = False):
+        """``mlp_forward`` / ``mlp_forward_cat`` on rows read by index (pdegym_mlp_forward_gather): row b is
+        ``[x[index[b]] | x2[index[b] if x2_indexed else b]]``, ``x`` the [M, D] storage (float32, or float64 with ``net.x_f64``), ``x2``
+        [B, n2] (or [M, n2] with ``x2_indexed``) float32 or None (the plain row), ``index`` int64 [B], ``y`` [B, out].  The bits of the
+        call on the materialised rows; an index entry outside [0, M) gives a NaN row and is never an address."""
+        import torch
+        M = int(x.shape[0]) if torch.is_tensor(x) and x.dim() == 2 else -1
+        for t_, name, want, rows in ((x, "x", torch.float64 if net.x_f64 else torch.float32, M),
+                                     (x2, "x2", torch.float32, M if x2_indexed else B),
+                                     (y, "y", torch.float64 if net.y_f64 else torch.float32, B)):
+            if t_ is None and name == "x2":
+                continue
+            if (not torch.is_tensor(t_) or not t_.is_cuda or t_.device != x.device or t_.dtype != want or t_.dim() != 2
+                    or t_.shape[0] != rows or t_.stride(1) != 1 or rows < 1):
+                raise N.NativeError(f"mlp_forward_gather: {name} must be a {want} HIP tensor [{rows}, width] with unit inner stride on x's device")
+        n2 = 0 if x2 is None else int(x2.shape[1])
+        if int(x.shape[1]) + n2 != int(net.layer[0].in_dim):
+            raise N.NativeError(f"mlp_forward_gather: x has {int(x.shape[1])} columns and x2 {n2}, the network takes {int(net.layer[0].in_dim)}")
+        g = self._mlp_gather_desc("mlp_forward_gather", x, x2, index, x2_indexed, B)
+        stride = lambda t_: t_.stride(0) if t_.shape[0] > 1 else t_.shape[1]      # noqa: E731
+        N.check(self.lib.pdegym_mlp_forward_gather(C.byref(net), x.data_ptr(), stride(x), (None if x2 is None else x2.data_ptr()),
+                                                   (0 if x2 is None else stride(x2)), n2, C.byref(g), y.data_ptr(), stride(y), B,
+                                                   N.current_stream_ptr(x.device)), "pdegym_mlp_forward_gather")
+
+    @_on_device_of("x")
+    def mlp_backward_gather(self, net: N.Mlp, x, x2, index, dy, weights, dw=None, db=None, dx2=None, params: bool = True, slabs: int = 0,
+                            wide: bool = False, x2_indexed: bool = False):
+        """``mlp_backward_cat`` on rows read by index (pdegym_mlp_backward_gather / _wide_gather): ``x`` the [M, D] storage, ``x2``
+        [B, n2] (or [M, n2] with ``x2_indexed``) or None, ``index`` int64 [B], ``dy`` [B, out].  No ``dx`` (a gradient of gathered rows is
+        a scatter-add); ``dx2`` [B, n2] only without ``x2_indexed``.  Bits: those of ``mlp_backward_cat`` on the materialised rows."""
+        self._mlp_backward_cat_call(net, x, x2, dy, weights, dw, db, None, dx2, params, slabs, wide, index=index, x2_indexed=x2_indexed)
+
     @_on_device_of("x")
     def mlp_backward_cat(self, net: N.Mlp, x, x2, dy, weights, dw=None, db=None, dx=None, dx2=None, params: bool = True,
                          slabs: int = 0, wide: bool = False):
@@ -570,20 +616,28 @@ class HipBackend:
         ``x2`` [B, n2] float32 or None (n2 = 0: the plain row), ``dx`` [B, D] and ``dx2`` [B, n2] float32 or None.  ``params`` true:
         the three launches, ``dw`` / ``db`` as for ``mlp_backward``; false: ONE launch for ``dx`` / ``dx2`` alone -- ``dw`` and ``db``
         must be None (or lists of None), no workspace is touched.  Bits: those of the shadowed pass on the concatenated rows."""
+        self._mlp_backward_cat_call(net, x, x2, dy, weights, dw, db, dx, dx2, params, slabs, wide)
+
+    def _mlp_backward_cat_call(self, net, x, x2, dy, weights, dw, db, dx, dx2, params, slabs, wide, index=None, x2_indexed=False):
+        """The argument checks and the call of pdegym_mlp_backward[_wide]_cat, or with ``index`` of pdegym_mlp_backward[_wide]_gather
+        (one argument structure; ``x`` then has M rows, ``x2`` M with ``x2_indexed``, everything else the B of ``dy``)."""
         import torch
-        entry = "mlp_backward_wide_cat" if wide else "mlp_backward_cat"
-        B, nl = int(x.shape[0]) if x.dim() == 2 else -1, int(net.n_layers)
+        gather = index is not None
+        entry = ("mlp_backward_wide" if wide else "mlp_backward") + ("_gather" if gather else "_cat")
+        M = int(x.shape[0]) if x.dim() == 2 else -1
+        B, nl = (int(dy.shape[0]) if torch.is_tensor(dy) and dy.dim() == 2 else -1) if gather else M, int(net.n_layers)
         n2 = 0 if x2 is None else (int(x2.shape[1]) if torch.is_tensor(x2) and x2.dim() == 2 else -1)
         D = int(net.layer[0].in_dim) - n2
         want_x = torch.float64 if net.x_f64 else torch.float32
-        rows = (("x", x, want_x, D), ("x2", x2, torch.float32, n2), ("dy", dy, torch.float32, int(net.layer[nl - 1].out_dim)),
-                ("dx", dx, torch.float32, D), ("dx2", dx2, torch.float32, n2))
-        for name, t_, dtype, width in rows:
+        rows = (("x", x, want_x, D, M), ("x2", x2, torch.float32, n2, M if x2_indexed else B),
+                ("dy", dy, torch.float32, int(net.layer[nl - 1].out_dim), B), ("dx", dx, torch.float32, D, B), ("dx2", dx2, torch.float32, n2, B))
+        for name, t_, dtype, width, n in rows:
             if t_ is None and name in ("x2", "dx", "dx2"):
                 continue
             if (not torch.is_tensor(t_) or not t_.is_cuda or t_.device != x.device or t_.dtype != dtype or t_.dim() != 2
-                    or tuple(t_.shape) != (B, width) or (width > 1 and t_.stride(1) != 1) or (B > 1 and t_.stride(0) < width)):
-                raise N.NativeError(f"{entry}: {name} must be a {dtype} HIP tensor [{B}, {width}] with unit inner stride on x's device")
+                    or tuple(t_.shape) != (n, width) or (width > 1 and t_.stride(1) != 1) or (n > 1 and t_.stride(0) < width)):
+                raise N.NativeError(f"{entry}: {name} must be a {dtype} HIP tensor [{n}, {width}] with unit inner stride on x's device")
+        g = self._mlp_gather_desc(entry, x, x2, index, x2_indexed, B) if gather else None
         dw = [None] * nl if dw is None else dw
         db = [None] * nl if db is None else db
         if not (len(weights) == len(dw) == len(db) == nl):
@@ -601,7 +655,7 @@ class HipBackend:
                     raise N.NativeError(f"{entry}: {name}[{l}] must be a contiguous float32 HIP tensor {shp} on x's device")
             a.w[l] = weights[l].data_ptr()
             a.dw[l], a.db[l] = (None if dw[l] is None else dw[l].data_ptr()), (None if db[l] is None else db[l].data_ptr())
-        stride = lambda t_: t_.stride(0) if B > 1 else t_.shape[1]      # noqa: E731
+        stride = lambda t_: t_.stride(0) if t_.shape[0] > 1 else t_.shape[1]      # noqa: E731
         a.x, a.x_stride, a.dy, a.dy_stride = x.data_ptr(), stride(x), dy.data_ptr(), stride(dy)
         if x2 is not None:
             a.x2, a.x2_stride, a.n2 = x2.data_ptr(), stride(x2), n2
@@ -617,7 +671,8 @@ class HipBackend:
                 N.check(need, f"pdegym_{shadowed}_workspace")
             ws = (self._mlp_backward_wide_workspace if wide else self._mlp_backward_workspace)(x.device, need)
             a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
-        N.check(getattr(self.lib, f"pdegym_{entry}")(C.byref(net), C.byref(a), B, N.current_stream_ptr(x.device)), f"pdegym_{entry}")
+        extra = (C.byref(g),) if gather else ()
+        N.check(getattr(self.lib, f"pdegym_{entry}")(C.byref(net), C.byref(a), *extra, B, N.current_stream_ptr(x.device)), f"pdegym_{entry}")
 
     def _mlp_backward_workspace(self, device, nbytes: int):
         """The workspace of ``mlp_backward``: one uint8 tensor per (device, size), kept (every launch of one stream uses it in turn)."""

@@ -33,6 +33,15 @@ constexpr int kRows = 16;                   // observation rows per workgroup (t
 constexpr int kMaxWidth = PDEGYM_MLP_MAX_WIDTH;
 constexpr int kXChunk = 512;                // observation entries per row staged in LDS at a time
 
+// rows by index (pdegym_mlp_forward_gather): the INDEXED instantiations, which are never MASKED, take it in the place of rows_not, so
+// that every other instantiation keeps the argument list it had
+struct RowIndex {
+  const long long* index;      // [B]
+  long long M;                 // rows of x (and of x2 when x2_indexed)
+  int x2_indexed;
+};
+using MaskPointer = const uint8_t* __restrict__;
+
 // NT = 16-neuron tiles per wave, WV = waves per workgroup: one tile per wave throughout -- 4 waves for layers of up to 64
 // units, 8 up to 128, 16 up to 256.  The reduction is bound by the latency of the weight stream, and more waves keep more
 // loads in flight per CU than fewer waves with more tiles each (257-256-256-1 at B = 4096: 27.7 us with 4 waves x 4 tiles,
@@ -44,12 +53,17 @@ constexpr int kXChunk = 512;                // observation entries per row stage
 // stored, and a workgroup without one returns before it requests a weight (and before its first barrier: the condition is the same
 // in every wave).  Dead rows are staged and reduced like any other -- the rows of a tile are independent in the MFMA, so a live row's
 // bits do not depend on them -- which keeps the reduction the unmasked kernel's, instruction for instruction.  Compiled apart as well.
-template <int NT, int WV, typename TX, typename TY, bool GAUSS, bool CAT, bool MASKED = false>
+// INDEXED (pdegym_mlp_forward_gather): row b of the call is row index[b] of x (and of x2 with x2_indexed); only the CAT instantiations
+// have the form (n2 == 0: D = in_dim, the tail is never read), compiled apart as the others.  A wave loads the index entries of the rows
+// it stages once, before the first chunk; an entry outside [0, M) is replaced by row 0 for the address and the row is selected to NaN.
+template <int NT, int WV, typename TX, typename TY, bool GAUSS, bool CAT, bool MASKED = false, bool INDEXED = false>
 __global__ __launch_bounds__(64 * WV) void mlp_forward_kernel(pdegym_mlp N, const TX* __restrict__ x, long long x_stride,
                                                           TY* __restrict__ y, long long y_stride, int B, int ldx,
                                                           const float* __restrict__ x2, long long x2_stride, int D,
-                                                          const uint8_t* __restrict__ rows, const uint8_t* __restrict__ rows_not) {
+                                                          const uint8_t* __restrict__ rows,
+                                                          std::conditional_t<INDEXED, RowIndex, MaskPointer> rows_not) {
   static_assert(!MASKED || (!GAUSS && !CAT), "the masked launch takes plain rows and the plain head");
+  static_assert(!INDEXED || (CAT && !MASKED), "rows by index: the two-part instantiations, never the masked launch");
   // LDS: activations ping-pong between hb0 and hb1; the staged observation chunk shares its space with hb1 (first written
   // by the second layer, when the observations are no longer needed)
   extern __shared__ __attribute__((aligned(16))) float mlp_smem[];
@@ -69,6 +83,22 @@ __global__ __launch_bounds__(64 * WV) void mlp_forward_kernel(pdegym_mlp N, cons
     const bool live = r < B && rows[r] != 0 && !(rows_not && rows_not[r] != 0);
     live_rows = (unsigned)__ballot(live) & 0xffffu;
     if (live_rows == 0) return;      // workgroup-uniform
+  }
+
+  // INDEXED: the storage rows of the kRowsPerWave rows this wave stages, and whether their entries lie outside [0, M)
+  long long xrow[kRowsPerWave], x2row[kRowsPerWave];
+  bool outside[kRowsPerWave];
+  if constexpr (INDEXED) {
+    const RowIndex& gth = rows_not;
+#pragma unroll
+    for (int rr = 0; rr < kRowsPerWave; ++rr) {
+      const int r = row0 + kRowsPerWave * wave + rr;
+      const long long j = r < B ? gth.index[r] : 0;
+      const bool inside = (unsigned long long)j < (unsigned long long)gth.M;      // one comparison: j >= 0 and j < M
+      xrow[rr] = inside ? j : 0;
+      x2row[rr] = gth.x2_indexed ? xrow[rr] : (r < B ? r : 0);
+      outside[rr] = !inside;
+    }
   }
 
   // weights of the first pipeline stage of the coming layer: requested before the barrier that publishes its inputs
@@ -135,12 +165,19 @@ __global__ __launch_bounds__(64 * WV) void mlp_forward_kernel(pdegym_mlp N, cons
             const bool row_ok = row0 + r < B;
             const TX* src = x + (long long)(row_ok ? row0 + r : 0) * x_stride + c0;
             const float* tail = CAT ? x2 + (long long)(row_ok ? row0 + r : 0) * x2_stride : nullptr;
+            if constexpr (INDEXED) {
+              src = x + xrow[rr] * x_stride + c0;
+              tail = x2 + x2row[rr] * x2_stride;
+            }
 #pragma unroll
             for (int i = 0; i < kXChunk / 64; ++i) {
               const int c = lane + 64 * i;
               if (CAT) {      // column c0 + c of the row: the first part, or entry c0 + c - D of the tail
                 v[rr][i] = 0.f;
                 if (row_ok && c < clen) v[rr][i] = c0 + c < D ? (float)src[c] : tail[c0 + c - D];
+                if constexpr (INDEXED) {
+                  if (row_ok && c < clen && outside[rr]) v[rr][i] = __builtin_nanf("");
+                }
               } else {
                 v[rr][i] = (row_ok && c < clen) ? (float)src[c] : 0.f;
               }
@@ -213,6 +250,7 @@ struct Tail {
   int D;
   const uint8_t* rows;
   const uint8_t* rows_not;
+  const pdegym_mlp_gather* g;      // rows by index (pdegym_mlp_forward_gather); nullptr: row b is row b
 };
 
 template <int NT, int WV, typename TX, typename TY, bool GAUSS>
@@ -222,7 +260,11 @@ static void launch_mlp_nt(const pdegym_mlp* net, const TX* xp, long long xs, TY*
   const int ldx = lds_stride(kin) > ldh ? lds_stride(kin) : ldh;
   const size_t lds_bytes = (size_t)kRows * (ldh + ldx) * sizeof(float);         // <= 50 KB: below the 64 KB that need no opt-in
   const dim3 grid((B + kRows - 1) / kRows), block(64 * WV);
-  if (tl.x2)
+  if (tl.g) {
+    const RowIndex gth = {reinterpret_cast<const long long*>(tl.g->index), tl.g->M, tl.g->x2_indexed};
+    hipLaunchKernelGGL((mlp_forward_kernel<NT, WV, TX, TY, GAUSS, true, false, true>), grid, block, lds_bytes, st, *net, xp, xs, yp, ys, B,
+                       ldx, tl.x2, tl.x2_stride, tl.D, nullptr, gth);
+  } else if (tl.x2)
     hipLaunchKernelGGL((mlp_forward_kernel<NT, WV, TX, TY, GAUSS, true>), grid, block, lds_bytes, st, *net, xp, xs, yp, ys, B, ldx, tl.x2,
                        tl.x2_stride, tl.D, nullptr, nullptr);
   else if constexpr (!GAUSS && std::is_same<TY, float>::value) {
@@ -256,7 +298,7 @@ static void launch_mlp(const pdegym_mlp* net, const void* x, long long xs, void*
 // one dispatch
 static int mlp_forward_rows(const pdegym_mlp* net, const void* x, int64_t x_stride, const float* x2, int64_t x2_stride, int32_t n2,
                             void* y, int64_t y_stride, int32_t B, void* stream, const uint8_t* rows = nullptr,
-                            const uint8_t* rows_not = nullptr) {
+                            const uint8_t* rows_not = nullptr, const pdegym_mlp_gather* g = nullptr) {
   if (!net || !x || !y) return pdegym::fail(-3, "null pointer");
   if (rows && (net->head != PDEGYM_MLP_HEAD_PLAIN || net->noise || net->y_f64))
     return pdegym::fail(-2, "mlp_forward_masked: the plain head, no noise and float32 y");
@@ -293,12 +335,12 @@ static int mlp_forward_rows(const pdegym_mlp* net, const void* x, int64_t x_stri
   for (int l = 0; l < net->n_layers; ++l) width = net->layer[l].out_dim > width ? net->layer[l].out_dim : width;
   hipStream_t st = (hipStream_t)stream;
   const long long xs = x_stride, ys = y_stride;
-  const Tail tl = {x2, x2_stride, net->layer[0].in_dim - n2, rows, rows_not};
+  const Tail tl = {x2, x2_stride, net->layer[0].in_dim - n2, rows, rows_not, g};
   if (net->x_f64 && net->y_f64) launch_mlp<double, double>(net, x, xs, y, ys, B, width, tl, st);
   else if (net->x_f64) launch_mlp<double, float>(net, x, xs, y, ys, B, width, tl, st);
   else if (net->y_f64) launch_mlp<float, double>(net, x, xs, y, ys, B, width, tl, st);
   else launch_mlp<float, float>(net, x, xs, y, ys, B, width, tl, st);
-  return pdegym::check_launch(n2 ? "mlp_forward_cat" : (rows ? "mlp_forward_masked" : "mlp_forward"));
+  return pdegym::check_launch(g ? "mlp_forward_gather" : n2 ? "mlp_forward_cat" : (rows ? "mlp_forward_masked" : "mlp_forward"));
 }
 
 extern "C" int pdegym_mlp_forward(const pdegym_mlp* net, const void* x, int64_t x_stride, void* y, int64_t y_stride, int32_t B,
@@ -318,4 +360,18 @@ extern "C" int pdegym_mlp_forward_cat(const pdegym_mlp* net, const void* x, int6
   if (!x2) return pdegym::fail(-3, "null pointer");
   if (!pdegym::is_aligned(x2, 4)) return pdegym::fail(-2, "mlp_forward_cat: x2 must be 4-byte aligned");
   return mlp_forward_rows(net, x, x_stride, x2, x2_stride, n2, y, y_stride, B, stream);
+}
+
+// Rows by index: row b of the call is row g->index[b] of x (include/pdegym.h).  The CAT instantiations with the index; n2 == 0 is the
+// plain row (D = in_dim).
+extern "C" int pdegym_mlp_forward_gather(const pdegym_mlp* net, const void* x, int64_t x_stride, const float* x2, int64_t x2_stride,
+                                         int32_t n2, const pdegym_mlp_gather* g, void* y, int64_t y_stride, int32_t B, void* stream) {
+  if (!g || !g->index) return pdegym::fail(-1, "mlp_forward_gather: null gather descriptor or index");
+  if (!pdegym::is_aligned(g->index, 8)) return pdegym::fail(-2, "mlp_forward_gather: index must be 8-byte aligned");
+  if (g->M < 1) return pdegym::fail(-2, "mlp_forward_gather: M must be >= 1");
+  if (n2 < 0 || n2 > 8) return pdegym::fail(-2, "mlp_forward_gather: n2 must be 0..8");
+  if (g->x2_indexed && !n2) return pdegym::fail(-2, "mlp_forward_gather: x2_indexed with n2 == 0");
+  if (n2 && !x2) return pdegym::fail(-3, "null pointer");
+  if (n2 && !pdegym::is_aligned(x2, 4)) return pdegym::fail(-2, "mlp_forward_gather: x2 must be 4-byte aligned");
+  return mlp_forward_rows(net, x, x_stride, n2 ? x2 : nullptr, n2 ? x2_stride : 0, n2, y, y_stride, B, stream, nullptr, nullptr, g);
 }

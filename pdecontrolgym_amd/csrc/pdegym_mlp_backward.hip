@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "pdegym.h"
 #include "pdegym_common.h"
@@ -66,7 +67,20 @@ struct Plan {
   int D;
 };
 
+// rows by index (pdegym_mlp_backward_gather): the plan of the INDEXED instantiations, the others take Plan as they did
+struct GatherPlan : Plan {
+  const long long* index;      // [B]: row b of the call is row index[b] of x (and of x2 with x2_indexed)
+  long long M;                 // rows of x; an entry outside [0, M) is never an address, its row reads as NaN
+  int x2_indexed;
+};
+
 __device__ __forceinline__ v4f mma(float a, float b, v4f acc) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0); }
+
+// v of lane l, l wave-uniform
+__device__ __forceinline__ long long lane_value(long long v, int l) {
+  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, l), hi = (unsigned)__builtin_amdgcn_readlane((int)(v >> 32), l);
+  return (long long)(((unsigned long long)hi << 32) | lo);
+}
 
 __device__ __forceinline__ int slab_begin(const Plan& P, int slab) { return (int)((long long)slab * P.tiles / P.slabs); }
 
@@ -79,8 +93,11 @@ __device__ __forceinline__ float act_backward(float dh, float h, int act) {
 
 // CAT: rows in two parts.  PARAMS false: the input gradient alone -- no dW / db products, no dZ_0 in the workspace, no partial stores
 // (pdegym_mlp_backward_cat with params == 0; the only launch of that call).  pdegym_mlp_backward runs <TX, false, true>, the code it was.
-template <typename TX, bool CAT, bool PARAMS>
-__global__ __launch_bounds__(256) void mlp_backward_tiles(pdegym_mlp N, Plan P, int ldx) {
+// INDEXED (pdegym_mlp_backward_gather; CAT instantiations only): a wave loads the index entries of the four rows it stages once per
+// tile, before the first chunk.
+template <typename TX, bool CAT, bool PARAMS, bool INDEXED = false>
+__global__ __launch_bounds__(256) void mlp_backward_tiles(pdegym_mlp N, std::conditional_t<INDEXED, GatherPlan, Plan> P, int ldx) {
+  static_assert(!INDEXED || CAT, "rows by index: the two-part instantiations");
   extern __shared__ __attribute__((aligned(16))) float bw_smem[];
   float* const hs = bw_smem;                                   // [kLayers][16][kLdh]: the activations of every layer
   float* const gs = hs + kLayers * kRows * kLdh;               // [2][16][kLdh]: dH / dZ of the layer at hand, and of the one below
@@ -115,6 +132,18 @@ __global__ __launch_bounds__(256) void mlp_backward_tiles(pdegym_mlp N, Plan P, 
       v4f acc[1] = {(v4f){0.f, 0.f, 0.f, 0.f}};
       v4f wfirst[kStage][1];
       if (l == 0) {
+        // INDEXED: lane l holds the storage row of row 4 wave + l % 4, one of the four this wave stages, and whether its entry lies
+        // outside [0, M); the staging loop reads them with the wave-uniform rr (lane_value: scalar row bases)
+        long long xrow = 0, x2row = 0;
+        int outside = 0;
+        if constexpr (INDEXED) {
+          const int r = row0 + 4 * wave + (lane & 3);
+          const long long j = r < B ? P.index[r] : 0;
+          const bool inside = (unsigned long long)j < (unsigned long long)P.M;      // one comparison: j >= 0 and j < M
+          xrow = inside ? j : 0;
+          x2row = P.x2_indexed ? xrow : (r < B ? r : 0);
+          outside = !inside;
+        }
         for (int c0 = 0; c0 < K; c0 += kXChunk) {
           const int clen = (K - c0) < kXChunk ? (K - c0) : kXChunk;
           const int cpad = (clen + 15) & ~15;
@@ -124,9 +153,18 @@ __global__ __launch_bounds__(256) void mlp_backward_tiles(pdegym_mlp N, Plan P, 
             const TX* src = x + (long long)(row_ok ? row0 + r : 0) * P.x_stride + c0;
             if (CAT) {      // column c0 + c: the first part, or entry c0 + c - D of the tail
               const float* tail = P.x2 + (long long)(row_ok ? row0 + r : 0) * P.x2_stride;
+              bool nan_row = false;
+              if constexpr (INDEXED) {
+                src = x + lane_value(xrow, rr) * P.x_stride + c0;
+                tail = P.x2 + lane_value(x2row, rr) * P.x2_stride;
+                nan_row = __builtin_amdgcn_readlane(outside, rr) != 0;
+              }
               for (int c = lane; c < cpad; c += 64) {
                 float v = 0.f;
                 if (row_ok && c < clen) v = c0 + c < P.D ? (float)src[c] : tail[c0 + c - P.D];
+                if constexpr (INDEXED) {
+                  if (row_ok && c < clen && nan_row) v = __builtin_nanf("");
+                }
                 xs[r * ldx + c] = v;
               }
             } else {
@@ -275,8 +313,10 @@ __global__ __launch_bounds__(256) void mlp_backward_tiles(pdegym_mlp N, Plan P, 
 }
 
 // dW_0 partial of (64 input columns blockIdx.x, slab blockIdx.y) = dZ_0^T X over the slab's rows, ascending.  No LDS, no barrier.
-template <typename TX, bool CAT>
-__global__ __launch_bounds__(256) void mlp_backward_dw0(Plan P) {
+// INDEXED: a lane loads the index entries of its four rows once per tile, outside the loops over the columns.
+template <typename TX, bool CAT, bool INDEXED = false>
+__global__ __launch_bounds__(256) void mlp_backward_dw0(std::conditional_t<INDEXED, GatherPlan, Plan> P) {
+  static_assert(!INDEXED || CAT, "rows by index: the two-part instantiations");
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int li = lane & 15, lg = lane >> 4;
   const int K = P.in[0], H = P.out[0], B = P.B;
@@ -292,13 +332,30 @@ __global__ __launch_bounds__(256) void mlp_backward_dw0(Plan P) {
     float a[4], b[4][4];
 #pragma unroll
     for (int s = 0; s < 4; ++s) a[s] = P.dz0[(long long)(row0 + 4 * s + lg) * kWidth + 16 * wave + li];
+    long long xrow[4], x2row[4];      // INDEXED: the storage rows of rows row0 + 4 s + lg
+    bool outside[4];
+    if constexpr (INDEXED) {
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        const int r = row0 + 4 * s + lg;
+        const long long j = r < B ? P.index[r] : 0;
+        const bool inside = (unsigned long long)j < (unsigned long long)P.M;      // one comparison: j >= 0 and j < M
+        xrow[s] = inside ? j : 0;
+        x2row[s] = P.x2_indexed ? xrow[s] : (r < B ? r : 0);
+        outside[s] = !inside;
+      }
+    }
 #pragma unroll
     for (int t = 0; t < 4; ++t)
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
         const int r = row0 + 4 * s + lg, i = i0 + 16 * t + li;
         const bool ok = r < B && i < K;
-        if (CAT) {
+        if constexpr (INDEXED) {
+          b[t][s] = 0.f;
+          if (ok) b[t][s] = i < P.D ? (float)x[xrow[s] * P.x_stride + i] : P.x2[x2row[s] * P.x2_stride + (i - P.D)];
+          if (ok && outside[s]) b[t][s] = __builtin_nanf("");
+        } else if (CAT) {
           b[t][s] = 0.f;
           if (ok) b[t][s] = i < P.D ? (float)x[(long long)r * P.x_stride + i] : P.x2[(long long)r * P.x2_stride + (i - P.D)];
         } else {
@@ -487,9 +544,19 @@ int pdegym_mlp_backward(const pdegym_mlp* net, const pdegym_mlp_backward_args* a
 // Rows in two parts, the parameter gradients on request (include/pdegym.h).  params != 0: the three launches above on the CAT
 // instantiations; params == 0: the tile kernel alone, without its dW / db half, over the library's own slabs (a partition of the
 // tiles among workgroups that no result depends on).
-int pdegym_mlp_backward_cat(const pdegym_mlp* net, const pdegym_mlp_backward_cat_args* a, int32_t B, void* stream) {
+// g: rows by index (pdegym_mlp_backward_gather), the same launches on the INDEXED instantiations; nullptr: row b is row b.
+static int backward_cat_rows(const pdegym_mlp* net, const pdegym_mlp_backward_cat_args* a, const pdegym_mlp_gather* g, int32_t B,
+                             void* stream) {
   if (int rc = check_net(net)) return rc;
   if (!a) return pdegym::fail(-1, "null arguments");
+  if (g) {
+    if (!pdegym::is_aligned(g->index, 8)) return pdegym::fail(-2, "mlp_backward_gather: index must be 8-byte aligned");
+    if (g->M < 1) return pdegym::fail(-2, "mlp_backward_gather: M must be >= 1");
+    if (a->dx) return pdegym::fail(-2, "mlp_backward_gather: dx must be NULL (a gradient of gathered rows is a scatter-add)");
+    if (a->dx2 && g->x2_indexed) return pdegym::fail(-2, "mlp_backward_gather: dx2 needs x2_indexed == 0");
+    if (g->x2_indexed && !a->n2) return pdegym::fail(-2, "mlp_backward_gather: x2_indexed with n2 == 0");
+  }
+  const int64_t x_rows = g ? g->M : B, x2_rows = g && g->x2_indexed ? g->M : B;
   const bool params = a->params != 0;
   const int slabs = resolve_slabs(B, params ? a->slabs : 0);
   if (slabs < 0) return slabs;
@@ -525,11 +592,12 @@ int pdegym_mlp_backward_cat(const pdegym_mlp* net, const pdegym_mlp_backward_cat
   const int64_t need = params ? (dz0_floats(B) + (int64_t)slabs * per_slab_floats(net)) * (int64_t)sizeof(float) : 0;
   if (params && a->workspace_bytes < need) return pdegym::fail(-2, "workspace smaller than pdegym_mlp_backward_workspace answers");
 
-  Range in[3 + 3 * kLayers], out[3 + 2 * kLayers];
+  Range in[4 + 3 * kLayers], out[3 + 2 * kLayers];
   int n_in = 0, n_outr = 0;
-  in[n_in++] = extent(a->x, B, a->x_stride, D, net->x_f64 ? 8 : 4);
-  in[n_in++] = extent(n2 ? a->x2 : nullptr, B, a->x2_stride, n2, 4);
+  in[n_in++] = extent(a->x, x_rows, a->x_stride, D, net->x_f64 ? 8 : 4);
+  in[n_in++] = extent(n2 ? a->x2 : nullptr, x2_rows, a->x2_stride, n2, 4);
   in[n_in++] = extent(a->dy, B, a->dy_stride, n_out, 4);
+  in[n_in++] = extent(g ? g->index : nullptr, 1, B, B, 8);
   for (int l = 0; l < nl; ++l) {
     const pdegym_mlp_layer& L = net->layer[l];
     const int64_t cells = (int64_t)L.out_dim * L.in_dim;
@@ -568,6 +636,25 @@ int pdegym_mlp_backward_cat(const pdegym_mlp* net, const pdegym_mlp_backward_cat
   const size_t lds_bytes = (size_t)((kLayers + 2) * kRows * kLdh + kRows * ldx) * sizeof(float);
   const dim3 grid0((unsigned)((K0 + 63) / 64), (unsigned)slabs);
   const dim3 block(256), grid_reduce((unsigned)((P.per_slab + 255) / 256));
+  if (g) {
+    GatherPlan G = {};
+    static_cast<Plan&>(G) = P;
+    G.index = reinterpret_cast<const long long*>(g->index), G.M = g->M, G.x2_indexed = g->x2_indexed;
+    if (!params) {
+      if (net->x_f64) mlp_backward_tiles<double, true, false, true><<<dim3(slabs), block, lds_bytes, st>>>(*net, G, ldx);
+      else mlp_backward_tiles<float, true, false, true><<<dim3(slabs), block, lds_bytes, st>>>(*net, G, ldx);
+      return pdegym::check_launch("mlp_backward_gather");
+    }
+    if (net->x_f64) {
+      mlp_backward_tiles<double, true, true, true><<<dim3(slabs), block, lds_bytes, st>>>(*net, G, ldx);
+      mlp_backward_dw0<double, true, true><<<grid0, block, 0, st>>>(G);
+    } else {
+      mlp_backward_tiles<float, true, true, true><<<dim3(slabs), block, lds_bytes, st>>>(*net, G, ldx);
+      mlp_backward_dw0<float, true, true><<<grid0, block, 0, st>>>(G);
+    }
+    mlp_backward_reduce<<<grid_reduce, block, 0, st>>>(P);
+    return pdegym::check_launch("mlp_backward_gather");
+  }
   if (!params) {
     if (net->x_f64) mlp_backward_tiles<double, true, false><<<dim3(slabs), block, lds_bytes, st>>>(*net, P, ldx);
     else mlp_backward_tiles<float, true, false><<<dim3(slabs), block, lds_bytes, st>>>(*net, P, ldx);
@@ -582,6 +669,18 @@ int pdegym_mlp_backward_cat(const pdegym_mlp* net, const pdegym_mlp_backward_cat
   }
   mlp_backward_reduce<<<grid_reduce, block, 0, st>>>(P);
   return pdegym::check_launch("mlp_backward_cat");
+}
+
+int pdegym_mlp_backward_cat(const pdegym_mlp* net, const pdegym_mlp_backward_cat_args* a, int32_t B, void* stream) {
+  return backward_cat_rows(net, a, nullptr, B, stream);
+}
+
+// Rows by index (include/pdegym.h): row b of the call is row g->index[b] of x; dw, db (and dx2 with x2_indexed == 0) as
+// pdegym_mlp_backward_cat forms them on the materialised rows.
+int pdegym_mlp_backward_gather(const pdegym_mlp* net, const pdegym_mlp_backward_cat_args* a, const pdegym_mlp_gather* g, int32_t B,
+                               void* stream) {
+  if (!g || !g->index) return pdegym::fail(-1, "mlp_backward_gather: null gather descriptor or index");
+  return backward_cat_rows(net, a, g, B, stream);
 }
 
 }  // extern "C"

@@ -31,6 +31,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "pdegym.h"
 #include "pdegym_common.h"
@@ -81,6 +82,13 @@ struct Plan {
   int D;
 };
 
+// rows by index (pdegym_mlp_backward_wide_gather): the plan of the INDEXED instantiations, the others take Plan as they did
+struct GatherPlan : Plan {
+  const long long* index;      // [B]: row b of the call is row index[b] of x (and of x2 with x2_indexed)
+  long long M;                 // rows of x; an entry outside [0, M) is never an address, its row reads as NaN
+  int x2_indexed;
+};
+
 __device__ __forceinline__ v4f mma(float a, float b, v4f acc) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0); }
 
 __device__ __forceinline__ int slab_begin(const Plan& P, int slab) { return (int)((long long)slab * P.tiles / P.slabs); }
@@ -95,8 +103,12 @@ __device__ __forceinline__ float act_backward(float dh, float h, int act) {
 // CAT: rows in two parts.  PARAMS false: the input gradient alone -- neither dZ_l nor H_{l-1} goes to the workspace
 // (pdegym_mlp_backward_wide_cat with params == 0; the only launch of that call).  pdegym_mlp_backward_wide runs <TX, false, true>, the
 // code it was.
-template <typename TX, bool CAT, bool PARAMS>
-__global__ __launch_bounds__(64 * kWaves) void mlp_backward_wide_tiles(pdegym_mlp N, Plan P, int ldx) {
+// INDEXED (pdegym_mlp_backward_wide_gather; CAT instantiations only): a wave loads the index entry of the one row it stages once,
+// before the first chunk.
+template <typename TX, bool CAT, bool PARAMS, bool INDEXED = false>
+__global__ __launch_bounds__(64 * kWaves) void mlp_backward_wide_tiles(pdegym_mlp N, std::conditional_t<INDEXED, GatherPlan, Plan> P,
+                                                                       int ldx) {
+  static_assert(!INDEXED || CAT, "rows by index: the two-part instantiations");
   extern __shared__ __attribute__((aligned(16))) float bww_smem[];
   float* const hs = bww_smem;                                  // [kLayers][16][kLdh]: the activations of every layer
   float* const gs = hs + kLayers * kRows * kLdh;               // [2][16][kLdh]: dH / dZ of the layer at hand, and of the one below
@@ -121,6 +133,17 @@ __global__ __launch_bounds__(64 * kWaves) void mlp_backward_wide_tiles(pdegym_ml
     v4f acc[1] = {(v4f){0.f, 0.f, 0.f, 0.f}};
     v4f wfirst[kStage][1];
     if (l == 0) {
+      // INDEXED: the storage row of the row this wave stages, and whether its entry lies outside [0, M)
+      long long xrow = 0, x2row = 0;
+      bool outside = false;
+      if constexpr (INDEXED) {
+        const int r = row0 + wave;
+        const long long j = r < B ? P.index[r] : 0;
+        const bool inside = (unsigned long long)j < (unsigned long long)P.M;      // one comparison: j >= 0 and j < M
+        xrow = inside ? j : 0;
+        x2row = P.x2_indexed ? xrow : (r < B ? r : 0);
+        outside = !inside;
+      }
       for (int c0 = 0; c0 < K; c0 += kXChunk) {
         const int clen = (K - c0) < kXChunk ? (K - c0) : kXChunk;
         const int cpad = (clen + 15) & ~15;
@@ -130,9 +153,16 @@ __global__ __launch_bounds__(64 * kWaves) void mlp_backward_wide_tiles(pdegym_ml
           const TX* src = x + (long long)(row_ok ? row0 + r : 0) * P.x_stride + c0;
           if (CAT) {      // column c0 + c: the first part, or entry c0 + c - D of the tail
             const float* tail = P.x2 + (long long)(row_ok ? row0 + r : 0) * P.x2_stride;
+            if constexpr (INDEXED) {
+              src = x + xrow * P.x_stride + c0;
+              tail = P.x2 + x2row * P.x2_stride;
+            }
             for (int c = lane; c < cpad; c += 64) {
               float v = 0.f;
               if (row_ok && c < clen) v = c0 + c < P.D ? (float)src[c] : tail[c0 + c - P.D];
+              if constexpr (INDEXED) {
+                if (row_ok && c < clen && outside) v = __builtin_nanf("");
+              }
               xs[r * ldx + c] = v;
             }
           } else {
@@ -251,8 +281,10 @@ __global__ __launch_bounds__(64 * kWaves) void mlp_backward_wide_tiles(pdegym_ml
 
 // The partial dW_l of (work item blockIdx.x = layer, 64 units, 64 inputs; slab blockIdx.y) = dZ_l^T H_{l-1} over the slab's rows,
 // ascending, and with input block 0 the partial db_l = dZ_l^T 1.  No LDS, no barrier.
-template <typename TX, bool CAT>
-__global__ __launch_bounds__(256) void mlp_backward_wide_accumulate(Plan P) {
+// INDEXED: a lane loads the index entries of its four rows once per tile (first layer's work items), outside the loops over the columns.
+template <typename TX, bool CAT, bool INDEXED = false>
+__global__ __launch_bounds__(256) void mlp_backward_wide_accumulate(std::conditional_t<INDEXED, GatherPlan, Plan> P) {
+  static_assert(!INDEXED || CAT, "rows by index: the two-part instantiations");
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int li = lane & 15, lg = lane >> 4;
   // the layer of this work item and its figures, selected with constant indices (the plan lives in the kernel's arguments)
@@ -280,6 +312,21 @@ __global__ __launch_bounds__(256) void mlp_backward_wide_accumulate(Plan P) {
     float a[4], b[4][4];
 #pragma unroll
     for (int s = 0; s < 4; ++s) a[s] = dzl[(long long)(row0 + 4 * s + lg) * hp + u0 + li];
+    long long xrow[4], x2row[4];      // INDEXED: the storage rows of rows row0 + 4 s + lg
+    bool outside[4];
+    if constexpr (INDEXED) {
+      if (l == 0) {
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+          const int r = row0 + 4 * s + lg;
+          const long long j = r < B ? P.index[r] : 0;
+          const bool inside = (unsigned long long)j < (unsigned long long)P.M;      // one comparison: j >= 0 and j < M
+          xrow[s] = inside ? j : 0;
+          x2row[s] = P.x2_indexed ? xrow[s] : (r < B ? r : 0);
+          outside[s] = !inside;
+        }
+      }
+    }
 #pragma unroll
     for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -287,7 +334,11 @@ __global__ __launch_bounds__(256) void mlp_backward_wide_accumulate(Plan P) {
         const int r = row0 + 4 * s + lg, i = i0 + 16 * t + li;
         if (l == 0) {
           const bool ok = r < B && i < K;
-          if (CAT) {
+          if constexpr (INDEXED) {
+            b[t][s] = 0.f;
+            if (ok) b[t][s] = i < P.D ? (float)x[xrow[s] * P.x_stride + i] : P.x2[x2row[s] * P.x2_stride + (i - P.D)];
+            if (ok && outside[s]) b[t][s] = __builtin_nanf("");
+          } else if (CAT) {
             b[t][s] = 0.f;
             if (ok) b[t][s] = i < P.D ? (float)x[(long long)r * P.x_stride + i] : P.x2[(long long)r * P.x2_stride + (i - P.D)];
           } else {
@@ -432,15 +483,31 @@ int64_t workspace_bytes(const pdegym_mlp* net, int32_t B, int slabs) {
   return (tiles_of(B) * kRows * row_floats(net) + (int64_t)slabs * per_slab_floats(net)) * (int64_t)sizeof(float);
 }
 
+// G: rows by index (pdegym_mlp_backward_wide_gather), the INDEXED instantiations of the first two kernels; nullptr: row b is row b
 template <typename TX, bool CAT, bool PARAMS>
-int launch_all(const pdegym_mlp* net, const Plan& P, hipStream_t st) {
-  static signed char attr[pdegym::kMaxDevices] = {};
-  if (!pdegym::raise_dynamic_lds_limit(reinterpret_cast<const void*>(&mlp_backward_wide_tiles<TX, CAT, PARAMS>), kMaxLdsBytes, attr))
+int launch_all(const pdegym_mlp* net, const Plan& P, hipStream_t st, const GatherPlan* G = nullptr) {
+  static signed char attr[pdegym::kMaxDevices] = {}, attr_indexed[pdegym::kMaxDevices] = {};
+  if constexpr (CAT) {
+    if (G && !pdegym::raise_dynamic_lds_limit(reinterpret_cast<const void*>(&mlp_backward_wide_tiles<TX, CAT, PARAMS, true>), kMaxLdsBytes,
+                                              attr_indexed))
+      return pdegym::fail(-4, "cannot raise the dynamic LDS limit of mlp_backward_wide_tiles");
+  }
+  if (!G && !pdegym::raise_dynamic_lds_limit(reinterpret_cast<const void*>(&mlp_backward_wide_tiles<TX, CAT, PARAMS>), kMaxLdsBytes, attr))
     return pdegym::fail(-4, "cannot raise the dynamic LDS limit of mlp_backward_wide_tiles");
   const int K0 = P.in[0];
   const int kin = ((K0 < kXChunk ? K0 : kXChunk) + 15) & ~15;
   const int ldx = lds_stride(kin);
   const size_t lds_bytes = (size_t)((kLayers + 2) * kRows * kLdh + kRows * ldx) * sizeof(float);      // 101 .. 130 KB: above the 64 KB a kernel gets without asking
+  if constexpr (CAT) {
+    if (G) {
+      launch(mlp_backward_wide_tiles<TX, CAT, PARAMS, true>, dim3((unsigned)P.tiles), dim3(64 * kWaves), lds_bytes, st, *net, *G, ldx);
+      if (PARAMS) {
+        launch(mlp_backward_wide_accumulate<TX, CAT, true>, dim3((unsigned)P.item0[P.n_layers], (unsigned)P.slabs), dim3(256), 0, st, *G);
+        launch(mlp_backward_wide_reduce, dim3((unsigned)((P.per_slab + 255) / 256)), dim3(256), 0, st, P);
+      }
+      return pdegym::check_launch("mlp_backward_wide_gather");
+    }
+  }
   launch(mlp_backward_wide_tiles<TX, CAT, PARAMS>, dim3((unsigned)P.tiles), dim3(64 * kWaves), lds_bytes, st, *net, P, ldx);
   if (PARAMS) {
     launch(mlp_backward_wide_accumulate<TX, CAT>, dim3((unsigned)P.item0[P.n_layers], (unsigned)P.slabs), dim3(256), 0, st, P);
@@ -526,9 +593,19 @@ int pdegym_mlp_backward_wide(const pdegym_mlp* net, const pdegym_mlp_backward_ar
 
 // Rows in two parts, the parameter gradients on request (include/pdegym.h).  params != 0: the three launches above on the CAT
 // instantiations; params == 0: the tile kernel alone, without its workspace stores.
-int pdegym_mlp_backward_wide_cat(const pdegym_mlp* net, const pdegym_mlp_backward_cat_args* a, int32_t B, void* stream) {
+// g: rows by index (pdegym_mlp_backward_wide_gather), the same launches on the INDEXED instantiations; nullptr: row b is row b.
+static int backward_wide_cat_rows(const pdegym_mlp* net, const pdegym_mlp_backward_cat_args* a, const pdegym_mlp_gather* g, int32_t B,
+                                  void* stream) {
   if (int rc = check_net(net)) return rc;
   if (!a) return pdegym::fail(-1, "null arguments");
+  if (g) {
+    if (!pdegym::is_aligned(g->index, 8)) return pdegym::fail(-2, "mlp_backward_wide_gather: index must be 8-byte aligned");
+    if (g->M < 1) return pdegym::fail(-2, "mlp_backward_wide_gather: M must be >= 1");
+    if (a->dx) return pdegym::fail(-2, "mlp_backward_wide_gather: dx must be NULL (a gradient of gathered rows is a scatter-add)");
+    if (a->dx2 && g->x2_indexed) return pdegym::fail(-2, "mlp_backward_wide_gather: dx2 needs x2_indexed == 0");
+    if (g->x2_indexed && !a->n2) return pdegym::fail(-2, "mlp_backward_wide_gather: x2_indexed with n2 == 0");
+  }
+  const int64_t x_rows = g ? g->M : B, x2_rows = g && g->x2_indexed ? g->M : B;
   const bool params = a->params != 0;
   const int slabs = resolve_slabs(B, params ? a->slabs : 0);
   if (slabs < 0) return slabs;
@@ -564,11 +641,12 @@ int pdegym_mlp_backward_wide_cat(const pdegym_mlp* net, const pdegym_mlp_backwar
   const int64_t need = params ? workspace_bytes(net, B, slabs) : 0;
   if (params && a->workspace_bytes < need) return pdegym::fail(-2, "workspace smaller than pdegym_mlp_backward_wide_workspace answers");
 
-  Range in[3 + 3 * kLayers], out[3 + 2 * kLayers];
+  Range in[4 + 3 * kLayers], out[3 + 2 * kLayers];
   int n_in = 0, n_outr = 0;
-  in[n_in++] = extent(a->x, B, a->x_stride, D, net->x_f64 ? 8 : 4);
-  in[n_in++] = extent(n2 ? a->x2 : nullptr, B, a->x2_stride, n2, 4);
+  in[n_in++] = extent(a->x, x_rows, a->x_stride, D, net->x_f64 ? 8 : 4);
+  in[n_in++] = extent(n2 ? a->x2 : nullptr, x2_rows, a->x2_stride, n2, 4);
   in[n_in++] = extent(a->dy, B, a->dy_stride, n_out, 4);
+  in[n_in++] = extent(g ? g->index : nullptr, 1, B, B, 8);
   for (int l = 0; l < nl; ++l) {
     const pdegym_mlp_layer& L = net->layer[l];
     const int64_t cells = (int64_t)L.out_dim * L.in_dim;
@@ -610,8 +688,26 @@ int pdegym_mlp_backward_wide_cat(const pdegym_mlp* net, const pdegym_mlp_backwar
   P.part = ws;
   P.per_slab = at, P.n_layers = nl, P.B = B, P.tiles = (int)tiles_of(B), P.slabs = slabs;
   hipStream_t st = (hipStream_t)stream;
-  if (!params) return net->x_f64 ? launch_all<double, true, false>(net, P, st) : launch_all<float, true, false>(net, P, st);
-  return net->x_f64 ? launch_all<double, true, true>(net, P, st) : launch_all<float, true, true>(net, P, st);
+  GatherPlan G = {};
+  if (g) {
+    static_cast<Plan&>(G) = P;
+    G.index = reinterpret_cast<const long long*>(g->index), G.M = g->M, G.x2_indexed = g->x2_indexed;
+  }
+  const GatherPlan* Gp = g ? &G : nullptr;
+  if (!params) return net->x_f64 ? launch_all<double, true, false>(net, P, st, Gp) : launch_all<float, true, false>(net, P, st, Gp);
+  return net->x_f64 ? launch_all<double, true, true>(net, P, st, Gp) : launch_all<float, true, true>(net, P, st, Gp);
+}
+
+int pdegym_mlp_backward_wide_cat(const pdegym_mlp* net, const pdegym_mlp_backward_cat_args* a, int32_t B, void* stream) {
+  return backward_wide_cat_rows(net, a, nullptr, B, stream);
+}
+
+// Rows by index (include/pdegym.h): row b of the call is row g->index[b] of x; dw, db (and dx2 with x2_indexed == 0) as
+// pdegym_mlp_backward_wide_cat forms them on the materialised rows.
+int pdegym_mlp_backward_wide_gather(const pdegym_mlp* net, const pdegym_mlp_backward_cat_args* a, const pdegym_mlp_gather* g, int32_t B,
+                                    void* stream) {
+  if (!g || !g->index) return pdegym::fail(-1, "mlp_backward_wide_gather: null gather descriptor or index");
+  return backward_wide_cat_rows(net, a, g, B, stream);
 }
 
 }  // extern "C"

@@ -263,13 +263,37 @@ class FusedMLP:
             net.noise, net.noise_stride = noise.data_ptr(), (1 if actions.dim() == 2 else int(actions.shape[2]))
         return net
 
-    def _check_tail(self, x, tail, what):
+    def _check_index(self, x, index, tail, tail_indexed, rows, what):
+        """``index`` as the rows of the storage ``x`` [M, D] a call reads: a contiguous int64 [N] tensor on x's device, on a backend with
+        the gather entry points, without ``rows=``; ``tail_indexed`` only with an index and a tail.  Returns N (x's rows without index)."""
+        import torch
+        if index is None:
+            if tail_indexed:
+                raise ValueError(f"FusedMLP.{what}: tail_indexed=True needs index=")
+            return x.shape[0]
+        if not (hasattr(self.backend, "mlp_forward_gather") and hasattr(self.backend, "mlp_backward_gather")):
+            raise ValueError(f"FusedMLP.{what}: index= needs a backend with mlp_forward_gather / mlp_backward_gather, "
+                             f"{type(self.backend).__name__} has none")
+        if rows is not None:
+            raise ValueError(f"FusedMLP.{what}: rows= and index= do not combine (the masked launch reads row b)")
+        if not torch.is_tensor(index) or index.dtype != torch.int64 or index.dim() != 1 or not index.is_contiguous():
+            raise ValueError(f"FusedMLP.{what}: index must be a contiguous int64 [N] tensor")
+        if index.device != x.device:
+            raise ValueError(f"FusedMLP.{what}: index is on {index.device}, the observations on {x.device}")
+        if tail_indexed and tail is None:
+            raise ValueError(f"FusedMLP.{what}: tail_indexed=True needs tail=")
+        return index.shape[0]
+
+    def _check_tail(self, x, tail, what, rows=None):
         """``tail`` as the second part of the rows whose first part is ``x`` [B, D]: float32 [B, n2] on x's device, 1 <= n2 <= 8, the
-        widths adding up to ``in_dim``; on a backend with the two-part entry points.  ``ValueError`` otherwise."""
+        widths adding up to ``in_dim``; on a backend with the two-part entry points.  ``ValueError`` otherwise.  ``rows``: the rows the
+        tail must have when they are not x's (a call with ``index``)."""
         import torch
         if not (hasattr(self.backend, "mlp_forward_cat") and hasattr(self.backend, "mlp_backward_cat")):
             raise ValueError(f"FusedMLP.{what}: tail= needs a backend with mlp_forward_cat / mlp_backward_cat, {type(self.backend).__name__} has none")
-        if not torch.is_tensor(tail) or tail.dim() != 2 or tail.shape[0] != x.shape[0]:
+        if rows is not None and (not torch.is_tensor(tail) or tail.dim() != 2 or tail.shape[0] != rows):
+            raise ValueError(f"FusedMLP.{what}: tail must be a [{rows}, n2] tensor (the index's N rows, or the storage's M with tail_indexed)")
+        if rows is None and (not torch.is_tensor(tail) or tail.dim() != 2 or tail.shape[0] != x.shape[0]):
             raise ValueError(f"FusedMLP.{what}: tail must be a [B, n2] tensor with the observations' B = {x.shape[0]}")
         if tail.dtype != torch.float32:
             raise ValueError(f"FusedMLP.{what}: tail must be float32, got {tail.dtype}")
@@ -280,8 +304,15 @@ class FusedMLP:
         if x.shape[1] + tail.shape[1] != self.in_dim:
             raise ValueError(f"observation rows have {x.shape[1]} entries and tail rows {tail.shape[1]}, the network takes {self.in_dim}")
 
-    def forward_into(self, obs, out, clamp="default", noise=None, tail=None, rows=None, rows_not=None):
-        """``tail`` (float32 [B, n2], n2 <= 8): the rows are ``[obs | tail]``, read from the two tensors as they are -- SB3's
+    def forward_into(self, obs, out, clamp="default", noise=None, tail=None, rows=None, rows_not=None, index=None, tail_indexed=False):
+        """``index`` (contiguous int64 [N] on the observations' device): ``obs`` is a STORAGE of M rows -- a replay buffer's or a
+        rollout's observations -- and row b of the call is ``obs[index[b]]``, read in place by the first layer
+        (pdegym_mlp_forward_gather: no ``obs[index]`` copy); ``out`` and ``noise`` have N rows, ``tail`` N rows too, or the storage's M with
+        ``tail_indexed=True`` (row b's tail is then ``tail[index[b]]``: the stored actions).  Bits: those of the call on the gathered
+        rows.  An entry outside [0, M) is never an address: its row of ``out`` is NaN.  Not with ``rows=``.  Inside a stream capture
+        the ADDRESS of ``index`` is baked into the graph: keep one static index tensor and copy each minibatch's indices into it.
+
+        ``tail`` (float32 [B, n2], n2 <= 8): the rows are ``[obs | tail]``, read from the two tensors as they are -- SB3's
         ``critic(obs, actions)`` -- with the bits of the call on ``torch.cat([obs, tail], 1)``.  Without it:
 
         out[b, :] = net(obs[b, :]); ``obs`` [B, in_dim] (any trailing shape that flattens to in_dim), ``out`` [B, out_dim]
@@ -299,10 +330,10 @@ class FusedMLP:
         bits of the unmasked call, and what the other rows of ``obs`` hold (NaN included) does not matter.  No compaction, no
         allocation, no synchronisation: V(terminal observation) on the truncated rows of a rollout inside a captured graph.  Plain
         head, float32 ``out``, no ``noise``, no ``tail``."""
-        B = obs.shape[0]
-        x = obs.reshape(B, -1)
+        x = obs.reshape(obs.shape[0], -1)
+        B = self._check_index(x, index, tail, tail_indexed, rows if rows is not None else rows_not, "forward_into")
         if tail is not None:
-            self._check_tail(x, tail, "forward_into")
+            self._check_tail(x, tail, "forward_into", rows=None if index is None else (x.shape[0] if tail_indexed else B))
         elif x.shape[1] != self.in_dim:
             raise ValueError(f"observation rows have {x.shape[1]} entries, the network takes {self.in_dim}")
         y = out.reshape(B, self.out_dim)
@@ -328,6 +359,8 @@ class FusedMLP:
                 if m is not None and (m.dtype != torch.uint8 or m.numel() != B or m.device != x.device or not m.is_contiguous()):
                     raise ValueError(f"{name} must be a contiguous uint8 tensor of {B} flags on the observations' device")
             self.backend.mlp_forward(net, x, y, B, rows=rows.reshape(B), rows_not=None if rows_not is None else rows_not.reshape(B))
+        elif index is not None:
+            self.backend.mlp_forward_gather(net, _rows(x), None if tail is None else _rows(tail), index, y, B, x2_indexed=bool(tail_indexed))
         elif tail is not None:
             self.backend.mlp_forward_cat(net, x, _rows(tail), y, B)
         else:
@@ -379,8 +412,17 @@ class FusedMLP:
             ps += [p for m in self._heads for p in (m.weight, m.bias) if p is not None]
         return ps
 
-    def with_grad(self, obs, tail=None, params=True):
-        """``tail`` (float32 [B, n2], n2 <= 8): the rows are ``[obs | tail]`` -- SB3's ``critic(obs, actions)`` -- and ``tail`` receives its
+    def with_grad(self, obs, tail=None, params=True, index=None, tail_indexed=False):
+        """``index`` (contiguous int64 [N] on the observations' device): ``obs`` is a storage of M rows and row b of the call is
+        ``obs[index[b]]``, read in place by the forward AND the backward launches (pdegym_mlp_forward_gather, pdegym_mlp_backward_gather /
+        _wide_gather); what is saved for the backward is the storage and the index themselves, never a copy of the rows.  ``tail`` has N
+        rows, or M with ``tail_indexed=True``.  The storage receives no gradient (it would be a scatter-add over duplicated entries):
+        ``ValueError`` when ``obs`` requires grad, and when ``tail`` does with ``tail_indexed``; a dense ``tail`` that requires grad gets its
+        ``[N, n2]`` gradient (SAC's actor step: stored observation, fresh action).  Bits: those of the call on the gathered rows.  Inside
+        a stream capture the ADDRESS of ``index`` is baked into the graph: keep one static index tensor and copy each minibatch's
+        indices into it.
+
+        ``tail`` (float32 [B, n2], n2 <= 8): the rows are ``[obs | tail]`` -- SB3's ``critic(obs, actions)`` -- and ``tail`` receives its
         own ``[B, n2]`` gradient when it requires grad (``obs``, float32 and requiring grad, the ``[B, D]`` one of the first part: no
         full-width dx exists).  ``params=False``: no gradient goes to ``grad_parameters()`` and the backward is ONE launch that forms
         none (the critic pass of SAC's actor step); the same pass runs when no parameter requires grad.  Bits: those of the call on
@@ -399,14 +441,18 @@ class FusedMLP:
         import torch
         if self._backward_entry() is None:
             raise ValueError(f"FusedMLP.with_grad: {self.backward_limit()}")
-        B = obs.shape[0]
-        x = obs.reshape(B, -1)
+        x = obs.reshape(obs.shape[0], -1)
+        B = self._check_index(x, index, tail, tail_indexed, None, "with_grad")
         if tail is not None:
-            self._check_tail(x, tail, "with_grad")
+            self._check_tail(x, tail, "with_grad", rows=None if index is None else (x.shape[0] if tail_indexed else B))
         elif x.shape[1] != self.in_dim:
             raise ValueError(f"observation rows have {x.shape[1]} entries, the network takes {self.in_dim}")
         if x.dtype not in (torch.float32, torch.float64):
             raise ValueError(f"FusedMLP.with_grad: obs must be float32 or float64, got {x.dtype}")
+        if index is not None and obs.requires_grad:
+            raise ValueError("FusedMLP.with_grad: obs requires grad and is read by index: a gradient of gathered rows would be a scatter-add")
+        if tail_indexed and tail.requires_grad:
+            raise ValueError("FusedMLP.with_grad: tail requires grad and is read by index (tail_indexed=True)")
         two_part = hasattr(self.backend, "mlp_forward_cat") and hasattr(self.backend, "mlp_backward_cat")
         if not params and not two_part:
             raise ValueError(f"FusedMLP.with_grad: params=False needs a backend with mlp_backward_cat, {type(self.backend).__name__} has none")
@@ -416,16 +462,22 @@ class FusedMLP:
         else:
             self.refresh()
         ps = self.grad_parameters()
+        if index is not None:
+            if not params:
+                ps = [p.detach() for p in ps]
+            return _with_grad_function(gather=True).apply(self, bool(params), x, tail, index, bool(tail_indexed), *ps)
         if tail is not None or not params or (two_part and not any(p.requires_grad for p in ps)):
             if not params:      # detached: no edge to the parameters (saved all the same: a backward after an in-place step is refused)
                 ps = [p.detach() for p in ps]
             return _with_grad_function(cat=True).apply(self, bool(params), x, tail, *ps)
         return _with_grad_function().apply(self, x, *ps)
 
-    def __call__(self, obs, tail=None):
+    def __call__(self, obs, tail=None, index=None, tail_indexed=False):
+        """``forward_into`` with a fresh ``out`` of the observations' dtype: [B, out_dim], or [N, out_dim] with ``index`` [N]."""
         import torch
-        out = torch.empty(obs.shape[0], self.out_dim, dtype=obs.dtype, device=obs.device)
-        return self.forward_into(obs, out, tail=tail)      # (squashed-Gaussian head: a ValueError -- it has no default box; use forward_into)
+        n = obs.shape[0] if index is None or not torch.is_tensor(index) else index.shape[0]
+        out = torch.empty(n, self.out_dim, dtype=obs.dtype, device=obs.device)
+        return self.forward_into(obs, out, tail=tail, index=index, tail_indexed=tail_indexed)      # (squashed-Gaussian head: a ValueError -- it has no default box; use forward_into)
 
 
 def _rows(t):
@@ -436,15 +488,15 @@ def _rows(t):
     return t
 
 
-_function = _cat_function = None
+_function = _cat_function = _gather_function = None
 
 
-def _with_grad_function(cat=False):
+def _with_grad_function(cat=False, gather=False):
     """The ``torch.autograd.Function`` behind ``FusedMLP.with_grad`` (built on first use: this module imports torch lazily).  ``cat``:
-    the one behind ``with_grad(obs, tail, params)``, on the two-part entry points."""
-    global _function, _cat_function
+    the one behind ``with_grad(obs, tail, params)``, on the two-part entry points; ``gather``: the one behind ``with_grad(..., index=)``."""
+    global _function, _cat_function, _gather_function
     if _function is not None:
-        return _cat_function if cat else _function
+        return _gather_function if gather else (_cat_function if cat else _function)
     import torch
 
     class FusedMLPFunction(torch.autograd.Function):
@@ -525,5 +577,45 @@ def _with_grad_function(cat=False):
                     grads += [dw[-1][rows]] + ([db[-1][rows]] if db[-1] is not None else [])
             return (None, None, dx, dx2) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[4:]))
 
-    _function, _cat_function = FusedMLPFunction, FusedMLPCatFunction
-    return _cat_function if cat else _function
+    class FusedMLPGatherFunction(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, policy, params, x, tail, index, tail_indexed, *ps):
+            xd, td = _rows(x), (None if tail is None else _rows(tail))
+            n_out = int(policy.layers[-1][0].shape[0])
+            y = torch.empty(index.shape[0], n_out, dtype=torch.float32, device=xd.device)
+            policy.backend.mlp_forward_gather(policy._net(None, xd.dtype == torch.float64, plain=True), xd, td, index, y, index.shape[0],
+                                              x2_indexed=tail_indexed)
+            ctx.policy, ctx.tail_indexed, ctx.has_tail = policy, tail_indexed, td is not None
+            ctx.want_dx2 = td is not None and not tail_indexed and bool(ctx.needs_input_grad[3])
+            ctx.want_params = params and any(ctx.needs_input_grad[6:])
+            ctx.save_for_backward(xd, index, *(() if td is None else (td,)), *ps)      # the storage and the index: no copy of the rows
+            return y
+
+        @staticmethod
+        def backward(ctx, dy):
+            policy = ctx.policy
+            xd, index, td = ctx.saved_tensors[0], ctx.saved_tensors[1], (ctx.saved_tensors[2] if ctx.has_tail else None)
+            none = (None,) * (6 + len(ctx.needs_input_grad[6:]))
+            if not (ctx.want_params or ctx.want_dx2):
+                return none
+            dy = dy.to(torch.float32).contiguous()
+            weights = [w.detach() for w, _, _ in policy.layers]
+            dw = db = None
+            if ctx.want_params:
+                dw = [torch.empty_like(w) for w in weights]
+                db = [None if b is None else torch.empty_like(b.detach()) for _, b, _ in policy.layers]
+            dx2 = torch.empty(td.shape, dtype=torch.float32, device=td.device) if ctx.want_dx2 else None
+            policy.backend.mlp_backward_gather(policy._net(None, xd.dtype == torch.float64, plain=True), xd, td, index, dy, weights, dw, db, dx2,
+                                               params=ctx.want_params, wide=not policy.fits_backward(), x2_indexed=ctx.tail_indexed)
+            if not ctx.want_params:
+                return (None, None, None, dx2) + none[4:]
+            heads = policy._heads is not None
+            grads = [g for w_, b_ in zip(dw[:-1] if heads else dw, db[:-1] if heads else db) for g in (w_, b_) if g is not None]
+            if heads:      # rows 0 .. A-1 of the fused last layer are mu's, rows A .. 2A-1 log_std's
+                A = dw[-1].shape[0] // 2
+                for rows in (slice(0, A), slice(A, 2 * A)):
+                    grads += [dw[-1][rows]] + ([db[-1][rows]] if db[-1] is not None else [])
+            return (None, None, None, dx2, None, None) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[6:]))
+
+    _function, _cat_function, _gather_function = FusedMLPFunction, FusedMLPCatFunction, FusedMLPGatherFunction
+    return _gather_function if gather else (_cat_function if cat else _function)

@@ -92,12 +92,7 @@ __global__ __launch_bounds__(64 * WV) void mlp_forward_kernel(pdegym_mlp N, cons
     const RowIndex& gth = rows_not;
 #pragma unroll
     for (int rr = 0; rr < kRowsPerWave; ++rr) {
-      const int r = row0 + kRowsPerWave * wave + rr;
-      const long long j = r < B ? gth.index[r] : 0;
-      const bool inside = (unsigned long long)j < (unsigned long long)gth.M;      // one comparison: j >= 0 and j < M
-      xrow[rr] = inside ? j : 0;
-      x2row[rr] = gth.x2_indexed ? xrow[rr] : (r < B ? r : 0);
-      outside[rr] = !inside;
+      indexed_row(gth.index, gth.M, gth.x2_indexed, row0 + kRowsPerWave * wave + rr, B, xrow[rr], x2row[rr], outside[rr]);
     }
   }
 

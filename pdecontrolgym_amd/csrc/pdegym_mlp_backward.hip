@@ -22,6 +22,12 @@
 // pdegym_mlp_backward_cat (rows in two parts, the critic(obs, action) call) launches the same kernels,
 // instantiated with CAT (two-part addressing of the first layer's input and of dx) and, for params == 0, without PARAMS (the tile
 // kernel alone: no dW / db products, no workspace).
+//
+// What this unit has in common with pdegym_mlp_backward_wide.hip lives in pdegym_mlp_backward_common.h: the argument checks of all
+// entry points, the overlap scan, the slab and workspace arithmetic, the fill of the plan's common members, and mma / act_backward /
+// slab_begin / the slab sum of the kernels; how an index entry becomes a row (rows by index) in pdegym_mlp_tile.h.  Here: the
+// limits, the slab choice, the workspace layout, the kernels and their launches.  Kernel code that both units have and that no helper
+// could hold without changing an instantiation says where its twin is.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -29,16 +35,15 @@
 
 #include "pdegym.h"
 #include "pdegym_common.h"
+#include "pdegym_mlp_backward_common.h"
 #include "pdegym_mlp_tile.h"
 
 namespace {
 
-using namespace pdegym_mlp_tile;     // v4f, lds_stride, kStage, activate, load_w, reduce_blocks
+using namespace pdegym_mlp_tile;     // v4f, lds_stride, kStage, activate, load_w, reduce_blocks, indexed_row
+using namespace pdegym_mlp_backward_common;      // kRows, kLayers, mma, slab_begin, act_backward, slab_sum; the host checks
 
-constexpr int kRows = 16;                   // rows per tile (the M of the MFMA tile)
 constexpr int kWidth = 64;                  // widest layer output this file takes
-constexpr int kMaxIn = 1024;                // widest first-layer input
-constexpr int kLayers = PDEGYM_MLP_MAX_LAYERS;
 constexpr int kLdh = lds_stride(kWidth);    // LDS row stride of a [16, 64] block: 16 rows x one float, or x one float4, hit distinct banks
 constexpr int kXChunk = 512;                // observation entries per row staged at a time, as in the forward kernel
 constexpr int kMaxSlabs = 256;              // the library's choice: min(tiles, 256) -- B = 32768: 256 slabs of 128 rows
@@ -74,21 +79,10 @@ struct GatherPlan : Plan {
   int x2_indexed;
 };
 
-__device__ __forceinline__ v4f mma(float a, float b, v4f acc) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0); }
-
 // v of lane l, l wave-uniform
 __device__ __forceinline__ long long lane_value(long long v, int l) {
   const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, l), hi = (unsigned)__builtin_amdgcn_readlane((int)(v >> 32), l);
   return (long long)(((unsigned long long)hi << 32) | lo);
-}
-
-__device__ __forceinline__ int slab_begin(const Plan& P, int slab) { return (int)((long long)slab * P.tiles / P.slabs); }
-
-// torch's backward ops (tanh_backward, threshold_backward), each operation rounded on its own
-__device__ __forceinline__ float act_backward(float dh, float h, int act) {
-  if (act == PDEGYM_MLP_TANH) return __fmul_rn(dh, __fsub_rn(1.0f, __fmul_rn(h, h)));
-  if (act == PDEGYM_MLP_RELU) return h <= 0.f ? 0.f : dh;      // a NaN activation passes the gradient
-  return dh;
 }
 
 // CAT: rows in two parts.  PARAMS false: the input gradient alone -- no dW / db products, no dZ_0 in the workspace, no partial stores
@@ -117,8 +111,8 @@ __global__ __launch_bounds__(256) void mlp_backward_tiles(pdegym_mlp N, std::con
     for (int t = 0; t < 4; ++t) accw[l][t] = (v4f){0.f, 0.f, 0.f, 0.f};
   }
 
-  const int t_end = slab_begin(P, blockIdx.x + 1);
-  for (int tile = slab_begin(P, blockIdx.x); tile < t_end; ++tile) {
+  const int t_end = slab_begin(blockIdx.x + 1, P.tiles, P.slabs);
+  for (int tile = slab_begin(blockIdx.x, P.tiles, P.slabs); tile < t_end; ++tile) {
     const int row0 = tile * kRows;
     // ---- forward, as pdegym_mlp_forward computes it: the same operands in the same order --------------------------------------------
 #pragma unroll
@@ -137,14 +131,11 @@ __global__ __launch_bounds__(256) void mlp_backward_tiles(pdegym_mlp N, std::con
         long long xrow = 0, x2row = 0;
         int outside = 0;
         if constexpr (INDEXED) {
-          const int r = row0 + 4 * wave + (lane & 3);
-          const long long j = r < B ? P.index[r] : 0;
-          const bool inside = (unsigned long long)j < (unsigned long long)P.M;      // one comparison: j >= 0 and j < M
-          xrow = inside ? j : 0;
-          x2row = P.x2_indexed ? xrow : (r < B ? r : 0);
-          outside = !inside;
+          bool out;      // (outside is an int: readlane takes one)
+          indexed_row(P.index, P.M, P.x2_indexed, row0 + 4 * wave + (lane & 3), B, xrow, x2row, out);
+          outside = out;
         }
-        for (int c0 = 0; c0 < K; c0 += kXChunk) {
+        for (int c0 = 0; c0 < K; c0 += kXChunk) {      // (the staging has a twin in mlp_backward_wide_tiles: one row per wave there)
           const int clen = (K - c0) < kXChunk ? (K - c0) : kXChunk;
           const int cpad = (clen + 15) & ~15;
           for (int rr = 0; rr < 4; ++rr) {
@@ -237,6 +228,7 @@ __global__ __launch_bounds__(256) void mlp_backward_tiles(pdegym_mlp N, std::con
         }
       }
       // dH_{l-1} = dZ_l W_l (into dx for the first layer): A[row][unit] = dZ, B[unit][input] = W row-major, units in blocks of 16
+      // (a twin of this product is in mlp_backward_wide_tiles, pdegym_mlp_backward_wide.hip: 16 waves and its own kLdh)
       if (l >= 1 || P.dx || (CAT && P.dx2)) {
         const float* __restrict__ W = P.w[l];
         const int in_tiles = (K + 15) >> 4, unit_blocks = (H + 15) >> 4;
@@ -285,6 +277,7 @@ __global__ __launch_bounds__(256) void mlp_backward_tiles(pdegym_mlp N, std::con
 
   // ---- the slab's partial sums --------------------------------------------------------------------------------------------------------
   if (!PARAMS) return;
+  // (the stores of a db column and of a dW tile have twins below and in mlp_backward_wide_accumulate, pdegym_mlp_backward_wide.hip)
   float* const part = P.part + (long long)blockIdx.x * P.per_slab;
 #pragma unroll
   for (int l = 0; l < kLayers; ++l) {
@@ -326,8 +319,8 @@ __global__ __launch_bounds__(256) void mlp_backward_dw0(std::conditional_t<INDEX
   v4f acc[4];
 #pragma unroll
   for (int t = 0; t < 4; ++t) acc[t] = (v4f){0.f, 0.f, 0.f, 0.f};
-  const int t_end = slab_begin(P, blockIdx.y + 1);
-  for (int tile = slab_begin(P, blockIdx.y); tile < t_end; ++tile) {
+  const int t_end = slab_begin(blockIdx.y + 1, P.tiles, P.slabs);
+  for (int tile = slab_begin(blockIdx.y, P.tiles, P.slabs); tile < t_end; ++tile) {
     const int row0 = tile * kRows;
     float a[4], b[4][4];
 #pragma unroll
@@ -336,14 +329,7 @@ __global__ __launch_bounds__(256) void mlp_backward_dw0(std::conditional_t<INDEX
     bool outside[4];
     if constexpr (INDEXED) {
 #pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        const int r = row0 + 4 * s + lg;
-        const long long j = r < B ? P.index[r] : 0;
-        const bool inside = (unsigned long long)j < (unsigned long long)P.M;      // one comparison: j >= 0 and j < M
-        xrow[s] = inside ? j : 0;
-        x2row[s] = P.x2_indexed ? xrow[s] : (r < B ? r : 0);
-        outside[s] = !inside;
-      }
+      for (int s = 0; s < 4; ++s) indexed_row(P.index, P.M, P.x2_indexed, row0 + 4 * s + lg, B, xrow[s], x2row[s], outside[s]);
     }
 #pragma unroll
     for (int t = 0; t < 4; ++t)
@@ -351,7 +337,7 @@ __global__ __launch_bounds__(256) void mlp_backward_dw0(std::conditional_t<INDEX
       for (int s = 0; s < 4; ++s) {
         const int r = row0 + 4 * s + lg, i = i0 + 16 * t + li;
         const bool ok = r < B && i < K;
-        if constexpr (INDEXED) {
+        if constexpr (INDEXED) {      // (this load has a twin in mlp_backward_wide_accumulate, pdegym_mlp_backward_wide.hip)
           b[t][s] = 0.f;
           if (ok) b[t][s] = i < P.D ? (float)x[xrow[s] * P.x_stride + i] : P.x2[x2row[s] * P.x2_stride + (i - P.D)];
           if (ok && outside[s]) b[t][s] = __builtin_nanf("");
@@ -396,250 +382,49 @@ __global__ __launch_bounds__(256) void mlp_backward_reduce(Plan P) {
     if (e >= P.off_b[l] && e < P.off_b[l] + P.out[l]) dst = P.db[l] ? P.db[l] + (e - P.off_b[l]) : nullptr;
   }
   if (!dst) return;
-  const float* src = P.part + e;
-  float sum = src[0];
-  int k = 1;
-  for (; k + 8 <= P.slabs; k += 8) {
-    float v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = src[(long long)(k + j) * P.per_slab];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) sum = __fadd_rn(sum, v[j]);
-  }
-  for (; k < P.slabs; ++k) sum = __fadd_rn(sum, src[(long long)k * P.per_slab]);
-  *dst = sum;
+  *dst = slab_sum(P.part + e, P.slabs, P.per_slab);
 }
 
-struct Range {
-  const char* lo;
-  const char* hi;      // one past the last byte
-  bool overlaps(const Range& o) const { return lo && o.lo && lo < o.hi && o.lo < hi; }
-};
+// the workspace in front of the partials: dz0, [16, 64] per tile
+int64_t tile_floats(const pdegym_mlp*) { return kRows * kWidth; }
 
-// bytes [p, p + ((rows - 1) * stride + width) * size): the part of a [rows, stride] array the call touches
-Range extent(const void* p, int64_t rows, int64_t stride, int64_t width, int64_t size) {
-  const char* c = (const char*)p;
-  return {c, c ? c + ((rows - 1) * stride + width) * size : c};
-}
+int own_slabs(int tiles) { return tiles < kMaxSlabs ? tiles : kMaxSlabs; }
 
-// the descriptor limits of the backward pass; 0, or the code of pdegym::fail
-int check_net(const pdegym_mlp* net) {
-  if (!net) return pdegym::fail(-1, "null descriptor");
-  if (net->n_layers < 1 || net->n_layers > kLayers) return pdegym::fail(-2, "n_layers must be 1..4");
-  if (net->head != PDEGYM_MLP_HEAD_PLAIN) return pdegym::fail(-2, "mlp_backward: the head must be PLAIN (a squashed-Gaussian head is applied by the caller)");
-  if (net->clamp) return pdegym::fail(-2, "mlp_backward: clamp must be 0");
-  if (net->noise) return pdegym::fail(-2, "mlp_backward: noise must be NULL");
-  for (int l = 0; l < net->n_layers; ++l) {
-    const pdegym_mlp_layer& L = net->layer[l];
-    if (!L.w) return pdegym::fail(-3, "null weight pointer");
-    if (!pdegym::is_aligned(L.w, 16)) return pdegym::fail(-2, "layer weights (w) must be 16-byte aligned");
-    if (L.in_dim < 1 || L.out_dim < 1) return pdegym::fail(-2, "layer dimensions must be >= 1");
-    if (L.out_dim > kWidth) return pdegym::fail(-2, "mlp_backward: a layer wider than 64 units");
-    if (l == 0 && L.in_dim > kMaxIn) return pdegym::fail(-2, "mlp_backward: in_dim above 1024");
-    if (l > 0 && L.in_dim != net->layer[l - 1].out_dim) return pdegym::fail(-2, "layer input size does not match the previous layer");
-    if (L.act < PDEGYM_MLP_IDENTITY || L.act > PDEGYM_MLP_RELU) return pdegym::fail(-2, "unknown activation");
-  }
-  return 0;
-}
+constexpr Entry kEntry = {"mlp_backward", kWidth, own_slabs, tile_floats};
 
-// the number of slabs in use (the library's choice for 0), or the code of pdegym::fail
-int resolve_slabs(int32_t B, int32_t slabs) {
-  if (B < 1) return pdegym::fail(-2, "B must be >= 1");
-  const int tiles = (int)(((int64_t)B + kRows - 1) / kRows);
-  if (slabs < 0) return pdegym::fail(-2, "slabs must be >= 0");
-  if (slabs > tiles) return pdegym::fail(-2, "more slabs than tiles of 16 rows");
-  return slabs ? slabs : (tiles < kMaxSlabs ? tiles : kMaxSlabs);
-}
-
-int per_slab_floats(const pdegym_mlp* net) {
-  int n = 0;
-  for (int l = 0; l < net->n_layers; ++l) n += net->layer[l].out_dim * (net->layer[l].in_dim + 1);
-  return n;
-}
-
-int64_t dz0_floats(int32_t B) { return (((int64_t)B + kRows - 1) / kRows) * kRows * kWidth; }
-
-}  // namespace
-
-extern "C" {
-
-int64_t pdegym_mlp_backward_workspace(const pdegym_mlp* net, int32_t B, int32_t slabs) {
-  if (int rc = check_net(net)) return rc;
-  const int s = resolve_slabs(B, slabs);
-  if (s < 0) return s;
-  return (dz0_floats(B) + (int64_t)s * per_slab_floats(net)) * (int64_t)sizeof(float);
-}
-
-int pdegym_mlp_backward(const pdegym_mlp* net, const pdegym_mlp_backward_args* a, int32_t B, void* stream) {
-  if (int rc = check_net(net)) return rc;
-  if (!a) return pdegym::fail(-1, "null arguments");
-  const int slabs = resolve_slabs(B, a->slabs);
-  if (slabs < 0) return slabs;
-  const int nl = net->n_layers, K0 = net->layer[0].in_dim, n_out = net->layer[nl - 1].out_dim;
-  if (!a->x || !a->dy) return pdegym::fail(-3, "null x/dy");
-  if (!a->workspace) return pdegym::fail(-3, "null workspace");
-  if (!pdegym::is_aligned(a->workspace, 4)) return pdegym::fail(-2, "workspace must be 4-byte aligned");
-  for (int l = 0; l < nl; ++l) {
-    if (!a->dw[l]) return pdegym::fail(-3, "null dw");
-    if (!a->w[l] && (l > 0 || a->dx)) return pdegym::fail(-3, "null row-major weights (w[0] is needed with dx, the others always)");
-    if (a->db[l] && !net->layer[l].b) return pdegym::fail(-3, "db given for a layer without bias");
-    if (!a->db[l] && net->layer[l].b) return pdegym::fail(-3, "null db for a layer with bias");
-  }
-  if (a->dx && net->x_f64) return pdegym::fail(-2, "dx needs float32 x");
-  if (a->x_stride < K0 || a->dy_stride < n_out || (a->dx && a->dx_stride < K0)) return pdegym::fail(-2, "row stride shorter than the row");
-  const int64_t need = (dz0_floats(B) + (int64_t)slabs * per_slab_floats(net)) * (int64_t)sizeof(float);
-  if (a->workspace_bytes < need) return pdegym::fail(-2, "workspace smaller than pdegym_mlp_backward_workspace answers");
-
-  Range in[2 + 3 * kLayers], out[2 + 2 * kLayers];
-  int n_in = 0, n_outr = 0;
-  in[n_in++] = extent(a->x, B, a->x_stride, K0, net->x_f64 ? 8 : 4);
-  in[n_in++] = extent(a->dy, B, a->dy_stride, n_out, 4);
-  for (int l = 0; l < nl; ++l) {
-    const pdegym_mlp_layer& L = net->layer[l];
-    const int64_t cells = (int64_t)L.out_dim * L.in_dim;
-    in[n_in++] = extent(a->w[l], 1, cells, cells, 4);
-    in[n_in++] = extent(L.w, 1, 0, (int64_t)((L.in_dim + 3) / 4) * L.out_dim * 4, 4);
-    in[n_in++] = extent(L.b, 1, L.out_dim, L.out_dim, 4);
-    out[n_outr++] = extent(a->dw[l], 1, cells, cells, 4);
-    out[n_outr++] = extent(a->db[l], 1, L.out_dim, L.out_dim, 4);
-  }
-  out[n_outr++] = extent(a->dx, B, a->dx_stride, K0, 4);
-  out[n_outr++] = extent(a->workspace, 1, need, need, 1);
-  for (int i = 0; i < n_outr; ++i) {
-    for (int j = 0; j < n_in; ++j)
-      if (out[i].overlaps(in[j])) return pdegym::fail(-3, "an output or the workspace overlaps an input");
-    for (int j = i + 1; j < n_outr; ++j)
-      if (out[i].overlaps(out[j])) return pdegym::fail(-3, "two outputs overlap (the workspace counts as one)");
-  }
-
+// All three entry points.  params != 0: the three launches; params == 0 (two-part rows alone): the tile kernel alone, without its
+// dW / db half, over the library's own slabs (a partition of the tiles among workgroups that no result depends on).
+// two_part false: pdegym_mlp_backward, the <TX, false, true> instantiations; else the CAT ones.
+// g: rows by index (pdegym_mlp_backward_gather), the same launches on the INDEXED instantiations; nullptr: row b is row b.
+int backward_rows(const pdegym_mlp* net, const pdegym_mlp_backward_cat_args* a, const pdegym_mlp_gather* g, bool two_part, int32_t B,
+                  void* stream) {
+  Call c;
+  if (int rc = check_call(kEntry, net, a, g, two_part, B, c)) return rc;
+  const bool params = c.params;
+  const int slabs = c.slabs, K0 = net->layer[0].in_dim;
   Plan P = {};
-  P.x = a->x, P.x_stride = a->x_stride, P.dy = a->dy, P.dy_stride = a->dy_stride, P.dx = a->dx, P.dx_stride = a->dx_stride;
-  P.dz0 = static_cast<float*>(a->workspace);
-  P.part = P.dz0 + dz0_floats(B);
-  int at = 0;
-  for (int l = 0; l < nl; ++l) {
-    const pdegym_mlp_layer& L = net->layer[l];
-    P.w[l] = a->w[l], P.dw[l] = a->dw[l], P.db[l] = a->db[l], P.in[l] = L.in_dim, P.out[l] = L.out_dim;
-    P.off_w[l] = at, at += L.out_dim * L.in_dim;
-    P.off_b[l] = at, at += L.out_dim;
-  }
-  P.per_slab = at, P.n_layers = nl, P.B = B, P.tiles = (int)(((int64_t)B + kRows - 1) / kRows), P.slabs = slabs;
+  fill_plan(P, net, a, B, c);
+  P.dz0 = params ? static_cast<float*>(a->workspace) : nullptr;
+  P.part = params ? P.dz0 + P.tiles * tile_floats(net) : nullptr;
   hipStream_t st = (hipStream_t)stream;
   const int kin = ((K0 < kXChunk ? K0 : kXChunk) + 15) & ~15;
   const int ldx = lds_stride(kin);
   const size_t lds_bytes = (size_t)((kLayers + 2) * kRows * kLdh + kRows * ldx) * sizeof(float);      // <= 58 KB: no opt-in needed
   const dim3 grid0((unsigned)((K0 + 63) / 64), (unsigned)slabs);
   const dim3 block(256), grid_reduce((unsigned)((P.per_slab + 255) / 256));
-  if (net->x_f64) {
-    mlp_backward_tiles<double, false, true><<<dim3(slabs), block, lds_bytes, st>>>(*net, P, ldx);
-    mlp_backward_dw0<double, false><<<grid0, block, 0, st>>>(P);
-  } else {
-    mlp_backward_tiles<float, false, true><<<dim3(slabs), block, lds_bytes, st>>>(*net, P, ldx);
-    mlp_backward_dw0<float, false><<<grid0, block, 0, st>>>(P);
-  }
-  mlp_backward_reduce<<<grid_reduce, block, 0, st>>>(P);
-  return pdegym::check_launch("mlp_backward");
-}
-
-// Rows in two parts, the parameter gradients on request (include/pdegym.h).  params != 0: the three launches above on the CAT
-// instantiations; params == 0: the tile kernel alone, without its dW / db half, over the library's own slabs (a partition of the
-// tiles among workgroups that no result depends on).
-// g: rows by index (pdegym_mlp_backward_gather), the same launches on the INDEXED instantiations; nullptr: row b is row b.
-static int backward_cat_rows(const pdegym_mlp* net, const pdegym_mlp_backward_cat_args* a, const pdegym_mlp_gather* g, int32_t B,
-                             void* stream) {
-  if (int rc = check_net(net)) return rc;
-  if (!a) return pdegym::fail(-1, "null arguments");
-  if (g) {
-    if (!pdegym::is_aligned(g->index, 8)) return pdegym::fail(-2, "mlp_backward_gather: index must be 8-byte aligned");
-    if (g->M < 1) return pdegym::fail(-2, "mlp_backward_gather: M must be >= 1");
-    if (a->dx) return pdegym::fail(-2, "mlp_backward_gather: dx must be NULL (a gradient of gathered rows is a scatter-add)");
-    if (a->dx2 && g->x2_indexed) return pdegym::fail(-2, "mlp_backward_gather: dx2 needs x2_indexed == 0");
-    if (g->x2_indexed && !a->n2) return pdegym::fail(-2, "mlp_backward_gather: x2_indexed with n2 == 0");
-  }
-  const int64_t x_rows = g ? g->M : B, x2_rows = g && g->x2_indexed ? g->M : B;
-  const bool params = a->params != 0;
-  const int slabs = resolve_slabs(B, params ? a->slabs : 0);
-  if (slabs < 0) return slabs;
-  const int nl = net->n_layers, K0 = net->layer[0].in_dim, n_out = net->layer[nl - 1].out_dim, n2 = a->n2;
-  if (n2 < 0 || n2 > 8) return pdegym::fail(-2, "mlp_backward_cat: n2 must be 0..8");
-  if (n2 >= K0) return pdegym::fail(-2, "mlp_backward_cat: n2 must be below the first layer's in_dim (D >= 1)");
-  const int D = K0 - n2;
-  if (!a->x || !a->dy) return pdegym::fail(-3, "null x/dy");
-  if (n2 && !a->x2) return pdegym::fail(-3, "null x2");
-  if (!n2 && a->dx2) return pdegym::fail(-2, "mlp_backward_cat: dx2 given with n2 == 0");
-  if (n2 && !pdegym::is_aligned(a->x2, 4)) return pdegym::fail(-2, "x2 must be 4-byte aligned");
-  if (a->dx2 && !pdegym::is_aligned(a->dx2, 4)) return pdegym::fail(-2, "dx2 must be 4-byte aligned");
-  if (params) {
-    if (!a->workspace) return pdegym::fail(-3, "null workspace");
-    if (!pdegym::is_aligned(a->workspace, 4)) return pdegym::fail(-2, "workspace must be 4-byte aligned");
-  } else if (!a->dx && !a->dx2) {
-    return pdegym::fail(-3, "params == 0: one of dx and dx2 is required");
-  }
-  const bool want_dx = a->dx || a->dx2;
-  for (int l = 0; l < nl; ++l) {
-    if (params) {
-      if (!a->dw[l]) return pdegym::fail(-3, "null dw");
-      if (a->db[l] && !net->layer[l].b) return pdegym::fail(-3, "db given for a layer without bias");
-      if (!a->db[l] && net->layer[l].b) return pdegym::fail(-3, "null db for a layer with bias");
-    } else if (a->dw[l] || a->db[l]) {
-      return pdegym::fail(-2, "params == 0: dw and db must all be NULL");
+  if (!two_part) {
+    if (net->x_f64) {
+      mlp_backward_tiles<double, false, true><<<dim3(slabs), block, lds_bytes, st>>>(*net, P, ldx);
+      mlp_backward_dw0<double, false><<<grid0, block, 0, st>>>(P);
+    } else {
+      mlp_backward_tiles<float, false, true><<<dim3(slabs), block, lds_bytes, st>>>(*net, P, ldx);
+      mlp_backward_dw0<float, false><<<grid0, block, 0, st>>>(P);
     }
-    if (!a->w[l] && (l > 0 || want_dx)) return pdegym::fail(-3, "null row-major weights (w[0] is needed with dx / dx2, the others always)");
+    mlp_backward_reduce<<<grid_reduce, block, 0, st>>>(P);
+    return pdegym::check_launch("mlp_backward");
   }
-  if (a->dx && net->x_f64) return pdegym::fail(-2, "dx needs float32 x");
-  if (a->x_stride < D || a->dy_stride < n_out || (a->dx && a->dx_stride < D) || (n2 && a->x2_stride < n2) || (a->dx2 && a->dx2_stride < n2))
-    return pdegym::fail(-2, "row stride shorter than the row");
-  const int64_t need = params ? (dz0_floats(B) + (int64_t)slabs * per_slab_floats(net)) * (int64_t)sizeof(float) : 0;
-  if (params && a->workspace_bytes < need) return pdegym::fail(-2, "workspace smaller than pdegym_mlp_backward_workspace answers");
-
-  Range in[4 + 3 * kLayers], out[3 + 2 * kLayers];
-  int n_in = 0, n_outr = 0;
-  in[n_in++] = extent(a->x, x_rows, a->x_stride, D, net->x_f64 ? 8 : 4);
-  in[n_in++] = extent(n2 ? a->x2 : nullptr, x2_rows, a->x2_stride, n2, 4);
-  in[n_in++] = extent(a->dy, B, a->dy_stride, n_out, 4);
-  in[n_in++] = extent(g ? g->index : nullptr, 1, B, B, 8);
-  for (int l = 0; l < nl; ++l) {
-    const pdegym_mlp_layer& L = net->layer[l];
-    const int64_t cells = (int64_t)L.out_dim * L.in_dim;
-    in[n_in++] = extent(a->w[l], 1, cells, cells, 4);
-    in[n_in++] = extent(L.w, 1, 0, (int64_t)((L.in_dim + 3) / 4) * L.out_dim * 4, 4);
-    in[n_in++] = extent(L.b, 1, L.out_dim, L.out_dim, 4);
-    out[n_outr++] = extent(a->dw[l], 1, cells, cells, 4);
-    out[n_outr++] = extent(a->db[l], 1, L.out_dim, L.out_dim, 4);
-  }
-  out[n_outr++] = extent(a->dx, B, a->dx_stride, D, 4);
-  out[n_outr++] = extent(a->dx2, B, a->dx2_stride, n2, 4);
-  out[n_outr++] = extent(params ? a->workspace : nullptr, 1, need, need, 1);
-  for (int i = 0; i < n_outr; ++i) {
-    for (int j = 0; j < n_in; ++j)
-      if (out[i].overlaps(in[j])) return pdegym::fail(-3, "an output or the workspace overlaps an input");
-    for (int j = i + 1; j < n_outr; ++j)
-      if (out[i].overlaps(out[j])) return pdegym::fail(-3, "two outputs overlap (the workspace counts as one)");
-  }
-
-  Plan P = {};
-  P.x = a->x, P.x_stride = a->x_stride, P.dy = a->dy, P.dy_stride = a->dy_stride, P.dx = a->dx, P.dx_stride = a->dx_stride;
-  P.x2 = a->x2, P.x2_stride = a->x2_stride, P.dx2 = a->dx2, P.dx2_stride = a->dx2_stride, P.D = D;
-  P.dz0 = params ? static_cast<float*>(a->workspace) : nullptr;
-  P.part = params ? P.dz0 + dz0_floats(B) : nullptr;
-  int at = 0;
-  for (int l = 0; l < nl; ++l) {
-    const pdegym_mlp_layer& L = net->layer[l];
-    P.w[l] = a->w[l], P.dw[l] = a->dw[l], P.db[l] = a->db[l], P.in[l] = L.in_dim, P.out[l] = L.out_dim;
-    P.off_w[l] = at, at += L.out_dim * L.in_dim;
-    P.off_b[l] = at, at += L.out_dim;
-  }
-  P.per_slab = at, P.n_layers = nl, P.B = B, P.tiles = (int)(((int64_t)B + kRows - 1) / kRows), P.slabs = slabs;
-  hipStream_t st = (hipStream_t)stream;
-  const int kin = ((K0 < kXChunk ? K0 : kXChunk) + 15) & ~15;
-  const int ldx = lds_stride(kin);
-  const size_t lds_bytes = (size_t)((kLayers + 2) * kRows * kLdh + kRows * ldx) * sizeof(float);
-  const dim3 grid0((unsigned)((K0 + 63) / 64), (unsigned)slabs);
-  const dim3 block(256), grid_reduce((unsigned)((P.per_slab + 255) / 256));
   if (g) {
-    GatherPlan G = {};
-    static_cast<Plan&>(G) = P;
-    G.index = reinterpret_cast<const long long*>(g->index), G.M = g->M, G.x2_indexed = g->x2_indexed;
+    const GatherPlan G = gather_plan<GatherPlan>(P, g);
     if (!params) {
       if (net->x_f64) mlp_backward_tiles<double, true, false, true><<<dim3(slabs), block, lds_bytes, st>>>(*net, G, ldx);
       else mlp_backward_tiles<float, true, false, true><<<dim3(slabs), block, lds_bytes, st>>>(*net, G, ldx);
@@ -671,8 +456,19 @@ static int backward_cat_rows(const pdegym_mlp* net, const pdegym_mlp_backward_ca
   return pdegym::check_launch("mlp_backward_cat");
 }
 
+}  // namespace
+
+extern "C" {
+
+int64_t pdegym_mlp_backward_workspace(const pdegym_mlp* net, int32_t B, int32_t slabs) { return workspace_query(kEntry, net, B, slabs); }
+
+int pdegym_mlp_backward(const pdegym_mlp* net, const pdegym_mlp_backward_args* a, int32_t B, void* stream) {
+  return backward_rows(net, TwoPart(a).p, nullptr, false, B, stream);
+}
+
+// Rows in two parts, the parameter gradients on request (include/pdegym.h).
 int pdegym_mlp_backward_cat(const pdegym_mlp* net, const pdegym_mlp_backward_cat_args* a, int32_t B, void* stream) {
-  return backward_cat_rows(net, a, nullptr, B, stream);
+  return backward_rows(net, a, nullptr, true, B, stream);
 }
 
 // Rows by index (include/pdegym.h): row b of the call is row g->index[b] of x; dw, db (and dx2 with x2_indexed == 0) as
@@ -680,7 +476,7 @@ int pdegym_mlp_backward_cat(const pdegym_mlp* net, const pdegym_mlp_backward_cat
 int pdegym_mlp_backward_gather(const pdegym_mlp* net, const pdegym_mlp_backward_cat_args* a, const pdegym_mlp_gather* g, int32_t B,
                                void* stream) {
   if (!g || !g->index) return pdegym::fail(-1, "mlp_backward_gather: null gather descriptor or index");
-  return backward_cat_rows(net, a, g, B, stream);
+  return backward_rows(net, a, g, true, B, stream);
 }
 
 }  // extern "C"

@@ -42,6 +42,19 @@ __device__ __forceinline__ float squashed_gaussian(float mu, float log_std, bool
   return pdegym::clip_keep_nan(c, N.lo, N.hi);
 }
 
+// Rows by index (include/pdegym.h: pdegym_mlp_gather), the ONE copy of how an index entry becomes a row: row r of a call of B rows is
+// row index[r] of a storage of M rows.  An entry outside [0, M) is never an address: row 0 stands in for it and `outside` tells the
+// caller to select the row's values to NaN.  The x2 row is the indexed row, or row r itself.  Values, not the kernel's argument
+// structure: see pdegym_mlp_backward_common.h.
+__device__ __forceinline__ void indexed_row(const long long* index, long long M, int x2_indexed, int r, int B, long long& xrow,
+                                            long long& x2row, bool& outside) {
+  const long long j = r < B ? index[r] : 0;
+  const bool inside = (unsigned long long)j < (unsigned long long)M;      // one comparison: j >= 0 and j < M
+  xrow = inside ? j : 0;
+  x2row = x2_indexed ? xrow : (r < B ? r : 0);
+  outside = !inside;
+}
+
 // lane i <- lane i + A of its row of 16 lanes, A = 1 .. 8 wave-uniform (DPP row_shl:A, one v_mov_b32_dpp: no LDS round trip as a
 // ds_bpermute would be); lanes i + A >= 16 of a row get 0.  Every lane of the wave must be active (pdegym_common.h, at pinned_from_left).
 __device__ __forceinline__ float row_lane_plus(float v, int A) {

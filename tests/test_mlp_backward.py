@@ -199,8 +199,47 @@ def test_every_backward_kernel_has_an_output_contract_test():
         assert tests and all(callable(getattr(G, t, None)) for t in tests), (k, tests)
 
 
+def test_the_backward_units_share_one_header():
+    """csrc/pdegym_mlp_backward_common.h holds what pdegym_mlp_backward.hip and pdegym_mlp_backward_wide.hip have in common, each piece
+    once (the kernels' mma / act_backward / slab_begin / slab_sum; Range, extent, the overlap scan, the descriptor and argument checks,
+    the slab and workspace arithmetic, the plan fill), and pdegym_mlp_tile.h how an index entry becomes a row: neither unit defines
+    one of these or scans for overlaps itself, and all three entry points of a unit go through the one argument check."""
+    from pdecontrolgym_amd import build
+    code = lambda f: re.sub(r"//[^\n]*", "", open(os.path.join(build.CSRC, f)).read())      # noqa: E731
+    hdr, tile = code("pdegym_mlp_backward_common.h"), code("pdegym_mlp_tile.h")
+    shared = ("mma", "slab_begin", "act_backward", "slab_sum", "failf", "extent", "check_overlap", "check_net", "tiles_of", "resolve_slabs",
+              "per_slab_floats", "workspace_bytes", "workspace_query", "check_call", "fill_plan", "gather_plan")
+    defined = lambda name, src: re.findall(r"^(?:template <[^\n]*>\n)?(?:__device__ __forceinline__ |inline )?[\w:]+\s+" + name + r"\(", src, re.M)      # noqa: E731
+    for name in shared:
+        assert len(defined(name, hdr)) == 1, name
+    for struct in ("Range", "Entry", "Call", "TwoPart"):
+        assert len(re.findall(r"^struct %s \{" % struct, hdr, re.M)) == 1, struct
+    assert len(defined("indexed_row", tile)) == 1 and not defined("indexed_row", hdr)
+    assert "__global__" not in hdr and "<<<" not in hdr and "hipLaunchKernel" not in hdr      # every kernel and launch stays in its unit
+    # not a translation unit; the library's fingerprint hashes every file of csrc/, so it sees the header as it sees pdegym_mlp_tile.h
+    import inspect
+    assert "pdegym_mlp_backward_common.h" not in build.SOURCES and "os.listdir(CSRC)" in inspect.getsource(build._fingerprint)
+    for unit, run, entries in (("pdegym_mlp_backward.hip", "backward_rows", ("pdegym_mlp_backward", "pdegym_mlp_backward_cat", "pdegym_mlp_backward_gather")),
+                               ("pdegym_mlp_backward_wide.hip", "backward_wide_rows",
+                                ("pdegym_mlp_backward_wide", "pdegym_mlp_backward_wide_cat", "pdegym_mlp_backward_wide_gather"))):
+        src = code(unit)
+        assert '#include "pdegym_mlp_backward_common.h"' in src and "using namespace pdegym_mlp_backward_common;" in src, unit
+        assert not [n for n in shared + ("indexed_row",) if defined(n, src)], (unit, [n for n in shared if defined(n, src)])
+        assert "struct Range" not in src and ".overlaps(" not in src and "extent(" not in src, unit
+        assert "unsigned long long)P.M" not in src and "P.index[" not in src, unit      # (the index entry: indexed_row alone reads it)
+        # one call of the shared check, in the function every entry point of the unit returns through
+        assert len(re.findall(r"(?<!\w)check_call\(", src)) == 1 and len(re.findall(r"(?<!\w)check_net\(", src)) == 0, unit
+        body = re.search(r"^int " + run + r"\(.*?^\}", src, re.S | re.M).group(0)
+        assert "check_call(kEntry, net, a, g, two_part, B, c)" in body, unit
+        for name in entries:
+            entry = re.search(r"^int " + name + r"\(.*?^\}", src, re.S | re.M).group(0)
+            assert len(re.findall(r"return " + run + r"\(net, ", entry)) == 1, (unit, name)
+    fwd = code("pdegym_mlp.hip")
+    assert "indexed_row(" in fwd and "unsigned long long)gth.M" not in fwd
+
+
 # ---- argument validation of the entry points, host half under ASan + UBSan ----------------------------------------------------------
-SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"]
+SAN =["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"]
 
 
 @pytest.mark.skipif(shutil.which("hipcc") is None, reason="needs hipcc")
